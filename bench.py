@@ -10,10 +10,18 @@ i.e. the reference's `--normalize` Criteo benchmark
 
 Prints ONE JSON line (rank 0).  value = rows/s over all ranks (weak scaling:
 every rank owns its own N-row shard; fit statistics are merged over RCCL).
+
+A plain run sets up, warms up, times --steps steps and prints the line
+(ms_per_step = milliseconds of one timed step).  --full adds everything else
+the line can carry: profiled / per-kernel passes and the roofline, the CPU
+baseline and the parity legs against the oracle, the extra_configs entries and,
+with --gpus > 1, the collective self-check and the exchange breakdown.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -31,6 +39,9 @@ CRITEO_CARDS = [39884406, 39043, 17289, 7420, 20263, 3, 7120, 1543, 63, 38532951
                 36]
 N_CONT = 13
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+# --dump-outputs: rows written per output column (39 columns x 1 MiB of float64) and their seed
+DUMP_ROWS = 1 << 17
+DUMP_SEED = 20261016
 
 
 def synth_criteo(n, device, seed=20260923, n_cat=26, n_cont=N_CONT, scramble=True):
@@ -98,6 +109,32 @@ def build_workflow(cat_names, cont_names, out_path):
     cats = cat_names >> ops.Categorify(out_path=out_path, defer_artifacts=True)
     conts = cont_names >> ops.FillMissing() >> ops.Normalize()
     return nvt.Workflow(cats + conts)
+
+
+def dump_outputs(out, wf, path):
+    """What one step returned to its caller, as float64 .npy files under `path`: every output
+    column at the same DUMP_ROWS rows (a seeded sample; every row of a smaller frame), NaN where
+    a row is null, and the statistics the step's fit gave Normalize (normalize_means.npy /
+    normalize_stds.npy, in output column order).  Runs after the timed steps."""
+    from nvtabular_amd.node import iter_nodes
+
+    os.makedirs(path, exist_ok=True)
+    n = len(out)
+    rows = np.arange(n) if n <= DUMP_ROWS else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    for name, col in out.items():
+        if col.fill is not None:
+            col = col.materialize()
+        idx = torch.from_numpy(rows).to(col.data.device)
+        vals = col.data.index_select(0, idx).to(torch.float64).cpu().numpy()
+        if col.valid is not None:
+            vb = col.valid.index_select(0, idx >> 3).cpu().numpy()
+            vals[((vb >> (rows & 7)) & 1) == 0] = np.nan
+        np.save(os.path.join(path, f"{name}.npy"), vals)
+    norm_op = [nd.op for nd in iter_nodes(wf.output_node) if type(nd.op).__name__ == "Normalize"][0]
+    conts = [c for c in out.columns if c in norm_op.means]
+    np.save(os.path.join(path, "normalize_means.npy"), np.array([norm_op.means[c] for c in conts], np.float64))
+    np.save(os.path.join(path, "normalize_stds.npy"), np.array([norm_op.stds[c] for c in conts], np.float64))
 
 
 def _cpu_column_job(args):
@@ -1297,7 +1334,21 @@ def main():
     ap.add_argument("--cpu-baseline-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-procs", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-tmp", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: profiled and per-kernel "
+                         "passes (roofline), fresh-workflow step, full-frame properties, CPU baseline and "
+                         "parity against the oracle, the extra_configs entries; with --gpus > 1 the "
+                         "collective self-check, the exchange breakdown and the multi-partition entry")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<column>.npy "
+                         f"(float64; the same {DUMP_ROWS} seeded rows of every output column, NaN where "
+                         "null) and the fitted Normalize statistics as DIR/normalize_means.npy / "
+                         "DIR/normalize_stds.npy (rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.only_extra and not args.full:
+        ap.error("--only-extra selects among the --full entries: add --full")
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args.cpu_baseline_worker, args.cpu_baseline_tmp or tempfile.mkdtemp(),
                             args.cpu_baseline_procs)
@@ -1343,8 +1394,8 @@ def main():
         else:
             td.init_process_group(backend, rank=rank, world_size=world)
         assert td.get_world_size() == args.gpus, (td.get_world_size(), args.gpus)
-        selfcheck = collective_selfcheck(device, backend)
-        if not selfcheck["ok_on_every_rank"]:
+        selfcheck = collective_selfcheck(device, backend) if args.full else None
+        if selfcheck is not None and not selfcheck["ok_on_every_rank"]:
             if rank == 0:
                 print(json.dumps({"metric": "rows/sec + GB/s (Criteo Categorify+FillMissing+Normalize "
                                             "fit+transform, HBM-resident)", "value": None,
@@ -1436,62 +1487,68 @@ def main():
     dt = time.perf_counter() - t0
     n_alloc = torch.cuda.memory_stats(device).get("num_device_alloc", 0) - n_alloc0
     timed_marks = list(marks)
-    # ---- second pass, same steps, HIP events on every kernel family (inside the library,
-    # on the launch streams): GPU-busy time of the real, overlapped pipeline.
-    barrier()
-    K.profile_begin()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
-    barrier()
-    dt_prof = time.perf_counter() - t1
-    rep = K.profile_report()
-    # ---- third pass: the same steps with the cross-stream overlap switched off (vocabularies
-    # ordered inside fit, their streams joined before transform), so that every kernel family
-    # is timed running ALONE: these are the per-kernel durations the roofline is computed from
-    # (under overlap a bandwidth-bound kernel's own duration stretches while the step shrinks).
-    from nvtabular_amd.ops import categorify as _cat
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, wf, args.dump_outputs)
+    if not args.full:
+        gc.enable()
+        del out
+    else:
+        # ---- second pass, same steps, HIP events on every kernel family (inside the library,
+        # on the launch streams): GPU-busy time of the real, overlapped pipeline.
+        barrier()
+        K.profile_begin()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            out = step()
+        barrier()
+        dt_prof = time.perf_counter() - t1
+        rep = K.profile_report()
+        # ---- third pass: the same steps with the cross-stream overlap switched off (vocabularies
+        # ordered inside fit, their streams joined before transform), so that every kernel family
+        # is timed running ALONE: these are the per-kernel durations the roofline is computed from
+        # (under overlap a bandwidth-bound kernel's own duration stretches while the step shrinks).
+        from nvtabular_amd.ops import categorify as _cat
 
-    saved = (K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS)
-    K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS = False, False, 1
-    os.environ["NVT_FINALIZE_SERIAL"] = "1"  # read by the library at every finalize call
-    os.environ["NVT_ENCODE_STREAMS"] = "1"   # ... and at every nvt_encode_many call
-    step()
-    barrier()
-    K.profile_begin()
-    t2 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
-    barrier()
-    dt_serial = time.perf_counter() - t2
-    prof = K.profile_report()["kernels"]
-    K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS = saved
-    os.environ.pop("NVT_FINALIZE_SERIAL", None)
-    os.environ.pop("NVT_ENCODE_STREAMS", None)
-    gc.enable()
-    del out
-    # a second hint-less step, now that the library's code objects are loaded and the caching
-    # allocator holds the blocks: what a FRESH workflow costs beyond a steady-state refit
-    # (presample, conservative path choice, 1024-bucket range path) without the process warm-up
-    wf_cold = build_workflow(cat_names, cont_names, os.path.join(tmp, f"gpu{rank}_cold2"))
-    barrier()
-    t3 = time.perf_counter()
-    wf_cold.fit(ds)
-    out = wf_cold.transform(frame)
-    barrier()
-    fresh_ms = 1e3 * (time.perf_counter() - t3)
-    cold_info["fresh_workflow_warm_process_ms"] = round(fresh_ms, 2)
-    # full-frame parity of the TIMED frame (the state the timed steps left behind: same workflow,
-    # same frame), through the size-independent properties of tests/test_gpu_fullsize.py
-    full_frame = None
-    if world == 1:
-        try:
-            full_frame = property_checks(wf, [frame], [wf.transform(frame)], cat_names, cont_names)
-        except Exception as e:  # never break the line
-            full_frame = {"full_frame_ok": False, "error": repr(e)}
-    del out, wf_cold
+        saved = (K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS)
+        K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS = False, False, 1
+        os.environ["NVT_FINALIZE_SERIAL"] = "1"  # read by the library at every finalize call
+        os.environ["NVT_ENCODE_STREAMS"] = "1"   # ... and at every nvt_encode_many call
+        step()
+        barrier()
+        K.profile_begin()
+        t2 = time.perf_counter()
+        for _ in range(args.steps):
+            out = step()
+        barrier()
+        dt_serial = time.perf_counter() - t2
+        prof = K.profile_report()["kernels"]
+        K.ASYNC_FINALIZE, _cat.LAZY_FINALIZE, K.COUNT_STREAMS = saved
+        os.environ.pop("NVT_FINALIZE_SERIAL", None)
+        os.environ.pop("NVT_ENCODE_STREAMS", None)
+        gc.enable()
+        del out
+        # a second hint-less step, now that the library's code objects are loaded and the caching
+        # allocator holds the blocks: what a FRESH workflow costs beyond a steady-state refit
+        # (presample, conservative path choice, 1024-bucket range path) without the process warm-up
+        wf_cold = build_workflow(cat_names, cont_names, os.path.join(tmp, f"gpu{rank}_cold2"))
+        barrier()
+        t3 = time.perf_counter()
+        wf_cold.fit(ds)
+        out = wf_cold.transform(frame)
+        barrier()
+        fresh_ms = 1e3 * (time.perf_counter() - t3)
+        cold_info["fresh_workflow_warm_process_ms"] = round(fresh_ms, 2)
+        # full-frame parity of the TIMED frame (the state the timed steps left behind: same workflow,
+        # same frame), through the size-independent properties of tests/test_gpu_fullsize.py
+        full_frame = None
+        if world == 1:
+            try:
+                full_frame = property_checks(wf, [frame], [wf.transform(frame)], cat_names, cont_names)
+            except Exception as e:  # never break the line
+                full_frame = {"full_frame_ok": False, "error": repr(e)}
+        del out, wf_cold
     dist_diag = None
-    if world > 1:
+    if world > 1 and args.full:
         # ONE more fit + transform, outside every timed region, with the exchange's sections timed
         # (device-synchronised marks) and the bytes of every collective form counted: the first
         # RCCL run explains itself -- where the ranks wait, what crosses the links
@@ -1515,9 +1572,12 @@ def main():
     if world > 1:
         import torch.distributed as td
 
-        t = torch.tensor([dt, dt_prof, dt_serial], device=device, dtype=torch.float64)
+        t = torch.tensor([dt, dt_prof, dt_serial] if args.full else [dt], device=device, dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
-        dt, dt_prof, dt_serial = (float(v) for v in t.tolist())
+        if args.full:
+            dt, dt_prof, dt_serial = (float(v) for v in t.tolist())
+        else:
+            dt = float(t[0])
 
     ms_per_step = 1e3 * dt / args.steps
     rows_per_s = world * n * args.steps / dt
@@ -1531,7 +1591,7 @@ def main():
     # the third pass; a family = all paths / columns of one operator stage).  achieved = the
     # family's algorithmic bytes per step / its time per step; "launch" = one column's pass.
     roofline = None
-    if prof:
+    if args.full and prof:
         ncols = {"cat": C, "cont": Kc}
         fam = {}
         for scope, (tot_ms, launches, _) in prof.items():
@@ -1588,16 +1648,21 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": ms_per_step,
-        "gpu_busy_ms_per_step": round(rep["busy_ms"] / args.steps, 3),
-        "profiled_pass_ms_per_step": round(1e3 * dt_prof / args.steps, 3),
-        "cold_step_ms": round(cold_ms, 2),
-        "cold_step": cold_info,
+    }
+    if args.full:
+        result["gpu_busy_ms_per_step"] = round(rep["busy_ms"] / args.steps, 3)
+        result["profiled_pass_ms_per_step"] = round(1e3 * dt_prof / args.steps, 3)
+    result["cold_step_ms"] = round(cold_ms, 2)
+    result["cold_step"] = cold_info
+    if args.full:
         # what a user's FIRST fit of a workflow costs in a warm process (no cardinality hints:
         # presample + conservative paths); `value` is the steady-state refit
-        "fresh_fit": {"ms_per_step": round(fresh_ms, 2), "rows_per_s": world * n / (fresh_ms / 1e3),
-                      "frac_of_hbm_peak": world * n / (fresh_ms / 1e3) * ((26 * 4 + N_CONT * 4) + (26 * 12 + N_CONT * 12))
-                      / 1e9 / (HBM_PEAK_GBS * world),
-                      "state": "fresh workflow (no hints), process warm"},
+        result["fresh_fit"] = {
+            "ms_per_step": round(fresh_ms, 2), "rows_per_s": world * n / (fresh_ms / 1e3),
+            "frac_of_hbm_peak": world * n / (fresh_ms / 1e3) * ((26 * 4 + N_CONT * 4) + (26 * 12 + N_CONT * 12))
+            / 1e9 / (HBM_PEAK_GBS * world),
+            "state": "fresh workflow (no hints), process warm"}
+    result.update({
         "host_timeline_ms": _host_timeline(timed_marks),
         # hipMalloc calls the caching allocator had to make inside the timed region (0 = the
         # warm-up reached the steady-state footprint)
@@ -1622,10 +1687,11 @@ def main():
         "algorithmic_GBps": gbs,
         "frac_of_hbm_peak": gbs / (HBM_PEAK_GBS * world),
         "algorithmic_bytes_per_step": bytes_per_row * n,
-        "step_traffic_bytes": step_traffic,  # HBM bytes per step from the committed PMC passes
-        "roofline": roofline,
-    }
-    if rank == 0 and not args.no_cpu_baseline:
+    })
+    if args.full:
+        result["step_traffic_bytes"] = step_traffic  # HBM bytes per step from the committed PMC passes
+        result["roofline"] = roofline
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (rank 0 only, also when world > 1: its own shard, a single-rank fit for the parity leg)
         from nvtabular_amd import dist as _dist
 
@@ -1647,7 +1713,7 @@ def main():
                     reference_tie_break_step_ms(frame, cat_names, cont_names, tmp), 1)
         except Exception as e:
             result["reference_tie_break_step_ms"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_extra and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.no_cpu_baseline:
         # entries beside the headline number (never `value`); none of them may break the line
         try:
             result["eager_artifacts_step_ms"] = round(
@@ -1675,7 +1741,7 @@ def main():
                 extras[key] = {"error": repr(e)}
             torch.cuda.empty_cache()
         result["extra_configs"] = extras
-    if world > 1:
+    if world > 1 and args.full:
         result["collective_selfcheck"] = selfcheck
         result["dist_breakdown"] = dist_diag
         if not args.no_extra:
@@ -1709,6 +1775,7 @@ def main():
         import torch.distributed as td
 
         td.destroy_process_group()
+    shutil.rmtree(tmp, ignore_errors=True)
     if parity_failed:
         print("bench.py: PARITY FAILED: " + ", ".join(result["parity_failed"]), file=sys.stderr)
         sys.exit(3)

@@ -129,18 +129,31 @@ def expected_groupby(inp):
     return out
 
 
+def save_npz(path, **arrays):
+    """np.savez_compressed with LZMA in place of deflate (np.load reads both): keeps every
+    fixture file under 1 MiB."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(v), allow_pickle=False)
+            z.writestr(k + ".npy", buf.getvalue())
+
+
 def main():
     inp = make_inputs()
     exp = expected(inp)
-    np.savez_compressed(os.path.join(HERE, "hotpath_v1.npz"),
-                        **{"in_" + k: v for k, v in inp.items()},
-                        **{"out_" + k: v for k, v in exp.items()})
+    save_npz(os.path.join(HERE, "hotpath_v1.npz"),
+             **{"in_" + k: v for k, v in inp.items()},
+             **{"out_" + k: v for k, v in exp.items()})
     print({k: (v.shape, v.dtype) for k, v in exp.items()})
     inp = make_inputs_groupby()
     exp = expected_groupby(inp)
-    np.savez_compressed(os.path.join(HERE, "groupby_v1.npz"),
-                        **{"in_" + k: v for k, v in inp.items()},
-                        **{"out_" + k: v for k, v in exp.items()})
+    save_npz(os.path.join(HERE, "groupby_v1.npz"),
+             **{"in_" + k: v for k, v in inp.items()},
+             **{"out_" + k: v for k, v in exp.items()})
     print({k: (v.shape, v.dtype) for k, v in exp.items()})
 
 

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def test_bench_spawns_its_own_ranks_gloo_rehearsal(tmp_path):
     env.pop("RANK", None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows",
                           "400000", "--steps", "2", "--warmup", "1", "--cpu-sample", "100000",
-                          "--multipart", "3"],
+                          "--multipart", "3", "--full"],
                          capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -57,7 +58,7 @@ def _bench(tmp_path, env_extra, *args):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "400000", "--steps", "2",
-                           "--warmup", "1", "--cpu-sample", "100000", "--no-extra", *args],
+                           "--warmup", "1", "--cpu-sample", "100000", "--no-extra", "--full", *args],
                           capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
 
 
@@ -76,6 +77,30 @@ def test_bench_parity_is_loud(tmp_path):
     assert rec["parity_ok"] is False and rec["parity_failed"] == ["headline"]
     assert rec["parity"]["categorify_mismatch_columns"] == ["C7"]
     assert "PARITY FAILED" in bad.stderr
+
+
+def test_bench_plain_run_times_and_dumps_only(tmp_path):
+    """Without --full the line carries the headline alone (no profiled passes, no oracle legs) and
+    --dump-outputs writes every output column of the last timed step at the same seeded rows."""
+    import bench
+
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "400000", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert res.returncode == 0, res.stderr[-2000:]
+    rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["unit"] == "rows/s" and rec["higher_is_better"] is True and rec["dtype"]
+    assert not {"roofline", "cpu_baseline", "parity", "extra_configs", "fresh_fit"} & set(rec)
+    names = sorted(os.listdir(tmp_path / "dump"))
+    cols = [f"C{j}.npy" for j in range(1, 27)] + [f"I{j}.npy" for j in range(1, 14)]
+    assert names == sorted(cols + ["normalize_means.npy", "normalize_stds.npy"])
+    for f in cols:
+        a = np.load(tmp_path / "dump" / f)
+        assert a.dtype == np.float64 and a.shape == (bench.DUMP_ROWS,), (f, a.dtype, a.shape)
+    assert np.isfinite(np.load(tmp_path / "dump" / "I1.npy")).all()
+    assert np.load(tmp_path / "dump" / "C1.npy").min() >= 0
+    assert np.load(tmp_path / "dump" / "normalize_stds.npy").shape == (13,)
 
 
 @pytest.mark.timeout(400)

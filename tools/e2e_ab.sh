@@ -1,7 +1,7 @@
 #!/bin/bash
 # end_to_end entry under a few host-side settings (one box)
 cd /root/repo; out=gpurun_out/e2e_ab; mkdir -p $out
-run() { name=$1; shift; env "$@" timeout 300 python bench.py --only-extra end_to_end > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; env "$@" timeout 300 python bench.py --full --only-extra end_to_end > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 try:
     r=json.load(open("$out/$name.json"))["extra_configs"]["end_to_end"]

@@ -1,9 +1,10 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 # round-3 evidence: kernel stats + HBM traffic counters of the bench command (run on the GPU box)
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_r03; rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 export NVT_READBACK_TIMEOUT=60
-B="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extra"
+B="python $ROOT/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-extra"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o stats -- $B > $out/stats.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out -o fetch -- $B > $out/fetch.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out -o write -- $B > $out/write.log 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A / B / A / B of one environment switch inside one box: tools/var_ab.sh <outdir> <VAR=a> <VAR=b>
 cd /root/repo; out=gpurun_out/$1; mkdir -p $out
-run() { name=$1; shift; env "$@" timeout 200 python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; env "$@" timeout 200 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 try:
     r=json.load(open("$out/$name.json")); fam=r["roofline"]["per_family"]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # unprofiled vs profiled step time under different cross-stream hand-off variants
 cd /root/repo; out=gpurun_out/$1; mkdir -p $out
-run() { name=$1; shift; env "$@" timeout 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; env "$@" timeout 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 try:
     r=json.load(open("$out/$name.json")); print("$name", {k:round(r[k],2) for k in ("ms_per_step","gpu_busy_ms_per_step","profiled_pass_ms_per_step")})

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A / B of a compile-time switch of nvt_dense_count.hip on the GPU box: tools/var_build.sh <outdir> "<flags A>" "<flags B>"
 cd /root/repo; out=gpurun_out/$1; mkdir -p $out
-run() { name=$1; timeout 200 python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; timeout 200 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 try:
     r=json.load(open("$out/$name.json")); print("$name", {k:round(r[k],2) for k in ("ms_per_step","gpu_busy_ms_per_step")}, {k:v for k,v in r["roofline"]["per_kernel_ms_per_step"].items() if "dense_count_h" in k})

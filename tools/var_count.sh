@@ -1,7 +1,7 @@
 #!/bin/bash
 # step time with 1 / 2 / 3 counting streams
 cd /root/repo; out=gpurun_out/$1; mkdir -p $out
-run() { name=$1; shift; env "$@" timeout 200 python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
+run() { name=$1; shift; env "$@" timeout 200 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-extra > $out/$name.json 2> $out/$name.err; python - <<PY
 import json
 try:
     r=json.load(open("$out/$name.json")); print("$name", {k:round(r[k],2) for k in ("ms_per_step","gpu_busy_ms_per_step","profiled_pass_ms_per_step")}, r["parity_checked_rows"] if "parity_checked_rows" in r else "")
