@@ -902,6 +902,49 @@ int nvt_prof_report(char *buf, uint64_t cap, uint64_t *needed);
 void nvt_range_push(const char *name);
 void nvt_range_pop(void);
 
+/* ---- string categoricals: Arrow string buffers -> 64-bit surrogate keys ----
+ * A string column is keyed by pandas.util.hash_array(v, categorize=False) viewed as int64, the
+ * surrogate the host path (nvtabular_amd/strings.py) computes; these entries compute the same
+ * bits from the column's Arrow buffers.  Restated from pandas 2.3.3:
+ *   pandas/core/util/hashing.py:44        _default_hash_key "0123456789123456"  -> nvt_str_hash
+ *   pandas/core/util/hashing.py:326       hash_object_array (pandas/_libs/hashing.pyx):
+ *                                         SipHash-2-4 of the UTF-8 bytes        -> nvt_str_hash
+ *   pandas/core/util/hashing.py:333-338   _hash_ndarray's final mixing step     -> nvt_str_hash
+ *   pandas/core/util/hashing.py:318-323   factorize + hash of the categories    -> nvt_str_dedup,
+ *                                         (the {surrogate -> string} table)        nvt_str_gather
+ * `offsets` holds n + 1 int32 (Arrow string) or int64 (large_string) entries, offset_bytes = 4
+ * or 8; offsets[0] may be non-zero (a sliced array): `chars` points at the byte offsets[0]
+ * names, must be 4-byte aligned and readable up to the 4-byte boundary after the last byte.
+ * Null rows (valid bit 0) get the key 0.
+ *
+ * nvt_str_hash: out[i] = surrogate of string i (one lane per string, aligned 4-byte loads).
+ * nvt_str_take_keys: dictionary-encoded columns: out[i] = dict_keys[indices[i]] (0 for a null
+ *   row, or an index outside [0, n_dict)); index_bytes = 4 or 8.
+ * nvt_str_dedup: the first row of every distinct key among the valid rows, in row order:
+ *   out_keys[j] = its key, out_strs[j] = its string (index[row] when `index` is given -- the
+ *   dictionary entry of a dictionary-encoded row --, else the row itself); out_counts[0] =
+ *   distinct keys, out_counts[1] = valid rows whose bytes differ from those of the first row
+ *   of their key (64-bit collisions).  Strings come from offsets / chars (n_strings entries).
+ *   out_keys / out_strs hold n entries.  ws: nvt_str_dedup_ws_bytes(n), 256-byte aligned (an
+ *   open-addressing table claimed by 64-bit CAS; the key INT64_MIN has a slot of its own).
+ * nvt_str_gather: strings strs[0 .. m) -> out_offsets[m + 1] (int64, from 0) + out_chars
+ *   (out_capacity bytes, < 4 GiB; a string that would end past it is not copied, and
+ *   out_offsets[m] then exceeds out_capacity).  ws: nvt_str_gather_ws_bytes(m), 256-byte
+ *   aligned. */
+int nvt_str_hash(const void *offsets, int offset_bytes, const uint8_t *chars, const uint8_t *valid,
+                 uint64_t n, int64_t *out, void *stream);
+int nvt_str_take_keys(const int64_t *dict_keys, uint64_t n_dict, const void *indices, int index_bytes,
+                      const uint8_t *valid, uint64_t n, int64_t *out, void *stream);
+int nvt_str_dedup_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_str_dedup(const int64_t *keys, const uint8_t *valid, uint64_t n, const void *index, int index_bytes,
+                  const void *offsets, int offset_bytes, const uint8_t *chars, uint64_t n_strings, void *ws,
+                  uint64_t ws_bytes, int64_t *out_keys, int64_t *out_strs, uint64_t *out_counts,
+                  void *stream);
+int nvt_str_gather_ws_bytes(uint64_t m, uint64_t *bytes);
+int nvt_str_gather(const int64_t *strs, uint64_t m, const void *offsets, int offset_bytes,
+                   const uint8_t *chars, uint64_t n_strings, void *ws, uint64_t ws_bytes,
+                   int64_t *out_offsets, uint8_t *out_chars, uint64_t out_capacity, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -233,6 +233,12 @@ SIGNATURES.update({
     "nvt_prof_report": [C.c_char_p, _u64, C.POINTER(_u64)],
     "nvt_range_push": [C.c_char_p],
     "nvt_range_pop": [],
+    "nvt_str_hash": [_vp, _i32, _vp, _vp, _u64, _vp, _vp],
+    "nvt_str_take_keys": [_vp, _u64, _vp, _i32, _vp, _u64, _vp, _vp],
+    "nvt_str_dedup_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_str_dedup": [_vp, _vp, _u64, _vp, _i32, _vp, _i32, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp],
+    "nvt_str_gather_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_str_gather": [_vp, _u64, _vp, _i32, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
 })
 
 _RESTYPES = {

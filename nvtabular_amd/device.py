@@ -147,7 +147,7 @@ class DeviceColumn:
     @staticmethod
     def from_pandas(s: pd.Series, device=None) -> "DeviceColumn":
         device = device or default_device()
-        from .strings import string_column_to_device  # local: avoids a cycle
+        from .strings import string_series_to_device  # local: avoids a cycle
 
         if s.dtype == object or pd.api.types.is_string_dtype(s.dtype):
             nn = s.dropna()
@@ -162,7 +162,7 @@ class DeviceColumn:
                     leaf_col = DeviceColumn(torch.empty(0, dtype=torch.int64, device=device))
                 leaf_col.offsets = torch.from_numpy(offsets).to(device)
                 return leaf_col
-            return string_column_to_device(s, device)
+            return string_series_to_device(s, device)
         if isinstance(s.dtype, pd.api.extensions.ExtensionDtype):
             # pandas nullable / arrow-backed numerics: values + mask
             mask = s.isna().to_numpy()
@@ -196,9 +196,20 @@ class DeviceColumn:
             off = np.asarray(arr.offsets).astype(np.int64)
             leaves.offsets = torch.from_numpy(off - off[0]).to(device)
             return leaves
-        if pa.types.is_string(arr.type) or pa.types.is_large_string(arr.type) or \
-                pa.types.is_dictionary(arr.type):
+        if pa.types.is_string(arr.type) or pa.types.is_large_string(arr.type):
+            # strings are keyed on the device from Arrow's own buffers (kernels_strings)
+            from . import kernels_strings as KS
+
+            if KS.fits(arr):
+                return KS.column_from_string_array(arr, device)
             return DeviceColumn.from_pandas(arr.to_pandas(), device)
+        if pa.types.is_dictionary(arr.type):
+            from . import kernels_strings as KS
+
+            if KS.is_string_type(arr.dictionary.type) and arr.dictionary.null_count == 0 and \
+                    KS.fits(arr.dictionary):
+                return KS.column_from_dictionary_array(arr, device)
+            return DeviceColumn.from_arrow(arr.dictionary_decode(), device)
         np_dt = arr.type.to_pandas_dtype()
         n = len(arr)
         valid = None

@@ -909,11 +909,9 @@ class Categorify(StatOperator):
             s = value[kn]
             isnull = s.isna().to_numpy()
             if s.dtype == object or pd.api.types.is_string_dtype(s.dtype):
-                from ..strings import string_key64
+                from ..strings import string_keys
 
-                hk = np.zeros(len(s), dtype=np.int64)
-                if (~isnull).any():
-                    hk[~isnull] = string_key64(s.to_numpy(dtype=object)[~isnull])
+                hk = string_keys(s, dev).cpu().numpy()   # (0 under a null, as the encoder expects)
             else:
                 hk = s.fillna(0).to_numpy().astype(np.int64)
             nm |= (isnull.astype(np.uint8) << j)

@@ -398,7 +398,7 @@ class JoinGroupby(StatOperator):
 
 def _stats_from_frame(df: pd.DataFrame, key_cols) -> _Stats:
     """Rebuild the device stat table from a cat_stats parquet frame."""
-    from ..strings import string_key64
+    from ..strings import string_keys
 
     dev = torch.device("cuda", torch.cuda.current_device())
     keys, nm = [], np.zeros(len(df), dtype=np.uint8)
@@ -406,13 +406,10 @@ def _stats_from_frame(df: pd.DataFrame, key_cols) -> _Stats:
         s = df[c]
         isnull = s.isna().to_numpy()
         if s.dtype == object or pd.api.types.is_string_dtype(s.dtype):
-            hk = np.zeros(len(s), dtype=np.int64)
-            if (~isnull).any():
-                hk[~isnull] = string_key64(s.to_numpy(dtype=object)[~isnull])
+            keys.append(string_keys(s, dev))   # (0 under a null)
         else:
-            hk = s.fillna(0).to_numpy().astype(np.int64)
+            keys.append(torch.from_numpy(s.fillna(0).to_numpy().astype(np.int64)).to(dev))
         nm |= isnull.astype(np.uint8) << j
-        keys.append(torch.from_numpy(hk).to(dev))
     cols = {
         c: torch.from_numpy(df[c].to_numpy().astype(np.float64)).to(dev)
         for c in df.columns if c not in key_cols
