@@ -945,6 +945,55 @@ int nvt_str_gather(const int64_t *strs, uint64_t m, const void *offsets, int off
                    const uint8_t *chars, uint64_t n_strings, void *ws, uint64_t ws_bytes,
                    int64_t *out_offsets, uint8_t *out_chars, uint64_t out_capacity, void *stream);
 
+/* ---- row compaction: ops.Filter / ops.Dropna ----
+ * Dropping rows is three steps over a PLAN, a workspace of nvt_compact_ws_bytes(n) bytes, 256-byte
+ * aligned, that covers n rows in tiles of 2048 (n < 2^32 - 2048):
+ *   1. a keep mask: a bitmap over the tiles plus a uint32 count of kept rows per tile, written in
+ *      one launch by nvt_compact_keep_mask (row i is kept iff mask[i] != 0; bool / uint8, n bytes),
+ *      nvt_compact_keep_dropna (row i is kept iff every descriptor column is valid there: bitmap
+ *      bit 1, and not NaN for NVT_F32 / NVT_F64; ONE launch per 64 descriptors, ANDed together)
+ *      or nvt_compact_list_keep (the leaves of a list column: a leaf is kept iff its row is kept
+ *      in row_plan; offsets are the n + 1 int64 row offsets, offsets[0] possibly non-zero);
+ *   2. nvt_compact_plan: the exclusive scan of the tile counts (nvt_scan.hpp, no inter-workgroup
+ *      waits); *out_m (device uint64, optional) = m, the kept rows;
+ *   3. nvt_compact_many: ONE launch per 64 descriptors (blockIdx.y = column) moves the kept rows
+ *      of every column, in row order, to [0, m) of its output: `width` = 1, 4 or 8 bytes per
+ *      value (bool, uint8, int32, int64, float32, float64), each descriptor with its own plan and
+ *      n (the leaves of a list column go with their leaf plan).  src_valid / dst_valid (both or
+ *      neither): the validity bitmap compacted bit-exactly; the call zeroes dst_valid first, over
+ *      ceil(m / 64) * 8 bytes (the padding of every bitmap here), so bits past m are 0.
+ * nvt_compact_list_offsets: the m + 1 new offsets (from 0) of a list column whose leaves were
+ *   compacted with leaf_plan (n_leaves = 0: every list is empty and leaf_plan may be NULL).
+ * Every entry is stream-ordered and does not synchronise; n = 0 is a no-op.  Nothing is read back:
+ * the caller sizes the outputs from *out_m. */
+#define NVT_COMPACT_MAX_COLS 64
+typedef struct nvt_dropna_col {
+  const void *x;            /* values (read for NVT_F32 / NVT_F64 only)         */
+  const uint8_t *valid;     /* bitmap or NULL                                   */
+  int32_t dtype;            /* NVT_F32 .. NVT_U8                                */
+  int32_t reserved;
+} nvt_dropna_col;
+typedef struct nvt_compact_col {
+  const void *src;          /* n values                                         */
+  void *dst;                /* m values                                         */
+  const uint8_t *src_valid; /* bitmap or NULL                                   */
+  uint8_t *dst_valid;       /* bitmap of ceil(m / 64) * 8 bytes, 4-byte aligned, or NULL */
+  const void *plan;         /* the plan of these n rows                          */
+  uint64_t n;
+  int32_t width;            /* bytes per value: 1, 4 or 8                       */
+  int32_t reserved;
+} nvt_compact_col;
+int nvt_compact_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_compact_keep_mask(const uint8_t *mask, uint64_t n, void *ws, uint64_t ws_bytes, void *stream);
+int nvt_compact_keep_dropna(const nvt_dropna_col *cols, int ncols, uint64_t n, void *ws, uint64_t ws_bytes,
+                            void *stream);
+int nvt_compact_list_keep(const int64_t *offsets, uint64_t n, const void *row_plan, uint64_t n_leaves,
+                          void *leaf_ws, uint64_t leaf_ws_bytes, void *stream);
+int nvt_compact_plan(uint64_t n, void *ws, uint64_t ws_bytes, uint64_t *out_m, void *stream);
+int nvt_compact_many(const nvt_compact_col *cols, int ncols, void *stream);
+int nvt_compact_list_offsets(const int64_t *offsets, uint64_t n, const void *row_plan, const void *leaf_plan,
+                             uint64_t n_leaves, int64_t *out_offsets, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

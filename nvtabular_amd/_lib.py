@@ -241,6 +241,29 @@ SIGNATURES.update({
     "nvt_str_gather": [_vp, _u64, _vp, _i32, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
 })
 
+
+class DropnaCol(C.Structure):
+    """nvt_dropna_col: one column tested by nvt_compact_keep_dropna."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CompactCol(C.Structure):
+    """nvt_compact_col: one column moved by nvt_compact_many."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("src_valid", _vp), ("dst_valid", _vp), ("plan", _vp),
+                ("n", _u64), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+COMPACT_MAX_COLS = 64   # include/nvt_hip.h NVT_COMPACT_MAX_COLS
+SIGNATURES.update({
+    "nvt_compact_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_compact_keep_mask": [_vp, _u64, _vp, _u64, _vp],
+    "nvt_compact_keep_dropna": [C.POINTER(DropnaCol), _i32, _u64, _vp, _u64, _vp],
+    "nvt_compact_list_keep": [_vp, _u64, _vp, _u64, _vp, _u64, _vp],
+    "nvt_compact_plan": [_u64, _vp, _u64, _vp, _vp],
+    "nvt_compact_many": [C.POINTER(CompactCol), _i32, _vp],
+    "nvt_compact_list_offsets": [_vp, _u64, _vp, _vp, _u64, _vp, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

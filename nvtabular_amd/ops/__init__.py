@@ -5,7 +5,9 @@ from .base import Operator, StatOperator  # noqa: F401
 from .bucketize import Bucketize  # noqa: F401
 from .categorify import Categorify, get_embedding_sizes  # noqa: F401
 from .clip_log import Clip, LogOp  # noqa: F401
+from .dropna import Dropna  # noqa: F401
 from .fill import FillMissing  # noqa: F401
+from .filter import Filter  # noqa: F401
 from .groupby import Groupby  # noqa: F401
 from .hash_bucket import HashBucket  # noqa: F401
 from .hashed_cross import HashedCross  # noqa: F401
