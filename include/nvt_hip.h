@@ -994,6 +994,82 @@ int nvt_compact_many(const nvt_compact_col *cols, int ncols, void *stream);
 int nvt_compact_list_offsets(const int64_t *offsets, uint64_t n, const void *row_plan, const void *leaf_plan,
                              uint64_t n_leaves, int64_t *out_offsets, void *stream);
 
+/* ---- hash join against an external table: ops.JoinExternal ----
+ * Keys: 1 to NVT_JOIN_MAX_KEYS components, each read in its native dtype (NVT_F32 .. NVT_U8) and
+ * reduced to a canonical 64-bit word plus a null bit: NVT_JOIN_INT compares by value (integers of
+ * any width, string surrogates), NVT_JOIN_FLOAT by double value (-0.0 == 0.0, integers converted
+ * to double; a float column needs it).  A null component is a validity bit 0 or a NaN; nulls
+ * match nulls, as in pandas' merge.
+ * Build (once per external table):
+ *   nvt_join_hash: per external row its tag (one component: the word; more: a fingerprint of the
+ *     words and null bits), the null bits (bit k = component k) and, for 2+ components, the
+ *     words [nkeys][n] that verify a fingerprint hit;
+ *   the caller groups the rows by (tag, null bits) with a stable sort, permutes its payload
+ *     columns into that order and picks `empty`, a tag no external key has;
+ *   nvt_join_insert: the distinct tags into an open-addressing table of nvt_join_table_bytes
+ *     (16-byte slots {tag, first, count}, load <= 0.5) with a 64-bit CAS; the caller fills the
+ *     slots with {empty, 0, 0} first.  One component: the null group is not inserted, it is
+ *     described by null_first / null_count of the index.
+ * Probe (per partition, n left rows, no read-back):
+ *   nvt_join_probe_gather: left join on unique keys; per left row the matched external row's
+ *     value of every payload column, 0 and a cleared validity bit on a miss (dst_valid required:
+ *     ceil(n / 64) * 8 bytes, 8-byte aligned, bits past n are 0); *unmatched (device, optional)
+ *     += the rows without a match;
+ *   nvt_join_probe: out_first[i] = grouped position of the first matching external row or -1,
+ *     out_count[i] = k (inner) or max(1, k) (left), out_keep[i] = match, *out_total (device)
+ *     += sum of out_count; every output but out_first is optional;
+ *   nvt_join_offsets: exclusive scan of counts[0 .. n] in place (counts[n] = 0 on entry, the
+ *     total below 2^32), with a workspace of nvt_join_scan_ws_bytes(n) bytes;
+ *   nvt_join_expand: per output row j < m its left row (the last i with offsets[i] <= j) and its
+ *     external position (first[i] + j - offsets[i], or -1 where first[i] < 0);
+ *   nvt_join_gather: dst[j] = src[idx[j]] for every column (0 and a cleared validity bit where
+ *     idx[j] < 0); dst_valid optional.
+ * At most NVT_JOIN_MAX_COLS columns per launch; every entry is stream-ordered and n = 0 is a no-op. */
+#define NVT_JOIN_MAX_KEYS 4
+#define NVT_JOIN_MAX_COLS 16
+#define NVT_JOIN_INT 0
+#define NVT_JOIN_FLOAT 1
+typedef struct nvt_join_key {
+  const void *x;            /* n values                                         */
+  const uint8_t *valid;     /* bitmap or NULL                                   */
+  int32_t dtype;            /* NVT_F32 .. NVT_U8                                */
+  int32_t mode;             /* NVT_JOIN_INT / NVT_JOIN_FLOAT                    */
+} nvt_join_key;
+typedef struct nvt_join_index {
+  const void *slots;        /* capacity 16-byte slots, 16-byte aligned          */
+  uint64_t capacity;        /* a power of two                                   */
+  uint64_t empty;           /* tag of an empty slot                             */
+  const uint64_t *words;    /* [nkeys][n_ext] grouped words (nkeys >= 2)        */
+  const uint8_t *nulls;     /* [n_ext] grouped null bits (nkeys >= 2)           */
+  uint64_t n_ext;
+  uint64_t null_first;      /* one component: the null group's rows             */
+  uint64_t null_count;
+  int32_t nkeys;
+  int32_t reserved;
+} nvt_join_index;
+typedef struct nvt_join_col {
+  const void *src;          /* external (or left) values                        */
+  const uint8_t *src_valid; /* bitmap or NULL                                   */
+  void *dst;                /* one value per output row                         */
+  uint8_t *dst_valid;       /* bitmap of ceil(rows / 64) * 8 bytes, or NULL     */
+  int32_t width;            /* bytes per value: 1, 4 or 8                       */
+  int32_t reserved;
+} nvt_join_col;
+int nvt_join_table_bytes(uint64_t n_groups, uint64_t *capacity, uint64_t *bytes);
+int nvt_join_hash(const nvt_join_key *keys, int nkeys, uint64_t n, uint64_t *out_tag, uint64_t *out_words,
+                  uint8_t *out_nulls, void *stream);
+int nvt_join_insert(void *slots, uint64_t capacity, uint64_t empty, const uint64_t *tags, const uint32_t *first,
+                    const uint32_t *count, uint64_t n_groups, void *stream);
+int nvt_join_probe(const nvt_join_index *ix, const nvt_join_key *keys, int nkeys, uint64_t n, int inner,
+                   int64_t *out_first, uint32_t *out_count, uint8_t *out_keep, uint64_t *out_total, void *stream);
+int nvt_join_probe_gather(const nvt_join_index *ix, const nvt_join_key *keys, int nkeys, uint64_t n,
+                          const nvt_join_col *cols, int ncols, uint64_t *unmatched, void *stream);
+int nvt_join_scan_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_join_offsets(uint32_t *counts, uint64_t n, void *ws, uint64_t ws_bytes, void *stream);
+int nvt_join_expand(const uint32_t *offsets, const int64_t *first, uint64_t n, uint64_t m, int64_t *out_left,
+                    int64_t *out_ext, void *stream);
+int nvt_join_gather(const int64_t *idx, uint64_t m, const nvt_join_col *cols, int ncols, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -264,6 +264,39 @@ SIGNATURES.update({
     "nvt_compact_list_offsets": [_vp, _u64, _vp, _vp, _u64, _vp, _vp],
 })
 
+class JoinKey(C.Structure):
+    """nvt_join_key: one key component read by the join entries."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("dtype", C.c_int32), ("mode", C.c_int32)]
+
+
+class JoinIndex(C.Structure):
+    """nvt_join_index: the hash index of an external table."""
+    _fields_ = [("slots", _vp), ("capacity", _u64), ("empty", _u64), ("words", _vp), ("nulls", _vp),
+                ("n_ext", _u64), ("null_first", _u64), ("null_count", _u64), ("nkeys", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class JoinCol(C.Structure):
+    """nvt_join_col: one column moved by nvt_join_probe_gather / nvt_join_gather."""
+    _fields_ = [("src", _vp), ("src_valid", _vp), ("dst", _vp), ("dst_valid", _vp), ("width", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+JOIN_MAX_KEYS, JOIN_MAX_COLS = 4, 16   # include/nvt_hip.h NVT_JOIN_MAX_*
+JOIN_INT, JOIN_FLOAT = 0, 1
+SIGNATURES.update({
+    "nvt_join_table_bytes": [_u64, C.POINTER(_u64), C.POINTER(_u64)],
+    "nvt_join_hash": [C.POINTER(JoinKey), _i32, _u64, _vp, _vp, _vp, _vp],
+    "nvt_join_insert": [_vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
+    "nvt_join_probe": [C.POINTER(JoinIndex), C.POINTER(JoinKey), _i32, _u64, _i32, _vp, _vp, _vp, _vp, _vp],
+    "nvt_join_probe_gather": [C.POINTER(JoinIndex), C.POINTER(JoinKey), _i32, _u64, C.POINTER(JoinCol), _i32,
+                              _vp, _vp],
+    "nvt_join_scan_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_join_offsets": [_vp, _u64, _vp, _u64, _vp],
+    "nvt_join_expand": [_vp, _vp, _u64, _u64, _vp, _vp, _vp],
+    "nvt_join_gather": [_vp, _u64, C.POINTER(JoinCol), _i32, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

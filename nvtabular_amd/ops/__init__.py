@@ -11,6 +11,7 @@ from .filter import Filter  # noqa: F401
 from .groupby import Groupby  # noqa: F401
 from .hash_bucket import HashBucket  # noqa: F401
 from .hashed_cross import HashedCross  # noqa: F401
+from .join_external import JoinExternal  # noqa: F401
 from .join_groupby import JoinGroupby  # noqa: F401
 from .lambdaop import LambdaOp  # noqa: F401
 from .normalize import Normalize, NormalizeMinMax  # noqa: F401
