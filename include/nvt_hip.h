@@ -1070,6 +1070,73 @@ int nvt_join_expand(const uint32_t *offsets, const int64_t *first, uint64_t n, u
                     int64_t *out_ext, void *stream);
 int nvt_join_gather(const int64_t *idx, uint64_t m, const nvt_join_col *cols, int ncols, void *stream);
 
+/* ---- session features: ops.ListSlice / ops.ValueCount / ops.DifferenceLag ----
+ * A list column is its leaves plus n + 1 int64 row offsets (offsets[0] possibly non-zero: leaf 0
+ * of the values is the leaf offsets[0] names).  Everything here is 64 bits wide: a column may hold
+ * more than 2^32 leaves.
+ * ListSlice: output row i = row[start:end] of input row i as Python slices it (negative indices
+ *   count from the row's end, both clamped to the row; `end` = INT64_MAX is "to the end").
+ *   nvt_list_slice_offsets: the n + 1 new offsets (from 0) into out_offsets; out_offsets[n] is the
+ *     number of output leaves (the caller reads it back to size the outputs).  ws:
+ *     nvt_list_slice_ws_bytes(n) bytes, 8-byte aligned.  n > 0.
+ *   nvt_list_slice_many: ONE launch per NVT_LIST_MAX_COLS descriptors moves the leaves of every
+ *     column that shares `offsets`; the work is spread over the `total` OUTPUT leaves.  Ragged:
+ *     out_offsets from nvt_list_slice_offsets, total = out_offsets[n], pad_width = 0.  Padded:
+ *     out_offsets = NULL, every output row is pad_width leaves (total = n * pad_width, nothing is
+ *     read back): the sliced row, then pad_bits (the low `width` bytes) in leaves that are valid.
+ *     src_valid / dst_valid: the leaf bitmap carried bit-exactly, ceil(total / 64) * 8 bytes
+ *     written in whole 64-bit words (bits past `total` are 0); a padded column may pass dst_valid
+ *     without src_valid.  total = 0 is a no-op.
+ * ValueCount: nvt_list_len_minmax folds min / max of offsets[i + 1] - offsets[i] over the n rows
+ *   of every descriptor into acc[0] / acc[1] (device int64, the caller starts them at INT64_MAX /
+ *   INT64_MIN and may accumulate several partitions); n = 0 adds nothing.
+ * DifferenceLag: nvt_difference_lag_many writes, for every descriptor, out[i] = x[i] - x[j] with
+ *   j = i - shift where 0 <= j < n, every partition column (0 to NVT_LAG_MAX_KEYS) is non-null and
+ *   equal at i and j (floats by value, NaN is null) and x is valid at both; NaN elsewhere.  NVT_I32
+ *   / NVT_I64 / NVT_U8 values are converted to double before the subtraction and the difference is
+ *   rounded to float; NVT_F64 subtracts in double, NVT_F32 in float (what pandas computes).  ONE
+ *   launch per NVT_LIST_MAX_COLS descriptors.
+ * Every entry is stream-ordered and does not synchronise. */
+#define NVT_LIST_MAX_COLS 32
+#define NVT_LAG_MAX_KEYS 4
+typedef struct nvt_list_col {
+  const void *src;          /* input leaves                                     */
+  void *dst;                /* `total` output leaves                            */
+  const uint8_t *src_valid; /* leaf bitmap or NULL                              */
+  uint8_t *dst_valid;       /* ceil(total / 64) * 8 bytes, 8-byte aligned, or NULL */
+  uint64_t pad_bits;        /* the pad value's bits (padded mode)               */
+  int32_t width;            /* bytes per leaf: 1, 4 or 8                        */
+  int32_t reserved;
+} nvt_list_col;
+typedef struct nvt_list_len_col {
+  const int64_t *offsets;   /* n + 1 row offsets                                */
+  uint64_t n;
+  int64_t *acc;             /* device {min, max}                                */
+} nvt_list_len_col;
+typedef struct nvt_lag_key {
+  const void *x;            /* n values of a partition column                   */
+  const uint8_t *valid;     /* bitmap or NULL                                   */
+  int32_t dtype;            /* NVT_F32 .. NVT_U8                                */
+  int32_t reserved;
+} nvt_lag_key;
+typedef struct nvt_lag_col {
+  const void *x;            /* n values                                         */
+  const uint8_t *valid;     /* bitmap or NULL                                   */
+  float *out;               /* n differences                                    */
+  int64_t shift;
+  int32_t dtype;            /* NVT_F32 .. NVT_U8                                */
+  int32_t reserved;
+} nvt_lag_col;
+int nvt_list_slice_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_list_slice_offsets(const int64_t *offsets, uint64_t n, int64_t start, int64_t end, int64_t *out_offsets,
+                           void *ws, uint64_t ws_bytes, void *stream);
+int nvt_list_slice_many(const nvt_list_col *cols, int ncols, const int64_t *offsets, uint64_t n, int64_t start,
+                        int64_t end, const int64_t *out_offsets, uint64_t total, uint64_t pad_width,
+                        void *stream);
+int nvt_list_len_minmax(const nvt_list_len_col *cols, int ncols, void *stream);
+int nvt_difference_lag_many(const nvt_lag_key *keys, int nkeys, const nvt_lag_col *cols, int ncols, uint64_t n,
+                            void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -10,7 +10,8 @@ import nvtabular_amd as _impl
 for _name in ("ops", "workflow", "io", "schema", "selector", "node", "graph_json", "dist"):
     sys.modules[f"{__name__}.{_name}"] = importlib.import_module(f"nvtabular_amd.{_name}")
 for _sub in ("categorify", "normalize", "fill", "join_groupby", "target_encoding", "hash_bucket",
-             "lambdaop", "groupby", "clip_log", "hashed_cross", "bucketize", "filter", "dropna", "join_external"):
+             "lambdaop", "groupby", "clip_log", "hashed_cross", "bucketize", "filter", "dropna", "join_external",
+             "list_slice", "value_counts", "difference_lag"):
     try:
         sys.modules[f"{__name__}.ops.{_sub}"] = importlib.import_module(f"nvtabular_amd.ops.{_sub}")
     except ImportError:  # (an operator module this engine does not carry)

@@ -297,6 +297,37 @@ SIGNATURES.update({
     "nvt_join_gather": [_vp, _u64, C.POINTER(JoinCol), _i32, _vp],
 })
 
+class ListCol(C.Structure):
+    """nvt_list_col: one column moved by nvt_list_slice_many."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("src_valid", _vp), ("dst_valid", _vp), ("pad_bits", _u64),
+                ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ListLenCol(C.Structure):
+    """nvt_list_len_col: one offsets tensor reduced by nvt_list_len_minmax."""
+    _fields_ = [("offsets", _vp), ("n", _u64), ("acc", _vp)]
+
+
+class LagKey(C.Structure):
+    """nvt_lag_key: one partition column of nvt_difference_lag_many."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LagCol(C.Structure):
+    """nvt_lag_col: one (column, shift) output of nvt_difference_lag_many."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("out", _vp), ("shift", _i64), ("dtype", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+LIST_MAX_COLS, LAG_MAX_KEYS = 32, 4   # include/nvt_hip.h NVT_LIST_MAX_COLS / NVT_LAG_MAX_KEYS
+SIGNATURES.update({
+    "nvt_list_slice_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_list_slice_offsets": [_vp, _u64, _i64, _i64, _vp, _vp, _u64, _vp],
+    "nvt_list_slice_many": [C.POINTER(ListCol), _i32, _vp, _u64, _i64, _i64, _vp, _u64, _u64, _vp],
+    "nvt_list_len_minmax": [C.POINTER(ListLenCol), _i32, _vp],
+    "nvt_difference_lag_many": [C.POINTER(LagKey), _i32, C.POINTER(LagCol), _i32, _u64, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

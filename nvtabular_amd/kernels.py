@@ -1219,6 +1219,7 @@ class EncodeTable:
         self._src = None       # key-sorted source list of the one-pass ordering, same lifetime
         self.ready = None      # Event recorded behind the sort / build on an internal stream
         self.pending = False   # True until the current stream has been made to wait for it
+        self._release = False  # True between fill_encode_desc and release_ordering (encode_many)
         # the LDS head of the cache-mode encode, built ONCE per vocabulary by
         # nvt_vocab_finalize_many (include/nvt_hip.h nvt_vocab_col.head_image): only tables whose
         # vocabulary is ordered there (defer_build) get one
@@ -1404,13 +1405,25 @@ class EncodeTable:
         d.range_aux = ptr(self.range_aux)
         d.head_image = ptr(self.head_image)
         if self.pending:
-            d.wait_event = self.ready.handle  # nvt_encode_many waits on the launch stream
+            # nvt_encode_many waits on the launch stream.  The ordering's buffers are let go by
+            # release_ordering(), AFTER that call is enqueued: dropped here, a block as large as a
+            # label column (the n + 1 entry list of the sort path) went straight to the `out` of
+            # the next column, whose encode waits for its OWN vocabulary only and wrote its labels
+            # over the counts this vocabulary's ordering pass was still reading
+            d.wait_event = self.ready.handle
             self.pending = False
+            self._release = True
+        else:
+            d.wait_event = None
+
+    def release_ordering(self):
+        """Behind nvt_encode_many (which joined its streams into the launch stream, each behind
+        the ready events it was given): the scratch of the finished ordering may be recycled."""
+        if self._release:
+            self._release = False
             self.sort_tmp = None
             self._counts = None
             self._src = None
-        else:
-            d.wait_event = None
 
     def encode(
         self,
@@ -1485,8 +1498,12 @@ def encode_many(items, out_dtype: torch.dtype = torch.int64):
         tab.fill_encode_desc(d, keys, valid, null_label, oov_label, nb, out)
         outs[i] = out
         keep.append(keys)
-    if items:
-        check(_lib.load().nvt_encode_many(descs, len(items), stream_ptr()), "nvt_encode_many")
+    try:
+        if items:
+            check(_lib.load().nvt_encode_many(descs, len(items), stream_ptr()), "nvt_encode_many")
+    finally:
+        for it in items:
+            it[0].release_ordering()
     return outs
 
 

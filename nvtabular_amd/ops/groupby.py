@@ -129,6 +129,8 @@ class Groupby(Operator):
         #    pandas' groupby(dropna=True), ordered by key like groupby(sort=True)
         agg = GroupAgg("groupby", self.groupby_cols, [])
         agg.update(frame)
+        if agg.table is None and agg.sorted_comp is not None:
+            agg._demote()   # (a large single-key partition was grouped by the sort path)
         comp = agg.table.compact()
         keep = comp["null_mask"] == 0
         gkeys = [k[keep] for k in comp["keys"]]
