@@ -253,7 +253,10 @@ int nvt_fill_normalize(const void *x, int dtype, const uint8_t *valid, uint64_t 
  * fused with a pending FillMissing constant:
  *   v = isnull(x) ? (has_fill ? fill_val : null) : x;  v = clamp(v, vmin, vmax);
  *   out = do_log ? logf((float)v + 1) : v          (nulls stay null; NaN for float outputs)
- * out_dtype: NVT_F32 / NVT_F64, or the input dtype for integer clipping without log. */
+ * out_dtype: NVT_F32 / NVT_F64, or the input dtype for integer clipping without log.  Integer
+ * clipping clamps in the integer type (a value inside the bounds is returned bit for bit);
+ * fill_val / vmin / vmax must then be integers of that type with |v| <= 2^53, else NVT_EINVAL.
+ * The same holds for fill_val of nvt_fill_normalize with an integer out_dtype. */
 int nvt_clip_log(const void *x, int dtype, const uint8_t *valid, uint64_t n, int has_fill,
                  double fill_val, int has_min, double vmin, int has_max, double vmax, int do_log,
                  void *out, int out_dtype, void *stream);

@@ -42,7 +42,15 @@ template <typename T>
 __device__ __forceinline__ void moments_body(const T *__restrict__ x,
                                              const uint8_t *__restrict__ valid, uint64_t n,
                                              int has_fill, double fill_val,
-                                             double *__restrict__ partials) {
+                                             double *__restrict__ partials, unsigned nblk) {
+  // nblk: the blocks that share this column (the column's own stream_grid); partials has one
+  // slot per LAUNCHED block.  A batched launch is as wide as its longest column: the blocks past
+  // nblk add exact zeros, so the rows each block sums -- and the result -- do not depend on what
+  // else is in the batch.
+  if (blockIdx.x >= nblk) {
+    if (threadIdx.x < 3) partials[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = 0.0;
+    return;
+  }
   constexpr int VEC = VecOf<T>::n;
   double cnt = 0, sum = 0, sq = 0;
   auto acc = [&](T raw, bool ok) {
@@ -56,7 +64,7 @@ __device__ __forceinline__ void moments_body(const T *__restrict__ x,
     sq += v * v;
   };
   const uint64_t nvec = n / VEC;
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  const uint64_t stride = (uint64_t)nblk * kBlock;
   // 4 independent 16-byte loads (+ bitmap bytes) in flight per lane: with one load per
   // iteration the kernel ran at 2.9 TB/s, latency-bound
   constexpr int U = 4;
@@ -107,13 +115,14 @@ __global__ __launch_bounds__(kBlock) void moments_kernel(const T *__restrict__ x
                                                          const uint8_t *__restrict__ valid,
                                                          uint64_t n, int has_fill, double fill_val,
                                                          double *__restrict__ partials) {
-  moments_body<T>(x, valid, n, has_fill, fill_val, partials);
+  moments_body<T>(x, valid, n, has_fill, fill_val, partials, gridDim.x);
 }
 
 // Batched form (nvt_moments_many): blockIdx.y = column; every column of a Normalize.fit
 // partition in ONE launch (the per-column version was 26 launches per partition for Criteo's
-// 13 continuous columns).  Same grid.x and block-to-row mapping as the single-column kernel,
-// so the partial sums -- and therefore the results -- are bit-identical to it.
+// 13 continuous columns).  Each column keeps the grid.x (MomCol::grid) and block-to-row mapping
+// of the single-column kernel, so the partial sums -- and therefore the results -- are
+// bit-identical to it, whatever the lengths and types of the other columns.
 constexpr int kBatchCols = 32;
 struct MomCol {
   const void *x;
@@ -122,6 +131,7 @@ struct MomCol {
   double fill_val;
   double *out3;
   int dtype, has_fill;
+  unsigned grid;
 };
 struct MomBatch {
   MomCol c[kBatchCols];
@@ -130,10 +140,10 @@ __global__ __launch_bounds__(kBlock) void moments_many_kernel(MomBatch b, double
   const MomCol &c = b.c[blockIdx.y];
   double *p = partials + (uint64_t)blockIdx.y * 3 * gridDim.x;
   switch (c.dtype) {
-    case NVT_F32: moments_body<float>((const float *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p); break;
-    case NVT_F64: moments_body<double>((const double *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p); break;
-    case NVT_I32: moments_body<int32_t>((const int32_t *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p); break;
-    default: moments_body<int64_t>((const int64_t *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p); break;
+    case NVT_F32: moments_body<float>((const float *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p, c.grid); break;
+    case NVT_F64: moments_body<double>((const double *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p, c.grid); break;
+    case NVT_I32: moments_body<int32_t>((const int32_t *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p, c.grid); break;
+    default: moments_body<int64_t>((const int64_t *)c.x, c.valid, c.n, c.has_fill, c.fill_val, p, c.grid); break;
   }
 }
 
@@ -458,8 +468,26 @@ __global__ __launch_bounds__(kBlock) void clip_log_kernel(
     OUT *__restrict__ out) {
   constexpr int VEC = VecOf<T>::n;
   const double qnan = std::numeric_limits<double>::quiet_NaN();
+  // integer in -> the same integer type out: the reference assigns only where the comparison
+  // is true (clip.py:49-55), so a value inside the bounds passes through bit for bit.  A round
+  // trip through double would change |x| > 2^53 and overflow at INT64_MAX.  nvt_clip_log has
+  // checked that the bounds and the fill constant are integers T can hold.
+  constexpr bool kIntExact = std::is_integral<T>::value && std::is_same<T, OUT>::value;
+  const int64_t ifill = kIntExact && has_fill ? (int64_t)fill_val : 0;
+  const int64_t ilo = kIntExact && has_min ? (int64_t)vmin : 0;
+  const int64_t ihi = kIntExact && has_max ? (int64_t)vmax : 0;
   auto f = [&](T raw, bool ok) -> OUT {
     bool isnull = !ok || is_nan(raw);
+    if constexpr (kIntExact) {
+      T v = raw;
+      if (isnull) {
+        if (!has_fill) return (OUT)0;
+        v = (T)ifill;
+      }
+      if (has_min && v < (T)ilo) v = (T)ilo;
+      if (has_max && v > (T)ihi) v = (T)ihi;
+      return v;
+    }
     double v = (double)raw;
     if (isnull) {
       if (!has_fill) {
@@ -662,6 +690,13 @@ int fill_norm_launch(const void *x, const uint8_t *valid, uint64_t n, int has_fi
   return NVT_OK;
 }
 
+// A double parameter that an integer kernel converts to its column type T (NVT_I32 / NVT_I64):
+// it must be an integer, T must hold it, and the double must carry it exactly (|b| <= 2^53).
+inline bool int_param_fits(int dtype, double b) {
+  const double lim = dtype == NVT_I32 ? 2147483648.0 : 9007199254740992.0;
+  return b == floor(b) && b >= -lim && b <= (dtype == NVT_I32 ? lim - 1.0 : lim);
+}
+
 }  // namespace nvt
 
 using namespace nvt;
@@ -722,6 +757,7 @@ int nvt_moments_many(const nvt_moments_col *cols, int ncols, void *partials, voi
       m.dtype = c.dtype;
       m.has_fill = c.has_fill;
       const unsigned g = stream_grid(c.n / (16 / dtype_bytes(c.dtype)) + 1, kBlock * 4, 4);
+      m.grid = g;
       grid = g > grid ? g : grid;
       bytes += c.n * dtype_bytes(c.dtype);
     }
@@ -798,6 +834,8 @@ int nvt_fill_normalize_many(const nvt_fillnorm_col *cols, int ncols, void *strea
                     "filled must be 4-byte aligned");
       NVT_CHECK_ARG(odt == NVT_F32 || odt == NVT_F64 || !c.do_norm,
                     "normalised output must be f32/f64");
+      NVT_CHECK_ARG(odt == NVT_F32 || odt == NVT_F64 || !c.has_fill || int_param_fits(odt, c.fill_val),
+                    "integer fill: fill_val must be an integer of the column type with |v| <= 2^53");
       FnCol &f = b.c[live++];
       f.x = c.x;
       f.valid = c.valid;
@@ -872,7 +910,9 @@ int nvt_fill_normalize(const void *x, int dtype, const uint8_t *valid, uint64_t 
       case NVT_I32: NVT_FN(int32_t, float);
       case NVT_I64: NVT_FN(int64_t, float);
     }
-  } else if (!do_norm && out_dtype == dtype) {
+  } else if (!do_norm && out_dtype == dtype && (dtype == NVT_I32 || dtype == NVT_I64)) {
+    NVT_CHECK_ARG(!has_fill || int_param_fits(dtype, fill_val),
+                  "integer fill: fill_val must be an integer of the column type with |v| <= 2^53");
     switch (dtype) {
       case NVT_I32: NVT_FN(int32_t, int32_t);
       case NVT_I64: NVT_FN(int64_t, int64_t);
@@ -917,7 +957,13 @@ int nvt_clip_log(const void *x, int dtype, const uint8_t *valid, uint64_t n, int
       case NVT_I32: NVT_CL(int32_t, double);
       case NVT_I64: NVT_CL(int64_t, double);
     }
-  } else if (!do_log && out_dtype == dtype) {
+  } else if (!do_log && out_dtype == dtype && (dtype == NVT_I32 || dtype == NVT_I64)) {
+    // the integer kernel clamps in T: every parameter it uses must be an integer that T holds
+    // and that a double carries exactly (|b| <= 2^53)
+    NVT_CHECK_ARG((!has_fill || int_param_fits(dtype, fill_val)) &&
+                      (!has_min || int_param_fits(dtype, vmin)) &&
+                      (!has_max || int_param_fits(dtype, vmax)),
+                  "integer clip: fill / bounds must be integers of the column type with |b| <= 2^53");
     switch (dtype) {
       case NVT_I32: NVT_CL(int32_t, int32_t);
       case NVT_I64: NVT_CL(int64_t, int64_t);

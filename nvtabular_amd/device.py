@@ -131,14 +131,10 @@ class DeviceColumn:
         """Apply a pending FillMissing constant (one fused fill pass)."""
         if self.fill is None:
             return self
-        data = self.data
-        if data.dtype == torch.bool:
-            data = data.view(torch.uint8)
+        data = K.numeric(self.data)  # bool / uint8 -> int64
         out_dt = data.dtype
         fv = float(self.fill)
         if out_dt in (torch.int32, torch.int64) and fv != int(fv):
-            out_dt = torch.float64
-        if out_dt == torch.uint8:
             out_dt = torch.float64
         out, _ = K.fill_normalize(data, self.valid, fv, False, 0.0, 1.0, out_dt)
         return DeviceColumn(out, None, self.offsets, None, self.strings)
@@ -169,7 +165,8 @@ class DeviceColumn:
             np_dt = getattr(s.dtype, "numpy_dtype", None)
             if np_dt is None:
                 np_dt = np.dtype(s.dtype.pyarrow_dtype.to_pandas_dtype())
-            vals = s.fillna(0).to_numpy(dtype=np_dt)
+            # (a nullable boolean column takes False, pandas refuses 0 there)
+            vals = s.fillna(False if np.dtype(np_dt).kind == "b" else 0).to_numpy(dtype=np_dt)
             data = torch.from_numpy(np.ascontiguousarray(vals)).to(device)
             valid = torch.from_numpy(pack_bitmap(~mask)).to(device) if mask.any() else None
             return DeviceColumn(data, valid)

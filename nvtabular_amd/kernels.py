@@ -1549,12 +1549,33 @@ def _partials(device) -> torch.Tensor:
     return _scratch[key]
 
 
+def numeric(x: torch.Tensor) -> torch.Tensor:
+    """A bool / uint8 column as int64 (``nvt_widen_i64``): the continuous kernels have no 1-byte
+    instantiations, so such a column is widened first, the way LogOp and Bucketize take it."""
+    return widen_i64(x) if x.dtype in (torch.bool, torch.uint8) else x
+
+
+def _check_int_params(what: str, dtype: torch.dtype, **params):
+    """The integer-in / integer-out kernels take their constants as doubles and convert them to
+    the column type: a constant must be an integer the type holds, and at most 2**53 in
+    magnitude so that the double carries it exactly."""
+    info = torch.iinfo(dtype)
+    lo, hi = max(info.min, -(2**53)), min(info.max, 2**53)
+    for name, b in params.items():
+        if b is None:
+            continue
+        if b != b or b in (float("inf"), float("-inf")) or int(b) != b or not lo <= int(b) <= hi:
+            raise ValueError(
+                f"{what}: {name}={b!r} is not an integer in [{lo}, {hi}] that a {dtype} column "
+                f"can take exactly; use a float64 output for it")
+
+
 def moments_accumulate(
     x: torch.Tensor, valid: Optional[torch.Tensor], out3: torch.Tensor, fill: Optional[float] = None
 ):
     """out3 (float64[3] on device) += {count, sum, sum of squares}."""
     _lib.require_gpu()
-    x = aligned(x.view(torch.uint8) if x.dtype == torch.bool else x)
+    x = aligned(numeric(x))
     with _timed("moments", x.numel() * x.element_size()):
         check(
             _lib.load().nvt_moments(
@@ -1576,7 +1597,7 @@ def moments_many(items):
     descs = (_lib.MomentsCol * len(items))()
     keep = []
     for d, (x, valid, fill, out3) in zip(descs, items):
-        x = aligned(x.view(torch.uint8) if x.dtype == torch.bool else x)
+        x = aligned(numeric(x))
         keep.append(x)
         d.x = x.data_ptr()
         d.valid = ptr(valid)
@@ -1610,6 +1631,8 @@ def fill_normalize_many(items):
         moments = item[8] if len(item) > 8 else None
         x = aligned(x)
         keep.append(x)
+        if not out_dtype.is_floating_point:
+            _check_int_params("fill_normalize_many", out_dtype, fill=fill)
         if moments is not None:
             assert moments.dtype == torch.float64 and moments.is_contiguous() and int(moments.numel()) >= 3
             keep.append(moments)
@@ -1660,6 +1683,8 @@ def fill_normalize(
     _lib.require_gpu()
     x = aligned(x)
     n = x.numel()
+    if not out_dtype.is_floating_point:
+        _check_int_params("fill_normalize", out_dtype, fill=fill)
     out = torch.empty(n, dtype=out_dtype, device=x.device)
     filled = torch.empty(n, dtype=torch.uint8, device=x.device) if want_filled_mask else None
     with _timed("fill_normalize", n * (x.element_size() + out.element_size())):
@@ -1675,10 +1700,19 @@ def fill_normalize(
 
 
 def clip_log(x, valid, fill, vmin, vmax, do_log: bool, out_dtype: torch.dtype) -> torch.Tensor:
-    """Clip / LogOp pass (optionally consuming a pending FillMissing constant)."""
+    """Clip / LogOp pass (optionally consuming a pending FillMissing constant).  Integer in ->
+    the same integer type out clamps in that type: values inside the bounds are untouched."""
     _lib.require_gpu()
     x = aligned(x)
     n = x.numel()
+    if not out_dtype.is_floating_point:
+        # a bound at or beyond the end of the type clips nothing (no value compares past it)
+        info = torch.iinfo(out_dtype)
+        if vmin is not None and vmin <= info.min:
+            vmin = None
+        if vmax is not None and vmax >= info.max:
+            vmax = None
+        _check_int_params("clip_log", out_dtype, fill=fill, min_value=vmin, max_value=vmax)
     out = torch.empty(n, dtype=out_dtype, device=x.device)
     with _timed("clip_log", n * (x.element_size() + out.element_size())):
         check(

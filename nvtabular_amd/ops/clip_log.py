@@ -28,13 +28,11 @@ class Clip(Operator):
         out = frame[col_selector.names].copy()
         for name in col_selector.names:
             col = frame[name]
-            data = col.data.view(torch.uint8) if col.data.dtype == torch.bool else col.data
+            data = K.numeric(col.data)  # bool / uint8 -> int64
             out_dt = data.dtype
             bounds = [b for b in (self.min_value, self.max_value, col.fill) if b is not None]
             if out_dt in (torch.int32, torch.int64) and any(float(b) != int(b) for b in bounds):
                 out_dt = torch.float64  # pandas upcasts an int column clipped to a float bound
-            if out_dt == torch.uint8:
-                out_dt = torch.float64
             res = K.clip_log(data, col.valid, col.fill, self.min_value, self.max_value, False, out_dt)
             keep_valid = None if (col.fill is not None or out_dt.is_floating_point) else col.valid
             out[name] = DeviceColumn(res, keep_valid, col.offsets)
@@ -48,9 +46,7 @@ class LogOp(Operator):
         frame, was_pandas = as_device_frame(df)
         for name in col_selector.names:
             col = frame[name]
-            data = col.data.view(torch.uint8) if col.data.dtype == torch.bool else col.data
-            if data.dtype == torch.uint8:
-                data = K.widen_i64(data)
+            data = K.numeric(col.data)  # bool / uint8 -> int64
             res = K.clip_log(data, col.valid, col.fill, None, None, True, torch.float32)
             frame[name] = DeviceColumn(res, None, col.offsets)
         return frame.to_pandas() if was_pandas else frame

@@ -27,8 +27,8 @@ class FillMissing(Operator):
         for name in col_selector.names:
             col = frame[name]
             if self.add_binary_cols:
-                data = col.data.view(torch.uint8) if col.data.dtype == torch.bool else col.data
-                out_dt = data.dtype if data.dtype != torch.uint8 else torch.float64
+                data = K.numeric(col.data)  # bool / uint8 -> int64
+                out_dt = data.dtype
                 fv = float(self.fill_val)
                 if out_dt in (torch.int32, torch.int64) and fv != int(fv):
                     out_dt = torch.float64

@@ -177,7 +177,7 @@ class Normalize(StatOperator):
             self._resolve()
         for name in col_selector.names:
             col = frame[name]
-            data = col.data.view(torch.uint8) if col.data.dtype == torch.bool else col.data
+            data = K.numeric(col.data)  # bool / uint8 -> int64
             if dev:   # (the fit's moments have not been asked for on the host yet)
                 items.append((data, col.valid, col.fill, True, 0.0, 0.0, out_dt, False, dev[name]))
             else:
@@ -224,7 +224,7 @@ class NormalizeMinMax(StatOperator):
             if state["acc"] is None:
                 state["acc"] = torch.full((len(state["names"]), 2), float("nan"),
                                           dtype=torch.float64, device=col.data.device)
-            K.minmax_accumulate(col.data, col.valid, state["acc"][i], first=False)
+            K.minmax_accumulate(K.numeric(col.data), col.valid, state["acc"][i], first=False)
 
     def fit_end(self, state, col_selector):
         from .. import dist
@@ -250,12 +250,12 @@ class NormalizeMinMax(StatOperator):
             col = frame[name]
             dif = self.maxs[name] - self.mins[name]
             if dif > 0:
-                out, _ = K.fill_normalize(col.data, col.valid, col.fill, True, self.mins[name], dif,
-                                          out_dt)
+                out, _ = K.fill_normalize(K.numeric(col.data), col.valid, col.fill, True,
+                                          self.mins[name], dif, out_dt)
             else:
                 # normalize.py:155-160: max == min -> x / (2x)  (0.5, NaN for x == 0)
                 c = col.materialize()
-                x = c.data.to(torch.float64)
+                x = K.numeric(c.data).to(torch.float64)
                 out = (x / (2 * x)).to(out_dt)
             new[name] = DeviceColumn(out, None, col.offsets)
         return new.to_pandas() if was_pandas else new

@@ -569,7 +569,7 @@ def test_virtual_shard_vocab_merge_matches_single_shot():
                                   (O.nvt_hash32(k0.cpu().numpy()) % G).astype("int32"))
 
 
-@pytest.mark.parametrize("dtype", ["float32", "float64", "int32"])
+@pytest.mark.parametrize("dtype", ["float32", "float64", "int32", "int64"])
 def test_fill_clip_log_vs_oracle(dtype):
     """The reference benchmark's default continuous branch: FillMissing >> Clip(min_value=0) >>
     LogOp (dask-nvtabular-criteo-benchmark.py:201-204; clip.py:49-55, logop.py:43-53)."""
@@ -579,11 +579,16 @@ def test_fill_clip_log_vs_oracle(dtype):
     rng = np.random.default_rng(4)
     n = 50_003
     x = (rng.normal(size=n) * 50).astype(dtype)
-    df = pd.DataFrame({"x": x.astype("float64") if dtype == "int32" else x})
+    if dtype == "int64":
+        # values no float64 holds: nanosecond timestamps, hashed ids, the type's limits
+        x[::7] = rng.integers(2**53, 2**63 - 1, len(x[::7]), dtype=np.int64) | 1
+        x[3::11] = -(rng.integers(2**53, 2**63 - 1, len(x[3::11]), dtype=np.int64) | 1)
+        x[:4] = [2**53 + 1, 1_700_000_000_123_456_789, 2**63 - 1, -(2**63)]
+    df = pd.DataFrame({"x": x.astype("float64") if dtype in ("int32", "int64") else x})
     df.loc[rng.random(n) < 0.2, "x"] = np.nan
     gdf = df.copy()
-    if dtype == "int32":
-        gdf["x"] = pd.array(np.where(df["x"].isna(), 0, df["x"]).astype("int32"), dtype="Int32")
+    if dtype in ("int32", "int64"):
+        gdf["x"] = pd.array(np.where(df["x"].isna(), 0, x), dtype=dtype.capitalize())
         gdf.loc[df["x"].isna(), "x"] = pd.NA
     wf = nvt.Workflow(["x"] >> ops.FillMissing() >> ops.Clip(min_value=0) >> ops.LogOp())
     got = wf.transform(gdf)["x"].to_numpy()
@@ -597,6 +602,21 @@ def test_fill_clip_log_vs_oracle(dtype):
     ec = O.clip_transform(df, ["x"], -10, 25)["x"]
     np.testing.assert_array_equal(np.isnan(c.to_numpy(dtype="float64")), ec.isna().to_numpy())
     np.testing.assert_allclose(c.to_numpy(dtype="float64"), ec.to_numpy(), rtol=0, atol=0, equal_nan=True)
+    if dtype in ("int32", "int64"):
+        # integer in -> integer out is exact in the integer type: a value inside the bounds is not
+        # touched, whatever float64 would make of it
+        # (on the device frame: a pandas result shows an integer column with nulls as float64)
+        from nvtabular_amd.device import as_device_frame
+        from nvtabular_amd.selector import ColumnSelector
+
+        frame, _ = as_device_frame(gdf)
+        for lo, hi in ((-10, 25), (0, None), (None, 2**53)):
+            col = ops.Clip(min_value=lo, max_value=hi).transform(ColumnSelector(["x"]), frame)["x"]
+            assert str(col.data.dtype) == f"torch.{dtype}"
+            ei = O.clip_transform(gdf, ["x"], lo, hi)["x"]
+            ok = col.valid_mask_host()
+            np.testing.assert_array_equal(~ok, ei.isna().to_numpy())
+            np.testing.assert_array_equal(col.data.cpu().numpy()[ok], ei[ok].to_numpy(dtype=dtype))
     with pytest.raises(ValueError):
         ops.Clip()
 
