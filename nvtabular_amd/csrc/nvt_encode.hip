@@ -70,7 +70,10 @@ __global__ __launch_bounds__(kBlock) void enc_build_kernel(const K *__restrict__
     K key = vocab[i];
     int64_t label = first_label + (int64_t)i;
     if (key == EMPTY) {
-      *sentinel_label = label;
+      // the sentinel key lives in a word of its own; a vocabulary may hold it more than once like
+      // any other key, and the first (lowest) label wins here too: the cleared word is -1, the
+      // largest value of an unsigned minimum (labels are never negative)
+      atomicMin(reinterpret_cast<unsigned long long *>(sentinel_label), (unsigned long long)label);
       continue;
     }
     uint64_t slot = (uint64_t)slot_hash(key) & mask;
@@ -1255,6 +1258,9 @@ int build_launch(const K *vocab, uint64_t n, int64_t first_label, void *table, u
   NVT_CHECK_ARG(capacity >= 64 && (capacity & (capacity - 1)) == 0, "capacity must be 2^k >= 64");
   NVT_CHECK_ARG(capacity > n, "capacity must exceed the vocabulary size");
   NVT_CHECK_ARG(sizeof(K) == 8 || first_label + (int64_t)n < INT32_MAX, "labels overflow int32");
+  // (a negative label reads as "not in the vocabulary" in every encode kernel, and would lose
+  // against the cleared sentinel word in enc_build_kernel's unsigned minimum)
+  NVT_CHECK_ARG(first_label >= 0, "first_label must not be negative");
   auto *t = reinterpret_cast<EncSlot<K> *>(table);
   NVT_PROF("encode_build", 0, s);
   enc_clear_kernel<K><<<stream_grid(capacity, kBlock * 4), kBlock, 0, s>>>(t, capacity,

@@ -58,6 +58,62 @@ def test_argument_validation_needs_no_gpu():
     assert lib.nvt_image_build(arr, 0, 0, buf, 64, None) == 0          # nothing to do
 
 
+def test_encode_entry_points_refuse_bad_arguments_before_any_launch():
+    """nvt_encode_* / nvt_encode_build_* / nvt_encode_many: every refusal is NVT_EINVAL, names its
+    argument in nvt_last_error and comes before the first launch (host buffers stand in for device
+    memory: nothing is read through them)."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    raw = (C.c_uint8 * 4096)()
+    base = (C.addressof(raw) + 63) & ~63           # 64-byte aligned inside the buffer
+    keys, out, table, sent, vocab = base, base + 1024, base + 2048, base + 3072, base + 3200
+
+    def refused(rc, *words):
+        assert rc == _lib.NVT_EINVAL, rc
+        msg = lib.nvt_last_error()
+        for w in words:
+            assert w in msg, (w, msg)
+
+    for enc in (lib.nvt_encode_i32, lib.nvt_encode_i64):
+        # (keys, valid, n, table, capacity, sentinel, null, oov, nb, out, out_bytes, vocab, n_vocab, first, stream)
+        refused(enc(keys + 4, None, 8, table, 64, sent, 1, 2, 0, out, 8, None, 0, 3, None), b"keys/out", b"aligned")
+        refused(enc(keys, None, 8, table, 64, sent, 1, 2, 0, out + 8, 8, None, 0, 3, None), b"keys/out", b"aligned")
+        refused(enc(keys, None, 8, table, 96, sent, 1, 2, 0, out, 8, None, 0, 3, None), b"capacity")
+        refused(enc(keys, None, 8, table, 32, sent, 1, 2, 0, out, 8, None, 0, 3, None), b"capacity")
+        refused(enc(keys, None, 8, table, 64, sent, 1, 2, 0, out, 2, None, 0, 3, None), b"out_bytes")
+        refused(enc(keys, None, 8, None, 64, sent, 1, 2, 0, out, 8, None, 0, 3, None), b"null table")
+        refused(enc(None, None, 8, table, 64, sent, 1, 2, 0, out, 8, None, 0, 3, None), b"null keys/out")
+        assert enc(None, None, 0, table, 64, sent, 1, 2, 0, None, 8, None, 0, 3, None) == 0   # no rows: nothing to do
+    for build in (lib.nvt_encode_build_i32, lib.nvt_encode_build_i64):
+        # (vocab, n, first_label, table, capacity, sentinel, unique, stream)
+        refused(build(vocab, 10, 3, table, 96, sent, 0, None), b"capacity", b"2^k")
+        refused(build(vocab, 10, 3, table, 32, sent, 0, None), b"capacity")
+        refused(build(vocab, 64, 3, table, 64, sent, 0, None), b"capacity", b"exceed")     # capacity == n_vocab
+        refused(build(vocab, 100, 3, table, 64, sent, 1, None), b"capacity", b"exceed")    # capacity < n_vocab
+        refused(build(vocab, 10, 3, None, 64, sent, 0, None), b"null table")
+        refused(build(vocab, 10, 3, table, 64, None, 0, None), b"null table")
+    # int32 slots hold int32 labels: first_label + n_vocab must stay below INT32_MAX
+    refused(lib.nvt_encode_build_i32(vocab, 10, 2**31 - 11, table, 64, sent, 0, None), b"labels overflow int32")
+    refused(lib.nvt_encode_build_i32(vocab, 10, 2**40, table, 64, sent, 1, None), b"labels overflow int32")
+    refused(lib.nvt_encode_build_i64(vocab, 10, -1, table, 64, sent, 0, None), b"first_label")
+    # descriptors: key width and label width
+    d = (_lib.EncodeCol * 1)()
+    d[0].keys, d[0].out, d[0].table, d[0].sentinel_label = keys, out, table, sent
+    d[0].n, d[0].capacity, d[0].null_label, d[0].oov_label, d[0].first_label = 8, 64, 1, 2, 3
+    d[0].key_bytes, d[0].out_bytes = 3, 8
+    refused(lib.nvt_encode_many(d, 1, None), b"key_bytes", b"column 0")
+    d[0].key_bytes, d[0].out_bytes = 4, 2
+    refused(lib.nvt_encode_many(d, 1, None), b"out_bytes")
+    d[0].key_bytes, d[0].out_bytes = 8, 8
+    d[0].keys = keys + 8
+    refused(lib.nvt_encode_many(d, 1, None), b"keys/out", b"aligned")
+    refused(lib.nvt_encode_many(None, 1, None), b"null descriptors")
+    assert lib.nvt_encode_many(None, 0, None) == 0
+
+
 def test_ops_fail_loudly_without_gpu():
     import torch
 
