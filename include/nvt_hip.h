@@ -72,7 +72,13 @@ extern "C" {
 #define NVT_OVF_FULL 64ull    /* a bucket holds more than 3/4 * 16384 distinct keys            */
 #define NVT_ST_ROWS 4      /* rows consumed (nulls included)                 */
 /* words 5..7: scratch cursors of nvt_dense_count_*                                  */
-#define NVT_ST_MAXCOUNT 8  /* nvt_dense_count_*: largest count in the output list    */
+#define NVT_ST_MAXCOUNT 8  /* nvt_dense_count_*: largest count in the output list; the sentinel
+                              key's rows are not in the list of the hash paths and not in this
+                              word either.  The ordering passes would do with an upper bound
+                              (nvt_vocab_sort_*), but the value is EXACT on every path: the
+                              tree merge hands it on as the max_count of every merged list, and
+                              a bound that is only "at least" would grow from level to level
+                              and buy the vocabulary sort radix passes it does not need     */
 #define NVT_ST_BIG 9       /* range path: entries whose count is >= 255            */
 #define NVT_ST_NEED 10     /* range path, overflow bit1: entries the output list needs */
 #define NVT_STATE_WORDS 16
@@ -90,7 +96,9 @@ int nvt_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, void *t
 int nvt_count_i64(const int64_t *keys, const uint8_t *valid, uint64_t n, void *table,
                   uint64_t capacity, uint64_t *state, void *stream);
 /* weighted insert of an (key,count) list -- the tree-merge step (_mid_level_groupby)
- * and the owner-side merge after the multi-GPU exchange */
+ * and the owner-side merge after the multi-GPU exchange.  The list has no validity bitmap.
+ * An i32 slot keeps a uint32 count: sums that may pass 2^32 need an i64 table (the driver's
+ * weighted last resort widens int32 keys for that reason). */
 int nvt_count_merge_i32(const int32_t *keys, const int64_t *counts, uint64_t n, void *table,
                         uint64_t capacity, uint64_t *state, void *stream);
 int nvt_count_merge_i64(const int64_t *keys, const int64_t *counts, uint64_t n, void *table,

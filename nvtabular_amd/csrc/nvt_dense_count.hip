@@ -2286,6 +2286,7 @@ int dense_count(const K *keys, const uint8_t *valid, const int64_t *weights, uin
       NVT_CHECK_ARG((reinterpret_cast<uintptr_t>(keys) & 15) == 0, "keys must be 16-byte aligned");
       NVT_CHECK_ARG(n == 0 || (keys && out_keys && out_cnt), "null keys/out");
       NVT_CHECK_ARG(n < (1ull << 32), "at most 2^32-1 rows per call (32-bit LDS counters)");
+      NVT_CHECK_ARG(((path >> 8) & 0xFF) >= 6 && ((path >> 8) & 0xFF) <= 10, "range path: 64 .. 1024 buckets");
       if (clear_state) NVT_CHECK_HIP(hipMemsetAsync(state, 0, NVT_STATE_WORDS * 8, s));
       if (n == 0) return NVT_OK;
       return range_count_i32((const int32_t *)keys, valid, n, (path >> 8) & 0xFF, wsp, hot_image_ext,
@@ -2544,6 +2545,10 @@ int nvt_dense_count_many(const nvt_count_col *cols, int ncols, void *stream) {
       if (!((c.path & NVT_PATH_HOT) || range) || c.key_bytes != 4 || c.weights || c.n == 0 ||
           !c.hot_image)
         continue;
+      // (a column dense_count() is going to refuse is not sampled either: nothing is launched
+      // for a call that fails on its arguments)
+      if (!c.keys || (reinterpret_cast<uintptr_t>(c.keys) & 15) || !c.state || !c.ws) continue;
+      if (range && (((c.path >> 8) & 0xFF) < 6 || ((c.path >> 8) & 0xFF) > 10)) continue;
       hb.c[nh++] = {(const int32_t *)c.keys, c.valid, c.n, c.hot_image, range ? (c.path >> 8) & 0xFF : 0,
                     (range && (c.path & NVT_PATH_PIECES)) ? 1 : 0};
       if (nh == kHotBatch) {

@@ -682,10 +682,22 @@ class DenseCountJob:
         if self.weights is None:
             tab, st = count_into_new_table([self.keys], [self.valid], max(self.hint, 1 << 20))
         else:
-            tab = CountTable(self.keys.dtype, 2 * self.n)
-            tab.merge(self.keys, self.weights)
+            keys, weights, null_weight = self.keys, self.weights, 0
+            if self.valid is not None:
+                # nvt_count_merge_* takes a (key, count) list, no bitmap: the null rows leave here
+                # (torch plumbing for a rare path, as unpack_bitmap) and their weights are the nulls
+                ok = unpack_bitmap(self.valid, self.n)
+                null_weight = int(weights[~ok].sum().item())
+                keys, weights = keys[ok].contiguous(), weights[ok].contiguous()
+            # int32 tables keep uint32 counts (include/nvt_hip.h): weighted sums may pass 2^32, so
+            # int32 keys go through an int64 table, where the smallest int32 is a key like any other
+            tab = CountTable(torch.int64, 2 * max(int(keys.numel()), 1))   # (rows left after the nulls)
+            if keys.numel():
+                tab.merge(keys.to(torch.int64), weights)
             st = tab.read_state()
+            st[_lib.ST_NULLS] += null_weight
         k, c = tab.compact()
+        k = k.to(self.keys.dtype)   # (the int64 table of int32 keys: every key came from an int32, exact)
         mx = int(c.max().item()) if c.numel() else 0
         self.result = (k, c, st[_lib.ST_NULLS],
                        dict(path=-1, distinct=int(k.numel()), max_count=mx, rows=self.n))

@@ -114,6 +114,96 @@ def test_encode_entry_points_refuse_bad_arguments_before_any_launch():
     assert lib.nvt_encode_many(None, 0, None) == 0
 
 
+def test_count_entry_points_refuse_bad_arguments_before_any_launch():
+    """nvt_dense_count_i32 / _i64 / nvt_dense_count_many / nvt_dense_count_ws_bytes: every refusal is
+    NVT_EINVAL, names its argument in nvt_last_error and comes before the first launch (host buffers
+    stand in for device memory: nothing is read through them)."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    raw = (C.c_uint8 * 8192)()
+    base = (C.addressof(raw) + 63) & ~63
+    keys, outk, outc, state, ws, aux, wts = (base + 512 * i for i in range(7))
+    RANGE, SORT, HOT, PIECES = 9, 10, 16, 0x10000
+
+    def refused(rc, *words):
+        assert rc == _lib.NVT_EINVAL, (rc, lib.nvt_last_error())
+        msg = lib.nvt_last_error()
+        for w in words:
+            assert w in msg, (w, msg)
+
+    def many(**kw):
+        d = (_lib.CountCol * 1)()
+        c = dict(keys=keys, valid=None, weights=None, n=8, key_bytes=4, path=0, ws=ws, out_keys=outk,
+                 out_counts=outc, out_capacity=9, state=state, hot_image=None, range_table=None)
+        c.update(kw)
+        for name, v in c.items():
+            setattr(d[0], name, v)
+        return lib.nvt_dense_count_many(d, 1, None)
+
+    # (keys, valid, weights, n, path, ws, out_keys, out_counts, out_capacity, state, stream)
+    for fn in (lib.nvt_dense_count_i32, lib.nvt_dense_count_i64):
+        for path in (0, 6, 7, 1, 2, 3):
+            refused(fn(keys + 8, None, None, 8, path, ws, outk, outc, 9, state, None), b"keys", b"aligned")
+        refused(fn(keys, None, None, 8, 0, ws, outk, outc, 9, None, None), b"null state/workspace")
+        refused(fn(keys, None, None, 8, 0, None, outk, outc, 9, state, None), b"null state/workspace")
+        refused(fn(None, None, None, 8, 1, ws, outk, outc, 9, state, None), b"null keys/out")
+        for path in (4, 5, 8, 11, -1, 255):
+            refused(fn(keys, None, None, 8, path, ws, outk, outc, 9, state, None), b"path must be")
+        for path in (0 | HOT, 6 | HOT, 7 | HOT):               # the filter on a path that does not take it
+            refused(fn(keys, None, None, 8, path, ws, outk, outc, 9, state, None), b"hot filter")
+        refused(fn(keys, None, wts, 8, 1 | HOT, ws, outk, outc, 9, state, None), b"hot filter", b"without weights")
+    # paths 9 and 10 without the column's aux block (the single-column entry points have none)
+    refused(lib.nvt_dense_count_i32(keys, None, None, 8, RANGE | (8 << 8), ws, outk, outc, 9, state, None), b"aux block")
+    refused(lib.nvt_dense_count_i32(keys, None, None, 8, SORT, ws, outk, outc, 9, state, None), b"histogram block")
+    refused(lib.nvt_dense_count_i64(keys, None, None, 8, 2 | HOT, ws, outk, outc, 9, state, None), b"hot filter", b"int32")
+    refused(lib.nvt_dense_count_i64(keys, None, None, 8, RANGE | (8 << 8), ws, outk, outc, 9, state, None),
+            b"range path", b"int32")
+    refused(lib.nvt_dense_count_i64(keys, None, None, 8, SORT, ws, outk, outc, 9, state, None), b"sort path", b"int32")
+    # the descriptors of nvt_dense_count_many
+    refused(many(key_bytes=3), b"key_bytes", b"column 0")
+    refused(many(key_bytes=8, path=RANGE | (8 << 8), hot_image=aux), b"range path", b"int32")
+    refused(many(key_bytes=8, path=SORT, hot_image=aux), b"sort path", b"int32")
+    refused(many(weights=wts, path=RANGE | (8 << 8), hot_image=aux), b"range path", b"without weights")
+    refused(many(weights=wts, path=SORT, hot_image=aux), b"sort path", b"without weights")
+    refused(many(path=RANGE | (8 << 8)), b"aux block")
+    refused(many(path=RANGE | (8 << 8) | PIECES), b"aux block")
+    refused(many(path=SORT), b"histogram block")
+    for bits in (0, 5, 11, 255):
+        refused(many(path=RANGE | (bits << 8), hot_image=aux), b"64 .. 1024 buckets")
+    for path in (RANGE | (8 << 8), SORT, 1 | HOT, 0):
+        refused(many(path=path, hot_image=aux, keys=keys + 4), b"keys", b"aligned")
+        refused(many(path=path, hot_image=aux, state=None), b"null state/workspace")
+        refused(many(path=path, hot_image=aux, ws=None), b"null state/workspace")
+    refused(many(path=7 | HOT), b"hot filter")
+    refused(many(path=12), b"path must be")
+    refused(lib.nvt_dense_count_many(None, 1, None), b"null descriptors")
+    assert lib.nvt_dense_count_many(None, 0, None) == 0
+    # more distinct workspaces than internal streams (kSideStreams = 3)
+    d = (_lib.CountCol * 4)()
+    for i in range(4):
+        d[i].keys, d[i].n, d[i].key_bytes, d[i].path, d[i].ws = keys, 8, 4, 0, ws + 16 * i
+        d[i].out_keys, d[i].out_counts, d[i].out_capacity, d[i].state = outk, outc, 9, None
+    refused(lib.nvt_dense_count_many(d, 4, None), b"at most 3 distinct workspaces")
+    # the workspace size follows the same rules
+    nbytes = C.c_uint64()
+    refused(lib.nvt_dense_count_ws_bytes(3, 1000, 0, 0, C.byref(nbytes)), b"key_bytes must be 4 or 8")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, 8, 0, C.byref(nbytes)), b"path must be")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, 0 | HOT, 0, C.byref(nbytes)), b"hot filter")
+    refused(lib.nvt_dense_count_ws_bytes(8, 1000, 1 | HOT, 0, C.byref(nbytes)), b"hot filter")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, 1 | HOT, 1, C.byref(nbytes)), b"hot filter")
+    refused(lib.nvt_dense_count_ws_bytes(8, 1000, RANGE | (8 << 8), 0, C.byref(nbytes)), b"range path")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, RANGE | (8 << 8), 1, C.byref(nbytes)), b"range path")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, RANGE | (5 << 8), 0, C.byref(nbytes)), b"64 .. 1024 buckets")
+    refused(lib.nvt_dense_count_ws_bytes(4, 1000, RANGE | (11 << 8), 0, C.byref(nbytes)), b"64 .. 1024 buckets")
+    refused(lib.nvt_dense_count_ws_bytes(8, 1000, SORT, 0, C.byref(nbytes)), b"sort path")
+    refused(lib.nvt_range_table_bytes(11, C.byref(nbytes)), b"64 .. 1024 buckets")
+    for path in (0, 6, 7, 1, 2, 3, 1 | HOT, RANGE | (6 << 8), RANGE | (10 << 8) | PIECES, SORT):
+        assert lib.nvt_dense_count_ws_bytes(4, 1000, path, 0, C.byref(nbytes)) == 0 and nbytes.value > 0
+
+
 def test_ops_fail_loudly_without_gpu():
     import torch
 
