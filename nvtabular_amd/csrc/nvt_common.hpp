@@ -36,20 +36,6 @@ void set_error(const char *fmt, ...);
 
 #define NVT_CHECK_LAUNCH() NVT_CHECK_HIP(hipGetLastError())
 
-// Run-time A / B switches between kernel variants (NVT_ENC_PIPE, NVT_SORT_LEGACY ...) exist only in
-// variant libraries built with -DNVT_AB_SWITCHES (tools/build_variant.sh, tools/var_libs.sh): the
-// default library takes the default side of every one of them at compile time.  (Configuration that
-// a deployment may set -- NVT_ENCODE_STREAMS, NVT_FINALIZE_SERIAL, NVT_ROCTX, NVT_EVENT_TIMING,
-// NVT_ENC_STATS -- stays on getenv.)
-inline const char *ab_env(const char *name) {
-#ifdef NVT_AB_SWITCHES
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 // Grid for a streaming (HBM-bound) kernel: enough workgroups to fill 256 CUs
 // several times over, capped so every block still gets a long grid-stride run.
 inline unsigned stream_grid(uint64_t work_items, unsigned per_block, unsigned blocks_per_cu = 8) {
@@ -97,11 +83,7 @@ __device__ __forceinline__ uint32_t mul24_hash(int32_t key) {
 }
 // bucket of the hot-key image (sample kernel and every kernel that looks keys up in it)
 __device__ __forceinline__ uint32_t hot_image_bucket(int32_t key, uint32_t mask) {
-#ifndef NVT_HOT_FMIX
   return (mul24_hash(key) >> 20) & mask;  // (mask <= 4095)
-#else
-  return (slot_hash(key) >> 13) & mask;
-#endif
 }
 
 // ---- validity bitmaps --------------------------------------------------------

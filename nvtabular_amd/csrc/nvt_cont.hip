@@ -26,12 +26,8 @@ __device__ __forceinline__ void load_vec(const T *p, T (&v)[VecOf<T>::n]) {
   // (non-temporal: a column is streamed once per kernel; moments 0.40 -> 0.377 ms, fill +
   // normalize 1.49 -> 1.44 ms for the 13 Criteo columns.  Non-temporal STORES of the float64
   // output made fill + normalize slower: 1.47 -> 1.74 ms)
-#ifdef NVT_CONT_PLAIN_LOAD
-  int4 raw = *reinterpret_cast<const int4 *>(p);
-#else
   typedef int v4i_ntl __attribute__((ext_vector_type(4)));
   v4i_ntl raw = __builtin_nontemporal_load(reinterpret_cast<const v4i_ntl *>(p));
-#endif
   memcpy(v, &raw, 16);
 }
 

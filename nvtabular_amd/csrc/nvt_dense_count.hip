@@ -264,19 +264,11 @@ constexpr unsigned kRepFill = 256;  // replicate hot keys per lane group while f
 
 // hash of stage 1: home slot from bits >= kStageHomeShift, key class from the (up to 3) bits
 // at kStageClassShift
-#ifndef NVT_STAGE_FMIX
 __device__ __forceinline__ uint32_t stage_hash(int32_t key) { return mul24_hash(key); }
 template <typename K>
 struct StageBits {
   static constexpr int home = sizeof(K) == 4 ? 18 : 17, cls = sizeof(K) == 4 ? 15 : 0;
 };
-#else
-__device__ __forceinline__ uint32_t stage_hash(int32_t key) { return slot_hash(key); }
-template <typename K>
-struct StageBits {
-  static constexpr int home = 17, cls = 0;
-};
-#endif
 __device__ __forceinline__ uint64_t stage_hash(int64_t key) { return slot_hash(key); }
 template <typename K, int SLOTS>
 __device__ __forceinline__ uint32_t home_slot(K key) {
@@ -299,14 +291,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
   __shared__ unsigned rcnt[kRanges], wtot[kRanges / kWave];
   __shared__ unsigned lfill, lovf, s_next;
   __shared__ unsigned long long s_nulls, s_sent;
-#ifdef NVT_STAGE_TIMING
-  long long tm[8];
-  int tmi = 0;
-#define NVT_STM() do { if (threadIdx.x == 0) tm[tmi++] = clock64(); } while (0)
-#else
-#define NVT_STM() do {} while (0)
-#endif
-  NVT_STM();
   for (int i = threadIdx.x; i < SLOTS; i += kStageBS) {
     lkeys[i] = EMPTY;
     lcnt[i] = 0;
@@ -320,7 +304,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
     s_sent = 0;
   }
   __syncthreads();
-  NVT_STM();
   const unsigned split = 1u << split_bits, split_mask = split - 1;
   const unsigned q = (blockIdx.x >> 3) & split_mask;
   const unsigned slab = ((blockIdx.x >> (3 + split_bits)) << 3) | (blockIdx.x & 7);
@@ -459,15 +442,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
         atomicAdd(&lcnt[hit ? hq[qi] : (uint32_t)SLOTS + lane_id()], (C)1);
         missbits |= ((lv & !hit) ? 1u : 0u) << qi;
       }
-#ifdef NVT_STAGE_SPARSE_MISS
-      if (missbits) {
-#pragma unroll
-        for (int qi = 0; qi < NKB; ++qi)
-          if (((missbits >> qi) & 1) &&
-              !lds_add<K, C, SLOTS>(lkeys, lcnt, &lfill, kq[qi], (C)1, hq[qi]))
-            failed = true;
-      }
-#else
       // The probe chain of a miss is a loop of dependent LDS round trips, and with a few percent
       // of misses SOME lane misses at every one of the NKB key positions: walked position by
       // position the wave paid NKB chains per batch with a handful of lanes active in each.
@@ -487,7 +461,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
           if (!lds_add<K, C, SLOTS>(lkeys, lcnt, &lfill, mk, (C)1, mh)) failed = true;
         }
       }
-#endif
     }
     for (uint64_t i = nvec * VEC + first; i < n; i += stride) {
       if (bit_valid(valid, i))
@@ -523,12 +496,10 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
       }
     }
   }
-  NVT_STM();
   if (failed) atomicOr(&lovf, 1u);
   if (q == 0 && my_nulls) atomicAdd(&s_nulls, my_nulls);
   if (my_sent) atomicAdd(&s_sent, my_sent);
   __syncthreads();
-  NVT_STM();
   if (lovf || lfill > (unsigned)max_fill(SLOTS)) {
     if (threadIdx.x == 0) atomicOr((unsigned long long *)&state[DS_OVF], 1ull);
     // stage 2 must not read stale offsets from this list
@@ -540,10 +511,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
     if (s_sent) atomicAdd((unsigned long long *)&state[DS_SENT], s_sent);
     if (blockIdx.x == 0) atomicAdd((unsigned long long *)&state[DS_ROWS], (unsigned long long)n);
   }
-#ifdef NVT_EXP_NOFLUSH
-  for (int r = threadIdx.x; r <= kRanges; r += kStageBS) seg_off[(uint64_t)r * nlists + blockIdx.x] = 0;
-  return;
-#endif
   // ---- flush grouped by home range: LDS histogram -> scan -> ranked scatter ----
   constexpr int RSHIFT = (SLOTS == 16384 ? 14 : SLOTS == 8192 ? 13 : 12) - 8;
   for (int i = threadIdx.x; i < SLOTS; i += kStageBS) {
@@ -583,13 +550,6 @@ __global__ __launch_bounds__(kStageBS) void lds_stage_kernel(
       oc[pos] = (int64_t)lcnt[i];
     }
   }
-#ifdef NVT_STAGE_TIMING
-  __syncthreads();
-  NVT_STM();
-  if (threadIdx.x == 0)
-    for (int t = 1; t < tmi; ++t)
-      atomicAdd((unsigned long long *)&state[9 + t], (unsigned long long)(tm[t] - tm[t - 1]));
-#endif
 }
 
 // Path S, stage 2: workgroup (q, r) merges segment r of the kSlabs partial lists of class q.
@@ -916,11 +876,6 @@ struct HotSampleCol {
   int nb_log2;  // > 0: also derive the key ranges of the range path (image[NVT_RANGE_AUX_*])
   int pieces;   // range path: also decide on the piecewise map (NVT_PATH_PIECES: after an overflow)
 };
-#ifdef NVT_NO_PIECEWISE
-constexpr bool kPiecewise = false;
-#else
-constexpr bool kPiecewise = true;
-#endif
 constexpr int kHotBatch = 32;
 struct HotSampleBatch {
   HotSampleCol c[kHotBatch];
@@ -1159,7 +1114,7 @@ __global__ __launch_bounds__(1024) void hot_sample_kernel(const HotSampleBatch b
     s_map[2] = mul;
     s_map[3] = (uint64_t)sh;
   }
-  if (nb_log2 >= 6 && kPiecewise && batch.c[blockIdx.x].pieces) {
+  if (nb_log2 >= 6 && batch.c[blockIdx.x].pieces) {
     // ---- piecewise map: the caller put kRpPieces + 1 splitters (order-preserving u32 images,
     // strictly increasing) into the aux block -- taken from an EXACT key-ordered (key, count)
     // list of an earlier pass over this column (kernels.range_splitters: rows and distinct keys

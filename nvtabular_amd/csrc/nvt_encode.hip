@@ -207,28 +207,18 @@ typedef int nvt_v4i __attribute__((ext_vector_type(4)));
 template <typename V>
 __device__ __forceinline__ V nt_load16(const V *p) {
   static_assert(sizeof(V) == 16, "16-byte vectors only");
-#ifdef NVT_NO_NT
-  return *p;
-#else
   nvt_v4i r = __builtin_nontemporal_load(reinterpret_cast<const nvt_v4i *>(p));
   V v;
   memcpy(&v, &r, 16);
   return v;
-#endif
 }
 template <typename V>
 __device__ __forceinline__ void nt_store16(V v, V *p) {
   static_assert(sizeof(V) == 16, "16-byte vectors only");
-#ifdef NVT_NO_NT
-  *p = v;
-#else
   nvt_v4i r;
   memcpy(&r, &v, 16);
   __builtin_nontemporal_store(r, reinterpret_cast<nvt_v4i *>(p));
-#endif
 }
-#define NVT_NT_LOAD(p) nt_load16(p)
-#define NVT_NT_STORE(v, p) nt_store16((v), (p))
 #ifndef NVT_HOT_DIV
 #define NVT_HOT_DIV 4
 #endif
@@ -246,36 +236,16 @@ struct HotCfg<int64_t> {
 
 // TWO (int32 keys, cache mode only): the staged head of the vocabulary lives in a 2-choice,
 // 2-slots-per-bucket table instead of a linear-probing one.  A lookup is exactly two
-// independent 16-byte LDS reads whatever the load (a MISS in the linear table walks ~2.5 slots
+// independent LDS bucket reads whatever the load (a MISS in the linear table walks ~2.5 slots
 // at 25 % load and ~8.5 at 75 %, which is why that table is only filled to a quarter), so the
-// table can be filled to 7/8: 14336 hot keys instead of 4096, 15-20 % fewer rows go on to the
-// table in HBM.  A key that finds both buckets full is simply not cached (the global table
-// holds every key).
-template <int NB, typename K>
-__device__ __forceinline__ void two_buckets(K key, uint32_t &b1, uint32_t &b2) {
-#ifndef NVT_ENC_NO_MUL24
-  if constexpr (sizeof(K) == 4) {
-    // both bucket indices from 24-bit multiplies of the same two words (nvt_common.hpp:
-    // mul24_hash; fmix32 + a third 32-bit multiply were ~28 issue slots per key, this is ~10)
-    static_assert(NB <= 8192, "13 index bits");
-    const uint32_t k = (uint32_t)key, lo = k ^ (k >> 7), hi = k >> 8;
-    b1 = ((__umul24(hi, 0x5BD1E9u) + __umul24(lo, 0x9E3779u)) >> 19) & (NB - 1);
-    b2 = ((__umul24(hi, 0x7FEB35u) + __umul24(lo, 0x846CA7u)) >> 19) & (NB - 1);
-    b2 = b2 == b1 ? b1 ^ 1u : b2;
-    return;
-  }
-#endif
-  const uint32_t h = (uint32_t)slot_hash(key);
-  b1 = (h >> 13) & (NB - 1);
-  b2 = (((h ^ (h >> 15)) * 0x2C1B3C6Du) >> 17) & (NB - 1);
-  b2 = b2 == b1 ? b1 ^ 1u : b2;
-}
-// HEAD16 (int32 keys, cache mode): the head's labels are frequency ranks -- first_label + the
+// table can be filled to 7/8.  A key that finds both buckets full is simply not cached (the
+// global table holds every key).  The head's labels are frequency ranks -- first_label + the
 // position of the key among the n_hot most frequent ones -- so a slot needs the key and a 16-bit
-// rank, 6 bytes instead of 8: {key0, key1} int2 per bucket + one word of two 16-bit ranks, and
-// 12288 buckets (144 KiB of the CU's 160) instead of 8192 (128 KiB): 21504 hot keys at 7/8 load
-// instead of 14336.  Fewer rows miss the head, and a miss is what the cache mode pays for (one
-// random 64-byte sector each).  Bucket index: 15 hash bits h, (3 h) >> 3.
+// rank, 6 bytes: {key0, key1} int2 per bucket + one word of two 16-bit ranks, 12288 buckets
+// (144 KiB of the CU's 160): 21504 hot keys at 7/8 load against 4096 in the linear table.  Fewer
+// rows miss the head, and a miss is what the cache mode pays for (one random 64-byte sector each;
+// VERDICT r04 item 4).  Bucket index: 15 hash bits h, (3 h) >> 3; both indices from 24-bit
+// multiplies of the same two words (nvt_common.hpp: mul24_hash).
 constexpr int kHead16Buckets = 12288;
 constexpr int kHead16Keys = kHead16Buckets * 2 / 8 * 7;   // 21504 < 65536
 __device__ __forceinline__ void two_buckets16(int32_t key, uint32_t &b1, uint32_t &b2) {
@@ -293,13 +263,12 @@ __device__ unsigned long long g_enc_stats[2];
 // first slot of the linear-probing LDS table
 template <int SLOTS, typename K>
 __device__ __forceinline__ uint32_t lds_home(K key) {
-#ifndef NVT_ENC_NO_MUL24
   if constexpr (sizeof(K) == 4) {
     static_assert(SLOTS <= 16384, "14 index bits");
     return (mul24_hash((int32_t)key) >> 18) & (SLOTS - 1);
+  } else {
+    return (uint32_t)(slot_hash(key) >> 13) & (SLOTS - 1);
   }
-#endif
-  return (uint32_t)(slot_hash(key) >> 13) & (SLOTS - 1);
 }
 
 struct HeadJob {
@@ -319,18 +288,19 @@ struct HeadJobs {
 // per step measured by returning right behind it); nvt_vocab_finalize_many now builds it ONCE per
 // vocabulary into a global image (enc_head_build_kernel, on the stream that orders the vocabulary:
 // off the critical path) and the launch's workgroups copy the image with coalesced loads.
-template <typename K, bool TWO, bool HEAD16, int SLOTS>
+template <typename K, bool TWO>
 __device__ __forceinline__ void build_head(unsigned char *lraw, long long *s_sent_p,
                                            const K *__restrict__ hot_keys, uint32_t n_hot,
                                            int64_t first_label) {
   constexpr K EMPTY = EncTraits<K>::empty;
+  constexpr int SLOTS = HotCfg<K>::slots;
   using L = decltype(EncSlot<K>::label);
   using C = typename EncTraits<K>::cas_t;
   EncSlot<K> *lt = reinterpret_cast<EncSlot<K> *>(lraw);
   int2 *tkeys = reinterpret_cast<int2 *>(lraw);
-  uint32_t *tlab = reinterpret_cast<uint32_t *>(lraw + (HEAD16 ? kHead16Buckets * 8 : 0));
+  uint32_t *tlab = reinterpret_cast<uint32_t *>(lraw + kHead16Buckets * 8);
   long long &s_sent = *s_sent_p;
-  if constexpr (HEAD16) {
+  if constexpr (TWO) {
     for (int i = threadIdx.x; i < kHead16Buckets; i += kEncBS) {
       tkeys[i] = make_int2((int)EMPTY, (int)EMPTY);
       tlab[i] = 0u;
@@ -349,7 +319,7 @@ __device__ __forceinline__ void build_head(unsigned char *lraw, long long *s_sen
       s_sent = first_label + (long long)i;
       continue;
     }
-    if constexpr (HEAD16) {
+    if constexpr (TWO) {
       uint32_t b1, b2;
       two_buckets16((int32_t)key, b1, b2);
       const uint32_t cand[4] = {2 * b1, 2 * b1 + 1, 2 * b2, 2 * b2 + 1};   // key words of the int2 array
@@ -360,20 +330,6 @@ __device__ __forceinline__ void build_head(unsigned char *lraw, long long *s_sen
         const int prev = atomicCAS(&kw[cand[c]], (int)EMPTY, (int)key);
         if (prev == (int)EMPTY) {
           lw[cand[c]] = (unsigned short)i;   // rank: i < n_hot <= kHead16Keys < 2^16
-          break;
-        }
-      }
-      continue;  // all four slots taken: not cached
-    }
-    if constexpr (TWO) {
-      uint32_t b1, b2;
-      two_buckets<SLOTS / 2>(key, b1, b2);
-      const uint32_t cand[4] = {2 * b1, 2 * b1 + 1, 2 * b2, 2 * b2 + 1};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        K prev = (K)atomicCAS(reinterpret_cast<C *>(&lt[cand[c]].key), (C)EMPTY, (C)key);
-        if (prev == EMPTY) {
-          lt[cand[c]].label = (L)(first_label + (int64_t)i);
           break;
         }
       }
@@ -392,14 +348,16 @@ __device__ __forceinline__ void build_head(unsigned char *lraw, long long *s_sen
   __syncthreads();
 }
 
-template <bool HEAD16>
+// bytes of the LDS head: 2-choice buckets of 6-byte slots, or the linear table of {key, label} slots
+template <typename K, bool TWO>
+constexpr int kHeadLdsBytes = TWO ? kHead16Buckets * 12 : HotCfg<K>::slots * (int)sizeof(EncSlot<K>);
+
 __global__ __launch_bounds__(kEncBS) void enc_head_build_many_kernel(HeadJobs jobs) {
-  constexpr int SLOTS = HotCfg<int32_t>::slots;
-  constexpr int kLdsBytes = HEAD16 ? kHead16Buckets * 12 : SLOTS * (int)sizeof(EncSlot<int32_t>);
+  constexpr int kLdsBytes = kHeadLdsBytes<int32_t, true>;
   __shared__ __align__(16) unsigned char lraw[kLdsBytes];
   __shared__ long long s_sent;
   const HeadJob j = jobs.j[blockIdx.x];
-  build_head<int32_t, true, HEAD16, SLOTS>(lraw, &s_sent, j.keys, j.n_hot, j.first_label);
+  build_head<int32_t, true>(lraw, &s_sent, j.keys, j.n_hot, j.first_label);
   const int4 *src = reinterpret_cast<const int4 *>(lraw);
   int4 *dst = reinterpret_cast<int4 *>(j.image);
   for (int i = threadIdx.x; i < kLdsBytes / 16; i += kEncBS) dst[i] = src[i];
@@ -509,45 +467,27 @@ __global__ __launch_bounds__(kBlock) void encode_small_kernel(
 }
 
 // GLOBAL = false: the whole vocabulary is staged (no table in HBM): the probe phases and their
-// registers disappear.  (UU = 3 / 4 key vectors per lane in flight, and a 2048-slot table with
-// two workgroups per CU for vocabularies <= 1024 keys, were each ~2 % slower: profiles/r02_notes.md)
-// RANGE (int32 keys): `table` is a range table (the per-bucket tables of the counting pass,
-// dumped; nvt_range.hpp): first slot from the monotone map, probing runs forward without
-// wrapping (an empty slot ends every chain).
-template <typename K, typename OUT, bool TWO = false, bool GLOBAL = true, int UU = 2,
-          int RANGE = 0,  // 0: hashed table, 1: bucket regions dumped by the counting pass, 2: flat
-          bool HEAD16 = false,
-          bool HALF = false>  // half the head (64 KiB), <= 64 VGPRs: TWO workgroups per CU
-__global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
+// registers disappear.  (3 / 4 key vectors per lane in flight instead of U = 2, and a 2048-slot
+// table with two workgroups per CU for vocabularies <= 1024 keys, were each ~2 % slower:
+// profiles/r02_notes.md)
+// TWO: cache mode of int32 keys with a hashed table in HBM (range tables go to encode_pipe_kernel).
+template <typename K, typename OUT, bool TWO = false, bool GLOBAL = true>
+__global__ __launch_bounds__(kEncBS, 1) void encode_hot_kernel(
     const K *__restrict__ keys, const uint8_t *__restrict__ valid, uint64_t n,
     const EncSlot<K> *__restrict__ table, uint64_t mask, const int64_t *__restrict__ sentinel_label,
     int64_t null_label, int64_t oov_label, uint32_t num_buckets, OUT *__restrict__ out,
-    const K *__restrict__ hot_keys, uint32_t n_hot, int64_t first_label,
-    const int32_t *__restrict__ range_aux = nullptr, int count_stats = 0,
+    const K *__restrict__ hot_keys, uint32_t n_hot, int64_t first_label, int count_stats = 0,
     const unsigned char *__restrict__ head_image = nullptr) {
-  static_assert(!HEAD16 || (TWO && sizeof(K) == 4), "HEAD16: the 2-choice head of int32 keys");
-  static_assert(!HALF || (TWO && !HEAD16), "HALF: the 2-choice head with 8-byte slots");
+  static_assert(!TWO || (GLOBAL && sizeof(K) == 4), "TWO: the 2-choice head of int32 keys in cache mode");
   constexpr bool global_needed = GLOBAL;
-  RangeMap rmap = {0u, 0u, 0u, 0, 0, 0u, nullptr, nullptr};
-  __shared__ uint32_t s_pieces[RANGE == 1 ? kRpPwWords : 1];
-  if constexpr (RANGE) rmap = load_map(range_aux);
-  if constexpr (RANGE == 1) stage_pieces(rmap, s_pieces, threadIdx.x, kEncBS);  // (barrier below)
-  auto first_slot = [&](K key) -> uint64_t {
-    if constexpr (RANGE) return rmap.table_slot((int32_t)key);
-    return (uint64_t)slot_hash(key) & mask;
-  };
-  auto next_slot = [&](uint64_t sl) -> uint64_t {
-    if constexpr (RANGE) return sl + 1;
-    return (sl + 1) & mask;
-  };
   constexpr K EMPTY = EncTraits<K>::empty;
   constexpr int VEC = EncTraits<K>::vec;
-  constexpr int SLOTS = HALF ? HotCfg<K>::slots / 2 : HotCfg<K>::slots;
-  constexpr int kLdsBytes = HEAD16 ? kHead16Buckets * 12 : SLOTS * (int)sizeof(EncSlot<K>);
+  constexpr int SLOTS = HotCfg<K>::slots;
+  constexpr int kLdsBytes = kHeadLdsBytes<K, TWO>;
   __shared__ __align__(16) unsigned char lraw[kLdsBytes];
   EncSlot<K> *lt = reinterpret_cast<EncSlot<K> *>(lraw);
-  int2 *tkeys = reinterpret_cast<int2 *>(lraw);                                     // HEAD16: {key0, key1}
-  uint32_t *tlab = reinterpret_cast<uint32_t *>(lraw + (HEAD16 ? kHead16Buckets * 8 : 0));  // two 16-bit ranks
+  int2 *tkeys = reinterpret_cast<int2 *>(lraw);                                 // TWO: {key0, key1}
+  uint32_t *tlab = reinterpret_cast<uint32_t *>(lraw + kHead16Buckets * 8);     // TWO: two 16-bit ranks
   __shared__ long long s_sent;  // label of the sentinel key when it is among the staged keys
   if (head_image != nullptr) {   // (uniform) prebuilt by nvt_vocab_finalize_many: coalesced copy
     const int4 *src = reinterpret_cast<const int4 *>(head_image);
@@ -556,14 +496,14 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
     if (threadIdx.x == 0) s_sent = *reinterpret_cast<const long long *>(head_image + kLdsBytes);
     __syncthreads();
   } else {
-    build_head<K, TWO, HEAD16, SLOTS>(lraw, &s_sent, hot_keys, n_hot, first_label);
+    build_head<K, TWO>(lraw, &s_sent, hot_keys, n_hot, first_label);
   }
   // a vocabulary staged in full needs neither the global table nor its sentinel word
   const int64_t sent = global_needed ? *sentinel_label : (int64_t)s_sent;
 
   // LDS lookup: label, or -1 when the key is not in the staged head of the vocabulary
   auto hot_lookup = [&](K key) -> int64_t {
-    if constexpr (HEAD16) {
+    if constexpr (TWO) {
       uint32_t b1, b2;
       two_buckets16((int32_t)key, b1, b2);
       const int2 a = tkeys[b1], c = tkeys[b2];
@@ -574,18 +514,6 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
       lab = c.x == (int)key ? (int)(lc & 0xFFFFu) : lab;
       lab = c.y == (int)key ? (int)(lc >> 16) : lab;
       return lab < 0 ? (int64_t)-1 : first_label + (int64_t)lab;
-    }
-    if constexpr (TWO) {
-      uint32_t b1, b2;
-      two_buckets<SLOTS / 2>(key, b1, b2);
-      const int4 a = reinterpret_cast<const int4 *>(lt)[b1];
-      const int4 c = reinterpret_cast<const int4 *>(lt)[b2];
-      int lab = -1;
-      lab = a.x == (int)key ? a.y : lab;
-      lab = a.z == (int)key ? a.w : lab;
-      lab = c.x == (int)key ? c.y : lab;
-      lab = c.z == (int)key ? c.w : lab;
-      return (int64_t)lab;
     }
     uint32_t s = lds_home<SLOTS>(key);
     while (true) {
@@ -607,7 +535,7 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
   const uint64_t stride = (uint64_t)gridDim.x * kEncBS;
   using VecT = typename std::conditional<sizeof(K) == 4, int4, longlong2>::type;
   const VecT *vkeys = reinterpret_cast<const VecT *>(keys);
-  constexpr int U = UU;
+  constexpr int U = 2;  // key vectors per lane in flight
   constexpr int NK = U * VEC;
   // software pipeline: the key vectors (and bitmap bytes) of iteration i+1 are requested
   // before iteration i is processed -- with one 1024-thread workgroup per CU the stream
@@ -621,7 +549,7 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
       uint64_t v = v0 + (uint64_t)u * stride;
       bits[u] = 0;
       if (v < nvec) {
-        pk[u] = NVT_NT_LOAD(&vkeys[v]);
+        pk[u] = nt_load16(&vkeys[v]);
         bits[u] = 0x10000u | (valid ? (unsigned)valid[(v * VEC) >> 3] : 0xFFu);  // raw byte
       }
     }
@@ -684,56 +612,20 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
       EncSlot<K> e[NK];
 #pragma unroll
       for (int q = 0; q < NK; ++q) {
-        slot[q] = first_slot(k[q]);
+        slot[q] = (uint64_t)slot_hash(k[q]) & mask;
         if (need[q]) e[q] = table[slot[q]];
       }
 #pragma unroll
       for (int q = 0; q < NK; ++q) {
         if (!need[q]) continue;
-        if constexpr (RANGE == 2) {
-          // flat table: a few slots one by one (keys that are spread over their range sit next
-          // to home); a key that is still unresolved then -- its vocabulary clusters in its
-          // range -- is searched by doubling + bisection behind this loop (runs are in key order)
-          int step = 0;
-          while (true) {
-            if (e[q].key == k[q]) {
-              lab[q] = (int64_t)e[q].label;
-              need[q] = false;
-              break;
-            }
-            if (e[q].key == EMPTY) {
-              need[q] = false;
-              break;
-            }
-            if (++step == kFlatLinear) break;   // need[q] stays set: slot[q] is below the key
-            slot[q] = slot[q] + 1;
-            e[q] = table[slot[q]];
-          }
-          continue;
-        }
         while (true) {  // collisions continue here (load factor <= 0.5: short chains)
           if (e[q].key == k[q]) {
             lab[q] = (int64_t)e[q].label;
             break;
           }
           if (e[q].key == EMPTY) break;
-          slot[q] = next_slot(slot[q]);
+          slot[q] = (slot[q] + 1) & mask;
           e[q] = table[slot[q]];
-        }
-      }
-      if constexpr (RANGE == 2) {
-        bool any = false;
-#pragma unroll
-        for (int q = 0; q < NK; ++q) any = any || need[q];
-        if (any) {  // (never taken for keys that are spread over their range)
-#pragma unroll   // (static indices: a rolled loop would put k[] / slot[] / lab[] into scratch)
-          for (int q = 0; q < NK; ++q) {
-            if (!need[q]) continue;
-            if (ukey((int32_t)e[q].key) > ukey((int32_t)k[q])) continue;   // already past it: not there
-            const uint64_t at = flat_gallop(reinterpret_cast<const unsigned long long *>(table),
-                                            mask + 1, slot[q], (int32_t)k[q]);
-            if (at != ~0ull) lab[q] = (int64_t)table[at].label;
-          }
         }
       }
     }
@@ -753,12 +645,12 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
         int4 a, b;
         memcpy(&a, &r[0], 16);
         memcpy(&b, &r[2], 16);
-        NVT_NT_STORE(a, &reinterpret_cast<int4 *>(dst)[0]);
-        NVT_NT_STORE(b, &reinterpret_cast<int4 *>(dst)[1]);
+        nt_store16(a, &reinterpret_cast<int4 *>(dst)[0]);
+        nt_store16(b, &reinterpret_cast<int4 *>(dst)[1]);
       } else if constexpr (VEC * sizeof(OUT) == 16) {
         int4 a;
         memcpy(&a, &r[0], 16);
-        NVT_NT_STORE(a, &reinterpret_cast<int4 *>(dst)[0]);
+        nt_store16(a, &reinterpret_cast<int4 *>(dst)[0]);
       } else {
         int2 a;
         memcpy(&a, &r[0], 8);
@@ -772,7 +664,7 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
     if (bit_valid(valid, i)) {
       int64_t lab = key == EMPTY ? sent : hot_lookup(key);
       if (lab < 0 && key != EMPTY && global_needed) {
-        uint64_t sl = first_slot(key);
+        uint64_t sl = (uint64_t)slot_hash(key) & mask;
         while (true) {
           const EncSlot<K> e1 = table[sl];
           if (e1.key == key) {
@@ -780,7 +672,7 @@ __global__ __launch_bounds__(kEncBS, HALF ? 2 : 1) void encode_hot_kernel(
             break;
           }
           if (e1.key == EMPTY) break;
-          sl = next_slot(sl);
+          sl = (sl + 1) & mask;
         }
       }
       r = finish(key, lab);
@@ -848,8 +740,7 @@ __global__ __launch_bounds__(kEncBS, 1) void encode_pipe_kernel(
   using K = int32_t;
   constexpr K EMPTY = EncTraits<K>::empty;
   constexpr int VEC = 4, U = 2, NK = U * VEC;
-  constexpr int SLOTS = HotCfg<K>::slots;
-  constexpr int kLdsBytes = kHead16Buckets * 12;
+  constexpr int kLdsBytes = kHeadLdsBytes<K, true>;
   RangeMap rmap = load_map(range_aux);
   __shared__ uint32_t s_pieces[RANGE == 1 ? kRpPwWords : 1];
   if constexpr (RANGE == 1) stage_pieces(rmap, s_pieces, threadIdx.x, kEncBS);  // (barrier below)
@@ -865,14 +756,11 @@ __global__ __launch_bounds__(kEncBS, 1) void encode_pipe_kernel(
     for (int i = threadIdx.x; i < kLdsBytes / 16; i += kEncBS) dst[i] = src[i];
     __syncthreads();
   } else {
-    build_head<K, true, true, SLOTS>(lraw, &s_sent, hot_keys, n_hot, first_label);
+    build_head<K, true>(lraw, &s_sent, hot_keys, n_hot, first_label);
   }
   const int32_t sent = (int32_t)*sentinel_label;   // (-1: the sentinel key is not in the vocabulary)
   const unsigned long long *tw = reinterpret_cast<const unsigned long long *>(table);
   const char *tbytes = reinterpret_cast<const char *>(table);
-#ifdef NVT_ENC_PIPE_TIMING
-  const long long t_begin = clock64();
-#endif
 
   unsigned st_miss = 0, st_rows = 0;  // (count_stats)
   // (the linear / piecewise form of the range map is decided once, outside the loops)
@@ -1158,28 +1046,6 @@ __global__ __launch_bounds__(kEncBS, 1) void encode_pipe_kernel(
   };
   if (RANGE == 1 && rmap.piece_slots != 0) run(std::true_type{});
   else run(std::false_type{});
-#ifdef NVT_ENC_PIPE_TIMING
-  // (experiment: g_enc_stats[0] += last wave's end - first wave's end, [1] += last wave's end - start)
-  {
-    __shared__ unsigned long long s_tmin, s_tmax;
-    if (threadIdx.x == 0) {
-      s_tmin = ~0ull;
-      s_tmax = 0;
-    }
-    const unsigned long long t_end = (unsigned long long)clock64();
-    __syncthreads();
-    if (lane_id() == 0) {
-      atomicMin(&s_tmin, t_end);
-      atomicMax(&s_tmax, t_end);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      atomicAdd(&g_enc_stats[0], s_tmax - s_tmin);
-      atomicAdd(&g_enc_stats[1], s_tmax - (unsigned long long)t_begin);
-    }
-    return;
-  }
-#endif
   if (count_stats) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -1283,13 +1149,6 @@ int build_launch(const K *vocab, uint64_t n, int64_t first_label, void *table, u
   return NVT_OK;
 }
 
-// the head-layout switch of this process (the image nvt_vocab_finalize_many builds and the layout
-// the cache-mode launch expects are decided by the same word)
-static bool enc_head16() {
-  static const bool v = ab_env("NVT_ENC_HEAD16") == nullptr || atoi(ab_env("NVT_ENC_HEAD16")) != 0;
-  return v;
-}
-
 template <typename K>
 int encode_launch(const K *keys, const uint8_t *valid, uint64_t n, const void *table,
                   uint64_t capacity, const int64_t *sentinel_label, int64_t null_label,
@@ -1313,120 +1172,75 @@ int encode_launch(const K *keys, const uint8_t *valid, uint64_t n, const void *t
   constexpr int VEC = EncTraits<K>::vec;
   auto *t = reinterpret_cast<const EncSlot<K> *>(table);
   NVT_PROF(sizeof(K) == 4 ? "encode_i32" : "encode_i64", n * (sizeof(K) + (uint64_t)out_bytes), s);
+  // the launches below differ in the label type only: `launch` gets the typed output pointer
+  auto with_out = [&](auto launch) {
+    if (out_bytes == 8) launch(reinterpret_cast<int64_t *>(out));
+    else launch(reinterpret_cast<int32_t *>(out));
+  };
   if (hot_keys != nullptr && n_vocab > 0) {
-    // head of the frequency-ordered vocabulary in LDS (load factor <= 0.75: LDS probes are
-    // cheap, every extra resident key is a saved trip to L2 / HBM)
-    // a vocabulary that fits entirely may fill the table to 75 % (every lookup is a hit);
-    // otherwise most lookups of the table MISS, and an unsuccessful linear probe costs
-    // ~2.5 slots at 50 % load but ~8.5 at 75 % (measured: 530 -> 1290 us on a 6 M-key column)
-    // fully staged (no global table) up to half load: linear probing of a table in which every
-    // lookup hits stays short there (a 73 %-full table made an 11.9 k-key column 229 instead
-    // of 129 us); larger vocabularies use the cache mode below
-    const uint64_t full_cap = kResident;
-    const uint64_t part_cap = (uint64_t)HotCfg<K>::slots / NVT_HOT_DIV;
-    uint32_t n_hot = (uint32_t)(n_vocab <= full_cap ? n_vocab : part_cap);
-    const int global_needed = n_vocab > n_hot;
-    unsigned hgrid = stream_grid(n / VEC + 1, kEncBS * 2, 1);
-    if constexpr (sizeof(K) == 4) {
-      static const bool two = ab_env("NVT_ENC_LINEAR") == nullptr;
-      // (range tables: `mask` = capacity - 1 bounds the search of a FLAT table -- capacity slots --
-      // and is unused for the dumped bucket tables, capacity 0)
-      if (global_needed && (two || range_aux != nullptr)) {  // cache mode: 2-choice table filled to 7/8
-        const bool head16 = enc_head16();
-        static const int stats = getenv("NVT_ENC_STATS") ? atoi(getenv("NVT_ENC_STATS")) : 0;
-        // NVT_ENC_HALF=1 (experiment): half the head, one key vector per lane and <= 64 VGPRs, so
-        // that TWO workgroups share a CU -- the waves of a cache-mode launch are parked 77 % of
-        // their cycles (SQ_WAIT_ANY), and one workgroup per CU is 4 waves per SIMD
-        static const bool half = ab_env("NVT_ENC_HALF") != nullptr && atoi(ab_env("NVT_ENC_HALF")) != 0;
-        const uint64_t cap2 = half ? (uint64_t)HotCfg<K>::slots / 16 * 7
-                                   : head16 ? (uint64_t)kHead16Keys : (uint64_t)HotCfg<K>::slots / 8 * 7;
-        n_hot = (uint32_t)(n_vocab < cap2 ? n_vocab : cap2);
-        if (half) hgrid = stream_grid(n / VEC + 1, kEncBS, 2);
-        static const bool use_image = ab_env("NVT_ENC_NO_HEAD_IMAGE") == nullptr;   // (A/B switch)
-        if (half || !use_image) head_image = nullptr;
-#define NVT_ENC_CACHE(OUTT, KIND, H16)                                                            \
-  encode_hot_kernel<K, OUTT, true, true, 2, KIND, H16><<<hgrid, kEncBS, 0, s>>>(                   \
-      keys, valid, n, t, capacity - 1, sentinel_label, null_label, oov_label, num_buckets,          \
-      reinterpret_cast<OUTT *>(out), hot_keys, n_hot, first_label, range_aux, stats,           \
-      reinterpret_cast<const unsigned char *>(head_image))
-#define NVT_ENC_CACHE_HALF(OUTT, KIND)                                                            \
-  encode_hot_kernel<K, OUTT, true, true, 1, KIND, false, true><<<hgrid, kEncBS, 0, s>>>(           \
-      keys, valid, n, t, capacity - 1, sentinel_label, null_label, oov_label, num_buckets,          \
-      reinterpret_cast<OUTT *>(out), hot_keys, n_hot, first_label, range_aux, stats)
-#define NVT_ENC_PIPE(OUTT, KIND)                                                                  \
-  encode_pipe_kernel<OUTT, KIND><<<hgrid, kEncBS, 0, s>>>(                                         \
-      keys, valid, n, t, capacity - 1, sentinel_label, null_label, oov_label, num_buckets,          \
-      reinterpret_cast<OUTT *>(out), hot_keys, n_hot, first_label, range_aux, stats,           \
-      reinterpret_cast<const unsigned char *>(head_image))
-        // the software pipeline (encode_pipe_kernel) is the cache-mode kernel of the range tables with
-        // the 6-byte head; NVT_ENC_PIPE=0 keeps the phase-serial one for A/B runs
-        static const bool pipe = ab_env("NVT_ENC_PIPE") == nullptr || atoi(ab_env("NVT_ENC_PIPE")) != 0;
-#define NVT_ENC_CACHE_K(KIND)                                                \
-  do {                                                                       \
-    if (half) {                                                              \
-      if (out_bytes == 8) NVT_ENC_CACHE_HALF(int64_t, KIND);                 \
-      else NVT_ENC_CACHE_HALF(int32_t, KIND);                                \
-    } else if (head16) {                                                     \
-      if (out_bytes == 8) NVT_ENC_CACHE(int64_t, KIND, true);                \
-      else NVT_ENC_CACHE(int32_t, KIND, true);                               \
-    } else {                                                                 \
-      if (out_bytes == 8) NVT_ENC_CACHE(int64_t, KIND, false);               \
-      else NVT_ENC_CACHE(int32_t, KIND, false);                              \
-    }                                                                        \
-  } while (0)
-#define NVT_ENC_PIPE_K(KIND)                                                 \
-  do {                                                                       \
-    if (out_bytes == 8) NVT_ENC_PIPE(int64_t, KIND);                         \
-    else NVT_ENC_PIPE(int32_t, KIND);                                        \
-  } while (0)
-        const bool piped = pipe && head16 && !half && range_aux != nullptr;
-        // range tables -- capacity > 0: a FLAT range table of `capacity` slots (bounded search);
-        // 0: the bucket regions dumped by the counting pass; no range_aux: the hashed table
-        if (piped) {
-          if (capacity > 0) NVT_ENC_PIPE_K(2); else NVT_ENC_PIPE_K(1);
-        } else if (range_aux != nullptr) {
-          if (capacity > 0) NVT_ENC_CACHE_K(2); else NVT_ENC_CACHE_K(1);
-        } else {
-          NVT_ENC_CACHE_K(0);
+    // head of the frequency-ordered vocabulary in LDS
+    const unsigned hgrid = stream_grid(n / VEC + 1, kEncBS * 2, 1);
+    const uint64_t mask = capacity - 1;
+    if (resident) {
+      // fully staged (no global table) up to half load: linear probing of a table in which every
+      // lookup hits stays short there (a 73 %-full table made an 11.9 k-key column 229 instead
+      // of 129 us); larger vocabularies use the cache mode below
+      const uint32_t n_hot = (uint32_t)n_vocab;
+      if constexpr (sizeof(K) == 4) {
+        // small vocabularies with int64 labels: smaller tables, 256-thread workgroups, contiguous stores
+        if (out_bytes == 8 && n_vocab <= 2048) {
+          const unsigned sgrid = stream_grid(n / 2 + 1, kBlock * 8, 8);
+          if (n_vocab <= 1024)
+            encode_small_kernel<2048><<<sgrid, kBlock, 0, s>>>(
+                keys, valid, n, null_label, oov_label, num_buckets, reinterpret_cast<int64_t *>(out),
+                hot_keys, n_hot, first_label);
+          else
+            encode_small_kernel<4096><<<sgrid, kBlock, 0, s>>>(
+                keys, valid, n, null_label, oov_label, num_buckets, reinterpret_cast<int64_t *>(out),
+                hot_keys, n_hot, first_label);
+          NVT_CHECK_LAUNCH();
+          return NVT_OK;
         }
-#undef NVT_ENC_CACHE_HALF
-#undef NVT_ENC_CACHE_K
-#undef NVT_ENC_PIPE_K
-#undef NVT_ENC_PIPE
-#undef NVT_ENC_CACHE
-        NVT_CHECK_LAUNCH();
-        return NVT_OK;
       }
-    }
-#define NVT_ENC_HOT(OUTT, GL, UUU)                                                               \
-  encode_hot_kernel<K, OUTT, false, GL, UUU><<<hgrid, kEncBS, 0, s>>>(                            \
-      keys, valid, n, t, capacity - 1, sentinel_label, null_label, oov_label, num_buckets,        \
-      reinterpret_cast<OUTT *>(out), hot_keys, n_hot, first_label)
-    if constexpr (sizeof(K) == 4) {
-      // small vocabularies with int64 labels: smaller tables, 256-thread workgroups, contiguous stores
-      static const bool small_on = ab_env("NVT_ENC_NO_SMALL") == nullptr;   // (A/B switch)
-      if (!global_needed && out_bytes == 8 && small_on && n_vocab <= 2048) {
-        const unsigned sgrid = stream_grid(n / 2 + 1, kBlock * 8, 8);
-        if (n_vocab <= 1024)
-          encode_small_kernel<2048><<<sgrid, kBlock, 0, s>>>(
-              reinterpret_cast<const int32_t *>(keys), valid, n, null_label, oov_label, num_buckets,
-              reinterpret_cast<int64_t *>(out), reinterpret_cast<const int32_t *>(hot_keys), n_hot,
-              first_label);
-        else
-          encode_small_kernel<4096><<<sgrid, kBlock, 0, s>>>(
-              reinterpret_cast<const int32_t *>(keys), valid, n, null_label, oov_label, num_buckets,
-              reinterpret_cast<int64_t *>(out), reinterpret_cast<const int32_t *>(hot_keys), n_hot,
-              first_label);
-        NVT_CHECK_LAUNCH();
-        return NVT_OK;
-      }
-    }
-    if (global_needed) {
-      if (out_bytes == 8) NVT_ENC_HOT(int64_t, true, 2); else NVT_ENC_HOT(int32_t, true, 2);
+      with_out([&](auto *o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        encode_hot_kernel<K, OUT, false, false><<<hgrid, kEncBS, 0, s>>>(
+            keys, valid, n, t, mask, sentinel_label, null_label, oov_label, num_buckets, o, hot_keys,
+            n_hot, first_label);
+      });
+    } else if constexpr (sizeof(K) == 4) {
+      // cache mode: the 2-choice head filled to 7/8 (prebuilt as head_image when the caller has one);
+      // rows that miss it go on to the table in HBM
+      const uint32_t n_hot = (uint32_t)(n_vocab < (uint64_t)kHead16Keys ? n_vocab : (uint64_t)kHead16Keys);
+      static const int stats = getenv("NVT_ENC_STATS") ? atoi(getenv("NVT_ENC_STATS")) : 0;
+      const auto *image = reinterpret_cast<const unsigned char *>(head_image);
+      with_out([&](auto *o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        if (range_aux == nullptr)   // hashed table
+          encode_hot_kernel<K, OUT, true, true><<<hgrid, kEncBS, 0, s>>>(
+              keys, valid, n, t, mask, sentinel_label, null_label, oov_label, num_buckets, o, hot_keys,
+              n_hot, first_label, stats, image);
+        else if (capacity > 0)      // FLAT range table of `capacity` slots (`mask` bounds the search)
+          encode_pipe_kernel<OUT, 2><<<hgrid, kEncBS, 0, s>>>(
+              keys, valid, n, t, mask, sentinel_label, null_label, oov_label, num_buckets, o, hot_keys,
+              n_hot, first_label, range_aux, stats, image);
+        else                        // the bucket regions dumped by the counting pass (`mask` unused)
+          encode_pipe_kernel<OUT, 1><<<hgrid, kEncBS, 0, s>>>(
+              keys, valid, n, t, mask, sentinel_label, null_label, oov_label, num_buckets, o, hot_keys,
+              n_hot, first_label, range_aux, stats, image);
+      });
     } else {
-      if (out_bytes == 8) NVT_ENC_HOT(int64_t, false, 2); else NVT_ENC_HOT(int32_t, false, 2);
+      // int64 keys: the linear-probing head filled to a quarter -- most lookups of it MISS, and an
+      // unsuccessful linear probe costs ~2.5 slots at 50 % load but ~8.5 at 75 % (measured: 530 ->
+      // 1290 us on a 6 M-key column)
+      const uint32_t n_hot = (uint32_t)HotCfg<K>::slots / NVT_HOT_DIV;
+      with_out([&](auto *o) {
+        using OUT = std::remove_pointer_t<decltype(o)>;
+        encode_hot_kernel<K, OUT, false, true><<<hgrid, kEncBS, 0, s>>>(
+            keys, valid, n, t, mask, sentinel_label, null_label, oov_label, num_buckets, o, hot_keys,
+            n_hot, first_label);
+      });
     }
-#undef NVT_ENC_HOT
     NVT_CHECK_LAUNCH();
     return NVT_OK;
   }
@@ -1512,17 +1326,13 @@ namespace nvt {
 // vocabulary.  Entries with a null image / too few keys are skipped.
 int encode_head_build_many(const int32_t *const *vocab_keys, const uint64_t *n, const int64_t *first_label,
                            void *const *images, int count, hipStream_t s) {
-  static const bool half = ab_env("NVT_ENC_HALF") != nullptr && atoi(ab_env("NVT_ENC_HALF")) != 0;
-  if (half) return NVT_OK;   // (the experiment builds its smaller head per launch)
-  const bool h16 = enc_head16();
-  const uint64_t cap = h16 ? (uint64_t)kHead16Keys : (uint64_t)HotCfg<int32_t>::slots / 8 * 7;
+  const uint64_t cap = (uint64_t)kHead16Keys;
   HeadJobs jobs;
   int m = 0;
   auto flush = [&]() -> int {
     if (m == 0) return NVT_OK;
     NVT_PROF("vocab_order", 0, s);
-    if (h16) enc_head_build_many_kernel<true><<<m, kEncBS, 0, s>>>(jobs);
-    else enc_head_build_many_kernel<false><<<m, kEncBS, 0, s>>>(jobs);
+    enc_head_build_many_kernel<<<m, kEncBS, 0, s>>>(jobs);
     NVT_CHECK_LAUNCH();
     m = 0;
     return NVT_OK;

@@ -105,7 +105,6 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
     }
     if (c.ready_event) {
       NVT_CHECK_HIP(hipEventRecord((hipEvent_t)c.ready_event, s));
-      if (s != main_s && ab_env("NVT_FLUSH_QUERY")) (void)hipStreamQuery(s);
     } else if (s != main_s)
       need_join = true;
     return NVT_OK;
@@ -133,9 +132,8 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
   // by ONE chain of batched launches on the first internal stream (vocab_order_sorted_batch)
   // instead of ~10 launches per vocabulary spread over the streams -- the host took as long to
   // enqueue those as the GPU to run them
-  static const bool batch_order = ab_env("NVT_NO_ORDER_BATCH") == nullptr;
   std::vector<char> batched(ncols > 0 ? ncols : 0, 0);
-  if (batch_order) {
+  {
     std::vector<OrderSortedJob> jobs;
     std::vector<int> job_cols;
     for (int i : big) {
@@ -191,12 +189,11 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
       // key-sorted list of the range path: one stable counting pass orders it and fills the table
       NVT_CHECK_ARG(c.sort_tmp, "null sort_tmp");
       bool deferred = false;
-      static const bool batch_tail = ab_env("NVT_NO_TAIL_BATCH") == nullptr;
       int rc = vocab_order_from_sorted((const int32_t *)c.src_keys, c.src_counts, c.n, c.cls_hist,
                                        c.n_big, c.max_count, (int32_t *)c.keys, c.counts,
                                        c.sort_tmp, c.first_label, c.table, c.capacity,
                                        c.sentinel_label, c.range_aux, c.range_nb_log2, s,
-                                       batch_tail ? &deferred : nullptr, c.flat_slots);
+                                       &deferred, c.flat_slots);
       if (rc) return rc;
       if (deferred) {
         tails.push_back({(int32_t *)c.keys, c.counts, c.n_big, c.first_label, c.table, c.capacity,

@@ -1129,7 +1129,7 @@ int nvt_gb_update(nvt_gb_table *t, const int64_t *const *keys, const uint8_t *co
   }
   hipStream_t s = (hipStream_t)stream;
   NVT_PROF("groupby_update", 0, s);
-  if (n < (1ull << 15) || n >= (1ull << 30) || t->capacity > (1ull << 31) || ab_env("NVT_GB_ATOMIC")) {
+  if (n < (1ull << 15) || n >= (1ull << 30) || t->capacity > (1ull << 31)) {
     // tiny inputs (the sort would be launch latency) and > 2^30 rows per call: per-row atomics
     gb_update_kernel<<<stream_grid(n, kBlock * 2), kBlock, 0, s>>>(view_of(t), a, n);
     NVT_CHECK_LAUNCH();

@@ -59,7 +59,7 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
                             int32_t *out_keys, int64_t *out_cnts, void *tmp, int64_t first_label,
                             void *table, uint64_t capacity, int64_t *sentinel_label,
                             const int32_t *range_aux, int range_nb_log2, hipStream_t s,
-                            bool *tail_deferred = nullptr, uint64_t flat_slots = 0);
+                            bool *tail_deferred, uint64_t flat_slots = 0);
 // the same for several vocabularies that own a range table (dumped or flat): one launch per
 // stage for ALL of them, class-255 tails included
 struct OrderSortedJob {

@@ -130,16 +130,7 @@ __global__ __launch_bounds__(kRpBS) void rp_partition_kernel(
   RangeMap map = load_map(aux);
   __shared__ uint32_t s_pieces[kRpPwWords];
   stage_pieces(map, s_pieces, threadIdx.x, kRpBS);
-#ifdef NVT_RP_PART_TIMING
-  long long ptm[8];
-  int ptmi = 0;
-#define NVT_PTM() do { if (threadIdx.x == 0) ptm[ptmi++] = clock64(); } while (0)
-#else
-#define NVT_PTM() do {} while (0)
-#endif
-  NVT_PTM();
   __syncthreads();
-  NVT_PTM();
 
   // flush every bin that holds >= kRpLine keys (or, with `all`, whatever it holds): one
   // 16-lane group per bin, four bins per wave instruction; bin t is owned by thread t
@@ -194,12 +185,8 @@ __global__ __launch_bounds__(kRpBS) void rp_partition_kernel(
             if (l16 == 0) atomicOr(&s_ovf, 1u);
           } else {
             int32_t *dst = regions + ((uint64_t)bin * kRpG + g) * region_cap + done;
-#ifndef NVT_RP_NOFLUSHSTORE
             for (unsigned u = l16; u < nb_out; u += kRpLine) dst[u] = bsrc[u];
             if (l16 < pb) dst[frb + l16] = kEmpty;
-#else
-            if (done == 0xFFFFFFu) dst[0] = bsrc[0];
-#endif
           }
           // the keys that stay (< kRpLine of them) move to the front of the bin
           const unsigned rem = fb - nb_out;
@@ -376,10 +363,8 @@ __global__ __launch_bounds__(kRpBS) void rp_partition_kernel(
     }
   }
   __syncthreads();   // (the loop may end inside an epoch)
-  NVT_PTM();
   flush_bins(true, epoch & 1u);
   __syncthreads();
-  NVT_PTM();
   for (unsigned b = threadIdx.x; b < NB; b += kRpBS) fills[(uint64_t)b * kRpG + g] = flushed[b];
   for (int i = threadIdx.x; i < kHotBucketsR; i += kRpBS) {
     const int4 hbk = hot[i];
@@ -402,13 +387,6 @@ __global__ __launch_bounds__(kRpBS) void rp_partition_kernel(
     if (s_ovf) atomicOr((unsigned long long *)&state[NVT_ST_OVERFLOW], 1ull | NVT_OVF_REGION);
     if (g == 0) atomicAdd((unsigned long long *)&state[NVT_ST_ROWS], (unsigned long long)n);
   }
-#ifdef NVT_RP_PART_TIMING
-  __syncthreads();
-  NVT_PTM();
-  if (threadIdx.x == 0)
-    for (int q = 1; q < ptmi; ++q)
-      atomicAdd((unsigned long long *)&state[9 + q], (unsigned long long)(ptm[q] - ptm[q - 1]));
-#endif
 }
 
 // totals per hot slot = column sums of the per-workgroup counters (64 slots per workgroup x 16
@@ -466,14 +444,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
   RangeMap map = load_map(aux);
   __shared__ uint32_t s_pieces[kRpPwWords];
   stage_pieces(map, s_pieces, threadIdx.x, kRpBS);  // (barriers follow before the first use)
-#ifdef NVT_RANGE_TIMING
-  long long tm[8];
-  int tmi = 0;
-#define NVT_TM() do { if (threadIdx.x == 0) tm[tmi++] = clock64(); } while (0)
-#else
-#define NVT_TM() do {} while (0)
-#endif
-  NVT_TM();
   // (pass 1 overflowed a region: the run lengths are not to be trusted, nothing is gathered)
   const bool skip = (state[NVT_ST_OVERFLOW] & 1ull) != 0;
   if (threadIdx.x < kRpG) {
@@ -602,16 +572,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
           cur[u] = cur[u] == kEmpty ? kk[u] : cur[u];
         }
       }
-#ifdef NVT_RP_SEQ_INSERT
-#pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        if (kk[u] == kEmpty) continue;
-        if (cur[u] == kk[u])
-          atomicAdd(&lcnt[hs[u]], 1u);  // already at home: fire and forget
-        else
-          insert_from(kk[u], 1u, hs[u]);
-      }
-#else
       // Keys that are not at home yet walk their probe chains.  Key position by key position the
       // wave paid the LONGEST chain of its 64 lanes at each of the GB positions (a chain is a
       // loop of dependent LDS round trips); every lane walks ITS keys one after the other
@@ -665,10 +625,8 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
           }
         }
       }
-#endif
     }
   }
-  NVT_TM();
   // the hot keys of this range (indexed by bucket by the sample kernel), with the totals of
   // their counters
   // (the first of them per thread -- all of them unless a bucket holds > 1024 -- was loaded in front of
@@ -686,7 +644,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
   }
   if (failed) atomicOr(&lovf, 1u);
   __syncthreads();
-  NVT_TM();
   // workgroup-uniform (the global flag may be raised by another workgroup at any moment: it is
   // read ONCE, by one thread; threads that disagreed here used to split at the return below)
   if (threadIdx.x == 0)
@@ -752,7 +709,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
     if (lane == 0) s_base = excl;
   }
   __syncthreads();
-  NVT_TM();
   const unsigned long long base = s_base;
   if (b == NB - 1 && threadIdx.x == 0) {
     if (base + E > out_cap) {
@@ -811,7 +767,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
     }
     __syncthreads();
   }
-  NVT_TM();
   unsigned mx = 0;
   for (int it = 0; it < ITER; ++it) {
     const int i = it * kRpBS + (int)threadIdx.x;
@@ -860,27 +815,16 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
       }
       const uint64_t pos = base + p_i - (unsigned)(i - s) + rank;
       const unsigned c = lcnt[i];
-#ifndef NVT_RP_NOWRITE
       out_keys[pos] = k;
       out_cnt[pos] = (int64_t)c;
-#else
-      if (pos == 0xFFFFFFFFFFull) out_keys[0] = k;
-#endif
-#ifndef NVT_RP_NOHIST
       atomicAdd(&hist[c < 255u ? c : 255u], 1u);
-#endif
       mx = c > mx ? c : mx;
       dump = ((unsigned long long)(uint32_t)pos << 32) | (uint32_t)k;
     }
     // the table as it stands in LDS becomes this bucket's region of the encode table: slot ->
     // {key, position in the key-ordered list}; the ordering pass turns positions into labels
-#ifndef NVT_RP_NODUMP
     if (range_table != nullptr && i < NSL) range_table[(uint64_t)b * NSL + i] = dump;
-#else
-    if (range_table != nullptr && i < NSL && dump == 0x1234567ull) range_table[(uint64_t)b * NSL + i] = dump;
-#endif
   }
-  NVT_TM();
   // largest count of the bucket: waves -> LDS -> ONE device atomic per workgroup behind the last
   // barrier.  (Round 6, phase timers: every wave read state[NVT_ST_MAXCOUNT] with a device-scope
   // atomic load and raised it with atomicMax -- 16 waves x NB workgroups on one address -- and
@@ -894,12 +838,6 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
   if (range_table != nullptr && b == NB - 1 && threadIdx.x < kRpGuard)
     range_table[(uint64_t)NB * NSL + threadIdx.x] = kEncEmptySlot;
   __syncthreads();
-  NVT_TM();
-#ifdef NVT_RANGE_TIMING
-  if (threadIdx.x == 0)   // (summed over the buckets: tools/rp_phase_probe.py divides by NB)
-    for (int q = 1; q < tmi; ++q)
-      atomicAdd((unsigned long long *)&state[9 + q], (unsigned long long)(tm[q] - tm[q - 1]));
-#endif
   if (threadIdx.x == 0 && s_mx > 0)
     atomicMax(reinterpret_cast<unsigned long long *>(&state[NVT_ST_MAXCOUNT]), (unsigned long long)s_mx);
   if (threadIdx.x < 256) {
@@ -963,29 +901,7 @@ int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int n
   range_ws_layout(n, nb_log2, (char *)wsp, &w);
   const unsigned NB = 1u << nb_log2;
   const uint32_t cap = range_region_cap(n, nb_log2);
-  static const bool debug = ab_env("NVT_RANGE_DEBUG") != nullptr;
-  auto mark = [&](const char *what) {
-    if (debug) {
-      hipError_t e = hipStreamSynchronize(s);
-      fprintf(stderr, "[range n=%llu nb=%u cap=%u] %s: %s\n", (unsigned long long)n, NB, cap, what,
-              hipGetErrorString(e));
-      fflush(stderr);
-    }
-  };
-  mark("begin");
-  if (debug) {
-    int32_t prm[5];
-    (void)hipMemcpy(prm, aux + NVT_RANGE_AUX_LO, sizeof(prm), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[range] map: ulo=%u span=%u mul=%llu sh=%d; ws=%p regions=%p fills=%p hot_cnt=%p aux=%p\n",
-            (unsigned)prm[0], (unsigned)prm[1],
-            (unsigned long long)(uint32_t)prm[2] | ((unsigned long long)(uint32_t)prm[3] << 32), prm[4],
-            wsp, (void *)w.regions, (void *)w.fills, (void *)w.hot_cnt, (void *)aux);
-  }
   unsigned *hist = (unsigned *)(aux + NVT_RANGE_AUX_HIST);
-#ifdef NVT_RP_MEMSET
-  NVT_CHECK_HIP(hipMemsetAsync(w.status, 0, (uint64_t)NB * 8 + 64, s));
-  NVT_CHECK_HIP(hipMemsetAsync(aux + NVT_RANGE_AUX_HIST, 0, 256 * 4, s));
-#endif
 #define NVT_RP_PART(NBL)                                                                            \
   do {                                                                                              \
     if (pieces)                                                                                     \
@@ -995,18 +911,14 @@ int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int n
       rp_partition_kernel<NVT_RANGE_U, NBL, false><<<kRpG, kRpBS, 0, s>>>(                          \
           keys, valid, n, aux, nb_log2, cap, w.regions, w.fills, w.hot_cnt, state, w.status, hist); \
   } while (0)
-  static const bool rt_nb = ab_env("NVT_RANGE_RT_NB") != nullptr;  // (A/B: the run-time variant)
-  if (rt_nb) NVT_RP_PART(0);
-  else if (nb_log2 == 8) NVT_RP_PART(8);
+  if (nb_log2 == 8) NVT_RP_PART(8);
   else if (nb_log2 == 9) NVT_RP_PART(9);
   else if (nb_log2 == 10) NVT_RP_PART(10);
   else NVT_RP_PART(0);
 #undef NVT_RP_PART
   NVT_CHECK_LAUNCH();
-  mark("partition");
   hot_totals_kernel<<<kHotSlotsR / 64, 64 * kTotGroups, 0, s>>>(w.hot_cnt, kRpG, w.hot_tot);
   NVT_CHECK_LAUNCH();
-  mark("totals");
   if (pieces)
     rp_count_kernel<true><<<NB, kRpBS, 0, s>>>(w.regions, w.fills, cap, aux, w.hot_tot, nb_log2, w.status,
                                                w.ticket, out_keys, out_cnt, out_cap,
@@ -1018,7 +930,6 @@ int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int n
                                                 (unsigned *)(aux + NVT_RANGE_AUX_HIST),
                                                 (unsigned long long *)range_table, state);
   NVT_CHECK_LAUNCH();
-  mark("count");
   return NVT_OK;
 }
 

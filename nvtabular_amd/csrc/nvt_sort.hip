@@ -891,7 +891,7 @@ int vocab_sort(K *keys, int64_t *counts, uint64_t n, int64_t max_count, void *tm
     return NVT_OK;
   }
   if constexpr (sizeof(K) == 4) {
-    if (max_count > 0 && max_count < (1ll << 32) && n < (1ull << 30) && !ab_env("NVT_SORT_LEGACY"))
+    if (max_count > 0 && max_count < (1ll << 32) && n < (1ull << 30))
       return vocab_sort_onesweep(keys, counts, n, max_count, tmp, stream);
     if (max_count > 0 && max_count < (1ll << 32) && n < (1ull << 31))
       return vocab_sort_packed(keys, counts, n, max_count, tmp, stream);
@@ -1850,7 +1850,7 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
                             void *table, uint64_t capacity, int64_t *sentinel_label,
                             const int32_t *range_aux, int range_nb_log2, hipStream_t s,
                             bool *tail_deferred, uint64_t flat_slots) {
-  if (tail_deferred) *tail_deferred = false;
+  *tail_deferred = false;
   if (n == 0) return NVT_OK;
   NVT_CHECK_ARG(n < (1ull << 30), "at most 2^30-1 vocabulary entries");
   NVT_CHECK_ARG(n_big <= n, "n_big > n");
@@ -1905,8 +1905,8 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
     }
   }
   // the sort of class 255 and the labels of its entries: left to ONE batched launch for all the
-  // vocabularies of the call when the caller asks for it (vocab_order_tail_batch)
-  if (tail_deferred && vocab_sort_small_eligible(4, n_big, max_count)) {
+  // vocabularies of the call (vocab_order_tail_batch)
+  if (vocab_sort_small_eligible(4, n_big, max_count)) {
     *tail_deferred = true;
     return NVT_OK;
   }

@@ -49,8 +49,7 @@ every weighted instantiation.  Weight 0 and negative weights are left out: inclu
 not define them (the merge step only ever adds counts >= 1).
 
 Left out, by name: the vocabulary ordering kernels (cls_scatter, range_patch, flat_build, the radix
-and small sorts) beyond the order of the one table the piecewise case builds; the NVT_AB_SWITCHES
-variants, NVT_STAGE_TIMING, NVT_EXP_*; the multi-GPU exchange (dist._hip_merge_counts) and string
+and small sorts) beyond the order of the one table the piecewise case builds; the multi-GPU exchange (dist._hip_merge_counts) and string
 keys; the cold-start prefix sketch (nvt_prefix_distinct: columns of >= 2 M rows with hint 0).
 """
 import zlib

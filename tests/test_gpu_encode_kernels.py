@@ -31,9 +31,7 @@ three code paths -- the loop over the FULL steps of a workgroup, the vectors beh
 step, the rows behind the last vector: 2 097 152 rows are full steps alone, 4097 rows the other
 two alone, 2 * 2 097 152 + 4 * 5 + 3 all three with a second full step.
 
-Left out, by name: the NVT_AB_SWITCHES variants (NVT_ENC_LINEAR, NVT_ENC_HALF, NVT_ENC_HEAD16=0,
-NVT_ENC_PIPE=0, NVT_ENC_NO_SMALL, NVT_ENC_NO_HEAD_IMAGE), which the default library does not
-contain; NVT_ENC_STATS counting; src_labels (multi-GPU labelled shards, test_gpu_merge_sorted.py);
+Left out, by name: NVT_ENC_STATS counting; src_labels (multi-GPU labelled shards, test_gpu_merge_sorted.py);
 the piecewise range map (test_gpu_range_path.py reaches it through the workflow).
 """
 import zlib

@@ -1,6 +1,6 @@
 """Cache-mode encode: rows that miss the LDS head (and pay one random sector of the table in HBM)
-per transform of the bench frame, per column.  Run once per head layout:
-    NVT_ENC_STATS=1 NVT_ENC_HEAD16=0|1 python tools/enc_stats.py"""
+per transform of the bench frame, per column:
+    NVT_ENC_STATS=1 python tools/enc_stats.py"""
 import ctypes as C
 import json
 import os
@@ -21,7 +21,7 @@ n = int(os.environ.get("ROWS", 45_000_000))
 frame = bench.synth_criteo(n, dev)
 cats = [c for c in frame.columns if c.startswith("C")]
 lib = K._lib.load()
-out = {"rows": n, "head16": os.environ.get("NVT_ENC_HEAD16", "1") != "0", "columns": {}}
+out = {"rows": n, "columns": {}}
 tot_m = tot_r = 0
 with tempfile.TemporaryDirectory() as tmp:
     for c in cats:

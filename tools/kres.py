@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""kres.py <file.hip> [name filter] [extra hipcc flags...]: registers / scratch / LDS per kernel
+"""kres.py <file.hip> [name filter] [extra hipcc flags...]: registers / scratch / LDS / occupancy per kernel
 (hipcc -Rpass-analysis=kernel-resource-usage, device code only; runs on the CPU box)."""
 import re
 import subprocess
@@ -19,12 +19,12 @@ for line in err.splitlines():
         cur = m.group(1)
         rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/\w+\])?: (\S+)", line)
+    m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]+\])?: (\S+)", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
     name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()
     if flt and flt not in name:
         continue
-    print(f"{name[:100]:100s} vgpr {v.get('VGPRs')} spill {v.get('VGPRs Spill')} sgpr {v.get('TotalSGPRs')} "
+    print(f"{name:100s} vgpr {v.get('VGPRs')} spill {v.get('VGPRs Spill')} sgpr {v.get('TotalSGPRs')} "
           f"sspill {v.get('SGPRs Spill')} scratch {v.get('ScratchSize')} lds {v.get('LDS Size')} occ {v.get('Occupancy')}")

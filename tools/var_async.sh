@@ -12,5 +12,4 @@ run async X=1
 run async_again X=1
 run sync NVT_ASYNC_FINALIZE=0
 run timing NVT_EVENT_TIMING=1
-run query NVT_FLUSH_QUERY=1
 run serial NVT_FINALIZE_SERIAL=1
