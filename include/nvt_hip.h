@@ -1148,6 +1148,74 @@ int nvt_list_len_minmax(const nvt_list_len_col *cols, int ncols, void *stream);
 int nvt_difference_lag_many(const nvt_lag_key *keys, int nkeys, const nvt_lag_col *cols, int ncols, uint64_t n,
                             void *stream);
 
+/* ---- exact column medians: ops.FillMedian (MSD radix select) ----
+ * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a
+ * negative value and the sign bit of the others, integers flip the sign bit.  The two middle
+ * ranks k_lo = (m - 1) / 2 and k_hi = m / 2 of the m participating rows are selected digit by
+ * digit, 11 bits at a time from the top: 3 passes for NVT_F32 / NVT_I32, 6 for NVT_F64 / NVT_I64.
+ * A row takes part when its validity bit is set (or valid is NULL) and its value is not NaN; with
+ * has_fill the other rows take part with fill_val, cast to the column type (the (x, valid, fill)
+ * convention of nvt_moments_many).
+ *
+ * state: ncols blocks of NVT_SELECT_STATE_WORDS uint64 words on the device, 8-byte aligned.  The
+ *   caller zeroes a block and sets NVT_SELECT_ST_BITS (32 / 64) and NVT_SELECT_ST_ALLOW_CAND
+ *   before pass 0.  The launch sequence does not depend on the data and nothing is read back
+ *   between the launches:
+ *     for pass in 0 .. passes - 1:
+ *       select_hist_many once per chunk (partition) of the columns   -- histograms add up
+ *       [ranks of a job: sum the NVT_SELECT_ST_HIST words of every block over the ranks]
+ *       select_step
+ *       pass == 1: select_finish
+ *   select_hist_many: one launch per NVT_SELECT_MAX_COLS descriptors; descriptor i belongs to
+ *     state block i.  Adds, per column, the digit of pass `pass` of every participating row
+ *     whose higher digits equal the prefix of a rank to that rank's NVT_SELECT_BINS-bin histogram
+ *     (per-workgroup LDS histograms, one global atomic per non-empty bin; a row is binned once
+ *     while both ranks share a prefix).  Returns at once for a column that is done or has no
+ *     digit `pass`.
+ *   select_step: one workgroup per column.  Pass 0: m = the rows counted, and the ranks.  Every
+ *     pass: the bin that holds each rank is appended to the rank's prefix, the rank becomes
+ *     relative to the bin, the histograms are zeroed.  NVT_SELECT_ST_DONE is set behind the last
+ *     digit, or at once when m == 0.
+ *   candidate path: when, behind pass 0, the bins of the two ranks hold at most
+ *     NVT_SELECT_CAND_CAP rows (and NVT_SELECT_ST_ALLOW_CAND is set), the pass-1 launch copies
+ *     the keys of those rows to the block's candidate buffer instead of counting them, and
+ *     select_finish (one workgroup per column) resolves the remaining digits there and sets
+ *     NVT_SELECT_ST_DONE.  Ranks of a job each hold only their own candidates: they leave
+ *     NVT_SELECT_ST_ALLOW_CAND 0.
+ *   result: NVT_SELECT_ST_M, and the keys of the two ranks in NVT_SELECT_ST_KEY_LO / _KEY_HI.
+ * Every entry is stream-ordered and does not synchronise. */
+#define NVT_SELECT_MAX_COLS 32
+#define NVT_SELECT_MAX_PASSES 6
+#define NVT_SELECT_BINS 2048
+#define NVT_SELECT_CAND_CAP 65536
+#define NVT_SELECT_ST_M 0           /* participating rows                                   */
+#define NVT_SELECT_ST_RANK_LO 1     /* the ranks, relative to the rows that share the prefix */
+#define NVT_SELECT_ST_RANK_HI 2
+#define NVT_SELECT_ST_KEY_LO 3      /* the digits selected so far (the bits below are 0)     */
+#define NVT_SELECT_ST_KEY_HI 4
+#define NVT_SELECT_ST_DONE 5
+#define NVT_SELECT_ST_NCAND 6       /* keys in the candidate buffer                          */
+#define NVT_SELECT_ST_USE_CAND 7
+#define NVT_SELECT_ST_PATH 8        /* NVT_SELECT_PATH_*: which way the column went (0: m == 0) */
+#define NVT_SELECT_ST_BITS 9        /* caller: key width, 32 or 64                           */
+#define NVT_SELECT_ST_ALLOW_CAND 10 /* caller: != 0 allows the candidate path                */
+#define NVT_SELECT_ST_HIST 16       /* 2 * NVT_SELECT_BINS counts: low rank, high rank       */
+#define NVT_SELECT_ST_CAND (16 + 2 * NVT_SELECT_BINS)
+#define NVT_SELECT_STATE_WORDS (NVT_SELECT_ST_CAND + NVT_SELECT_CAND_CAP)
+#define NVT_SELECT_PATH_CAND 1
+#define NVT_SELECT_PATH_FULL 2
+typedef struct nvt_select_col {
+  const void *x;            /* n values of one chunk, 16-byte aligned            */
+  const uint8_t *valid;     /* bitmap or NULL                                    */
+  uint64_t n;
+  int32_t dtype;            /* NVT_F32 / NVT_F64 / NVT_I32 / NVT_I64             */
+  int32_t has_fill;
+  double fill_val;
+} nvt_select_col;
+int nvt_select_hist_many(const nvt_select_col *cols, int ncols, int pass, void *state, void *stream);
+int nvt_select_step(void *state, int ncols, int pass, void *stream);
+int nvt_select_finish(void *state, int ncols, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

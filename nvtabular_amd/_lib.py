@@ -328,6 +328,26 @@ SIGNATURES.update({
     "nvt_difference_lag_many": [C.POINTER(LagKey), _i32, C.POINTER(LagCol), _i32, _u64, _vp],
 })
 
+class SelectCol(C.Structure):
+    """nvt_select_col: one chunk of one column read by nvt_select_hist_many."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("n", _u64), ("dtype", C.c_int32), ("has_fill", C.c_int32),
+                ("fill_val", _dbl)]
+
+
+# include/nvt_hip.h NVT_SELECT_*
+SELECT_MAX_COLS, SELECT_BINS, SELECT_CAND_CAP = 32, 2048, 65536
+(SELECT_ST_M, SELECT_ST_RANK_LO, SELECT_ST_RANK_HI, SELECT_ST_KEY_LO, SELECT_ST_KEY_HI, SELECT_ST_DONE,
+ SELECT_ST_NCAND, SELECT_ST_USE_CAND, SELECT_ST_PATH, SELECT_ST_BITS, SELECT_ST_ALLOW_CAND) = range(11)
+SELECT_ST_HIST = 16
+SELECT_ST_CAND = SELECT_ST_HIST + 2 * SELECT_BINS
+SELECT_STATE_WORDS = SELECT_ST_CAND + SELECT_CAND_CAP
+SELECT_PATH_CAND, SELECT_PATH_FULL = 1, 2
+SIGNATURES.update({
+    "nvt_select_hist_many": [C.POINTER(SelectCol), _i32, _i32, _vp, _vp],
+    "nvt_select_step": [_vp, _i32, _i32, _vp],
+    "nvt_select_finish": [_vp, _i32, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

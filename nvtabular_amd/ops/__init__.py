@@ -7,7 +7,7 @@ from .categorify import Categorify, get_embedding_sizes  # noqa: F401
 from .clip_log import Clip, LogOp  # noqa: F401
 from .difference_lag import DifferenceLag  # noqa: F401
 from .dropna import Dropna  # noqa: F401
-from .fill import FillMissing  # noqa: F401
+from .fill import FillMedian, FillMissing  # noqa: F401
 from .filter import Filter  # noqa: F401
 from .groupby import Groupby  # noqa: F401
 from .hash_bucket import HashBucket  # noqa: F401
