@@ -30,6 +30,8 @@
  *   nvtabular/ops/normalize.py:150-186     NormalizeMinMax      -> nvt_minmax, nvt_fill_normalize
  *   nvtabular/ops/join_groupby.py:175-217  JoinGroupby.transform-> nvt_gb_lookup + nvt_gather_f64
  *   nvtabular/ops/target_encoding.py:301-384 _op_group_logic    -> nvt_gb_lookup + nvt_te_apply
+ *   nvtabular/ops/data_stats.py:52-92      DataStats.fit        -> nvt_col_profile_many (+ nvt_dense_count_many)
+ *   nvtabular/ops/reduce_dtype_size.py:40-56 ReduceDtypeSize    -> nvt_col_profile_many, nvt_cast_many
  *   cpp/nvtabular/inference/categorify.cc:145-252, fill.cc:91-102 (serving-time
  *   encode / fill loops) have the same element semantics as nvt_encode_* /
  *   nvt_fill_normalize.
@@ -55,6 +57,9 @@ extern "C" {
 #define NVT_I32 2
 #define NVT_I64 3
 #define NVT_U8 4
+/* narrow integers: outputs of nvt_cast_many only, every other entry point refuses them */
+#define NVT_I8 5
+#define NVT_I16 6
 
 /* sentinel keys marking an empty hash slot; rows holding this key value are
  * counted in state[NVT_ST_SENTINEL] instead of the table */
@@ -1215,6 +1220,53 @@ typedef struct nvt_select_col {
 int nvt_select_hist_many(const nvt_select_col *cols, int ncols, int pass, void *state, void *stream);
 int nvt_select_step(void *state, int ncols, int pass, void *stream);
 int nvt_select_finish(void *state, int ncols, void *stream);
+
+/* ---- column profile and narrowing casts: ops.DataStats / ops.ReduceDtypeSize ----
+ * nvt_col_profile_many: every statistic of every column of a partition in ONE read of the column
+ *   (one launch per NVT_PROFILE_MAX_COLS descriptors plus one small final launch; no atomics, so a
+ *   result does not depend on scheduling).  A row counts when its validity bit is set (or valid is
+ *   NULL) and its value is not NaN.  The accumulators are device memory the caller initialises and
+ *   may fold several calls (partitions) into:
+ *     counts[2]   int64 {rows seen, rows that count}, added; start at 0.
+ *     extrema[2]  {min, max} of the rows that count.  NVT_I32 / NVT_I64: int64, exact (the value
+ *                 never passes through a double); start at INT64_MAX / INT64_MIN.  NVT_F32 /
+ *                 NVT_F64: double, NaN = nothing folded in yet (as nvt_minmax); -0.0 orders below
+ *                 +0.0, so the zero that comes out does not depend on where the zeros sit.
+ *     sums[2]     double {sum, sum of squares} of the rows that count, each converted to double
+ *                 first, added (nvt_moments with has_fill = 0); start at 0.
+ *   x need only be aligned to its element size (a slice of a larger buffer); nothing outside
+ *   [x, x + n) is read.  A descriptor with n == 0 launches nothing and leaves its accumulators
+ *   untouched.  partials: NVT_PROFILE_SCRATCH_BYTES of device scratch, 8-byte aligned, shared by
+ *   the batches of one call (they run in stream order).  A null descriptor array, ncols <= 0, a
+ *   null accumulator or an unknown dtype is NVT_EINVAL before the first launch.
+ * nvt_cast_many: dst[i] = (dst type) src[i], one launch per NVT_PROFILE_MAX_COLS descriptors.
+ *   NVT_I32 -> NVT_I8 / NVT_I16 and NVT_I64 -> NVT_I8 / NVT_I16 / NVT_I32 keep the low bits (two's
+ *   complement wrap, numpy's astype); NVT_F64 -> NVT_F32 rounds to nearest, ties to even, NaN stays
+ *   NaN and overflow goes to +-inf.  Any other pair (widening, int <-> float, same type) is
+ *   NVT_EINVAL before the first launch.  src / dst need only be aligned to their element size; a
+ *   lane writes whole 16-byte stores when dst is 16-byte aligned.  Validity bitmaps are not
+ *   touched: the output column shares the input's.
+ * Both entries are stream-ordered and do not synchronise. */
+#define NVT_PROFILE_MAX_COLS 32
+#define NVT_PROFILE_SCRATCH_BYTES (32 * 5 * 1024 * 8)
+typedef struct nvt_profile_col {
+  const void *x;            /* n values                                          */
+  const uint8_t *valid;     /* bitmap or NULL                                    */
+  uint64_t n;
+  int32_t dtype;            /* NVT_F32 / NVT_F64 / NVT_I32 / NVT_I64             */
+  int32_t reserved;
+  int64_t *counts;          /* device int64[2]                                   */
+  void *extrema;            /* device int64[2] (integer dtype) or double[2]      */
+  double *sums;             /* device double[2]                                  */
+} nvt_profile_col;
+typedef struct nvt_cast_col {
+  const void *src;          /* n values of src_dtype                             */
+  void *dst;                /* n values of dst_dtype                             */
+  uint64_t n;
+  int32_t src_dtype, dst_dtype;
+} nvt_cast_col;
+int nvt_col_profile_many(const nvt_profile_col *cols, int ncols, void *partials, void *stream);
+int nvt_cast_many(const nvt_cast_col *cols, int ncols, void *stream);
 
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */

@@ -11,7 +11,8 @@ for _name in ("ops", "workflow", "io", "schema", "selector", "node", "graph_json
     sys.modules[f"{__name__}.{_name}"] = importlib.import_module(f"nvtabular_amd.{_name}")
 for _sub in ("categorify", "normalize", "fill", "join_groupby", "target_encoding", "hash_bucket",
              "lambdaop", "groupby", "clip_log", "hashed_cross", "bucketize", "filter", "dropna", "join_external",
-             "list_slice", "value_counts", "difference_lag"):
+             "list_slice", "value_counts", "difference_lag", "reduce_dtype_size", "data_stats",
+             "drop_low_cardinality", "add_metadata"):
     try:
         sys.modules[f"{__name__}.ops.{_sub}"] = importlib.import_module(f"nvtabular_amd.ops.{_sub}")
     except ImportError:  # (an operator module this engine does not carry)

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("NVT_HIP_LIB") or os.path.join(_HERE, "libnvt_hip.so")
 
 # dtype codes (include/nvt_hip.h)
 NVT_F32, NVT_F64, NVT_I32, NVT_I64, NVT_U8 = 0, 1, 2, 3, 4
+NVT_I8, NVT_I16 = 5, 6   # outputs of nvt_cast_many only
 NVT_GB_SUMSQ, NVT_GB_MINMAX = 1, 2
 NVT_EINVAL, NVT_EHIP, NVT_ENOMEM, NVT_EUNSUPPORTED = -1, -2, -3, -4   # include/nvt_hip.h
 ENCODE_HEAD_BYTES = 12288 * 12 + 64   # NVT_ENCODE_HEAD_BYTES
@@ -346,6 +347,24 @@ SIGNATURES.update({
     "nvt_select_hist_many": [C.POINTER(SelectCol), _i32, _i32, _vp, _vp],
     "nvt_select_step": [_vp, _i32, _i32, _vp],
     "nvt_select_finish": [_vp, _i32, _vp],
+})
+
+class ProfileCol(C.Structure):
+    """nvt_profile_col: one column read by nvt_col_profile_many."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("n", _u64), ("dtype", C.c_int32), ("reserved", C.c_int32),
+                ("counts", _vp), ("extrema", _vp), ("sums", _vp)]
+
+
+class CastCol(C.Structure):
+    """nvt_cast_col: one column converted by nvt_cast_many."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("n", _u64), ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32)]
+
+
+# include/nvt_hip.h NVT_PROFILE_*
+PROFILE_MAX_COLS, PROFILE_SCRATCH_BYTES = 32, 32 * 5 * 1024 * 8
+SIGNATURES.update({
+    "nvt_col_profile_many": [C.POINTER(ProfileCol), _i32, _vp, _vp],
+    "nvt_cast_many": [C.POINTER(CastCol), _i32, _vp],
 })
 
 _RESTYPES = {

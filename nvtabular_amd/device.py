@@ -5,7 +5,8 @@ The reference's operators receive pandas or cuDF dataframes
 device-side frame is ``DeviceFrame``: an ordered dict of ``DeviceColumn`` whose
 buffers live in HBM in Arrow layout --
 
-  data     1-D contiguous values (int32/int64/float32/float64/uint8/bool)
+  data     1-D contiguous values (int32/int64/float32/float64/uint8/bool; int8/int16 are what
+           ReduceDtypeSize writes -- they are carried and written out, no other operator takes them)
   valid    optional Arrow validity bitmap (uint8, LSB first, 1 = valid)
   offsets  optional int64 row offsets (list columns; ``data`` holds the leaves)
   fill     optional pending FillMissing constant (logical value of a null row);
@@ -33,6 +34,8 @@ _NP_TO_TORCH = {
     np.dtype("float64"): torch.float64,
     np.dtype("uint8"): torch.uint8,
     np.dtype("bool"): torch.bool,
+    np.dtype("int8"): torch.int8,
+    np.dtype("int16"): torch.int16,
 }
 _TORCH_TO_NP = {v: k for k, v in _NP_TO_TORCH.items()}
 
@@ -254,6 +257,9 @@ class DeviceColumn:
             if mask is not None:
                 out[~mask] = None
             flat = pd.Series(out, name=name)
+        elif mask is not None and not mask.all() and vals.dtype in (np.int8, np.int16):
+            # (a narrowed column stays narrow: pandas' nullable Int8 / Int16)
+            flat = pd.Series(pd.arrays.IntegerArray(np.where(mask, vals, 0).astype(vals.dtype), ~mask), name=name)
         elif mask is not None and not mask.all():
             if vals.dtype.kind in "iub":
                 vals = vals.astype(np.float64)  # pandas' int-with-null convention

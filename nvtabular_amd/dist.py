@@ -131,6 +131,8 @@ def all_reduce_sum(t: torch.Tensor) -> torch.Tensor:
 def _nan_reduce(t: torch.Tensor, op) -> torch.Tensor:
     if world_size() == 1:
         return t
+    if not t.is_floating_point():   # integers have no NaN: nothing to mask (int64 extrema travel exact)
+        return _all_reduce(t, op)
     big = float("inf") if op == td.ReduceOp.MIN else float("-inf")
     x = torch.where(torch.isnan(t), torch.full_like(t, big), t)
     _all_reduce(x, op)
@@ -988,22 +990,31 @@ def merge_groups(comp: Dict, nkeys: int, nvals: int, sumsq=False, minmax=False) 
     return out
 
 
+def merge_host_dicts(d: Optional[dict]) -> Optional[dict]:
+    """Union of one host dictionary per rank (later ranks win on equal keys).
+
+    COLLECTIVE: with more than one rank every rank must call it at the same point, also a rank
+    that has nothing to contribute (None) -- it counts as an empty dictionary.  Returns None only
+    when every rank passed None."""
+    if world_size() == 1:
+        return d
+    gathered = [None] * world_size()
+    td.all_gather_object(gathered, d)
+    if all(x is None for x in gathered):
+        return None
+    out = {}
+    for x in gathered:
+        out.update(x or {})
+    return out
+
+
 def merge_string_luts(lut: Optional[dict]) -> Optional[dict]:
     """Union of the per-rank {surrogate -> string} dictionaries (host objects).
 
     COLLECTIVE: with more than one rank every rank must call it for the same column, also a
     rank whose shard was empty (lut None) -- it contributes an empty dictionary.  Returns None
     only when no rank had strings."""
-    if world_size() == 1:
-        return lut
-    gathered = [None] * world_size()
-    td.all_gather_object(gathered, lut)
-    if all(d is None for d in gathered):
-        return None
-    out = {}
-    for d in gathered:
-        out.update(d or {})
-    return out
+    return merge_host_dicts(lut)
 
 
 def barrier():

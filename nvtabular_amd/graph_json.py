@@ -366,12 +366,61 @@ def _build_later_registry():
         op.medians = {k: float(v) for k, v in s.get("medians", {}).items()}
         return op
 
+    later = {}
+
+    def reduce_to(op, d):
+        return ({"float_dtype": _np_dtype_param(op.float_dtype)},
+                {"ranges": {str(k): _json_safe(list(v)) for k, v in op.ranges.items()},
+                 "dtypes": {str(k): np.dtype(v).name for k, v in op.dtypes.items()}})
+
+    def reduce_from(p, s, d):
+        op = ops.ReduceDtypeSize(float_dtype=_np_dtype_from_param(p.get("float_dtype")) or np.float32)
+        op.ranges = {k: tuple(v) for k, v in s.get("ranges", {}).items()}
+        op.dtypes = {k: np.dtype(v) for k, v in s.get("dtypes", {}).items()}
+        return op
+
+    def stats_from(p, s, d):
+        op = ops.DataStats()
+        op.fit_finalize({k: dict(v) for k, v in s.get("output", {}).items()})
+        return op
+
+    # (the reference's serializer defers these three, graph_serializer.py:920-922: the records below
+    # follow the layout of the operators it does write -- parameters in op_params, fitted state in
+    # op_state, as NormalizeMinMax keeps its minima)
+    later["nvtabular.ops.reduce_dtype_size.ReduceDtypeSize"] = (ops.ReduceDtypeSize, reduce_to, reduce_from)
+    later["nvtabular.ops.data_stats.DataStats"] = (
+        ops.DataStats, lambda op, d: ({}, {"output": _json_safe(op.output)}), stats_from)
+    later["nvtabular.ops.drop_low_cardinality.DropLowCardinality"] = (
+        ops.DropLowCardinality, lambda op, d: ({"min_cardinality": op.min_cardinality}, {}),
+        lambda p, s, d: ops.DropLowCardinality(min_cardinality=p.get("min_cardinality", 4)))
+
+    def meta_to(op, d):
+        return ({"tags": _tags_to_list(op.tags), "properties": _json_safe(op.properties)}, {})
+
+    def meta_from(cls):
+        def build(p, s, d):
+            tags, props = _tags_from_list(p.get("tags", [])), p.get("properties", {})
+            if cls is ops.AddMetadata:
+                return cls(tags=tags, properties=props)
+            if cls is ops.AddTags:
+                return cls(tags=tags)
+            if cls is ops.AddProperties:
+                return cls(properties=props)
+            return cls()   # (the TagAs* shorthands carry their tags themselves)
+        return build
+
+    # graph_serializer.py:485-502 writes every subclass as AddMetadata; here each keeps its class
+    for cls in (ops.AddMetadata, ops.AddTags, ops.AddProperties, ops.TagAsUserID, ops.TagAsItemID,
+                ops.TagAsUserFeatures, ops.TagAsItemFeatures):
+        later[f"nvtabular.ops.add_metadata.{cls.__name__}"] = (cls, meta_to, meta_from(cls))
+
     # graph_serializer.py:334-347
-    return {"nvtabular.ops.fill.FillMedian": (
+    later["nvtabular.ops.fill.FillMedian"] = (
         ops.FillMedian,
         lambda op, d: ({"add_binary_cols": op.add_binary_cols},
                        {"medians": {str(k): float(v) for k, v in op.medians.items()}}),
-        median_from)}
+        median_from)
+    return later
 
 
 _REGISTRY: Dict[str, tuple] = {}

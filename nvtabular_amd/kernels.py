@@ -1627,6 +1627,109 @@ def moments_many(items):
     check(lib.nvt_moments_many(descs, len(items), buf.data_ptr(), stream_ptr()), "nvt_moments_many")
 
 
+# accumulator row of col_profile_many: int64[6] = {rows, valid rows, min, max, sum, sum of squares};
+# min / max are int64 for an integer column and float64 bits for a float column, the sums float64 bits
+PROFILE_WORDS = 6
+_INT64_MAX, _INT64_MIN = (1 << 63) - 1, -(1 << 63)
+
+
+def profile_is_float(dt: torch.dtype) -> bool:
+    return dt in (torch.float32, torch.float64)
+
+
+def new_profile_acc(dtypes, device) -> torch.Tensor:
+    """int64 [len(dtypes), PROFILE_WORDS] on ``device``, every row empty: counts and sums 0, extrema
+    INT64_MAX / INT64_MIN (integer column; bool / uint8 count as integers) or NaN (float column)."""
+    import numpy as np
+
+    host = np.zeros((len(dtypes), PROFILE_WORDS), dtype=np.int64)
+    for i, dt in enumerate(dtypes):
+        if profile_is_float(dt):
+            host[i, 2:4] = np.array([np.nan, np.nan]).view(np.int64)
+        else:
+            host[i, 2:4] = (_INT64_MAX, _INT64_MIN)
+    return torch.from_numpy(host).to(device)
+
+
+def profile_rows(host, dtypes):
+    """The rows of a profile accumulator on the host (numpy int64 [k, PROFILE_WORDS]) as Python
+    scalars: [dict(rows, valid, min, max, sum, sumsq)]; min / max are exact ints for an integer
+    column, floats for a float column, None when no row counted."""
+    import numpy as np
+
+    host = np.ascontiguousarray(host, dtype=np.int64).reshape(-1, PROFILE_WORDS)
+    out = []
+    for row, dt in zip(host, dtypes):
+        valid = int(row[1])
+        lo, hi = (row[2:4].view(np.float64).tolist() if profile_is_float(dt) else row[2:4].tolist())
+        s, s2 = row[4:6].view(np.float64).tolist()
+        out.append(dict(rows=int(row[0]), valid=valid, min=lo if valid else None,
+                        max=hi if valid else None, sum=s, sumsq=s2))
+    return out
+
+
+def col_profile_many(items):
+    """items: [(x, valid, acc_row)]: acc_row (one row of ``new_profile_acc`` made for x's dtype) takes
+    rows, valid rows, min, max, sum and sum of squares of x -- every column in ONE read, one launch
+    for all of them (nvt_col_profile_many).  x may be a slice: only element alignment is needed.
+    A bool / uint8 column is widened to int64 first and a non-contiguous one is copied: one extra
+    pass and a temporary for such a column in front of the one read."""
+    if not items:
+        return
+    _lib.require_gpu()
+    lib = _lib.load()
+    descs = (_lib.ProfileCol * len(items))()
+    keep = []
+    for d, (x, valid, acc) in zip(descs, items):
+        x = numeric(x)
+        x = x if x.is_contiguous() else x.contiguous()
+        assert acc.dtype == torch.int64 and acc.is_contiguous() and int(acc.numel()) == PROFILE_WORDS
+        keep.append(x)
+        d.x = x.data_ptr()
+        d.valid = ptr(valid)
+        d.n = x.numel()
+        d.dtype = dtype_code(x.dtype)
+        base = acc.data_ptr()
+        d.counts, d.extrema, d.sums = base, base + 16, base + 32
+    dev = keep[0].device
+    key = ("profile", dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _scratch.get(key)
+    if buf is None:
+        buf = _scratch[key] = torch.empty(_lib.PROFILE_SCRATCH_BYTES // 8, dtype=torch.int64, device=dev)
+    check(lib.nvt_col_profile_many(descs, len(items), buf.data_ptr(), stream_ptr()), "nvt_col_profile_many")
+
+
+_CAST_CODE = {torch.int8: _lib.NVT_I8, torch.int16: _lib.NVT_I16, torch.int32: _lib.NVT_I32,
+              torch.int64: _lib.NVT_I64, torch.float32: _lib.NVT_F32, torch.float64: _lib.NVT_F64}
+
+
+def cast_many(items):
+    """items: [(x, dst_dtype[, out])] -> [out]: int32 / int64 to a narrower integer (the low bits:
+    numpy's astype) and float64 to float32, one launch for all columns (nvt_cast_many).  A cast to
+    x's own dtype returns x itself: no launch, no copy.  Any other pair raises."""
+    outs, jobs = [], []
+    for item in items:
+        x, dst = item[0], item[1]
+        if x.dtype == dst:
+            outs.append(x)
+            continue
+        if x.dtype not in _CAST_CODE or dst not in _CAST_CODE:
+            raise TypeError(f"cast_many: unsupported cast {x.dtype} -> {dst}")
+        x = x if x.is_contiguous() else x.contiguous()
+        out = item[2] if len(item) > 2 else torch.empty(x.numel(), dtype=dst, device=x.device)
+        assert out.dtype == dst and out.is_contiguous() and int(out.numel()) >= int(x.numel())
+        jobs.append((x, out))
+        outs.append(out)
+    if jobs:
+        _lib.require_gpu()
+        descs = (_lib.CastCol * len(jobs))()
+        for d, (x, out) in zip(descs, jobs):
+            d.src, d.dst, d.n = x.data_ptr(), out.data_ptr(), x.numel()
+            d.src_dtype, d.dst_dtype = _CAST_CODE[x.dtype], _CAST_CODE[out.dtype]
+        check(_lib.load().nvt_cast_many(descs, len(jobs), stream_ptr()), "nvt_cast_many")
+    return outs
+
+
 def fill_normalize_many(items):
     """items: [(x, valid, fill, do_norm, shift, scale, out_dtype, want_filled_mask[, moments])] ->
     [(out, filled or None)]; one launch per dtype combination (nvt_fill_normalize_many).

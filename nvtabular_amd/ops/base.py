@@ -44,6 +44,10 @@ _LOCKED_METHODS = ("transform", "fit_partition", "fit_end", "fit_finalize", "cle
 class Operator:
     """Base class for all transforms (merlin.dag.BaseOperator)."""
 
+    # True: compute_selector reads properties that a fit fills in (DropLowCardinality); Workflow.fit
+    # then refreshes the graph's schemas and selectors behind every fit phase
+    selector_from_fit = False
+
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)
         for name in _LOCKED_METHODS:

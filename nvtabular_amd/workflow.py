@@ -205,6 +205,9 @@ class Workflow:
             self._fit_root_schema = dataset.schema
         nodes = iter_nodes(self.output_node)
         stat_nodes = [n for n in nodes if isinstance(n.op, StatOperator)]
+        # an operator whose selector reads fitted properties (DropLowCardinality): the graph's schemas
+        # and selectors are recomputed behind every fit phase, not lazily with the output schema
+        refresh = any(getattr(n.op, "selector_from_fit", False) for n in nodes if n.op is not None)
         fitted: set = set()
         shard = (dist.rank(), dist.world_size()) if dist.world_size() > 1 else None
         roots = self._root_columns()
@@ -233,6 +236,8 @@ class Workflow:
                 with annotate(n.op.range_name("fit")):
                     n.op.fit_finalize(n.op.fit_end(states[id(n)], n.input_columns))
                 fitted.add(id(n))
+            if refresh:
+                self.fit_schema(dataset.schema)
         # what the first transform would otherwise build in front of its first lookup (the lookup
         # images shared by the groupby operators of a key column) is enqueued behind the fit's last
         # kernels: it runs while the host walks into the transform
@@ -241,7 +246,7 @@ class Workflow:
             if prepare is not None:
                 prepare()
         # properties such as embedding sizes depend on the fitted state: refreshed lazily
-        self._stale_schema_root = dataset.schema
+        self._stale_schema_root = None if refresh else dataset.schema
         if any(getattr(n.op, "dynamic_dtypes", False) for n in nodes if n.op is not None):
             self._capture_dtypes(dataset)
         return self
