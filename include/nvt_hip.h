@@ -1268,6 +1268,53 @@ typedef struct nvt_cast_col {
 int nvt_col_profile_many(const nvt_profile_col *cols, int ncols, void *partials, void *stream);
 int nvt_cast_many(const nvt_cast_col *cols, int ncols, void *stream);
 
+/* ---- hash partitioning of rows by key: Dataset.shuffle_by_keys ----
+ * nvt_partition_ids: pid[i] = (uint32)(((mix(tags[i]) >> 32) * P) >> 32) with tags from
+ *   nvt_join_hash (equal key tuples, nulls included, have equal tags) and the fixed finaliser
+ *     mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *             z ^= z >> 31                                    (64-bit arithmetic, wrapping)
+ *   The partition comes from the high half of mix(tag): the raw tag's low bits, which address the
+ *   join tables, do not decide the balance.
+ * nvt_partition_plan: a STABLE counting sort of the row indices by pid (every pid < P): perm lists
+ *   the rows of partition 0 in ascending row order, then those of partition 1, ...; counts[p] = rows
+ *   of partition p.  1 <= P <= NVT_PARTITION_MAX, n < 2^32, a 16-byte aligned workspace of
+ *   nvt_partition_plan_ws_bytes(n, P) bytes.  No result depends on timing: two runs on the same
+ *   input are bit-identical.  n = 0 is a no-op (counts is not written).  Workgroups walk tiles of
+ *   nvt_partition_tile_rows() = NVT_PARTITION_TILE rows.
+ * nvt_partition_gather_many: ONE output partition of m rows from nsegs segments.  Segment s covers
+ *   the output rows [segs[s].start, segs[s + 1].start) (the last one up to m; segs[0].start = 0,
+ *   starts ascending, empty segments allowed) and output row j of it is row
+ *   segs[s].idx[j - segs[s].start] of the segment's source -- idx is a slice of one input
+ *   partition's perm.  `segs` and the per-column tables src / src_valid are DEVICE arrays of nsegs
+ *   entries (the caller uploads them once for all its launches); the descriptors themselves are
+ *   host memory.  src_valid is NULL (no segment has a bitmap: dst_valid must be NULL) or a table
+ *   whose NULL entries mean "all valid"; then dst_valid (ceil(m / 64) * 8 bytes, 8-byte aligned) is
+ *   written whole, bits past m zero.  At most NVT_PARTITION_MAX_COLS columns per launch and
+ *   NVT_PARTITION_MAX_SEGS segments; m = 0 is a no-op.  Every entry is stream-ordered. */
+#define NVT_PARTITION_MAX 4096
+#define NVT_PARTITION_TILE 512
+#define NVT_PARTITION_MAX_COLS 16
+#define NVT_PARTITION_MAX_SEGS 1024
+typedef struct nvt_partition_seg {
+  const int64_t *idx;       /* source rows of the segment's output rows          */
+  uint64_t start;           /* first output row of the segment                   */
+} nvt_partition_seg;
+typedef struct nvt_partition_col {
+  const void *const *src;          /* DEVICE table [nsegs]: the column in each segment's source */
+  const uint8_t *const *src_valid; /* DEVICE table [nsegs] of bitmaps (entries may be NULL), or NULL */
+  void *dst;                       /* m values                                    */
+  uint8_t *dst_valid;              /* bitmap of ceil(m / 64) * 8 bytes, with src_valid */
+  int32_t width;                   /* bytes per value: 1, 2, 4 or 8               */
+  int32_t reserved;
+} nvt_partition_col;
+int nvt_partition_tile_rows(void);
+int nvt_partition_ids(const uint64_t *tags, uint64_t n, uint32_t P, uint32_t *pid, void *stream);
+int nvt_partition_plan_ws_bytes(uint64_t n, uint32_t P, uint64_t *bytes);
+int nvt_partition_plan(const uint32_t *pid, uint64_t n, uint32_t P, int64_t *perm, uint64_t *counts, void *ws,
+                       uint64_t ws_bytes, void *stream);
+int nvt_partition_gather_many(const nvt_partition_col *cols, int ncols, const nvt_partition_seg *segs, int nsegs,
+                              uint64_t m, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

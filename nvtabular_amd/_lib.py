@@ -367,6 +367,27 @@ SIGNATURES.update({
     "nvt_cast_many": [C.POINTER(CastCol), _i32, _vp],
 })
 
+class PartitionSeg(C.Structure):
+    """nvt_partition_seg: one segment of an output partition (a DEVICE array of these is passed)."""
+    _fields_ = [("idx", _vp), ("start", _u64)]
+
+
+class PartitionCol(C.Structure):
+    """nvt_partition_col: one column moved by nvt_partition_gather_many."""
+    _fields_ = [("src", _vp), ("src_valid", _vp), ("dst", _vp), ("dst_valid", _vp), ("width", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# include/nvt_hip.h NVT_PARTITION_*
+PARTITION_MAX, PARTITION_MAX_COLS, PARTITION_MAX_SEGS = 4096, 16, 1024
+SIGNATURES.update({
+    "nvt_partition_tile_rows": [],
+    "nvt_partition_ids": [_vp, _u64, _u32, _vp, _vp],
+    "nvt_partition_plan_ws_bytes": [_u64, _u32, C.POINTER(_u64)],
+    "nvt_partition_plan": [_vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp],
+    "nvt_partition_gather_many": [C.POINTER(PartitionCol), _i32, _vp, _i32, _u64, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

@@ -250,6 +250,50 @@ class Dataset:
         self.cpu = False
         return self
 
+    def shuffle_by_keys(self, keys, hive_data=None, npartitions=None) -> "Dataset":
+        """Move every row to the partition its key hashes to (merlin.io.Dataset.shuffle_by_keys): all
+        rows with the same values in ``keys`` end up in one partition, which is what per-partition
+        operators such as ``ops.Groupby`` and ``ops.DifferenceLag(partition_cols=...)`` assume.
+
+        * ``keys``: a column name or a list of 1 to 4 names; string, integer, bool and float columns
+          (a null is a key value of its own, -0.0 equals 0.0); list columns cannot be keys.
+        * ``npartitions``: output partitions, 1 to 4096; default ``self.npartitions``.  A partition
+          that receives no rows is still there, empty and with the right dtypes.
+        * ``hive_data``: ``None`` / ``False`` shuffle on the device.  ``True`` (the reference's
+          short cut for hive-partitioned directories) is not supported.
+
+        The shuffle runs eagerly on the device (kernels_partition.shuffle_frames) and is stable: an
+        output partition holds its rows of input partition 0 in their original order, then those
+        of input partition 1, and so on.  All input partitions and all output partitions are
+        resident at once -- about twice the dataset in HBM (list columns: a third copy of them while
+        the call runs); nothing is spilled to the host.
+        Returns a new in-memory Dataset with the same schema and column order."""
+        from . import _lib, dist
+
+        keys = [keys] if isinstance(keys, str) else list(keys)
+        if not keys:
+            raise ValueError("shuffle_by_keys needs at least one key column")
+        if len(keys) > _lib.JOIN_MAX_KEYS:
+            raise NotImplementedError(f"shuffle_by_keys takes at most {_lib.JOIN_MAX_KEYS} key columns, "
+                                      f"got {len(keys)}")
+        if hive_data:
+            raise NotImplementedError("hive-partitioned directories are not tracked by this Dataset")
+        P = self.npartitions if npartitions is None else int(npartitions)
+        if not 1 <= P <= _lib.PARTITION_MAX:
+            raise ValueError(f"npartitions must be 1 to {_lib.PARTITION_MAX}, got {P}")
+        schema = self.schema
+        missing = [k for k in keys if k not in schema]
+        if missing:
+            raise ValueError(f"shuffle_by_keys: unknown key columns {missing}")
+        lists = [k for k in keys if schema[k].is_list]
+        if lists:
+            raise TypeError(f"shuffle_by_keys: list columns cannot be keys: {lists}")
+        if dist.world_size() > 1:
+            raise NotImplementedError("shuffle_by_keys across ranks is not supported")
+        from .kernels_partition import shuffle_frames
+
+        return Dataset(shuffle_frames(list(self.to_iter()), keys, P), schema=schema)
+
     def to_parquet(self, output_path, shuffle=None, out_files_per_proc=None, dtypes=None,
                    cats=None, conts=None, labels=None, preserve_files=False, suffix=".parquet",
                    num_threads=0, compression=None, statistics=False, **_):

@@ -55,7 +55,7 @@ def key_modes(left_classes: Sequence[str], ext_classes: Sequence[str], on, on_ex
     return tuple(modes)
 
 
-def _key_descs(cols, modes):
+def key_descs(cols, modes):
     """nvt_join_key descriptors of the key columns (pending fills applied), and the tensors to keep
     alive while the launches are enqueued."""
     descs = (_lib.JoinKey * len(cols))()
@@ -99,7 +99,7 @@ class ExternalIndex:
         nk = len(on_ext)
         dev = next(iter(ext.items()))[1].data.device if ext.columns else torch.device("cuda")
         self.nkeys, self.n_ext, self.modes = nk, n, modes
-        keys, alive = _key_descs([ext[c] for c in on_ext], modes)
+        keys, alive = key_descs([ext[c] for c in on_ext], modes)
         tag = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         nulls = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
         words = torch.empty((nk, max(n, 1)), dtype=torch.int64, device=dev) if nk > 1 else None
@@ -233,7 +233,7 @@ def join_frame(left, on: List[str], ix: ExternalIndex, how: str, ext_names: List
             out[name] = DeviceColumn(col.data[:0], None, None, None, col.strings)
         return out
     stream = K.stream_ptr()
-    keys, alive = _key_descs([left[c] for c in on], ix.modes)
+    keys, alive = key_descs([left[c] for c in on], ix.modes)
     inner = how == "inner"
 
     if ix.unique and not inner:

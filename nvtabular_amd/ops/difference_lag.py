@@ -1,7 +1,8 @@
 """DifferenceLag (reference: nvtabular/ops/difference_lag.py): the difference between a row and the
 row ``shift`` places before it (after it for a negative shift) inside one partition -- the time
 since a user's previous interaction.  The frame must already be grouped by ``partition_cols`` and
-sorted inside the groups.
+sorted inside the groups; ``Dataset.shuffle_by_keys(keys=partition_cols)`` brings all rows of a key
+into one partition, in their original order.
 
 For row i and j = i - shift the value is ``x[i] - x[j]`` when 0 <= j < n, every partition column is
 non-null and equal at i and j and x is non-null at both; NaN otherwise.  The output is float32

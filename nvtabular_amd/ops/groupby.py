@@ -6,7 +6,8 @@ Row -> group assignment runs on the multi-key hash tables of the JoinGroupby pat
 (``nvt_gb_update`` / ``nvt_gb_index_build`` / ``nvt_gb_lookup``); ordering the rows inside the
 groups and the segmented reductions are torch device ops -- this operator is graph plumbing
 around the hot path, not one of its kernels.  Like the reference
-it works partition by partition: shuffle the dataset by the keys first.
+it works partition by partition: shuffle the dataset by the keys first, with
+``Dataset.shuffle_by_keys(keys=groupby_cols)``.
 """
 from __future__ import annotations
 
