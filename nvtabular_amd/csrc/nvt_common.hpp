@@ -45,6 +45,9 @@ inline unsigned stream_grid(uint64_t work_items, unsigned per_block, unsigned bl
   return (unsigned)(need < cap ? need : cap);
 }
 
+// workspace layouts: every block starts on a 16-byte boundary
+inline uint64_t pad16(uint64_t x) { return (x + 15) & ~15ull; }
+
 // ---- hashing ---------------------------------------------------------------
 // Public hash: murmur3 fmix64 of the sign-extended key.
 __host__ __device__ __forceinline__ uint64_t fmix64(uint64_t k) {

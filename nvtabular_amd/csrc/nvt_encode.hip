@@ -1286,7 +1286,7 @@ int encode_build_any(int key_bytes, const void *vocab, uint64_t n, int64_t first
 }
 
 // the two halves of a build, for callers that fill most of the table themselves (the one-pass
-// vocabulary ordering, nvt_sort.hip): clear, then insert a duplicate-free int32 key range
+// vocabulary ordering, nvt_vocab_order.hip): clear, then insert a duplicate-free int32 key range
 int encode_clear_any(int key_bytes, void *table, uint64_t capacity, int64_t *sentinel_label,
                      hipStream_t s) {
   NVT_CHECK_ARG(table && sentinel_label, "null table");

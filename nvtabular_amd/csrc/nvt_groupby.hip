@@ -733,7 +733,7 @@ __global__ __launch_bounds__(kBlock) void gb_lookup_kernel(GbView t, GbRowArgs a
 //   sgb_fold_total_kernel  per-key totals as the sum over the key's folds (TargetEncoding needs
 //                        both tables, categorify.py:1344-1540 run twice in the reference)
 // and the key -> group index for the transform side is a flat range table laid out from the
-// sorted keys (flat_build_kernel, nvt_sort.hip) instead of a second hash table.
+// sorted keys (flat_build_kernel, nvt_vocab_order.hip) instead of a second hash table.
 #ifndef NVT_SGB_ROWS
 #define NVT_SGB_ROWS 16
 #endif

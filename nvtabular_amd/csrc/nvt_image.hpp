@@ -1,5 +1,5 @@
 // Lookup images (include/nvt_hip.h "Lookup images"): what the kernels that BUILD the packed
-// per-group records (nvt_sort.hip: nvt_jg_image / nvt_te_image / nvt_image_pack; nvt_keydir.hip:
+// per-group records (nvt_flat_lookup.hip: nvt_jg_image / nvt_te_image / nvt_image_pack; nvt_keydir.hip:
 // nvt_image_build) and the kernels that READ them (nvt_flat_lookup_image, nvt_keydir_lookup_image)
 // share -- one definition of every value, so that a record holds the same bits whichever kernel
 // wrote it.

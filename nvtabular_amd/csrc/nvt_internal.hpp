@@ -51,7 +51,7 @@ int sort_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, void *
                    int32_t *out_keys, int64_t *out_cnt, uint64_t out_cap, uint64_t *state,
                    hipStream_t s);
 
-// nvt_sort.hip: vocabulary order of a KEY-SORTED (key, count) list (range path) in one stable
+// nvt_vocab_order.hip: vocabulary order of a KEY-SORTED (key, count) list (range path) in one stable
 // counting pass on min(count, 255) + encode table filled in the same pass
 uint64_t vocab_order_tmp_bytes(uint64_t n, uint64_t n_big);
 int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, uint64_t n,

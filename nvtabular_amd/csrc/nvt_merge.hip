@@ -266,11 +266,10 @@ __global__ __launch_bounds__(kBlock) void merge_payload_kernel(
   }
 }
 
-static inline uint64_t mg_pad16(uint64_t x) { return (x + 15) & ~15ull; }
 static inline uint64_t mg_tiles(uint64_t total) { return (total + kMgTile - 1) / kMgTile; }
 static inline uint64_t mg_col_ws(uint64_t total) {
   const uint64_t nt = mg_tiles(total);
-  return mg_pad16((nt + 1) * 4) + nt * 8 + 16;
+  return pad16((nt + 1) * 4) + nt * 8 + 16;
 }
 
 }  // namespace nvt
@@ -330,7 +329,7 @@ int nvt_merge_sorted_many(const nvt_merge_col *cols, int ncols, void *ws, uint64
       m.nb = (unsigned)d.nb;
       const uint64_t nt = mg_tiles(total);
       m.splits = reinterpret_cast<unsigned *>(p);
-      m.status = reinterpret_cast<unsigned long long *>(p + mg_pad16((nt + 1) * 4));
+      m.status = reinterpret_cast<unsigned long long *>(p + pad16((nt + 1) * 4));
       m.ticket = reinterpret_cast<unsigned *>(m.status + nt);
       p += mg_col_ws(total);
       b.tile_start[i + 1] = b.tile_start[i] + (unsigned)nt;

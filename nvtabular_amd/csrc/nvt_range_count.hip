@@ -13,7 +13,7 @@
 //     table is emitted: the (key, count) list leaves this path SORTED BY KEY.  The vocabulary
 //     order "count descending, key ascending" (categorify.py:1300,1316) then needs a single
 //     stable counting pass on min(count, 255) instead of a 7-pass radix sort
-//     (nvt_sort.hip: cls_scatter_kernel).
+//     (nvt_vocab_order.hip: cls_scatter_kernel).
 //
 //   rp_partition_kernel  256 workgroups x 1024 threads, contiguous row slabs.  Per row: hot
 //                        lookup (one 8-byte LDS read) -> counter, or bin append (one returning

@@ -13,16 +13,12 @@
 #include <type_traits>
 
 #include <cstdlib>
-#include <vector>
 
 #include "nvt_common.hpp"
 #include "nvt_internal.hpp"
 #include "nvt_prof.hpp"
-#include "nvt_range.hpp"
-#include "nvt_image.hpp"
 #include "nvt_scan.hpp"
-
-extern "C" int nvt_vocab_sort_tmp_bytes(int key_bytes, uint64_t n, uint64_t *bytes);
+#include "nvt_sort_tile.hpp"
 
 namespace nvt {
 
@@ -142,17 +138,6 @@ __global__ __launch_bounds__(kBlock) void sort_tile_hist_kernel(const K *__restr
   tile_hist[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
 }
 
-// peers = lanes of this wave holding the same digit (inactive lanes excluded)
-__device__ __forceinline__ unsigned long long match_digit(unsigned digit, bool active) {
-  unsigned long long peers = __ballot(active);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    unsigned long long m = __ballot((digit >> b) & 1);
-    peers &= ((digit >> b) & 1) ? m : ~m;
-  }
-  return peers;
-}
-
 template <typename K>
 __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(
     const K *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n, int pass,
@@ -214,18 +199,6 @@ __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(
 // 8-entry (32 / 64 B) runs straight from registers and the key passes ran at a third of
 // the speed of the (nearly sequential) count passes.
 // The first pass reads (keys, counts) and packs; the last unpacks into (keys, counts).
-constexpr int kS2BS = 256, kS2Rows = 16, kS2Tile = kS2BS * kS2Rows;  // 4096 entries
-
-__device__ __forceinline__ uint64_t comp_make(int32_t key, int64_t cnt) {
-  return ((uint64_t)(~(uint32_t)cnt) << 32) | (uint64_t)((uint32_t)key ^ 0x80000000u);
-}
-__device__ __forceinline__ int32_t comp_key(uint64_t c) { return (int32_t)((uint32_t)c ^ 0x80000000u); }
-__device__ __forceinline__ int64_t comp_cnt(uint64_t c) { return (int64_t)(uint32_t)~(uint32_t)(c >> 32); }
-
-// element (wave w, row r, lane l) of a tile: waves own contiguous 1024-element runs (stability)
-__device__ __forceinline__ uint64_t s2_elem(uint64_t tile, unsigned w, unsigned r, unsigned l) {
-  return tile * kS2Tile + (uint64_t)w * (kS2Rows * kWave) + (uint64_t)r * kWave + l;
-}
 
 template <bool FIRST>
 __global__ __launch_bounds__(kS2BS) void sort2_hist_kernel(const uint64_t *__restrict__ comp,
@@ -348,8 +321,6 @@ __global__ __launch_bounds__(kS2BS) void sort2_scatter_kernel(
   }
 }
 
-inline uint64_t pad16(uint64_t x) { return (x + 15) & ~15ull; }
-
 // ---- int32 keys, packed words, ONESWEEP: one histogram read + one scatter launch per pass ---
 // The three-launch passes above (tile histogram -> device scan -> scatter) cost ~21-28 launches
 // and two extra reads of the array per sort; Criteo's 26 vocabularies spent more time in the
@@ -366,7 +337,6 @@ inline uint64_t pad16(uint64_t x) { return (x + 15) & ~15ull; }
 //                     "R2 granule" form of cdna_hip_programming.md G16), so no fences are needed.
 constexpr int kOsMaxPass = 8;
 constexpr int kOsHistBlocks = 1024;  // 4 per CU: 256 left 4 waves per CU waiting for their loads
-constexpr unsigned kOsAgg = 1u << 30, kOsPrefix = 2u << 30, kOsMask = (1u << 30) - 1u;
 
 __global__ __launch_bounds__(kS2BS) void os_hist_kernel(const int32_t *__restrict__ keys,
                                                         const int64_t *__restrict__ cnts,
@@ -992,1088 +962,6 @@ int vocab_sort_small_batch(const SmallSortDesc *cols, int ncols, hipStream_t s) 
   return NVT_OK;
 }
 
-// ---- vocabulary order from a KEY-SORTED (key, count) list: ONE stable counting pass ---------
-// The range path of the counting stage (nvt_range_count.hip) emits its list in key order and a
-// histogram of cls = min(count, 255).  "count descending, key ascending" (categorify.py:1300,
-// 1316) is then: class 255 (count >= 255; a few thousand entries of a 45 M-row power-law
-// column, never more than rows / 255) in front, then classes 254 .. 1, every class in the key
-// order it already has.  One stable scatter by class does that for all but the first class,
-// whose entries are sorted afterwards by the (small) generic sort; the encode table is filled
-// by the same scatter, where every entry learns its label.  Against the 7-pass radix sort +
-// separate table build: 12 B read + 12 B written per entry instead of ~120, 4 launches
-// instead of 11.
-// Same tile geometry, ballot ranking and decoupled look-back as os_scatter_kernel above.
-__device__ __forceinline__ unsigned cls_digit(uint64_t comp) {
-  const uint32_t cnt = ~(uint32_t)(comp >> 32);
-  return 255u - (cnt < 255u ? cnt : 255u);
-}
-
-__device__ __forceinline__ void cls_scatter_body(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n,
-    const unsigned *__restrict__ cls_hist, unsigned *status, unsigned *ticket, int32_t *out_keys,
-    int64_t *out_cnts, unsigned long long *table, uint64_t mask, int64_t first_label,
-    int64_t *sentinel_label, int32_t *label_of, int32_t *big_src = nullptr) {
-  // big_src set (a SHARD of a list that several ranks own, nvt_vocab_label_shard): only the
-  // entries of class 255 are written out (compacted in key order at the front of out_*, with
-  // their positions in the shard), every other entry only gets its label
-  constexpr int NW = kS2BS / kWave;
-  __shared__ unsigned wcnt[NW][256];
-  __shared__ unsigned goff[256];
-  __shared__ unsigned wtot[NW], btot[NW];
-  __shared__ unsigned s_tile;
-  __shared__ uint64_t stage[kS2Tile];
-  const unsigned w = threadIdx.x / kWave, l = lane_id();
-  if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1u);
-#pragma unroll
-  for (int q = 0; q < NW; ++q) wcnt[q][threadIdx.x] = 0;
-  // class bases: digit d = 255 - cls, base[d] = entries of the classes in front of it
-  unsigned cbase;
-  {
-    const unsigned v = cls_hist[255 - threadIdx.x];
-    unsigned inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      unsigned o = __shfl_up(inc, off, 64);
-      if (l >= (unsigned)off) inc += o;
-    }
-    if (l == 63) btot[w] = inc;
-    __syncthreads();
-    unsigned wb = 0;
-    for (unsigned q = 0; q < w; ++q) wb += btot[q];
-    cbase = wb + inc - v;
-  }
-  const unsigned tile = s_tile;
-  uint64_t c[kS2Rows];
-  unsigned short local[kS2Rows];
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    const uint64_t i = s2_elem(tile, w, r, l);
-    c[r] = ~0ull;
-    if (i < n) c[r] = comp_make(keys[i], cnts[i]);
-  }
-  const uint64_t tile_base = (uint64_t)tile * kS2Tile;
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    const bool act = s2_elem(tile, w, r, l) < n;
-    const unsigned d = cls_digit(c[r]);
-    const unsigned long long peers = match_digit(d, act);
-    const unsigned rank = __popcll(peers & ((1ull << l) - 1ull));
-    const unsigned before = act ? wcnt[w][d] : 0;
-    __builtin_amdgcn_wave_barrier();
-    if (act && rank == 0) wcnt[w][d] = before + (unsigned)__popcll(peers);
-    __builtin_amdgcn_wave_barrier();
-    local[r] = (unsigned short)(before + rank);
-  }
-  __syncthreads();
-  {
-    const unsigned d = threadIdx.x;
-    unsigned t[NW], tot = 0;
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      t[q] = wcnt[q][d];
-      tot += t[q];
-    }
-    unsigned *my = status + (uint64_t)tile * 256 + d;
-    __hip_atomic_store(my, (tile == 0 ? kOsPrefix : kOsAgg) | tot, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    unsigned inc = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      unsigned o = __shfl_up(inc, off, 64);
-      if (l >= (unsigned)off) inc += o;
-    }
-    if (l == 63) wtot[w] = inc;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (unsigned q = 0; q < w; ++q) wbase += wtot[q];
-    const unsigned dstart = wbase + inc - tot;
-    unsigned run = dstart;
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-      wcnt[q][d] = run;
-      run += t[q];
-    }
-    unsigned excl = 0;
-    if (tile > 0) {
-      unsigned tb = tile - 1;
-      while (true) {
-        const unsigned v = __hip_atomic_load(status + (uint64_t)tb * 256 + d, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned f = v >> 30;
-        if (f == 0) {
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        excl += v & kOsMask;
-        if (f == 2) break;
-        --tb;
-      }
-      __hip_atomic_store(my, kOsPrefix | (excl + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    goff[d] = cbase + excl - dstart;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    const uint64_t i = s2_elem(tile, w, r, l);
-    if (i < n) {
-      const unsigned d = cls_digit(c[r]);
-      const unsigned sidx = wcnt[w][d] + local[r];
-      stage[sidx] = c[r];
-      // range table: label of the entry at position i of the key-ordered list (class 255 is
-      // labelled after its own sort: -1 here)
-      if (label_of != nullptr) label_of[i] = d != 0 ? (int32_t)(first_label + goff[d] + sidx) : -1;
-      if (big_src != nullptr && d == 0) big_src[goff[0] + sidx] = (int32_t)i;
-    }
-  }
-  __syncthreads();
-  const unsigned tile_n = (unsigned)(n - tile_base < (uint64_t)kS2Tile ? n - tile_base : kS2Tile);
-#pragma unroll 4
-  for (int j = 0; j < kS2Rows; ++j) {
-    const unsigned idx = j * kS2BS + threadIdx.x;
-    if (idx < tile_n) {
-      const uint64_t v = stage[idx];
-      const unsigned d = cls_digit(v);
-      if (big_src != nullptr && d != 0) continue;
-      const unsigned dst = goff[d] + idx;
-      const int32_t key = comp_key(v);
-      out_keys[dst] = key;
-      out_cnts[dst] = comp_cnt(v);
-      if (key == INT32_MIN && d != 0 && sentinel_label != nullptr) {
-        *sentinel_label = first_label + (int64_t)dst;
-      } else if (table != nullptr && d != 0) {  // class 255 gets its labels after its own sort
-        const int64_t label = first_label + (int64_t)dst;
-        {
-          const unsigned long long want = ((unsigned long long)(uint32_t)label << 32) | (uint32_t)key;
-          uint64_t slot = (uint64_t)slot_hash(key) & mask;
-          while (atomicCAS(&table[slot], kEncEmptySlot, want) != kEncEmptySlot) slot = (slot + 1) & mask;
-        }
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(kS2BS) void cls_scatter_kernel(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n,
-    const unsigned *__restrict__ cls_hist, unsigned *status, unsigned *ticket, int32_t *out_keys,
-    int64_t *out_cnts, unsigned long long *table, uint64_t mask, int64_t first_label,
-    int64_t *sentinel_label, int32_t *label_of) {
-  cls_scatter_body(keys, cnts, n, cls_hist, status, ticket, out_keys, out_cnts, table, mask,
-                   first_label, sentinel_label, label_of);
-}
-
-// ---- the same ordering for SEVERAL vocabularies per launch --------------------------------
-// A Criteo fit orders 13 key-sorted vocabularies; one launch chain per vocabulary (memsets,
-// scatter, patch / build: ~10 launches each) kept the HOST busy for as long as the kernels ran
-// (~130 launches, 1.0 ms of a 12 ms step).  Here every stage is ONE launch for all vocabularies
-// of the call: the tiles of all lists form one grid (a block finds its vocabulary in a prefix
-// table of 16 entries), streaming stages use blockIdx.y = vocabulary.
-constexpr int kOrdBatch = 16;
-struct OrdJob {
-  const int32_t *keys;
-  const int64_t *cnts;
-  const unsigned *cls_hist;
-  unsigned *status, *ticket;
-  int32_t *out_keys;
-  int64_t *out_cnts;
-  int32_t *label_of;
-  unsigned long long *table;
-  int64_t *sentinel_label;
-  int32_t *aux;
-  unsigned long long *fb_status;
-  unsigned long long n, capacity, nslots, flat_slots, first_label, status_words, fb_words;
-};
-struct OrdBatch {
-  OrdJob j[kOrdBatch];
-  unsigned tile_start[kOrdBatch + 1];
-  unsigned flat_start[kOrdBatch + 1];
-  int njobs;
-};
-__device__ __forceinline__ int ord_job_of(const unsigned *start, int n, unsigned b) {
-  int c = 0;
-  while (c + 1 < n && b >= start[c + 1]) ++c;
-  return c;
-}
-
-__global__ __launch_bounds__(kBlock) void ord_prep_kernel(OrdBatch b) {
-  const OrdJob &j = b.j[blockIdx.y];
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  const uint64_t t0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  for (uint64_t i = t0; i < j.status_words; i += stride) j.status[i] = 0;   // + the ticket word
-  for (uint64_t i = t0; i < j.fb_words; i += stride) j.fb_status[i] = 0;
-  if (j.flat_slots) {  // flat table: every slot empty before the build
-    for (uint64_t i = t0; i < j.capacity; i += stride) j.table[i] = kEncEmptySlot;
-  }
-  if (t0 == 0) *j.sentinel_label = -1;
-}
-
-__global__ __launch_bounds__(kS2BS) void cls_scatter_many_kernel(OrdBatch b) {
-  const int ji = ord_job_of(b.tile_start, b.njobs, blockIdx.x);
-  const OrdJob &j = b.j[ji];
-  cls_scatter_body(j.keys, j.cnts, j.n, j.cls_hist, j.status, j.ticket, j.out_keys, j.out_cnts,
-                   nullptr, 0, (int64_t)j.first_label, j.sentinel_label, j.label_of);
-}
-
-// Range table (dumped by the counting pass: slot = {key, position in the key-ordered list}):
-// positions -> labels.  One streaming pass: the slots are in key order, so label_of[] is read
-// front to back as well.
-__global__ __launch_bounds__(kBlock) void range_patch_kernel(unsigned long long *table,
-                                                             uint64_t nslots,
-                                                             const int32_t *__restrict__ label_of) {
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock * 2;
-  for (uint64_t s0 = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * 2; s0 < nslots; s0 += stride) {
-    ulonglong2 e = *reinterpret_cast<ulonglong2 *>(table + s0);  // nslots is even, 16-byte aligned
-    bool dirty = false;
-    if ((int32_t)(uint32_t)e.x != INT32_MIN) {
-      e.x = ((unsigned long long)(uint32_t)label_of[(uint32_t)(e.x >> 32)] << 32) | (uint32_t)e.x;
-      dirty = true;
-    }
-    if ((int32_t)(uint32_t)e.y != INT32_MIN) {
-      e.y = ((unsigned long long)(uint32_t)label_of[(uint32_t)(e.y >> 32)] << 32) | (uint32_t)e.y;
-      dirty = true;
-    }
-    if (dirty) *reinterpret_cast<ulonglong2 *>(table + s0) = e;
-  }
-}
-
-// labels of the (few) entries of class 255 after their own sort: vocab[j] -> first_label + j
-__global__ __launch_bounds__(kBlock) void range_fix_prefix_kernel(
-    unsigned long long *table, const int32_t *__restrict__ aux, const int32_t *__restrict__ vocab,
-    uint64_t n_big, int64_t first_label, int64_t *sentinel_label, uint64_t table_slots) {
-  const RangeMap map = load_map(aux);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n_big; j += stride) {
-    const int32_t key = vocab[j];
-    const int64_t label = first_label + (int64_t)j;
-    if (key == INT32_MIN) {
-      *sentinel_label = label;
-      continue;
-    }
-    uint64_t s = map.table_slot(key);
-    if (map.flat) {  // runs in key order: bounded search (keys that cluster in their range)
-      s = flat_find_from(table, table_slots, s, key, table[s]);
-      if (s != ~0ull) table[s] = ((unsigned long long)(uint32_t)label << 32) | (uint32_t)key;
-      continue;
-    }
-    while (true) {
-      const unsigned long long e = table[s];
-      if ((int32_t)(uint32_t)e == key) {
-        table[s] = ((unsigned long long)(uint32_t)label << 32) | (uint32_t)key;
-        break;
-      }
-      if ((int32_t)(uint32_t)e == INT32_MIN) break;  // cannot happen for a key of the vocabulary
-      ++s;
-    }
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void range_patch_many_kernel(OrdBatch b) {
-  const OrdJob &j = b.j[blockIdx.y];
-  if (j.flat_slots || j.nslots == 0) return;
-  unsigned long long *table = j.table;
-  const int32_t *__restrict__ label_of = j.label_of;
-  const uint64_t nslots = j.nslots;
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock * 2;
-  for (uint64_t s0 = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) * 2; s0 < nslots; s0 += stride) {
-    ulonglong2 e = *reinterpret_cast<ulonglong2 *>(table + s0);
-    bool dirty = false;
-    if ((int32_t)(uint32_t)e.x != INT32_MIN) {
-      e.x = ((unsigned long long)(uint32_t)label_of[(uint32_t)(e.x >> 32)] << 32) | (uint32_t)e.x;
-      dirty = true;
-    }
-    if ((int32_t)(uint32_t)e.y != INT32_MIN) {
-      e.y = ((unsigned long long)(uint32_t)label_of[(uint32_t)(e.y >> 32)] << 32) | (uint32_t)e.y;
-      dirty = true;
-    }
-    if (dirty) *reinterpret_cast<ulonglong2 *>(table + s0) = e;
-  }
-}
-
-struct FixJob {
-  unsigned long long *table;
-  const int32_t *aux, *vocab;
-  int64_t *sentinel_label;
-  unsigned long long n_big, first_label, table_slots;
-};
-struct FixBatch {
-  FixJob j[kOrdBatch];
-};
-__global__ __launch_bounds__(kBlock) void range_fix_prefix_many_kernel(FixBatch b) {
-  const FixJob &f = b.j[blockIdx.y];
-  const RangeMap map = load_map(f.aux);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < f.n_big; j += stride) {
-    const int32_t key = f.vocab[j];
-    const int64_t label = (int64_t)f.first_label + (int64_t)j;
-    if (key == INT32_MIN) {
-      *f.sentinel_label = label;
-      continue;
-    }
-    uint64_t s = map.table_slot(key);
-    if (map.flat) {
-      s = flat_find_from(f.table, f.table_slots, s, key, f.table[s]);
-      if (s != ~0ull) f.table[s] = ((unsigned long long)(uint32_t)label << 32) | (uint32_t)key;
-      continue;
-    }
-    while (true) {
-      const unsigned long long e = f.table[s];
-      if ((int32_t)(uint32_t)e == key) {
-        f.table[s] = ((unsigned long long)(uint32_t)label << 32) | (uint32_t)key;
-        break;
-      }
-      if ((int32_t)(uint32_t)e == INT32_MIN) break;
-      ++s;
-    }
-  }
-}
-
-// histogram of min(count, 255) of a (key, count) list that did not come from the range path (the
-// multi-GPU merge gathers key-sorted owner shards): what cls_scatter_kernel needs
-__global__ __launch_bounds__(kBlock) void class_hist_kernel(const int64_t *__restrict__ cnts,
-                                                            uint64_t n, unsigned *hist) {
-  __shared__ unsigned h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  unsigned ones = 0;  // class 1 is most of a power-law vocabulary: counted in a register
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t c = cnts[i];
-    if (c == 1)
-      ++ones;
-    else
-      atomicAdd(&h[c < 255 ? (c < 0 ? 0 : (unsigned)c) : 255u], 1u);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ones += __shfl_down(ones, off, 64);
-  if (lane_id() == 0 && ones) atomicAdd(&h[1], ones);
-  __syncthreads();
-  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
-}
-
-// ---- flat range table from a KEY-SORTED list: no atomics, no random inserts ---------------------
-// A vocabulary table with linear probing and a MONOTONE slot function can be laid out directly
-// from the sorted keys: home slots h_i = f(K_i) are non-decreasing in i, so the position of entry
-// i is p_i = max(h_i, p_{i-1} + 1) = i + max_{j <= i}(h_j - j) -- a prefix MAXIMUM over the list
-// (decoupled look-back over the tiles), after which every entry is written once, positions
-// increasing.  Against 36 M random 8-byte CAS inserts (the sort path's vocabularies, or the
-// union a multi-GPU merge gathers): one streaming pass.  Lookups probe forward from f(key) to
-// the key or an empty slot, exactly like the dumped tables of the range path (RangeMap.flat).
-// The largest displacement p_i - h_i goes to aux[NVT_FLAT_AUX_MAXDISP]: keys that cluster in
-// their range make long runs, the caller then builds an ordinary hashed table instead.
-__device__ __forceinline__ void flat_params_body(const int32_t *__restrict__ keys, uint64_t n,
-                                                 uint64_t slots, int32_t *aux) {
-  // span of the (sorted) keys, the sentinel key (smallest int32, not in the table) left out
-  const uint64_t first = (n > 1 && keys[0] == INT32_MIN) ? 1 : 0;
-  const uint64_t lo = ukey(keys[first]), hi = ukey(keys[n - 1]);
-  const uint64_t span = hi - lo, F = slots;  // any slot count < 2^32 (no power of two needed)
-  uint32_t mul;
-  int sh;
-  range_map_params(span, F, &mul, &sh);
-  aux[NVT_RANGE_AUX_LO] = (int32_t)(uint32_t)lo;
-  aux[NVT_RANGE_AUX_LO + 1] = (int32_t)(uint32_t)span;
-  aux[NVT_RANGE_AUX_LO + 2] = (int32_t)mul;
-  aux[NVT_RANGE_AUX_LO + 3] = 0;
-  aux[NVT_RANGE_AUX_LO + 4] = sh;
-  aux[NVT_RANGE_AUX_LO + 5] = 1;  // flat layout
-  aux[NVT_RANGE_AUX_LO + 6] = keys[0] == INT32_MIN ? 1 : 0;  // position 0 holds the smallest int32 (not in the table)
-  aux[NVT_FLAT_AUX_MAXDISP] = 0;
-}
-__global__ void flat_params_kernel(const int32_t *__restrict__ keys, uint64_t n, uint64_t slots,
-                                   int32_t *aux) {
-  flat_params_body(keys, n, slots, aux);
-}
-
-constexpr unsigned long long kFbAgg = 1ull << 62, kFbPrefix = 2ull << 62, kFbMask = (1ull << 62) - 1ull;
-constexpr long long kFbBias = 1ll << 40;  // h - i is > -2^30: biased to an unsigned value
-
-__device__ __forceinline__ void flat_build_body(
-    const int32_t *__restrict__ keys, const int32_t *__restrict__ label_of, uint64_t n,
-    int32_t *aux, unsigned long long *status, unsigned *ticket, unsigned long long *table,
-    uint64_t table_slots) {
-  constexpr int NW = kS2BS / kWave;
-  __shared__ unsigned long long wmax[NW];
-  __shared__ unsigned long long s_carry;
-  __shared__ unsigned s_tile;
-  if (threadIdx.x == 0) s_tile = atomicAdd(ticket, 1u);
-  __syncthreads();
-  const unsigned tile = s_tile, w = threadIdx.x / kWave, l = lane_id();
-  const RangeMap map = load_map(aux);
-  // element (wave w, row r, lane l): waves own contiguous 1024-entry runs (s2_elem)
-  int32_t k[kS2Rows];
-  unsigned long long d[kS2Rows];  // biased h - i, 0 = no entry
-  unsigned long long run = 0;     // running maximum over this wave's rows so far
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    const uint64_t i = s2_elem(tile, w, r, l);
-    k[r] = i < n ? keys[i] : INT32_MIN;
-    d[r] = 0;
-    if (i < n && k[r] != INT32_MIN) d[r] = (unsigned long long)((long long)map.fine(k[r]) - (long long)i + kFbBias);
-  }
-  // inclusive prefix maximum inside the wave's run: lanes of a row, then the rows in order
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    unsigned long long v = d[r];
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long o = __shfl_up(v, off, 64);
-      if (l >= (unsigned)off) v = o > v ? o : v;
-    }
-    v = run > v ? run : v;
-    d[r] = v;
-    run = __shfl(v, 63, 64);
-  }
-  if (l == 63) wmax[w] = run;
-  __syncthreads();
-  unsigned long long wprev = 0, tmax = 0;
-  for (int q = 0; q < NW; ++q) {
-    if (q < (int)w) wprev = wmax[q] > wprev ? wmax[q] : wprev;
-    tmax = wmax[q] > tmax ? wmax[q] : tmax;
-  }
-  if (threadIdx.x == 0) {
-    unsigned long long *my = status + tile;
-    __hip_atomic_store(my, (tile == 0 ? kFbPrefix : kFbAgg) | tmax, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long carry = 0;
-    if (tile > 0) {
-      unsigned tb = tile - 1;
-      while (true) {
-        const unsigned long long v = __hip_atomic_load(status + tb, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned f = (unsigned)(v >> 62);
-        if (f == 0) {
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        const unsigned long long val = v & kFbMask;
-        carry = val > carry ? val : carry;
-        if (f == 2) break;
-        --tb;
-      }
-      const unsigned long long incl = carry > tmax ? carry : tmax;
-      __hip_atomic_store(my, kFbPrefix | incl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    s_carry = carry;
-  }
-  __syncthreads();
-  const unsigned long long before = s_carry > wprev ? s_carry : wprev;
-  unsigned maxdisp = 0;
-#pragma unroll
-  for (int r = 0; r < kS2Rows; ++r) {
-    const uint64_t i = s2_elem(tile, w, r, l);
-    if (i >= n || k[r] == INT32_MIN) continue;
-    const unsigned long long m = d[r] > before ? d[r] : before;
-    const uint64_t p = (uint64_t)((long long)i + ((long long)m - kFbBias));
-    const uint64_t h = map.fine(k[r]);
-    const unsigned disp = (unsigned)(p - h < 0xFFFFFFFFull ? p - h : 0xFFFFFFFFull);
-    maxdisp = disp > maxdisp ? disp : maxdisp;
-    if (p < table_slots)
-      table[p] = ((unsigned long long)(uint32_t)(label_of ? label_of[i] : (int32_t)i) << 32) | (uint32_t)k[r];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned o = __shfl_down(maxdisp, off, 64);
-    maxdisp = o > maxdisp ? o : maxdisp;
-  }
-  if (l == 0 && maxdisp > 0) atomicMax(reinterpret_cast<unsigned *>(aux + NVT_FLAT_AUX_MAXDISP), maxdisp);
-}
-__global__ __launch_bounds__(kS2BS) void flat_build_kernel(
-    const int32_t *__restrict__ keys, const int32_t *__restrict__ label_of, uint64_t n,
-    int32_t *aux, unsigned long long *status, unsigned *ticket, unsigned long long *table,
-    uint64_t table_slots) {
-  flat_build_body(keys, label_of, n, aux, status, ticket, table, table_slots);
-}
-__global__ void flat_params_many_kernel(OrdBatch b) {
-  const OrdJob &j = b.j[blockIdx.x];
-  if (j.flat_slots) flat_params_body(j.keys, j.n, j.flat_slots, j.aux);
-}
-__global__ __launch_bounds__(kS2BS) void flat_build_many_kernel(OrdBatch b) {
-  const int ji = ord_job_of(b.flat_start, b.njobs, blockIdx.x);
-  const OrdJob &j = b.j[ji];
-  const uint64_t ntiles = (j.n + kS2Tile - 1) / kS2Tile;
-  flat_build_body(j.keys, j.label_of, j.n, j.aux, j.fb_status,
-                  reinterpret_cast<unsigned *>(j.fb_status + ntiles), j.table, j.capacity);
-}
-
-// key -> position in the sorted list through a flat range table whose labels are the positions
-// (groupby group ids, join_groupby.py:198-203 / target_encoding.py:350-371: the reference's left
-// merge on the key column).  Probing runs forward from the key's home slot; the entries along a
-// run are in key order, so a larger key ends an unsuccessful probe as an empty slot does.
-struct FlatIndexView {
-  RangeMap map;
-  int64_t offset;  // table key = column key - offset (0 for int32 columns)
-  bool has_min;
-  int64_t null_group;  // group of the rows whose key is null (-1: none; aux word LO + 10 holds it + 1)
-  const unsigned long long *table;
-  uint64_t slots;
-};
-
-__device__ __forceinline__ FlatIndexView flat_view(const int32_t *__restrict__ aux,
-                                                   const unsigned long long *table, uint64_t slots,
-                                                   int64_t offset) {
-  FlatIndexView v;
-  v.map = load_map(aux);
-  v.offset = offset;
-  v.has_min = aux[NVT_RANGE_AUX_LO + 6] != 0;
-  v.null_group = (int64_t)aux[NVT_RANGE_AUX_LO + 10] - 1;
-  v.table = table;
-  v.slots = slots;
-  return v;
-}
-
-template <typename K>
-__device__ __forceinline__ int64_t flat_probe(const FlatIndexView &v, const K *__restrict__ keys,
-                                              const uint8_t *__restrict__ valid, uint64_t i) {
-  int64_t kv;
-  if (!bit_valid(valid, i)) return v.null_group;   // null keys are one group (groupby dropna=False)
-  if (__builtin_sub_overflow((int64_t)keys[i], v.offset, &kv)) return -1;
-  if (kv < (int64_t)INT32_MIN || kv > (int64_t)INT32_MAX) return -1;
-  const int32_t k = (int32_t)kv;
-  if (k == INT32_MIN) return v.has_min ? 0 : -1;
-  const uint64_t home = v.map.fine(k);
-  if (home >= v.slots) return -1;
-  unsigned long long w = 0;
-  const uint64_t sl = flat_find_from(v.table, v.slots, home, k, v.table[home], &w);
-  return sl == ~0ull ? -1 : (int64_t)(uint32_t)(w >> 32);
-}
-
-template <typename K>
-__global__ __launch_bounds__(kBlock) void flat_lookup_kernel(
-    const K *__restrict__ keys, const uint8_t *__restrict__ valid, uint64_t n,
-    const int32_t *__restrict__ aux, const unsigned long long *__restrict__ table, uint64_t slots,
-    int64_t offset, int64_t *__restrict__ out) {
-  const FlatIndexView v = flat_view(aux, table, slots, offset);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-    out[i] = flat_probe(v, keys, valid, i);
-}
-
-// JoinGroupby.transform in one pass (join_groupby.py:198-217): probe, then the group's record
-// of `ncols` float64 statistics (one 32-byte sector for count / sum / mean / std) instead of a
-// group-id column in HBM and one random gather per statistic.
-constexpr int kGatherMaxCols = 16;
-struct GatherOuts {
-  void *out[kGatherMaxCols];
-  int dtype[kGatherMaxCols];
-  double miss[kGatherMaxCols];
-};
-
-template <typename OUT>
-__device__ __forceinline__ void gather_store(void *out, uint64_t i, double x) {
-  reinterpret_cast<OUT *>(out)[i] = (OUT)x;
-}
-
-template <typename K, int NC>
-__global__ __launch_bounds__(kBlock) void flat_lookup_gather_kernel(
-    const K *__restrict__ keys, const uint8_t *__restrict__ valid, uint64_t n,
-    const int32_t *__restrict__ aux, const unsigned long long *__restrict__ table, uint64_t slots,
-    int64_t offset, const double *__restrict__ records, GatherOuts o, unsigned long long *unseen) {
-  const FlatIndexView v = flat_view(aux, table, slots, offset);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  bool any_unseen = false;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t g = flat_probe(v, keys, valid, i);
-    any_unseen |= g < 0;
-    double x[NC];
-    const double *rec = records + (uint64_t)(g < 0 ? 0 : g) * NC;
-    if constexpr (NC % 2 == 0) {  // records are 16-byte aligned: two statistics per load
-#pragma unroll
-      for (int c = 0; c < NC; c += 2) {
-        const double2 p = *reinterpret_cast<const double2 *>(rec + c);
-        x[c] = p.x;
-        x[c + 1] = p.y;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) x[c] = rec[c];
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {  // compile-time c: descriptors stay in scalar registers
-      const double y = g < 0 ? o.miss[c] : x[c];
-      switch (o.dtype[c]) {
-        case NVT_F32: gather_store<float>(o.out[c], i, y); break;
-        case NVT_F64: gather_store<double>(o.out[c], i, y); break;
-        case NVT_I32: gather_store<int32_t>(o.out[c], i, y); break;
-        default: gather_store<int64_t>(o.out[c], i, y); break;
-      }
-    }
-  }
-  if (unseen && __ballot(any_unseen) != 0ull && lane_id() == 0) atomicOr(unseen, 1ull);
-}
-
-template <typename K>
-static int launch_gather(int ncols, unsigned grid, hipStream_t s, const K *keys, const uint8_t *valid,
-                         uint64_t n, const int32_t *aux, const unsigned long long *tab,
-                         uint64_t capacity, int64_t offset, const double *records,
-                         const GatherOuts &o, unsigned long long *flag) {
-#define NVT_G(NC)                                                                                 \
-  case NC:                                                                                        \
-    flat_lookup_gather_kernel<K, NC><<<grid, kBlock, 0, s>>>(keys, valid, n, aux, tab, capacity, \
-                                                             offset, records, o, flag);          \
-    break;
-  switch (ncols) {
-    NVT_G(1) NVT_G(2) NVT_G(3) NVT_G(4) NVT_G(5) NVT_G(6) NVT_G(7) NVT_G(8)
-    NVT_G(9) NVT_G(10) NVT_G(11) NVT_G(12) NVT_G(13) NVT_G(14) NVT_G(15) NVT_G(16)
-    default: return NVT_EINVAL;
-  }
-#undef NVT_G
-  return NVT_OK;
-}
-
-// TargetEncoding.transform in one pass (target_encoding.py:341-371): probe, then the group's
-// record {sum, count, (sum_f, count_f) for every fold} -- 16 * (kfold + 1) contiguous bytes.
-// A (group, fold) pair without rows is the reference's unmatched [fold, key] merge: y_mean.
-template <typename K, typename OUT>
-__global__ __launch_bounds__(kBlock) void flat_lookup_te_kernel(
-    const K *__restrict__ keys, const uint8_t *__restrict__ valid, uint64_t n,
-    const int32_t *__restrict__ aux, const unsigned long long *__restrict__ table, uint64_t slots,
-    int64_t offset, const uint8_t *__restrict__ fold, unsigned kfold,
-    const double *__restrict__ records, double p, double y_mean, OUT *__restrict__ out) {
-  const FlatIndexView v = flat_view(aux, table, slots, offset);
-  const unsigned stride_rec = 2 * (kfold + 1);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t g = flat_probe(v, keys, valid, i);
-    double r = y_mean;
-    if (g >= 0) {
-      const double *rec = records + (uint64_t)g * stride_rec;
-      const double2 tot = *reinterpret_cast<const double2 *>(rec);
-      if (fold) {
-        const double2 f = *reinterpret_cast<const double2 *>(rec + 2 + 2 * (unsigned)fold[i]);
-        if (f.y > 0.0) r = (tot.x - f.x + p * y_mean) / (tot.y - f.y + p);
-      } else {
-        r = (tot.x + p * y_mean) / (tot.y + p);
-      }
-    }
-    out[i] = (OUT)r;
-  }
-}
-
-// ---- lookup images: ONE probe and ONE record per row for every operator on a key column ----
-// JoinGroupby.transform and TargetEncoding.transform on the same key column are two left merges
-// on the same key in the reference (join_groupby.py:198-217, target_encoding.py:341-371).  Here
-// every such operator ("consumer") owns a byte range of ONE packed per-group record whose values
-// are already what a row receives, in the OUTPUT dtype: JoinGroupby's statistics cast to
-// float32 / int32, TargetEncoding's smoothed value for every fold ((kfold + 1) values: slot 0 =
-// no fold, slot 1 + f = rows of fold f) -- the formula depends on (group, fold) only, so
-// evaluating it per group at the end of the fit gives the row's value bit for bit.  A row then
-// costs one random sector for the probe and one for its record (<= 64 bytes), whatever the
-// number of operators and statistics; the kernel moves 4- or 8-byte words, it does not convert.
-template <typename K, int MAXC>
-__global__ __launch_bounds__(kBlock) void flat_lookup_image_kernel(
-    const K *__restrict__ keys, const uint8_t *__restrict__ valid, uint64_t n,
-    const int32_t *__restrict__ aux, const unsigned long long *__restrict__ table, uint64_t slots,
-    int64_t offset, const int32_t *__restrict__ gid_in, int32_t *__restrict__ gid_out,
-    const uint8_t *__restrict__ image, uint32_t stride_bytes, int ncols, ImageOuts o,
-    unsigned long long *unseen) {
-  const FlatIndexView v = flat_view(aux, table, slots, offset);
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  bool any_unseen = false;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t g = gid_in ? (int64_t)gid_in[i] : flat_probe(v, keys, valid, i);
-    if (gid_out) gid_out[i] = (int32_t)g;
-    any_unseen |= g < 0;
-    const uint8_t *rec = image + (uint64_t)(g < 0 ? 0 : g) * stride_bytes;
-    uint64_t x[MAXC];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {  // all loads first: they hit the one sector of the record
-      if (c < ncols) {
-        uint32_t at = o.off[c];
-        if (o.fold[c]) at += (1u + (uint32_t)o.fold[c][i]) * o.fstride[c];
-        x[c] = o.size[c] == 8 ? *reinterpret_cast<const uint64_t *>(rec + at)
-                              : (uint64_t)*reinterpret_cast<const uint32_t *>(rec + at);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      if (c < ncols) {
-        const uint64_t y = g < 0 ? o.miss[c] : x[c];
-        if (o.size[c] == 8) __builtin_nontemporal_store(y, reinterpret_cast<uint64_t *>(o.out[c]) + i);
-        else __builtin_nontemporal_store((uint32_t)y, reinterpret_cast<uint32_t *>(o.out[c]) + i);
-      }
-    }
-  }
-  if (unseen && __ballot(any_unseen) != 0ull && lane_id() == 0) atomicOr(unseen, 1ull);
-}
-
-// image[g * stride + off + 4|8 * c] = (dst dtype) src[c][g]: a consumer's statistics (float64 /
-// int64 arrays of one value per group) written into its byte range of the records
-struct ImagePackArgs {
-  const void *src[kImageMaxCols];
-  int src_dtype[kImageMaxCols];  // NVT_F64 / NVT_I64
-  int dst_dtype[kImageMaxCols];  // NVT_F32 / NVT_F64 / NVT_I32 / NVT_I64
-  uint32_t off[kImageMaxCols];
-};
-
-__global__ __launch_bounds__(kBlock) void image_pack_kernel(ImagePackArgs a, int ncols, uint64_t groups,
-                                                            uint8_t *__restrict__ image,
-                                                            uint32_t stride_bytes) {
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += stride) {
-    uint8_t *rec = image + g * stride_bytes;
-    for (int c = 0; c < ncols; ++c) {
-      const bool is_int = a.src_dtype[c] == NVT_I64;
-      const double x = is_int ? 0.0 : reinterpret_cast<const double *>(a.src[c])[g];
-      const int64_t xi = is_int ? reinterpret_cast<const int64_t *>(a.src[c])[g] : 0;
-      image_store(rec + a.off[c], a.dst_dtype[c], x, xi, is_int);
-    }
-  }
-}
-
-// JoinGroupby's byte range straight from the fit's accumulators (join_groupby.py:175-217 over
-// categorify.py:1087-1131 _bottom_level_groupby): count, sum, mean = sum / n, var = (sumsq -
-// sum * sum / n) / max(n - 1, 1) (NaN for n = 1), std = sqrt(var), min, max -- evaluated per group
-// in float64 like the column-wise path (ops/_groupby.py derive_stats), stored in the output dtype.
-__global__ __launch_bounds__(kBlock) void jg_image_kernel(JgImageArgs a, int ncols, uint64_t groups,
-                                                          uint8_t *__restrict__ image, uint32_t stride_bytes) {
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += stride) {
-    uint8_t *rec = image + g * stride_bytes;
-    const int64_t ni = a.count[g];
-    for (int c = 0; c < ncols; ++c) {
-      bool is_int;
-      const double x = jg_stat(a, c, g, ni, &is_int);
-      image_store(rec + a.off[c], a.dst_dtype[c], x, ni, is_int);
-    }
-  }
-}
-
-// TargetEncoding's byte range: (kfold + 1) values per group from the fit's statistics -- totals
-// {count, sum}[g] and the dense per-(group, fold) {count, sum}[g * kfold + f] of the sort path
-// (nvt_sgb_reduce) -- exactly the expression nvt_te_apply_folds evaluates per row
-// (target_encoding.py:350-371), once per (group, fold).  A thread per value: the fold arrays are
-// read in memory order, a record's values leave as one contiguous run.
-template <typename OUT>
-__global__ __launch_bounds__(kBlock) void te_image_kernel(
-    const int64_t *__restrict__ tot_count, const double *__restrict__ tot_sum,
-    const int64_t *__restrict__ fold_count, const double *__restrict__ fold_sum, unsigned kfold,
-    uint64_t groups, double p, double y_mean, uint8_t *__restrict__ image, uint32_t stride_bytes,
-    uint32_t off) {
-  const unsigned per = kfold + 1;
-  const uint64_t total = groups * per, stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += stride) {
-    const uint64_t g = e / per;
-    const unsigned slot = (unsigned)(e - g * per);
-    const double r = te_value(tot_count, tot_sum, fold_count, fold_sum, kfold, g, slot, p, y_mean);
-    *reinterpret_cast<OUT *>(image + g * stride_bytes + off + slot * sizeof(OUT)) = (OUT)r;
-  }
-}
-
-// ---- vocabulary order of a list that is SHARDED over the ranks of a multi-GPU fit -------------
-// Every rank owns a key range of the merged (key, count) list.  The order "count descending, key
-// ascending" of the union is: class 255 (count >= 255, sorted exactly once all ranks' few such
-// entries are gathered), then classes 254 .. 1, each in key order = owner by owner, every owner's
-// entries in the order they have.  The label of an entry of class c < 255 is therefore
-//   (entries of the classes in front of c, all owners) + (entries of class c on the owners in
-//   front of this one) + (its rank among this shard's entries of class c)
-// -- the last term is what the class scatter computes; the first two come in as class bases
-// (`cls_hist` here is the caller's difference array of those bases: the kernel's exclusive prefix
-// over the digits reproduces them modulo 2^32).  Every rank orders 1 / G of the union instead of
-// all of it.
-__global__ __launch_bounds__(kS2BS) void label_shard_kernel(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n,
-    const unsigned *__restrict__ cls_hist, unsigned *status, unsigned *ticket, int32_t *big_keys,
-    int64_t *big_cnts, int32_t *label_of, int32_t *big_src) {
-  cls_scatter_body(keys, cnts, n, cls_hist, status, ticket, big_keys, big_cnts, nullptr, 0, 0, nullptr,
-                   label_of, big_src);
-}
-
-// vocabulary + table from a key-sorted list whose entries carry their position in the vocabulary
-// order (labels[i], 0-based): ordered arrays by ONE scatter, absolute labels for the table build
-__global__ __launch_bounds__(kBlock) void label_scatter_kernel(
-    const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, const int32_t *__restrict__ labels,
-    uint64_t n, int64_t first_label, int32_t *__restrict__ out_keys, int64_t *__restrict__ out_cnts,
-    int32_t *__restrict__ abs_label, int64_t *sentinel_label) {
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int32_t k = keys[i];
-    const uint32_t l = (uint32_t)labels[i];
-    out_keys[l] = k;
-    out_cnts[l] = cnts[i];
-    abs_label[i] = (int32_t)(first_label + (int64_t)l);
-    if (k == INT32_MIN && sentinel_label != nullptr) *sentinel_label = first_label + (int64_t)l;
-  }
-}
-
-int vocab_from_labels(const int32_t *src_keys, const int64_t *src_cnts, const int32_t *labels, uint64_t n,
-                      int32_t *out_keys, int64_t *out_cnts, void *tmp, int64_t first_label, void *table,
-                      uint64_t capacity, int64_t *sentinel_label, const int32_t *range_aux,
-                      uint64_t flat_slots, hipStream_t s) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(n < (1ull << 30), "at most 2^30-1 vocabulary entries");
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  // same layout as vocab_order_from_sorted with n_big = 0: status | label_of[n] | flat-build status
-  int32_t *abs_label = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(tmp) + pad16(ntiles * 256 * 4 + 64));
-  unsigned long long *fb_status =
-      reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(abs_label) + pad16(n * 4));
-  const bool flat = table != nullptr && range_aux != nullptr && flat_slots > 0;
-  if (table != nullptr) {
-    if (flat) {
-      NVT_CHECK_ARG(flat_slots >= 64 && flat_slots < (1ull << 32), "flat table: 64 .. 2^32-1 slots");
-      NVT_CHECK_ARG(capacity >= flat_slots + n + 64, "flat table: slots + n + 64");
-    }
-    int rc = encode_clear_any(4, table, capacity, sentinel_label, s);  // (also: no sentinel key yet)
-    if (rc) return rc;
-  }
-  NVT_PROF("vocab_order", 0, s);
-  label_scatter_kernel<<<stream_grid(n, kBlock, 8), kBlock, 0, s>>>(src_keys, src_cnts, labels, n, first_label,
-                                                                    out_keys, out_cnts, abs_label,
-                                                                    table != nullptr ? sentinel_label : nullptr);
-  NVT_CHECK_LAUNCH();
-  if (flat) {
-    int32_t *aux = const_cast<int32_t *>(range_aux);
-    flat_params_kernel<<<1, 1, 0, s>>>(src_keys, n, flat_slots, aux);
-    NVT_CHECK_LAUNCH();
-    NVT_CHECK_HIP(hipMemsetAsync(fb_status, 0, ntiles * 8 + 64, s));
-    flat_build_kernel<<<(unsigned)ntiles, kS2BS, 0, s>>>(src_keys, abs_label, n, aux, fb_status,
-                                                        reinterpret_cast<unsigned *>(fb_status + ntiles),
-                                                        (unsigned long long *)table, capacity);
-    NVT_CHECK_LAUNCH();
-  } else if (table != nullptr) {
-    // an ordinary hashed table: the ordered keys carry the labels first_label + position
-    int rc = encode_insert_any(4, out_keys, n, first_label, table, capacity, sentinel_label, s);
-    if (rc) return rc;
-  }
-  return NVT_OK;
-}
-
-uint64_t vocab_order_tmp_bytes(uint64_t n, uint64_t n_big) {
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  uint64_t sort_bytes = 0;
-  if (n_big > 1) (void)nvt_vocab_sort_tmp_bytes(4, n_big, &sort_bytes);
-  // status words of the class scatter | sort scratch | label_of[n] | status words of the flat build
-  return pad16(ntiles * 256 * 4 + 64) + pad16(sort_bytes) + pad16(n * 4) + pad16(ntiles * 8 + 64) + 64;
-}
-
-int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, uint64_t n,
-                            const unsigned *cls_hist, uint64_t n_big, int64_t max_count,
-                            int32_t *out_keys, int64_t *out_cnts, void *tmp, int64_t first_label,
-                            void *table, uint64_t capacity, int64_t *sentinel_label,
-                            const int32_t *range_aux, int range_nb_log2, hipStream_t s,
-                            bool *tail_deferred, uint64_t flat_slots) {
-  *tail_deferred = false;
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(n < (1ull << 30), "at most 2^30-1 vocabulary entries");
-  NVT_CHECK_ARG(n_big <= n, "n_big > n");
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  unsigned *status = reinterpret_cast<unsigned *>(tmp);
-  unsigned *ticket = status + ntiles * 256;
-  uint64_t sort_bytes = 0;
-  if (n_big > 1) (void)nvt_vocab_sort_tmp_bytes(4, n_big, &sort_bytes);
-  char *sort_tmp = reinterpret_cast<char *>(tmp) + pad16(ntiles * 256 * 4 + 64);
-  int32_t *label_of = reinterpret_cast<int32_t *>(sort_tmp + pad16(sort_bytes));
-  unsigned long long *fb_status =
-      reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(label_of) + pad16(n * 4));
-  // range table (range_aux set): `table` holds {key, position} slots already (dumped by the
-  // counting pass) and only needs its positions replaced by labels -- no clear, no inserts.
-  // flat (flat_slots > 0, range_aux = the block that RECEIVES the map): the table is laid
-  // out from the sorted keys by a prefix maximum, see flat_build_kernel.
-  const bool flat = table != nullptr && range_aux != nullptr && flat_slots > 0;
-  const bool ranged = table != nullptr && range_aux != nullptr;
-  if (flat) {
-    NVT_CHECK_ARG(flat_slots >= 64 && flat_slots < (1ull << 32), "flat table: 64 .. 2^32-1 slots");
-    NVT_CHECK_ARG(capacity >= flat_slots + n + 64, "flat table: slots + n + 64");
-    int rc = encode_clear_any(4, table, capacity, sentinel_label, s);
-    if (rc) return rc;
-  } else if (table && !ranged) {
-    int rc = encode_clear_any(4, table, capacity, sentinel_label, s);
-    if (rc) return rc;
-  } else if (ranged) {
-    NVT_CHECK_HIP(hipMemsetAsync(sentinel_label, 0xFF, 8, s));  // -1: no sentinel key
-  }
-  {
-    NVT_PROF("vocab_order", 0, s);
-    NVT_CHECK_HIP(hipMemsetAsync(status, 0, ntiles * 256 * 4 + 64, s));
-    cls_scatter_kernel<<<(unsigned)ntiles, kS2BS, 0, s>>>(
-        src_keys, src_cnts, n, cls_hist, status, ticket, out_keys, out_cnts,
-        ranged ? nullptr : (unsigned long long *)table, capacity - 1, first_label, sentinel_label,
-        ranged ? label_of : nullptr);
-    NVT_CHECK_LAUNCH();
-    if (flat) {
-      int32_t *aux = const_cast<int32_t *>(range_aux);
-      flat_params_kernel<<<1, 1, 0, s>>>(src_keys, n, flat_slots, aux);
-      NVT_CHECK_LAUNCH();
-      NVT_CHECK_HIP(hipMemsetAsync(fb_status, 0, ntiles * 8 + 64, s));
-      flat_build_kernel<<<(unsigned)ntiles, kS2BS, 0, s>>>(
-          src_keys, label_of, n, aux, fb_status, reinterpret_cast<unsigned *>(fb_status + ntiles),
-          (unsigned long long *)table, capacity);
-      NVT_CHECK_LAUNCH();
-    } else if (ranged) {
-      const uint64_t nslots = ((uint64_t)1 << range_nb_log2) * kRpRegion + kRpGuard;
-      range_patch_kernel<<<stream_grid(nslots / 2, kBlock, 8), kBlock, 0, s>>>(
-          (unsigned long long *)table, nslots, label_of);
-      NVT_CHECK_LAUNCH();
-    }
-  }
-  // the sort of class 255 and the labels of its entries: left to ONE batched launch for all the
-  // vocabularies of the call (vocab_order_tail_batch)
-  if (vocab_sort_small_eligible(4, n_big, max_count)) {
-    *tail_deferred = true;
-    return NVT_OK;
-  }
-  if (n_big > 1) {
-    int rc = vocab_sort_any(4, out_keys, out_cnts, n_big, max_count, sort_tmp, s);
-    if (rc) return rc;
-  }
-  if (table && n_big > 0) {
-    if (ranged) {
-      NVT_PROF("encode_build", 0, s);
-      range_fix_prefix_kernel<<<stream_grid(n_big, kBlock), kBlock, 0, s>>>(
-          (unsigned long long *)table, range_aux, out_keys, n_big, first_label, sentinel_label,
-          capacity);
-      NVT_CHECK_LAUNCH();
-    } else {
-      int rc = encode_insert_any(4, out_keys, n_big, first_label, table, capacity, sentinel_label, s);
-      if (rc) return rc;
-    }
-  }
-  return NVT_OK;
-}
-
-// vocab_order_from_sorted for several vocabularies that own a range table (dumped or flat): every
-// stage one launch (ord_prep / cls_scatter_many / flat_params_many + flat_build_many /
-// range_patch_many), then the class-255 tails (one batched small sort + one label launch; a tail
-// too long for the small sort is sorted on its own).
-int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t s) {
-  for (int j0 = 0; j0 < njobs; j0 += kOrdBatch) {
-    const int nj = njobs - j0 < kOrdBatch ? njobs - j0 : kOrdBatch;
-    OrdBatch b;
-    memset(&b, 0, sizeof(b));
-    std::vector<OrderTail> tails;
-    bool any_flat = false, any_ranged = false;
-    for (int i = 0; i < nj; ++i) {
-      const OrderSortedJob &q = jobs[j0 + i];
-      NVT_CHECK_ARG(q.n > 0 && q.n < (1ull << 30), "1 .. 2^30-1 vocabulary entries");
-      NVT_CHECK_ARG(q.n_big <= q.n, "n_big > n");
-      NVT_CHECK_ARG(q.table && q.range_aux && q.tmp && q.sentinel_label, "range table jobs only");
-      const uint64_t ntiles = (q.n + kS2Tile - 1) / kS2Tile;
-      unsigned *status = reinterpret_cast<unsigned *>(q.tmp);
-      uint64_t sort_bytes = 0;
-      if (q.n_big > 1) (void)nvt_vocab_sort_tmp_bytes(4, q.n_big, &sort_bytes);
-      char *sort_tmp = reinterpret_cast<char *>(q.tmp) + pad16(ntiles * 256 * 4 + 64);
-      int32_t *label_of = reinterpret_cast<int32_t *>(sort_tmp + pad16(sort_bytes));
-      OrdJob &o = b.j[i];
-      o.keys = q.src_keys;
-      o.cnts = q.src_cnts;
-      o.cls_hist = q.cls_hist;
-      o.status = status;
-      o.ticket = status + ntiles * 256;
-      o.out_keys = q.out_keys;
-      o.out_cnts = q.out_cnts;
-      o.label_of = label_of;
-      o.table = reinterpret_cast<unsigned long long *>(q.table);
-      o.sentinel_label = q.sentinel_label;
-      o.aux = const_cast<int32_t *>(q.range_aux);
-      o.fb_status = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(label_of) + pad16(q.n * 4));
-      o.n = q.n;
-      o.capacity = q.capacity;
-      o.flat_slots = q.flat_slots;
-      o.nslots = q.flat_slots ? 0 : ((uint64_t)1 << q.range_nb_log2) * kRpRegion + kRpGuard;
-      o.first_label = (unsigned long long)q.first_label;
-      o.status_words = ntiles * 256 + 16;
-      o.fb_words = q.flat_slots ? ntiles + 8 : 0;
-      if (q.flat_slots) {
-        NVT_CHECK_ARG(q.flat_slots >= 64 && q.flat_slots < (1ull << 32), "flat table: 64 .. 2^32-1 slots");
-        NVT_CHECK_ARG(q.capacity >= q.flat_slots + q.n + 64, "flat table: slots + n + 64");
-        any_flat = true;
-      } else {
-        any_ranged = true;
-      }
-      b.tile_start[i + 1] = b.tile_start[i] + (unsigned)ntiles;
-      b.flat_start[i + 1] = b.flat_start[i] + (q.flat_slots ? (unsigned)ntiles : 0u);
-    }
-    b.njobs = nj;
-    {
-      NVT_PROF("vocab_order", 0, s);
-      ord_prep_kernel<<<dim3(any_flat ? 2048 : 64, nj), kBlock, 0, s>>>(b);
-      NVT_CHECK_LAUNCH();
-      cls_scatter_many_kernel<<<b.tile_start[nj], kS2BS, 0, s>>>(b);
-      NVT_CHECK_LAUNCH();
-      if (any_flat) {
-        flat_params_many_kernel<<<nj, 1, 0, s>>>(b);
-        NVT_CHECK_LAUNCH();
-        flat_build_many_kernel<<<b.flat_start[nj], kS2BS, 0, s>>>(b);
-        NVT_CHECK_LAUNCH();
-      }
-      if (any_ranged) {
-        range_patch_many_kernel<<<dim3(1024, nj), kBlock, 0, s>>>(b);
-        NVT_CHECK_LAUNCH();
-      }
-    }
-    for (int i = 0; i < nj; ++i) {
-      const OrderSortedJob &q = jobs[j0 + i];
-      if (q.n_big == 0) continue;
-      if (vocab_sort_small_eligible(4, q.n_big, q.max_count)) {
-        tails.push_back({q.out_keys, q.out_cnts, q.n_big, q.first_label, q.table, q.capacity,
-                         q.sentinel_label, q.range_aux});
-        continue;
-      }
-      // a class 255 beyond the one-workgroup sort (merged multi-partition vocabularies), or of
-      // one entry (nothing to sort)
-      if (q.n_big > 1) {
-        const uint64_t ntiles = (q.n + kS2Tile - 1) / kS2Tile;
-        char *sort_tmp = reinterpret_cast<char *>(q.tmp) + pad16(ntiles * 256 * 4 + 64);
-        int rc = vocab_sort_any(4, q.out_keys, q.out_cnts, q.n_big, q.max_count, sort_tmp, s);
-        if (rc) return rc;
-      }
-      NVT_PROF("encode_build", 0, s);
-      range_fix_prefix_kernel<<<stream_grid(q.n_big, kBlock), kBlock, 0, s>>>(
-          (unsigned long long *)q.table, q.range_aux, q.out_keys, q.n_big, q.first_label,
-          q.sentinel_label, q.capacity);
-      NVT_CHECK_LAUNCH();
-    }
-    if (!tails.empty()) {
-      int rc = vocab_order_tail_batch(tails.data(), (int)tails.size(), s);
-      if (rc) return rc;
-    }
-  }
-  return NVT_OK;
-}
-
-// class 255 of several vocabularies (vocab_order_from_sorted with tail_deferred): ONE batched
-// sort launch (a workgroup per vocabulary) instead of a one-workgroup launch per vocabulary,
-// then the labels of the sorted entries
-int vocab_order_tail_batch(const OrderTail *t, int nt, hipStream_t s) {
-  if (nt == 0) return NVT_OK;
-  std::vector<SmallSortDesc> d(nt);
-  for (int i = 0; i < nt; ++i) {
-    d[i].keys = t[i].keys;
-    d[i].counts = t[i].counts;
-    d[i].n = (unsigned)t[i].n_big;
-  }
-  int rc = vocab_sort_small_batch(d.data(), nt, s);
-  if (rc) return rc;
-  NVT_PROF("encode_build", 0, s);
-  // range tables (dumped or flat): the labels of all vocabularies in one launch
-  for (int i0 = 0; i0 < nt;) {
-    FixBatch fb;
-    memset(&fb, 0, sizeof(fb));
-    int nf = 0;
-    uint64_t longest = 0;
-    for (; i0 < nt && nf < kOrdBatch; ++i0) {
-      if (!t[i0].table || !t[i0].range_aux) continue;
-      fb.j[nf++] = {(unsigned long long *)t[i0].table, t[i0].range_aux, t[i0].keys,
-                    t[i0].sentinel_label, t[i0].n_big, (unsigned long long)t[i0].first_label,
-                    t[i0].capacity};
-      longest = t[i0].n_big > longest ? t[i0].n_big : longest;
-    }
-    if (nf) {
-      range_fix_prefix_many_kernel<<<dim3(stream_grid(longest, kBlock), nf), kBlock, 0, s>>>(fb);
-      NVT_CHECK_LAUNCH();
-    }
-  }
-  for (int i = 0; i < nt; ++i) {
-    if (!t[i].table) continue;
-    if (t[i].range_aux) {
-      continue;  // (labelled above)
-    } else {
-      rc = encode_insert_any(4, t[i].keys, t[i].n_big, t[i].first_label, t[i].table, t[i].capacity,
-                             t[i].sentinel_label, s);
-      if (rc) return rc;
-    }
-  }
-  return NVT_OK;
-}
-
 }  // namespace nvt
 
 using namespace nvt;
@@ -2091,39 +979,6 @@ int nvt_vocab_sort_tmp_bytes(int key_bytes, uint64_t n, uint64_t *bytes) {
   if (key_bytes == 4 && os_tmp_bytes(n) > *bytes) *bytes = os_tmp_bytes(n);
   return NVT_OK;
 }
-int nvt_class_hist(const int64_t *counts, uint64_t n, uint32_t *hist, void *stream) {
-  NVT_CHECK_ARG(hist && (n == 0 || counts), "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  NVT_CHECK_HIP(hipMemsetAsync(hist, 0, 256 * 4, s));
-  if (n == 0) return NVT_OK;
-  class_hist_kernel<<<stream_grid(n, kBlock * 8, 4), kBlock, 0, s>>>(counts, n, hist);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-int nvt_vocab_label_shard(const int32_t *keys, const int64_t *counts, uint64_t n, const uint32_t *class_base_diff,
-                          void *tmp, int32_t *label_of, int32_t *big_keys, int64_t *big_counts,
-                          int32_t *big_src, void *stream) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(keys && counts && class_base_diff && tmp && label_of && big_keys && big_counts && big_src,
-                "null pointer");
-  NVT_CHECK_ARG(n < (1ull << 30), "at most 2^30-1 entries");
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  unsigned *status = reinterpret_cast<unsigned *>(tmp);
-  NVT_PROF("vocab_order", 0, s);
-  NVT_CHECK_HIP(hipMemsetAsync(status, 0, ntiles * 256 * 4 + 64, s));
-  label_shard_kernel<<<(unsigned)ntiles, kS2BS, 0, s>>>(keys, counts, n, class_base_diff, status,
-                                                       status + ntiles * 256, big_keys, big_counts, label_of,
-                                                       big_src);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_vocab_order_tmp_bytes(uint64_t n, uint64_t n_big, uint64_t *bytes) {
-  NVT_CHECK_ARG(bytes, "null out pointer");
-  *bytes = vocab_order_tmp_bytes(n, n_big);
-  return NVT_OK;
-}
 int nvt_vocab_sort_i32(int32_t *keys, int64_t *counts, uint64_t n, int64_t max_count, void *tmp,
                        void *stream) {
   NVT_CHECK_ARG(n <= 1 || (keys && counts && tmp), "null pointer");
@@ -2133,275 +988,6 @@ int nvt_vocab_sort_i64(int64_t *keys, int64_t *counts, uint64_t n, int64_t max_c
                        void *stream) {
   NVT_CHECK_ARG(n <= 1 || (keys && counts && tmp), "null pointer");
   return vocab_sort_any(8, keys, counts, n, max_count, tmp, (hipStream_t)stream);
-}
-
-int nvt_flat_index_tmp_bytes(uint64_t n, uint64_t *bytes) {
-  NVT_CHECK_ARG(bytes, "null out");
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  *bytes = pad16(ntiles * 8 + 64) + 64;
-  return NVT_OK;
-}
-
-int nvt_flat_index_build(const int32_t *keys, uint64_t n, uint64_t slots, int32_t *aux, void *table,
-                         uint64_t capacity, void *tmp, void *stream) {
-  NVT_CHECK_ARG(keys && aux && table && tmp, "null pointer");
-  NVT_CHECK_ARG(n >= 1 && n < (1ull << 30), "1 .. 2^30-1 keys");
-  NVT_CHECK_ARG(slots >= 64 && slots < (1ull << 32), "slots must be 64 .. 2^32-1");
-  NVT_CHECK_ARG(capacity >= slots + n + 64, "flat table: slots + n + 64");
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_index", 0, s);
-  const uint64_t ntiles = (n + kS2Tile - 1) / kS2Tile;
-  unsigned long long *status = reinterpret_cast<unsigned long long *>(tmp);
-  // the sentinel label of an encode table has no meaning here: it lands in the status block and
-  // is wiped with it
-  int rc = encode_clear_any(4, table, capacity, reinterpret_cast<int64_t *>(status), s);
-  if (rc) return rc;
-  NVT_CHECK_HIP(hipMemsetAsync(status, 0, ntiles * 8 + 64, s));
-  flat_params_kernel<<<1, 1, 0, s>>>(keys, n, slots, aux);
-  NVT_CHECK_LAUNCH();
-  flat_build_kernel<<<(unsigned)ntiles, kS2BS, 0, s>>>(
-      keys, nullptr, n, aux, status, reinterpret_cast<unsigned *>(status + ntiles),
-      (unsigned long long *)table, capacity);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_flat_lookup(const void *keys, int dtype, const uint8_t *valid, uint64_t n, const int32_t *aux,
-                    const void *table, uint64_t capacity, int64_t key_offset, int64_t *out,
-                    void *stream) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(keys && aux && table && out, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_lookup", n * (dtype == NVT_I64 ? 8ull : 4ull), s);
-  const unsigned grid = stream_grid(n, kBlock * 2);
-  const unsigned long long *tab = reinterpret_cast<const unsigned long long *>(table);
-  switch (dtype) {
-    case NVT_I32:
-      flat_lookup_kernel<int32_t><<<grid, kBlock, 0, s>>>((const int32_t *)keys, valid, n, aux, tab, capacity,
-                                                          key_offset, out);
-      break;
-    case NVT_I64:
-      flat_lookup_kernel<int64_t><<<grid, kBlock, 0, s>>>((const int64_t *)keys, valid, n, aux, tab, capacity,
-                                                          key_offset, out);
-      break;
-    default:
-      set_error("nvt_flat_lookup: key dtype must be int32 / int64 (got %d)", dtype);
-      return NVT_EINVAL;
-  }
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-
-int nvt_flat_lookup_gather(const void *keys, int dtype, const uint8_t *valid, uint64_t n,
-                           const int32_t *aux, const void *table, uint64_t capacity,
-                           int64_t key_offset, const double *records, int ncols, void *const *outs,
-                           const int *out_dtypes, const double *miss, uint64_t *unseen, void *stream) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(keys && aux && table && records && outs && out_dtypes && miss, "null pointer");
-  NVT_CHECK_ARG(ncols >= 1 && ncols <= kGatherMaxCols, "1..16 statistics per call");
-  GatherOuts o;
-  memset(&o, 0, sizeof(o));
-  for (int c = 0; c < ncols; ++c) {
-    NVT_CHECK_ARG(outs[c], "null output column");
-    NVT_CHECK_ARG(out_dtypes[c] == NVT_F32 || out_dtypes[c] == NVT_F64 || out_dtypes[c] == NVT_I32 ||
-                      out_dtypes[c] == NVT_I64, "output dtype must be f32 / f64 / i32 / i64");
-    o.out[c] = outs[c];
-    o.dtype[c] = out_dtypes[c];
-    o.miss[c] = miss[c];
-  }
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_lookup", n * (dtype == NVT_I64 ? 8ull : 4ull), s);
-  const unsigned grid = stream_grid(n, kBlock * 2);
-  const unsigned long long *tab = reinterpret_cast<const unsigned long long *>(table);
-  unsigned long long *flag = reinterpret_cast<unsigned long long *>(unseen);
-  int rc;
-  if (dtype == NVT_I32)
-    rc = launch_gather<int32_t>(ncols, grid, s, (const int32_t *)keys, valid, n, aux, tab, capacity,
-                                key_offset, records, o, flag);
-  else if (dtype == NVT_I64)
-    rc = launch_gather<int64_t>(ncols, grid, s, (const int64_t *)keys, valid, n, aux, tab, capacity,
-                                key_offset, records, o, flag);
-  else {
-    set_error("nvt_flat_lookup_gather: key dtype must be int32 / int64 (got %d)", dtype);
-    return NVT_EINVAL;
-  }
-  if (rc) return rc;
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_flat_lookup_te(const void *keys, int dtype, const uint8_t *valid, uint64_t n, const int32_t *aux,
-                       const void *table, uint64_t capacity, int64_t key_offset, const uint8_t *fold,
-                       int kfold, const double *records, double p_smooth, double y_mean, void *out,
-                       int out_dtype, void *stream) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(keys && aux && table && records && out, "null pointer");
-  NVT_CHECK_ARG(kfold >= 1 && kfold <= 256 && ((kfold > 1) == (fold != nullptr)), "fold ids come with kfold > 1");
-  NVT_CHECK_ARG(dtype == NVT_I32 || dtype == NVT_I64, "key dtype must be int32 / int64");
-  NVT_CHECK_ARG(out_dtype == NVT_F32 || out_dtype == NVT_F64, "out dtype must be f32 / f64");
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("te_apply", n * (dtype == NVT_I64 ? 8ull : 4ull), s);
-  const unsigned grid = stream_grid(n, kBlock * 2);
-  const unsigned long long *tab = reinterpret_cast<const unsigned long long *>(table);
-  const unsigned kf = fold ? (unsigned)kfold : 0u;  // record stride 2 * (kf + 1)
-#define NVT_TE_LAUNCH(K, OUT)                                                                   \
-  flat_lookup_te_kernel<K, OUT><<<grid, kBlock, 0, s>>>((const K *)keys, valid, n, aux, tab,    \
-                                                        capacity, key_offset, fold, kf, records, \
-                                                        p_smooth, y_mean, (OUT *)out)
-  if (dtype == NVT_I32 && out_dtype == NVT_F32) NVT_TE_LAUNCH(int32_t, float);
-  else if (dtype == NVT_I32) NVT_TE_LAUNCH(int32_t, double);
-  else if (out_dtype == NVT_F32) NVT_TE_LAUNCH(int64_t, float);
-  else NVT_TE_LAUNCH(int64_t, double);
-#undef NVT_TE_LAUNCH
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_flat_lookup_image(const void *keys, int dtype, const uint8_t *valid, uint64_t n,
-                          const int32_t *aux, const void *table, uint64_t capacity, int64_t key_offset,
-                          const int32_t *gid_in, int32_t *gid_out, const void *image,
-                          uint32_t stride_bytes, int ncols, void *const *outs,
-                          const uint8_t *const *folds, const uint32_t *offs, const uint32_t *sizes,
-                          const uint64_t *miss_bits, uint64_t *unseen, void *stream) {
-  if (n == 0) return NVT_OK;
-  NVT_CHECK_ARG(aux && table && image && outs && offs && sizes && miss_bits, "null pointer");
-  NVT_CHECK_ARG(keys || gid_in, "keys or group ids");
-  NVT_CHECK_ARG(ncols >= 1 && ncols <= kImageMaxCols, "1..24 outputs");
-  NVT_CHECK_ARG(stride_bytes >= 8 && stride_bytes % 8 == 0, "record stride: a multiple of 8 bytes");
-  NVT_CHECK_ARG(dtype == NVT_I32 || dtype == NVT_I64, "key dtype must be int32 / int64");
-  ImageOuts o;
-  memset(&o, 0, sizeof(o));
-  for (int c = 0; c < ncols; ++c) {
-    NVT_CHECK_ARG(outs[c], "null output");
-    NVT_CHECK_ARG(sizes[c] == 4 || sizes[c] == 8, "values are 4 or 8 bytes");
-    NVT_CHECK_ARG(offs[c] % sizes[c] == 0, "value offsets are aligned to the value size");
-    o.out[c] = outs[c];
-    o.fold[c] = folds ? folds[c] : nullptr;
-    o.miss[c] = miss_bits[c];
-    o.off[c] = offs[c];
-    o.fstride[c] = sizes[c];
-    o.size[c] = sizes[c];
-    // (with a fold column the caller guarantees off + (kfold + 1) * size <= stride)
-    NVT_CHECK_ARG((uint64_t)offs[c] + sizes[c] <= stride_bytes, "value outside the record");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_lookup", n * (dtype == NVT_I64 ? 8ull : 4ull), s);
-  const unsigned grid = stream_grid(n, kBlock * 2);
-  const unsigned long long *tab = reinterpret_cast<const unsigned long long *>(table);
-  unsigned long long *flag = reinterpret_cast<unsigned long long *>(unseen);
-  const uint8_t *img = reinterpret_cast<const uint8_t *>(image);
-#define NVT_IMG(K, MAXC)                                                                          \
-  flat_lookup_image_kernel<K, MAXC><<<grid, kBlock, 0, s>>>((const K *)keys, valid, n, aux, tab,  \
-                                                            capacity, key_offset, gid_in, gid_out, \
-                                                            img, stride_bytes, ncols, o, flag)
-#define NVT_IMG_K(K)                    \
-  do {                                  \
-    if (ncols <= 2) NVT_IMG(K, 2);      \
-    else if (ncols <= 4) NVT_IMG(K, 4); \
-    else if (ncols <= 8) NVT_IMG(K, 8); \
-    else if (ncols <= 16) NVT_IMG(K, 16); \
-    else NVT_IMG(K, 24);                \
-  } while (0)
-  if (dtype == NVT_I32) NVT_IMG_K(int32_t);
-  else NVT_IMG_K(int64_t);
-#undef NVT_IMG_K
-#undef NVT_IMG
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_image_pack(const void *const *src, const int *src_dtypes, const int *dst_dtypes,
-                   const uint32_t *offs, int ncols, uint64_t groups, void *image,
-                   uint32_t stride_bytes, void *stream) {
-  if (groups == 0 || ncols == 0) return NVT_OK;
-  NVT_CHECK_ARG(src && src_dtypes && dst_dtypes && offs && image, "null pointer");
-  NVT_CHECK_ARG(ncols >= 1 && ncols <= kImageMaxCols, "1..24 columns");
-  ImagePackArgs a;
-  memset(&a, 0, sizeof(a));
-  for (int c = 0; c < ncols; ++c) {
-    NVT_CHECK_ARG(src[c], "null source column");
-    NVT_CHECK_ARG(src_dtypes[c] == NVT_F64 || src_dtypes[c] == NVT_I64, "sources are float64 / int64");
-    const int d = dst_dtypes[c];
-    NVT_CHECK_ARG(d == NVT_F32 || d == NVT_F64 || d == NVT_I32 || d == NVT_I64, "values are f32 / f64 / i32 / i64");
-    const uint32_t sz = (d == NVT_F32 || d == NVT_I32) ? 4u : 8u;
-    NVT_CHECK_ARG(offs[c] % sz == 0 && (uint64_t)offs[c] + sz <= stride_bytes, "value outside the record");
-    a.src[c] = src[c];
-    a.src_dtype[c] = src_dtypes[c];
-    a.dst_dtype[c] = d;
-    a.off[c] = offs[c];
-  }
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_index", groups * 8ull * ncols, s);
-  image_pack_kernel<<<stream_grid(groups, kBlock, 8), kBlock, 0, s>>>(
-      a, ncols, groups, reinterpret_cast<uint8_t *>(image), stride_bytes);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_jg_image(const int64_t *count, const double *const *sum, const double *const *sumsq,
-                 const double *const *mn, const double *const *mx, int nvals, const int *kinds,
-                 const int *vals, const int *dst_dtypes, const uint32_t *offs, int ncols, uint64_t groups,
-                 void *image, uint32_t stride_bytes, void *stream) {
-  if (groups == 0 || ncols == 0) return NVT_OK;
-  NVT_CHECK_ARG(count && kinds && vals && dst_dtypes && offs && image, "null pointer");
-  NVT_CHECK_ARG(ncols >= 1 && ncols <= kImageMaxCols, "1..24 columns");
-  NVT_CHECK_ARG(nvals >= 0 && nvals <= kJgMaxVals, "0..8 value columns");
-  JgImageArgs a;
-  memset(&a, 0, sizeof(a));
-  a.count = count;
-  for (int j = 0; j < nvals; ++j) {
-    a.sum[j] = sum ? sum[j] : nullptr;
-    a.sumsq[j] = sumsq ? sumsq[j] : nullptr;
-    a.mn[j] = mn ? mn[j] : nullptr;
-    a.mx[j] = mx ? mx[j] : nullptr;
-  }
-  for (int c = 0; c < ncols; ++c) {
-    const int k = kinds[c], j = vals[c], d = dst_dtypes[c];
-    NVT_CHECK_ARG(k >= 0 && k <= 6, "statistic kind 0..6");
-    NVT_CHECK_ARG(k == 0 || (j >= 0 && j < nvals), "value column out of range");
-    NVT_CHECK_ARG(k == 0 || a.sum[j] || k == 3 || k == 4, "null sum array");
-    NVT_CHECK_ARG((k != 3 || a.mn[j]) && (k != 4 || a.mx[j]) && (k < 5 || (a.sum[j] && a.sumsq[j])),
-                  "null accumulator array for a requested statistic");
-    NVT_CHECK_ARG(d == NVT_F32 || d == NVT_F64 || d == NVT_I32 || d == NVT_I64, "values are f32 / f64 / i32 / i64");
-    const uint32_t sz = (d == NVT_F32 || d == NVT_I32) ? 4u : 8u;
-    NVT_CHECK_ARG(offs[c] % sz == 0 && (uint64_t)offs[c] + sz <= stride_bytes, "value outside the record");
-    a.kind[c] = k;
-    a.val[c] = k == 0 ? 0 : j;
-    a.dst_dtype[c] = d;
-    a.off[c] = offs[c];
-  }
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_index", groups * 8ull * ncols, s);
-  jg_image_kernel<<<stream_grid(groups, kBlock, 8), kBlock, 0, s>>>(a, ncols, groups,
-                                                                    reinterpret_cast<uint8_t *>(image), stride_bytes);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
-}
-
-int nvt_te_image(const int64_t *tot_count, const double *tot_sum, const int64_t *fold_count,
-                 const double *fold_sum, int kfold, uint64_t groups, double p_smooth, double y_mean,
-                 int out_dtype, void *image, uint32_t stride_bytes, uint32_t off, void *stream) {
-  if (groups == 0) return NVT_OK;
-  NVT_CHECK_ARG(tot_count && tot_sum && image, "null pointer");
-  NVT_CHECK_ARG(kfold >= 0 && kfold <= 256, "kfold must be 0 (no folds) .. 256");
-  NVT_CHECK_ARG(kfold == 0 || (fold_count && fold_sum), "fold statistics come with kfold > 0");
-  NVT_CHECK_ARG(out_dtype == NVT_F32 || out_dtype == NVT_F64, "out dtype must be f32 / f64");
-  const uint32_t sz = out_dtype == NVT_F32 ? 4u : 8u;
-  NVT_CHECK_ARG(off % sz == 0 && (uint64_t)off + (uint64_t)(kfold + 1) * sz <= stride_bytes,
-                "values outside the record");
-  hipStream_t s = (hipStream_t)stream;
-  NVT_PROF("groupby_index", groups * 16ull * (kfold + 1), s);
-  const unsigned grid = stream_grid(groups * (uint64_t)(kfold + 1), kBlock * 2, 8);
-  uint8_t *img = reinterpret_cast<uint8_t *>(image);
-  if (out_dtype == NVT_F32)
-    te_image_kernel<float><<<grid, kBlock, 0, s>>>(tot_count, tot_sum, fold_count, fold_sum, (unsigned)kfold,
-                                                   groups, p_smooth, y_mean, img, stride_bytes, off);
-  else
-    te_image_kernel<double><<<grid, kBlock, 0, s>>>(tot_count, tot_sum, fold_count, fold_sum, (unsigned)kfold,
-                                                    groups, p_smooth, y_mean, img, stride_bytes, off);
-  NVT_CHECK_LAUNCH();
-  return NVT_OK;
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 //                     min(count, 255), largest count
 //
 // The (key, count) list leaves this path SORTED BY KEY like the range path's, so the vocabulary
-// is ordered by the one-pass class scatter (nvt_sort.hip: cls_scatter_kernel).
+// is ordered by the one-pass class scatter (nvt_vocab_order.hip: cls_scatter_kernel).
 #include "nvt_common.hpp"
 #include "nvt_internal.hpp"
 #include "nvt_prof.hpp"

@@ -204,6 +204,30 @@ def test_count_entry_points_refuse_bad_arguments_before_any_launch():
         assert lib.nvt_dense_count_ws_bytes(4, 1000, path, 0, C.byref(nbytes)) == 0 and nbytes.value > 0
 
 
+@pytest.mark.parametrize("n, n_big", [(1, 0), (1, 1), (4096, 0), (4097, 2), (4097, 4097), (1 << 20, 16385),
+                                      ((1 << 30) - 1, 0)])
+def test_vocab_order_workspace_layout(n, n_big):
+    """nvt_vocab_order_tmp_bytes is the layout of the ordering workspace (order_ws, nvt_vocab_order.hip)
+    written out: status words of the class scatter | sort scratch of class 255 | label_of[n] | status
+    words of the flat build, every block padded to 16 bytes, 64 bytes behind the last."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+
+    def pad16(x):
+        return (x + 15) & ~15
+
+    got, sort_bytes = C.c_uint64(), C.c_uint64(0)
+    assert lib.nvt_vocab_order_tmp_bytes(n, n_big, C.byref(got)) == 0
+    if n_big > 1:
+        assert lib.nvt_vocab_sort_tmp_bytes(4, n_big, C.byref(sort_bytes)) == 0 and sort_bytes.value > 0
+    ntiles = -(-n // 4096)
+    want = pad16(ntiles * 1024 + 64) + pad16(sort_bytes.value) + pad16(4 * n) + pad16(8 * ntiles + 64) + 64
+    assert got.value == want, (n, n_big, got.value, want)
+
+
 def test_ops_fail_loudly_without_gpu():
     import torch
 

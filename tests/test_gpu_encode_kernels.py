@@ -399,6 +399,61 @@ def test_vocabulary_sizes(K, kind, n_vocab):
         sweep(K, T, [4097, 9], out_dtype, seed_of(kind, n_vocab, out_dtype, 1), pats=("byte-runs",), nb=0)
 
 
+@pytest.mark.parametrize("kind", ["flat", "dumped", "labels"])
+def test_ordering_workspace_at_two_tiles(K, kind, monkeypatch):
+    """The ordering workspace (order_ws, csrc/nvt_vocab_order.hip) at its smallest shape with every block
+    in use: 4097 key-sorted entries = two tiles, a class-255 tail of several entries, and a table built
+    from label_of[] -- flat and dumped through vocab_order_sorted_batch, flat through vocab_from_labels
+    ("labels").  EncodeTable keeps a vocabulary this small in LDS, so its gate is lifted while the table
+    object is made; the ordered arrays, every slot of the table and the sentinel label are then read
+    back and compared with the numpy order (count descending, key ascending)."""
+    n, first, lo = 4097, 3, LO["int32"]
+    rng = np.random.default_rng(seed_of("two tiles", kind))
+    keys = np.sort(np.append(keyset("scrambled", n - 1, "int32", rng), np.int32(lo)))
+    counts = 1 + np.minimum(rng.zipf(2.0, n), 200).astype(np.int64)
+    counts[1 + rng.permutation(n - 1)[:4]] = (255, 400, 255, 1000)    # the tail, with a tie
+    counts[0] = 2                                                     # the smallest key: below the tail
+    n_big = int((counts >= 255).sum())
+    assert 4 <= n_big < 64
+    order = np.lexsort((keys, -counts))
+    pos = np.empty(n, np.int32)
+    pos[order] = np.arange(n, dtype=np.int32)
+    monkeypatch.setattr(K, "ENCODE_RESIDENT_I32", 0)
+    if kind == "dumped":
+        job = K.DenseCountJob(dev(rng.permutation(np.repeat(keys, counts))), None, None, hint=n)
+        job.path = K.PATH_RANGE
+        dk, dc, _, info = K.dense_count_many([job])[0]
+        assert info["path"] == K.PATH_RANGE and not info.get("range_failed") and info["n_big"] == n_big, info
+        R.first_mismatch(host(dk), keys, "two tiles: counted keys")
+        ok, oc = torch.empty_like(dk), torch.empty_like(dc)
+        tab = K.EncodeTable(ok, first, unique=True, defer_build=True,
+                            range_table=(info["range_table"], info["range_aux"], info["range_bits"]))
+        src = (dk, dc, info["cls_hist"], n_big, None)
+        slots = (1 << info["range_bits"]) * (16384 + 128) + 64         # kRpRegion, kRpGuard
+    else:
+        dk, dc = dev(keys), dev(counts)
+        ok, oc = torch.empty_like(dk), torch.empty_like(dc)
+        tab = K.EncodeTable(ok, first, unique=True, defer_build=True, range_table=None, flat=True)
+        src = (dk, dc, K.class_hist(dc), n_big, dev(pos) if kind == "labels" else None)
+        assert tab.flat_slots > 0 and tab.capacity == tab.flat_slots + n + 64
+        slots = tab.capacity
+    monkeypatch.undo()
+    assert tab.table is not None and tab.range_aux is not None
+    tab.head_image = None                                             # (the LDS head is not what is tested)
+    _finalize(K, tab, oc, counts.max(), src=src)
+    tab.wait_ready()
+    R.first_mismatch(host(ok), keys[order], f"two tiles, {kind}: vocabulary order")
+    R.first_mismatch(host(oc), counts[order], f"two tiles, {kind}: ordered counts")
+    words = host(tab.table.view(torch.uint8)).view(np.uint64)[:slots]
+    words = words[(words & 0xFFFFFFFF) != 0x80000000]                 # slots that hold a key
+    got_keys = (words & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+    got_labels = (words >> 32).astype(np.int64)
+    by_key = np.argsort(got_keys, kind="stable")
+    R.first_mismatch(got_keys[by_key], keys[1:], f"two tiles, {kind}: keys in the table")
+    R.first_mismatch(got_labels[by_key], first + pos[1:].astype(np.int64), f"two tiles, {kind}: labels in the table")
+    assert int(tab.sentinel_label.item()) == first + int(pos[0])
+
+
 # ---------------------------------------------------------------------------------------------
 # the smallest key of the type: the tables' empty marker, and an ordinary key
 # ---------------------------------------------------------------------------------------------

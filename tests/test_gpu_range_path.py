@@ -1,5 +1,5 @@
 """Range path (NVT_PATH_RANGE, csrc/nvt_range_count.hip) + one-pass vocabulary ordering
-(csrc/nvt_sort.hip cls_scatter): exact counts, key-ordered output, overflow fallback, and the
+(csrc/nvt_vocab_order.hip cls_scatter): exact counts, key-ordered output, overflow fallback, and the
 (count desc, key asc) order / encode table built from it -- against numpy / the oracle.
 Reference semantics: categorify.py:955-1051 (groupby-size), :1300,1316 (order), :1558-1807."""
 import numpy as np

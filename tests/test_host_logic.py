@@ -118,7 +118,7 @@ def test_graph_json_dtype_and_tag_records():
 
 
 def test_one_pass_class_order_equals_count_desc_key_asc():
-    """The rule behind nvt_sort.hip's cls_scatter_kernel, emulated in numpy: for a KEY-SORTED
+    """The rule behind nvt_vocab_order.hip's cls_scatter_kernel, emulated in numpy: for a KEY-SORTED
     (key, count) list, "count descending, key ascending" (categorify.py:1300,1316 with the stable
     tie rule) == class 255 (count >= 255) sorted on its own, followed by classes 254 .. 1, each in
     the key order the list already has.  (The GPU tests compare the kernel with the oracle; this
