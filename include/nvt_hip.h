@@ -1315,6 +1315,54 @@ int nvt_partition_plan(const uint32_t *pid, uint64_t n, uint32_t P, int64_t *per
 int nvt_partition_gather_many(const nvt_partition_col *cols, int ncols, const nvt_partition_seg *segs, int nsegs,
                               uint64_t m, void *stream);
 
+/* ---- device dataloader: batch gather of a chunk (nvtabular.loader.torch.TorchAsyncItr) ----
+ * nvt_batch_take_many: dst[j * dst_stride] = cast(src[index[j]]) for the m output rows of every
+ *   descriptor, ONE launch per NVT_TAKE_MAX_COLS descriptors (the entry loops).  index: m int64 on
+ *   the device, or NULL for the identity (then m <= n_src).  The index is read once per row and
+ *   used for every column of the launch.
+ *   dtypes: src_dtype NVT_F32 .. NVT_I16 (a bool column is NVT_U8); dst_dtype equal to src_dtype, or
+ *   NVT_I64 from any integer source, or NVT_F32 / NVT_F64 from any source.  Casts are C++
+ *   conversions (round to nearest even; numpy's astype bit for bit).
+ *   nulls: a source row whose bit in src_valid is clear, or an index[j] outside [0, n_src), writes 0
+ *   to an integer destination and NaN to a float destination; a NaN source stays NaN.  An
+ *   out-of-range index is never dereferenced.  dst_valid, when given, is the gathered bitmap
+ *   (out-of-range rows clear their bit): ceil(m / 64) * 8 bytes, 8-byte aligned, written in whole
+ *   64-bit words, bits past m zero.
+ *   layout: dst_stride (elements, >= 1) = 1 is a contiguous column; dst_stride = k with dst at
+ *   column c of a row-major [m, k] matrix is the stacked layout.  When the descriptors of ONE
+ *   launch cover every column of such a matrix exactly once (4- or 8-byte elements, 16-byte aligned
+ *   matrix, rows of at most NVT_TAKE_STAGE_ROW_BYTES bytes, at most NVT_TAKE_MAX_GROUPS matrices
+ *   per launch), a tile of 256 rows is staged in LDS and written out in 16-byte stores; any other
+ *   strided descriptor is written element by element.  src / dst aligned to their element size.
+ * nvt_take_list_offsets: out_offsets[0] = 0, out_offsets[j + 1] = out_offsets[j] + the length of
+ *   row index[j] (an out-of-range index is an empty row; index NULL = identity); out_offsets[m] is
+ *   the number of output leaves, which the caller reads back to size them.  ws:
+ *   nvt_take_list_ws_bytes(m) bytes, 8-byte aligned.
+ * nvt_take_list_many: the leaves of up to NVT_LIST_MAX_COLS columns per launch that share
+ *   `offsets`; the work is spread over the `total` OUTPUT leaves (row of a leaf: a search in
+ *   out_offsets), same casts and null policy, leaf bitmaps carried when dst_valid is given
+ *   (ceil(total / 64) * 8 bytes).  dst_stride must be 1.  total = 0 is a no-op.
+ * Every entry is stream-ordered and does not synchronise; m = 0 is a no-op. */
+#define NVT_TAKE_MAX_COLS 64
+#define NVT_TAKE_MAX_GROUPS 4
+#define NVT_TAKE_STAGE_ROW_BYTES 256
+typedef struct nvt_take_col {
+  const void *src;          /* n_src values (leaves: the column's leaves)       */
+  const uint8_t *src_valid; /* bitmap or NULL                                   */
+  void *dst;                /* first element written                            */
+  uint8_t *dst_valid;       /* gathered bitmap, 8-byte aligned, or NULL         */
+  int64_t dst_stride;       /* elements between two output rows, >= 1           */
+  int32_t src_dtype;        /* NVT_F32 .. NVT_I16                               */
+  int32_t dst_dtype;
+} nvt_take_col;
+int nvt_batch_take_many(const int64_t *index, uint64_t m, uint64_t n_src, const nvt_take_col *cols, int ncols,
+                        void *stream);
+int nvt_take_list_ws_bytes(uint64_t m, uint64_t *bytes);
+int nvt_take_list_offsets(const int64_t *offsets, uint64_t n_src, const int64_t *index, uint64_t m,
+                          int64_t *out_offsets, void *ws, uint64_t ws_bytes, void *stream);
+int nvt_take_list_many(const nvt_take_col *cols, int ncols, const int64_t *offsets, const int64_t *index,
+                       const int64_t *out_offsets, uint64_t m, uint64_t total, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -17,4 +17,6 @@ for _sub in ("categorify", "normalize", "fill", "join_groupby", "target_encoding
         sys.modules[f"{__name__}.ops.{_sub}"] = importlib.import_module(f"nvtabular_amd.ops.{_sub}")
     except ImportError:  # (an operator module this engine does not carry)
         pass
+for _name in ("loader", "loader.torch", "loader.backend"):
+    sys.modules[f"{__name__}.{_name}"] = importlib.import_module(f"nvtabular_amd.{_name}")
 sys.modules[__name__] = _impl

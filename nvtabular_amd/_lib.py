@@ -388,6 +388,21 @@ SIGNATURES.update({
     "nvt_partition_gather_many": [C.POINTER(PartitionCol), _i32, _vp, _i32, _u64, _vp],
 })
 
+class TakeCol(C.Structure):
+    """nvt_take_col: one column gathered by nvt_batch_take_many / nvt_take_list_many."""
+    _fields_ = [("src", _vp), ("src_valid", _vp), ("dst", _vp), ("dst_valid", _vp), ("dst_stride", _i64),
+                ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32)]
+
+
+# include/nvt_hip.h NVT_TAKE_*
+TAKE_MAX_COLS, TAKE_MAX_GROUPS, TAKE_STAGE_ROW_BYTES = 64, 4, 256
+SIGNATURES.update({
+    "nvt_batch_take_many": [_vp, _u64, _u64, C.POINTER(TakeCol), _i32, _vp],
+    "nvt_take_list_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_take_list_offsets": [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
+    "nvt_take_list_many": [C.POINTER(TakeCol), _i32, _vp, _vp, _vp, _u64, _u64, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

@@ -17,18 +17,19 @@
 // ValueCount: len_minmax_kernel folds min / max of offsets[i + 1] - offsets[i] into int64[2].
 // DifferenceLag: lag_kernel, one lane per row, every (column, shift) output of the batch.
 #include "nvt_common.hpp"
+#include "nvt_list_tile.hpp"
 #include "nvt_prof.hpp"
 #include "nvt_scan.hpp"
 
 namespace nvt {
 namespace {
 
-constexpr uint64_t kTile = 2048;            // rows (lengths) or output leaves (move) per tile
-constexpr int kStage = 2048 + 2;            // new offsets of one tile's rows held in LDS
+constexpr uint64_t kTile = kListTile;       // rows (lengths) or output leaves (move) per tile
+constexpr int kStage = kListStage;          // new offsets of one tile's rows held in LDS
 constexpr int kMaxCols = NVT_LIST_MAX_COLS;
 constexpr int kMaxKeys = NVT_LAG_MAX_KEYS;
 
-__host__ __device__ inline uint64_t ntiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
+__host__ __device__ inline uint64_t ntiles_of(uint64_t n) { return list_ntiles(n); }
 
 struct Slice {
   int64_t start, end;
@@ -40,15 +41,6 @@ __device__ __forceinline__ void slice_row(const Slice &s, int64_t L, int64_t &fi
   int64_t e = s.end < 0 ? (L + s.end > 0 ? L + s.end : 0) : (s.end < L ? s.end : L);
   first = a;
   cnt = e > a ? e - a : 0;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t u = __shfl_up(v, o, 64);
-    if (lane_id() >= (unsigned)o) v += u;
-  }
-  return v;
 }
 
 // ---- new offsets --------------------------------------------------------------------------------
@@ -116,17 +108,6 @@ struct LBatch {
   LCol c[kMaxCols];
   int ncols;
 };
-
-// the row r in [lo, hi] with a[r] <= p < a[r + 1] (it exists: a[lo] <= p < a[hi + 1])
-template <typename A>
-__device__ __forceinline__ uint64_t row_of(const A a, uint64_t lo, uint64_t hi, int64_t p) {
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi + 1) >> 1;
-    if (a[mid] <= p) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 template <bool PAD>
 __global__ __launch_bounds__(kBlock) void slice_move_kernel(LBatch b, const int64_t *__restrict__ off, uint64_t n,
