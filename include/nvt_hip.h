@@ -1363,6 +1363,81 @@ int nvt_take_list_offsets(const int64_t *offsets, uint64_t n_src, const int64_t 
 int nvt_take_list_many(const nvt_take_col *cols, int ncols, const int64_t *offsets, const int64_t *index,
                        const int64_t *out_offsets, uint64_t m, uint64_t total, void *stream);
 
+/* ---- delimited text (CSV / TSV) parsed on the device (nvtabular_amd/csv_text.py) ----
+ * `text` is one byte range of a file that ends in '\n': nbytes < 2^31 bytes, 16-byte aligned and
+ * readable up to the next multiple of 16 (the bytes past nbytes are never looked at).  sep is a
+ * byte other than '\n' and quote; quote is a byte or -1 (no quoting).  A separator or newline
+ * counts only outside quotes; a doubled quote inside a quoted field toggles the state twice.
+ * `state` is NVT_CSV_STATE_WORDS uint64 on the device, 8-byte aligned (NVT_CSV_ST_*).
+ * nvt_csv_count: pass 1 over tiles of NVT_CSV_TILE bytes + the scan of the tile records in ws
+ *   (nvt_csv_ws_bytes(nbytes) bytes, 16-byte aligned).  Writes state: FIELDS, ROWS, PARITY (1 =
+ *   the text ends inside a quoted field), BAD_ROW / QUOTE_ROW / BAD_FIELD = UINT64_MAX, SLOW = 0.
+ *   The caller reads FIELDS and ROWS back to size field_end.
+ * nvt_csv_index: pass 2 with the ws nvt_csv_count left.  field_end[i] (uint32) = position of the
+ *   i-th separator or newline, for the nfields = state[FIELDS] of them: field k of row r is the
+ *   bytes [field_end[r * ncols + k - 1] + 1, field_end[r * ncols + k]) (field 0 of row 0 starts
+ *   at byte 0).  The first row whose newline is not separator (row + 1) * ncols - 1 is posted to
+ *   state[BAD_ROW], the first row with a newline inside quotes to state[QUOTE_ROW] (atomic min).
+ * nvt_csv_parse_many: one lane per row parses field cols[i].k of every row as cols[i].dtype
+ *   (NVT_F32, NVT_F64, NVT_I32, NVT_I64), NVT_CSV_MAX_COLS descriptors per launch (the entry
+ *   loops).  A '\r' that ends the last field of a row is dropped and quotes around a field are
+ *   stripped.  An empty field is a null: 0 (NaN for floats) and a clear bit in out_valid
+ *   (ceil(nrows / 64) * 8 bytes, 8-byte aligned, written in whole words, bits past nrows zero).
+ *   Floats are bit-equal to strtod, NVT_F32 is that double rounded once; a field the device
+ *   parser declines (csv_parse_f64 in nvt_csv_parse.hpp) gets 0, a set bit in `slow` (same shape
+ *   as out_valid) and is counted in state[SLOW]: the caller parses those.  The smallest
+ *   row << 24 | k << 2 | code (code NVT_CSV_INVALID or NVT_CSV_OVERFLOW) of the fields that do
+ *   not parse goes to state[BAD_FIELD].  Needs nrows * ncols <= state[FIELDS] of the index.
+ * nvt_csv_str_offsets: field k of every row as a string column: byte length after unquoting and
+ *   collapsing doubled quotes, scanned into Arrow int32 offsets[nrows + 1] (offsets[nrows] = the
+ *   chars total), and validity (a field that is empty after unquoting is null).  A quoted field
+ *   with a quote inside that is not doubled is posted to state[BAD_FIELD] like a number that does
+ *   not parse (code NVT_CSV_INVALID).  ws: nvt_csv_str_ws_bytes(nrows) bytes, 8-byte aligned.
+ * nvt_csv_str_copy: the chars of that column at the offsets nvt_csv_str_offsets wrote.
+ * nvt_csv_parse_f64_host / nvt_csv_parse_i64_host: the device's scalar parsers run on the host
+ *   (tests): NVT_CSV_OK with *out set, NVT_CSV_DECLINED, NVT_CSV_INVALID or NVT_CSV_OVERFLOW.
+ * Every device entry is stream-ordered and does not synchronise; nbytes = 0 / nrows = 0 is a
+ * no-op. */
+#define NVT_CSV_TILE 4096
+#define NVT_CSV_SCAN_STEP 256   /* tile records one step of the tile scan covers */
+#define NVT_CSV_MAX_COLS 64
+#define NVT_CSV_STATE_WORDS 8
+#define NVT_CSV_ST_FIELDS 0
+#define NVT_CSV_ST_ROWS 1
+#define NVT_CSV_ST_PARITY 2
+#define NVT_CSV_ST_BAD_ROW 3
+#define NVT_CSV_ST_QUOTE_ROW 4
+#define NVT_CSV_ST_BAD_FIELD 5
+#define NVT_CSV_ST_SLOW 6
+#define NVT_CSV_OK 0
+#define NVT_CSV_DECLINED 1
+#define NVT_CSV_INVALID 2
+#define NVT_CSV_OVERFLOW 3
+typedef struct nvt_csv_col {
+  void *out;            /* nrows values of dtype                                  */
+  uint8_t *out_valid;   /* bitmap, ceil(nrows / 64) * 8 bytes, 8-byte aligned    */
+  uint8_t *slow;        /* float dtypes: bitmap of the declined fields; else NULL */
+  uint32_t k;           /* field of the row, < ncols                             */
+  int32_t dtype;        /* NVT_F32, NVT_F64, NVT_I32 or NVT_I64                  */
+} nvt_csv_col;
+int nvt_csv_ws_bytes(uint64_t nbytes, uint64_t *bytes);
+int nvt_csv_count(const uint8_t *text, uint64_t nbytes, int sep, int quote, void *ws, uint64_t ws_bytes,
+                  uint64_t *state, void *stream);
+int nvt_csv_index(const uint8_t *text, uint64_t nbytes, int sep, int quote, uint32_t ncols, const void *ws,
+                  uint64_t ws_bytes, uint32_t *field_end, uint64_t nfields, uint64_t *state, void *stream);
+int nvt_csv_parse_many(const uint8_t *text, uint64_t nbytes, const uint32_t *field_end, uint64_t nrows,
+                       uint32_t ncols, int quote, const nvt_csv_col *cols, int ndesc, uint64_t *state,
+                       void *stream);
+int nvt_csv_str_ws_bytes(uint64_t nrows, uint64_t *bytes);
+int nvt_csv_str_offsets(const uint8_t *text, uint64_t nbytes, const uint32_t *field_end, uint64_t nrows,
+                        uint32_t ncols, uint32_t k, int quote, int32_t *offsets, uint8_t *out_valid, void *ws,
+                        uint64_t ws_bytes, uint64_t *state, void *stream);
+int nvt_csv_str_copy(const uint8_t *text, uint64_t nbytes, const uint32_t *field_end, uint64_t nrows,
+                     uint32_t ncols, uint32_t k, int quote, const int32_t *offsets, uint8_t *chars,
+                     uint64_t chars_bytes, void *stream);
+int nvt_csv_parse_f64_host(const char *text, int len, double *out);
+int nvt_csv_parse_i64_host(const char *text, int len, int64_t *out);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -403,6 +403,28 @@ SIGNATURES.update({
     "nvt_take_list_many": [C.POINTER(TakeCol), _i32, _vp, _vp, _vp, _u64, _u64, _vp],
 })
 
+class CsvCol(C.Structure):
+    """nvt_csv_col: one numeric column parsed by nvt_csv_parse_many."""
+    _fields_ = [("out", _vp), ("out_valid", _vp), ("slow", _vp), ("k", _u32), ("dtype", C.c_int32)]
+
+
+# include/nvt_hip.h NVT_CSV_*
+CSV_TILE, CSV_SCAN_STEP, CSV_MAX_COLS, CSV_STATE_WORDS = 4096, 256, 64, 8
+(CSV_ST_FIELDS, CSV_ST_ROWS, CSV_ST_PARITY, CSV_ST_BAD_ROW, CSV_ST_QUOTE_ROW, CSV_ST_BAD_FIELD,
+ CSV_ST_SLOW) = range(7)
+CSV_OK, CSV_DECLINED, CSV_INVALID, CSV_OVERFLOW = 0, 1, 2, 3
+SIGNATURES.update({
+    "nvt_csv_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_csv_count": [_vp, _u64, _i32, _i32, _vp, _u64, _vp, _vp],
+    "nvt_csv_index": [_vp, _u64, _i32, _i32, _u32, _vp, _u64, _vp, _u64, _vp, _vp],
+    "nvt_csv_parse_many": [_vp, _u64, _vp, _u64, _u32, _i32, C.POINTER(CsvCol), _i32, _vp, _vp],
+    "nvt_csv_str_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_csv_str_offsets": [_vp, _u64, _vp, _u64, _u32, _u32, _i32, _vp, _vp, _vp, _u64, _vp, _vp],
+    "nvt_csv_str_copy": [_vp, _u64, _vp, _u64, _u32, _u32, _i32, _vp, _vp, _u64, _vp],
+    "nvt_csv_parse_f64_host": [C.c_char_p, _i32, C.POINTER(_dbl)],
+    "nvt_csv_parse_i64_host": [C.c_char_p, _i32, C.POINTER(_i64)],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

@@ -45,7 +45,11 @@ class _Collection:
 class Dataset:
     def __init__(self, path_or_source, engine=None, cpu=None, part_size=None,
                  part_mem_fraction=None, npartitions=None, names=None, schema=None,
-                 row_groups_per_part=1, **kwargs):
+                 row_groups_per_part=1, sep=",", header="infer", dtypes=None, quotechar='"', **kwargs):
+        """``engine``: "parquet", "csv" or None (a first file ending in .csv / .tsv / .txt selects
+        csv; anything else is read as parquet).  ``sep``, ``names``, ``header``, ``dtypes``,
+        ``part_size`` and ``quotechar`` belong to the csv engine (csv_text.py): delimited text is
+        cut into byte ranges of about ``part_size`` and parsed on the device."""
         self.cpu = bool(cpu)  # accepted for API compatibility; compute always runs on the GPU
         self.engine = engine
         self._schema = schema
@@ -58,6 +62,8 @@ class Dataset:
             self._init_frames(_split(src, npartitions or 1))
         elif isinstance(src, (list, tuple)) and src and not isinstance(src[0], (str, os.PathLike)):
             self._init_frames(list(src))
+        elif _csv_engine(src, engine):
+            self._init_csv(src, sep, names, header, dtypes, part_size, quotechar)
         else:
             self._init_parquet(src, row_groups_per_part, names)
 
@@ -69,6 +75,26 @@ class Dataset:
             f0 = frames[0]
             self._schema = Schema.from_frame(f0.schema if _is_arrow_table(f0) else f0)
         self._parts_fn = lambda columns=None: iter(self._frames)
+
+    def _init_csv(self, paths, sep, names, header, dtypes, part_size, quotechar):
+        """Delimited text: one partition per byte range (csv_text.CsvSource), parsed on the device
+        when it is read.  There is no ``_pieces``: row counts come from reading the partitions."""
+        from .csv_text import CsvSource
+
+        self.engine = "csv"
+        src = self._csv = CsvSource(paths, sep=sep, names=names, header=header, dtypes=dtypes,
+                                    part_size=part_size, quotechar=quotechar)
+        self._n = len(src.ranges)
+        if self._schema is None:
+            self._schema = src.schema()
+        self._forwards_shard = True   # a global list of byte ranges: rank r reads every world-th one
+
+        def gen(columns=None, shard=None):
+            for i in range(len(src.ranges)):
+                if shard is None or i % shard[1] == shard[0]:
+                    yield src.read_partition(i, columns)
+
+        self._parts_fn = gen
 
     def _init_parquet(self, paths, row_groups_per_part, names):
         import pyarrow.parquet as pq
@@ -822,6 +848,12 @@ def _prefetch_frames(host_parts, cols, depth: int = 2):
         except queue.Empty:
             pass
         t.join(timeout=30)
+
+
+def _csv_engine(src, engine) -> bool:
+    from .csv_text import select_engine
+
+    return select_engine(src, engine) == "csv"
 
 
 def _is_arrow_table(x) -> bool:
