@@ -1438,6 +1438,44 @@ int nvt_csv_str_copy(const uint8_t *text, uint64_t nbytes, const uint32_t *field
 int nvt_csv_parse_f64_host(const char *text, int len, double *out);
 int nvt_csv_parse_i64_host(const char *text, int len, int64_t *out);
 
+/* ---- datetime columns (nvtabular_amd/kernels_datetime.py) ----
+ * A datetime column is int64 counts since 1970-01-01T00:00:00 in a unit (NVT_DT_S / _MS / _US /
+ * _NS); a null is a clear bit in `valid`, whatever its slot holds.
+ * nvt_dt_field: out[i] = calendar field `field` of ts[i] on the proleptic Gregorian calendar
+ *   (NVT_DT_WEEKDAY: Monday = 0; NVT_DT_DAYOFYEAR and NVT_DT_QUARTER from 1), 0 for a null row.
+ *   Counts before the epoch round down: 1969-12-31 23:59:59 is on day -1.  No signed overflow for
+ *   any int64 input; the results are specified for years 1 to 9999.  ts 8-byte aligned, valid NULL
+ *   or ceil(n / 8) bytes, out 4-byte aligned.  Stream-ordered; n = 0 is a no-op.
+ * nvt_dt_fields_host: the same function looped on the host (no nulls).
+ * nvt_csv_parse_datetime: field cols[i].k of every row of an indexed CSV partition (nvt_csv_index)
+ *   as int64 nanoseconds (cols[i].dtype NVT_I64, slow unused), launched after nvt_csv_parse_many
+ *   with the same arguments.  Grammar: YYYY-MM-DD[(T| )HH:MM[:SS[.f{1,9}]]], nothing else.  The
+ *   empty field is a null (0 and a clear bit in out_valid); NVT_CSV_INVALID (wrong shape, a day the
+ *   month does not have, hour 24, second 60, a zone suffix, blanks) and NVT_CSV_OVERFLOW (outside
+ *   int64 nanoseconds, or INT64_MIN itself) are posted to state[BAD_FIELD] as nvt_csv_parse_many
+ *   posts them.
+ * nvt_csv_parse_datetime_host: the scalar parser run on the host (tests). */
+#define NVT_DT_S 0
+#define NVT_DT_MS 1
+#define NVT_DT_US 2
+#define NVT_DT_NS 3
+#define NVT_DT_YEAR 0
+#define NVT_DT_MONTH 1
+#define NVT_DT_DAY 2
+#define NVT_DT_HOUR 3
+#define NVT_DT_MINUTE 4
+#define NVT_DT_SECOND 5
+#define NVT_DT_WEEKDAY 6
+#define NVT_DT_DAYOFYEAR 7
+#define NVT_DT_QUARTER 8
+int nvt_dt_field(const int64_t *ts, const uint8_t *valid, uint64_t n, int unit, int field, int32_t *out,
+                 void *stream);
+int nvt_dt_fields_host(const int64_t *ts, uint64_t n, int unit, int field, int32_t *out);
+int nvt_csv_parse_datetime(const uint8_t *text, uint64_t nbytes, const uint32_t *field_end, uint64_t nrows,
+                           uint32_t ncols, int quote, const nvt_csv_col *cols, int ndesc, uint64_t *state,
+                           void *stream);
+int nvt_csv_parse_datetime_host(const char *text, int len, int64_t *out_ns);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

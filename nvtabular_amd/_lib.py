@@ -425,6 +425,16 @@ SIGNATURES.update({
     "nvt_csv_parse_i64_host": [C.c_char_p, _i32, C.POINTER(_i64)],
 })
 
+# include/nvt_hip.h NVT_DT_*
+DT_S, DT_MS, DT_US, DT_NS = range(4)
+(DT_YEAR, DT_MONTH, DT_DAY, DT_HOUR, DT_MINUTE, DT_SECOND, DT_WEEKDAY, DT_DAYOFYEAR, DT_QUARTER) = range(9)
+SIGNATURES.update({
+    "nvt_dt_field": [_vp, _vp, _u64, _i32, _i32, _vp, _vp],
+    "nvt_dt_fields_host": [_vp, _u64, _i32, _i32, _vp],
+    "nvt_csv_parse_datetime": [_vp, _u64, _vp, _u64, _u32, _i32, C.POINTER(CsvCol), _i32, _vp, _vp],
+    "nvt_csv_parse_datetime_host": [C.c_char_p, _i32, C.POINTER(_i64)],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

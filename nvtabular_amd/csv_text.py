@@ -7,7 +7,8 @@ every nominal boundary, so ``npartitions`` is known up front and no partition de
 
 Deviations from ``pandas.read_csv`` ("CSV in"): only the empty field is null (``NA``,
 ``null`` ... are strings), short rows are an error, blank lines are rows, whitespace is kept, a
-quoted field cannot hold a newline."""
+quoted field cannot hold a newline; ``parse_dates`` takes column names only and one fixed ISO-8601
+grammar (DESIGN.md, "Datetime columns")."""
 from __future__ import annotations
 
 import csv
@@ -26,6 +27,7 @@ MAX_PART_SIZE = 1 << 30          # field offsets are 32-bit and a range grows by
 SAMPLE_BYTES = 64 << 10          # dtype inference reads this much of the first file
 _WINDOW = 64 << 10               # bytes read per step when looking for the newline after a cut
 DTYPES = ("int32", "int64", "float32", "float64", "string")
+DATETIME = "datetime64[ns]"      # the dtype of a column named in parse_dates (never inferred)
 _UNITS = {"": 1, "b": 1, "k": 10 ** 3, "kb": 10 ** 3, "m": 10 ** 6, "mb": 10 ** 6, "g": 10 ** 9, "gb": 10 ** 9,
           "kib": 1 << 10, "mib": 1 << 20, "gib": 1 << 30}
 
@@ -123,15 +125,19 @@ def _dtype_name(name: str, dt) -> str:
     if s == "object":
         return "string"
     if s not in DTYPES:
+        hint = f"; name the column in parse_dates=['{name}'] to read ISO-8601 text" if s.startswith("datetime64") else ""
         raise TypeError(f"column '{name}': dtype {dt!r} is not supported by the csv engine "
-                        f"(int32, int64, float32, float64 or string)")
+                        f"(int32, int64, float32, float64 or string){hint}")
     return s
 
 
 class CsvSource:
     """Files, names, dtypes and byte ranges of a delimited-text dataset."""
 
-    def __init__(self, paths, sep=",", names=None, header="infer", dtypes=None, part_size=None, quotechar='"'):
+    def __init__(self, paths, sep=",", names=None, header="infer", dtypes=None, part_size=None, quotechar='"',
+                 parse_dates=None):
+        """``parse_dates``: names of the columns that hold ISO-8601 text
+        (``YYYY-MM-DD[(T| )HH:MM[:SS[.fffffffff]]]``, no zone); they become datetime64[ns]."""
         if not isinstance(sep, str) or len(sep.encode()) != 1 or sep in "\r\n":
             raise ValueError(f"sep must be one single-byte character other than a line end, got {sep!r}")
         if quotechar is not None and (not isinstance(quotechar, str) or len(quotechar.encode()) != 1
@@ -161,6 +167,18 @@ class CsvSource:
         if unknown:
             raise ValueError(f"dtypes: unknown column(s) {unknown}")
         self.dtypes: Dict[str, str] = {c: _dtype_name(c, dt) for c, dt in given.items()}
+        if parse_dates is None or parse_dates is False:
+            parse_dates = []
+        if isinstance(parse_dates, str) or not isinstance(parse_dates, (list, tuple)) or \
+                not all(isinstance(c, str) for c in parse_dates):
+            raise ValueError(f"parse_dates must be a list of column names, got {parse_dates!r}")
+        unknown = [c for c in parse_dates if c not in self.names]
+        if unknown:
+            raise ValueError(f"parse_dates: unknown column(s) {unknown}")
+        both = [c for c in parse_dates if c in given]
+        if both:
+            raise ValueError(f"column(s) {both} are named in both dtypes and parse_dates")
+        self.dtypes.update({c: DATETIME for c in parse_dates})
         if len(self.dtypes) < len(self.names):
             self._infer_dtypes()
         self.dtypes = {c: self.dtypes[c] for c in self.names}

@@ -11,6 +11,11 @@ buffers live in HBM in Arrow layout --
   offsets  optional int64 row offsets (list columns; ``data`` holds the leaves)
   fill     optional pending FillMissing constant (logical value of a null row);
            downstream kernels take it as a parameter so FillMissing costs no pass
+  logical  None, or numpy's datetime64[s|ms|us|ns]: ``data`` is then int64 counts since the epoch
+           in that unit, a null (NaT) is a cleared bit in ``valid`` -- the NaT pattern INT64_MIN
+           is never a value -- and ``strings`` / ``fill`` are None (``offsets`` too, but for the
+           ``list`` output of Groupby).  A time zone is dropped on the way in: the values are the
+           UTC instants ("Datetime columns")
 
 Operators accept either a pandas DataFrame (converted on entry and back on exit,
 so existing workflows drop in) or a DeviceFrame (stays resident).
@@ -91,15 +96,27 @@ def pack_bitmap(valid_bool: np.ndarray) -> np.ndarray:
     return bits
 
 
-class DeviceColumn:
-    __slots__ = ("data", "valid", "offsets", "fill", "strings")
+DATETIME_UNITS = ("s", "ms", "us", "ns")
 
-    def __init__(self, data, valid=None, offsets=None, fill=None, strings=None):
+
+def datetime_dtype(dt) -> np.dtype:
+    """``dt`` as numpy's datetime64[s|ms|us|ns]; anything else is a TypeError."""
+    dt = np.dtype(dt)
+    if dt.kind != "M" or np.datetime_data(dt) not in [(u, 1) for u in DATETIME_UNITS]:
+        raise TypeError(f"a datetime column is datetime64[s], [ms], [us] or [ns], not {dt}")
+    return dt
+
+
+class DeviceColumn:
+    __slots__ = ("data", "valid", "offsets", "fill", "strings", "logical")
+
+    def __init__(self, data, valid=None, offsets=None, fill=None, strings=None, *, logical=None):
         self.data = data
         self.valid = valid
         self.offsets = offsets
         self.fill = fill
         self.strings = strings  # host dict {surrogate int64 key -> str} for string columns
+        self.logical = datetime_dtype(logical) if logical is not None else None
 
     # ---- basic properties -------------------------------------------------
     def __len__(self):
@@ -118,7 +135,12 @@ class DeviceColumn:
         return self.data.device
 
     def shallow_copy(self) -> "DeviceColumn":
-        return DeviceColumn(self.data, self.valid, self.offsets, self.fill, self.strings)
+        return DeviceColumn(self.data, self.valid, self.offsets, self.fill, self.strings, logical=self.logical)
+
+    def like(self, data, valid=None, offsets=None) -> "DeviceColumn":
+        """The same kind of column (string dictionary, datetime unit) over other rows: what every
+        path that moves rows builds its outputs with."""
+        return DeviceColumn(data, valid, offsets, None, self.strings, logical=self.logical)
 
     def with_data(self, data, valid=None, keep_offsets=True) -> "DeviceColumn":
         return DeviceColumn(data, valid, self.offsets if keep_offsets else None, None, None)
@@ -148,6 +170,17 @@ class DeviceColumn:
         device = device or default_device()
         from .strings import string_series_to_device  # local: avoids a cycle
 
+        if getattr(s.dtype, "kind", None) == "M":
+            if getattr(s.dtype, "tz", None) is not None:
+                s = s.dt.tz_convert("UTC").dt.tz_localize(None)   # the UTC instants, naive
+            arr = s.to_numpy()
+            if np.datetime_data(arr.dtype)[0] not in DATETIME_UNITS:
+                arr = arr.astype("datetime64[ns]")
+            mask = np.isnat(arr)
+            vals = arr.view(np.int64).copy()
+            vals[mask] = 0
+            valid = torch.from_numpy(pack_bitmap(~mask)).to(device) if mask.any() else None
+            return DeviceColumn(torch.from_numpy(vals).to(device), valid, logical=arr.dtype)
         if s.dtype == object or pd.api.types.is_string_dtype(s.dtype):
             nn = s.dropna()
             if len(nn) and isinstance(nn.iloc[0], (list, np.ndarray, tuple)):
@@ -157,6 +190,8 @@ class DeviceColumn:
                 np.cumsum(lens, out=offsets[1:])
                 leaves = [v for r in s if r is not None for v in r]
                 leaf_col = DeviceColumn.from_pandas(pd.Series(leaves), device)
+                if leaf_col.logical is not None:   # (lists of timestamps are not the datetime type)
+                    raise TypeError(f"unsupported column dtype: lists of {leaf_col.logical}")
                 if len(leaves) == 0:
                     leaf_col = DeviceColumn(torch.empty(0, dtype=torch.int64, device=device))
                 leaf_col.offsets = torch.from_numpy(offsets).to(device)
@@ -193,6 +228,8 @@ class DeviceColumn:
             arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
         if pa.types.is_list(arr.type) or pa.types.is_large_list(arr.type):
             leaves = DeviceColumn.from_arrow(arr.flatten(), device)
+            # lists of timestamps are not the datetime type: the leaves are their int64 counts
+            leaves.logical = None
             off = np.asarray(arr.offsets).astype(np.int64)
             leaves.offsets = torch.from_numpy(off - off[0]).to(device)
             return leaves
@@ -210,6 +247,11 @@ class DeviceColumn:
                     KS.fits(arr.dictionary):
                 return KS.column_from_dictionary_array(arr, device)
             return DeviceColumn.from_arrow(arr.dictionary_decode(), device)
+        logical = None
+        if pa.types.is_timestamp(arr.type):
+            # the counts as they are (int64, the unit kept, a zone dropped): the integer path below
+            logical = np.dtype(f"datetime64[{arr.type.unit}]")
+            arr = arr.view(pa.int64())
         np_dt = arr.type.to_pandas_dtype()
         n = len(arr)
         valid = None
@@ -238,7 +280,7 @@ class DeviceColumn:
         if vals.dtype not in _NP_TO_TORCH:
             vals = vals.astype(np.int64 if vals.dtype.kind in "iu" else np.float64)
         data = to_device_async(vals, device)
-        return DeviceColumn(data, valid)
+        return DeviceColumn(data, valid, logical=logical)
 
     def valid_mask_host(self) -> Optional[np.ndarray]:
         if self.valid is None:
@@ -251,7 +293,12 @@ class DeviceColumn:
         col = self.materialize()
         vals = col.data.cpu().numpy()
         mask = col.valid_mask_host()
-        if col.strings is not None:
+        if col.logical is not None:
+            out = vals.view(col.logical).copy()
+            if mask is not None:
+                out[~mask] = np.datetime64("NaT")
+            flat = pd.Series(out, name=name)
+        elif col.strings is not None:
             lut = col.strings
             out = np.array([lut.get(int(k)) for k in vals], dtype=object)
             if mask is not None:
@@ -336,7 +383,7 @@ class DeviceFrame:
             if col.valid is not None:
                 bits = (col.valid[take >> 3] >> (take & 7).to(torch.uint8)) & 1
                 valid = pack_bitmap_device(bits.to(torch.bool))
-            out[name] = DeviceColumn(col.data[take], valid, offsets, None, col.strings)
+            out[name] = col.like(col.data[take], valid, offsets)
         return out
 
     def drop(self, columns: Iterable[str]) -> "DeviceFrame":
@@ -430,8 +477,8 @@ class DeviceFrame:
                     vb = hvalid.numpy()
                     bufs[0] = pa.py_buffer(vb)
                     nulls = -1  # let Arrow count
-                arr = pa.Array.from_buffers(pa.from_numpy_dtype(values.dtype), n_leaf, bufs,
-                                            null_count=nulls)
+                typ = pa.from_numpy_dtype(values.dtype if col.logical is None else col.logical)
+                arr = pa.Array.from_buffers(typ, n_leaf, bufs, null_count=nulls)
             if hoff is not None:
                 arr = pa.LargeListArray.from_arrays(pa.array(hoff.numpy()), arr)
             arrays[name] = arr
@@ -447,7 +494,7 @@ class DeviceFrame:
                 if start % 8:
                     raise ValueError("partition starts must be multiples of 8 rows for bitmaps")
                 valid = c.valid[start // 8 :]
-            out[k] = DeviceColumn(c.data[start:stop], valid, None, c.fill, c.strings)
+            out[k] = DeviceColumn(c.data[start:stop], valid, None, c.fill, c.strings, logical=c.logical)
         return out
 
 

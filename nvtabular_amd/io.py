@@ -45,11 +45,13 @@ class _Collection:
 class Dataset:
     def __init__(self, path_or_source, engine=None, cpu=None, part_size=None,
                  part_mem_fraction=None, npartitions=None, names=None, schema=None,
-                 row_groups_per_part=1, sep=",", header="infer", dtypes=None, quotechar='"', **kwargs):
+                 row_groups_per_part=1, sep=",", header="infer", dtypes=None, quotechar='"', parse_dates=None,
+                 **kwargs):
         """``engine``: "parquet", "csv" or None (a first file ending in .csv / .tsv / .txt selects
         csv; anything else is read as parquet).  ``sep``, ``names``, ``header``, ``dtypes``,
-        ``part_size`` and ``quotechar`` belong to the csv engine (csv_text.py): delimited text is
-        cut into byte ranges of about ``part_size`` and parsed on the device."""
+        ``part_size``, ``quotechar`` and ``parse_dates`` belong to the csv engine (csv_text.py):
+        delimited text is cut into byte ranges of about ``part_size`` and parsed on the device; the
+        columns named in ``parse_dates`` (ISO-8601 text) become datetime64[ns]."""
         self.cpu = bool(cpu)  # accepted for API compatibility; compute always runs on the GPU
         self.engine = engine
         self._schema = schema
@@ -63,7 +65,7 @@ class Dataset:
         elif isinstance(src, (list, tuple)) and src and not isinstance(src[0], (str, os.PathLike)):
             self._init_frames(list(src))
         elif _csv_engine(src, engine):
-            self._init_csv(src, sep, names, header, dtypes, part_size, quotechar)
+            self._init_csv(src, sep, names, header, dtypes, part_size, quotechar, parse_dates)
         else:
             self._init_parquet(src, row_groups_per_part, names)
 
@@ -76,14 +78,14 @@ class Dataset:
             self._schema = Schema.from_frame(f0.schema if _is_arrow_table(f0) else f0)
         self._parts_fn = lambda columns=None: iter(self._frames)
 
-    def _init_csv(self, paths, sep, names, header, dtypes, part_size, quotechar):
+    def _init_csv(self, paths, sep, names, header, dtypes, part_size, quotechar, parse_dates=None):
         """Delimited text: one partition per byte range (csv_text.CsvSource), parsed on the device
         when it is read.  There is no ``_pieces``: row counts come from reading the partitions."""
         from .csv_text import CsvSource
 
         self.engine = "csv"
         src = self._csv = CsvSource(paths, sep=sep, names=names, header=header, dtypes=dtypes,
-                                    part_size=part_size, quotechar=quotechar)
+                                    part_size=part_size, quotechar=quotechar, parse_dates=parse_dates)
         self._n = len(src.ranges)
         if self._schema is None:
             self._schema = src.schema()
@@ -541,7 +543,7 @@ class StagedPartition:
                 raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
             packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
             if sc.valid is None:
-                out[name] = DeviceColumn(packed)
+                out[name] = DeviceColumn(packed, logical=sc.logical)
                 continue
             nb = ((sc.rows + 63) // 64) * 8
             bitmap = sc.valid[:nb].to(device, non_blocking=True)
@@ -555,7 +557,7 @@ class StagedPartition:
                 ws = torch.empty(need.value, dtype=torch.uint8, device=device)
                 K.check(lib.nvt_expand_valid(packed.data_ptr(), sc.dtype.itemsize, bitmap.data_ptr(), sc.rows,
                                              data.data_ptr(), ws.data_ptr(), K.stream_ptr()), "nvt_expand_valid")
-            out[name] = DeviceColumn(data, bitmap)
+            out[name] = DeviceColumn(data, bitmap, logical=sc.logical)
         return DeviceFrame(out)
 PLAIN_WRITE_THREADS = int(os.environ.get("NVT_PARQUET_THREADS", "16"))
 PLAIN_ROW_GROUP = int(os.environ.get("NVT_PARQUET_ROW_GROUP", str(1 << 22)))
@@ -565,17 +567,20 @@ LAST_TIMING = {}   # seconds of the last plain write: staging (enqueue + pinned 
 
 def _plain_eligible(frame, dtypes) -> bool:
     """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
-    casts): the hand-written PLAIN writer takes the partition; anything else goes to pyarrow."""
+    casts) or a datetime column in ms / us / ns: the hand-written PLAIN writer takes the partition;
+    anything else (datetime64[s] too: parquet has no seconds unit) goes to pyarrow."""
     import numpy as np
     import torch
 
-    from .parquet_plain import supported_dtype
+    from .parquet_plain import supported_dtype, timestamp_unit
 
     np_of = {torch.int32: "int32", torch.int64: "int64", torch.float32: "float32", torch.float64: "float64"}
     if len(frame.columns) == 0:
         return False
     for name, col in frame.items():
         if col.strings is not None or col.offsets is not None or col.data.dtype not in np_of:
+            return False
+        if col.logical is not None and (timestamp_unit(col.logical) is None or (dtypes and name in dtypes)):
             return False
         if dtypes and name in dtypes and not supported_dtype(np.dtype(dtypes[name])):
             return False
@@ -627,8 +632,9 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                 names[j] = fname(j)
                 w = writers[j] = PlainParquetWriter(
                     os.path.join(output_path, names[j]), [c[0] for c in cols],
-                    [c[1].dtype for c in cols], pool=pool)
-            elif w.names != [c[0] for c in cols] or w.dtypes != [c[1].dtype for c in cols]:
+                    [c[1].dtype for c in cols], pool=pool, logical=[c[3] for c in cols])
+            elif w.names != [c[0] for c in cols] or w.dtypes != [c[1].dtype for c in cols] or \
+                    w.logical != [c[3] for c in cols]:
                 # (pyarrow's ParquetWriter raises on a schema change too; never cast silently)
                 raise ValueError(
                     f"to_parquet: partition schema {[(c[0], str(c[1].dtype)) for c in cols]} differs from "
@@ -664,7 +670,7 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                     if dtypes and name in dtypes:
                         data = data.to(t_of[str(np.dtype(dtypes[name]))])
                     mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
-                    cols.append((name, data, mask))
+                    cols.append((name, data, mask, col.logical))
                 on_gpu = any(c[1].is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
@@ -683,7 +689,7 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                         t_st = time.perf_counter()
                         ctx = torch.cuda.stream(copy_s) if on_gpu else _nullcontext()
                         with ctx:
-                            for name, data, mask in cols:
+                            for name, data, mask, logical in cols:
                                 vals, bm = data[s0:s1], None
                                 if mask is not None:
                                     m = mask[s0:s1]
@@ -705,7 +711,7 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                                         keep.append((mm,))
                                     stats.append(mm.numpy() if mm is not None else None)
                                 keep.append((vals, bm))
-                                host.append((name, hv.numpy(), hb.numpy() if hb is not None else None))
+                                host.append((name, hv.numpy(), hb.numpy() if hb is not None else None, logical))
                             event = None
                             if on_gpu:
                                 event = torch.cuda.Event()

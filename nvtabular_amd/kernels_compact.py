@@ -150,7 +150,7 @@ def _compact(frame, ws: torch.Tensor, n: int):
             dst_valid = torch.empty(_bitmap_bytes(mm), dtype=torch.uint8, device=dev)
         if mm > 0:
             jobs.append((data, dst, col.valid, dst_valid, lws, src_n))
-        out[name] = DeviceColumn(dst, dst_valid, None, col.fill, col.strings)
+        out[name] = DeviceColumn(dst, dst_valid, None, col.fill, col.strings, logical=col.logical)
     if jobs:
         descs = (_lib.CompactCol * len(jobs))()
         for d, (data, dst, valid, dst_valid, lws, src_n) in zip(descs, jobs):

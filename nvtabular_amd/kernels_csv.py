@@ -1,6 +1,7 @@
 """Delimited text -> DeviceFrame: the host driver of the nvt_csv_* entries (include/nvt_hip.h,
 csrc/nvt_csv.hip).  One partition's bytes are on the device already; this module indexes the
-fields, parses the numeric columns in one launch per 64 of them, builds Arrow buffers for the
+fields, parses the numeric columns in one launch per 64 of them and the ISO-8601 columns named in
+``parse_dates`` in a launch of their own (csrc/nvt_datetime.hip), builds Arrow buffers for the
 string columns and keys those as ``kernels_strings.column_from_string_array`` does.
 
 Two read-backs per partition: the field / row counts after the first pass (they size the index
@@ -19,6 +20,7 @@ from . import _lib
 from . import kernels as K
 from . import kernels_strings as KS
 from ._lib import check
+from .csv_text import DATETIME as _DATETIME   # the dtype of a column named in parse_dates
 
 _TORCH = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
 _CODE = {"int32": _lib.NVT_I32, "int64": _lib.NVT_I64, "float32": _lib.NVT_F32, "float64": _lib.NVT_F64}
@@ -33,6 +35,8 @@ def empty_frame(want, dtypes, device):
     for c in want:
         if dtypes[c] == "string":
             out[c] = DeviceColumn(torch.empty(0, dtype=torch.int64, device=device), None, None, None, {})
+        elif dtypes[c] == _DATETIME:
+            out[c] = DeviceColumn(torch.empty(0, dtype=torch.int64, device=device), logical=_DATETIME)
         else:
             out[c] = DeviceColumn(torch.empty(0, dtype=_TORCH[dtypes[c]], device=device))
     return DeviceFrame(out)
@@ -82,6 +86,12 @@ def _field_error(code: int, names, dtypes, where: str, text: str = None):
     name = names[k]
     if dtypes[name] == "string":
         what = "has a quote inside its quotes that is not doubled"
+    elif dtypes[name] == _DATETIME:
+        what = ("lies outside the range of datetime64[ns] (1677-09-21 to 2262-04-11)" if rc == _lib.CSV_OVERFLOW
+                else "is not YYYY-MM-DD[(T| )HH:MM[:SS[.fffffffff]]] (no zone, no blanks) or names no calendar day")
+        shown = f" {text!r}" if text is not None else ""
+        return ValueError(f"{where}: row {row}, column '{name}': the field{shown} {what}; "
+                          f"leave '{name}' out of parse_dates to read the column as text")
     else:
         what = f"does not fit {dtypes[name]}" if rc == _lib.CSV_OVERFLOW else f"does not parse as {dtypes[name]}"
     shown = f" {text!r}" if text is not None else ""
@@ -123,7 +133,8 @@ def parse_text(text: torch.Tensor, nbytes: int, host: np.ndarray, sep: int, quot
     if nrows == 0:
         return empty_frame(want, dtypes, dev)
     n = nrows
-    numeric = [c for c in want if dtypes[c] != "string"]
+    numeric = [c for c in want if dtypes[c] not in ("string", _DATETIME)]
+    dates = [c for c in want if dtypes[c] == _DATETIME]
     strings = [c for c in want if dtypes[c] == "string"]
     data, valid, slow = {}, {}, {}
     if numeric:
@@ -138,6 +149,16 @@ def parse_text(text: torch.Tensor, nbytes: int, host: np.ndarray, sep: int, quot
         K.stat_add("csv_parse_many")
         check(lib.nvt_csv_parse_many(text.data_ptr(), nbytes, field_end.data_ptr(), n, ncols, quote, descs,
                                      len(numeric), state.data_ptr(), s), "nvt_csv_parse_many")
+    if dates:
+        # a kernel of its own behind the numeric one (the float parser sets that one's registers)
+        descs = (_lib.CsvCol * len(dates))()
+        for d, c in zip(descs, dates):
+            data[c] = torch.empty(n, dtype=torch.int64, device=dev)
+            valid[c] = _words(n, dev)
+            d.out, d.out_valid, d.k, d.dtype = data[c].data_ptr(), valid[c].data_ptr(), names.index(c), _lib.NVT_I64
+        K.stat_add("csv_parse_datetime")
+        check(lib.nvt_csv_parse_datetime(text.data_ptr(), nbytes, field_end.data_ptr(), n, ncols, quote, descs,
+                                         len(dates), state.data_ptr(), s), "nvt_csv_parse_datetime")
     offsets = {}
     if strings:
         need = C.c_uint64()
@@ -189,4 +210,6 @@ def parse_text(text: torch.Tensor, nbytes: int, host: np.ndarray, sep: int, quot
         out[c] = DeviceColumn(keys, valid[c], None, None, KS.lookup_dict(keys, valid[c], b))
     for c in numeric:
         out[c] = DeviceColumn(data[c], valid[c])
+    for c in dates:
+        out[c] = DeviceColumn(data[c], valid[c], logical=_DATETIME)
     return DeviceFrame({c: out[c] for c in want})

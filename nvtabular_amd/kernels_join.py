@@ -164,7 +164,7 @@ class ExternalIndex:
             else:
                 data = col.data[order].contiguous()
                 valid = _permute_bits(col.valid, order) if col.valid is not None else None
-            self.payload[name] = DeviceColumn(data, valid, None, None, col.strings)
+            self.payload[name] = col.like(data, valid)
         self._alive = alive
         s = _lib.JoinIndex()
         s.slots = slots.data_ptr()
@@ -207,7 +207,7 @@ def _gather(idx: torch.Tensor, m: int, cols, force_valid: bool, dev):
             src = col.data.contiguous()
             dst, dst_valid = _alloc(src, m, force_valid or col.valid is not None, dev)
             jobs.append((src, col.valid, dst, dst_valid))
-            out[name] = DeviceColumn(dst, dst_valid, None, col.fill, col.strings)
+            out[name] = DeviceColumn(dst, dst_valid, None, col.fill, col.strings, logical=col.logical)
         if m:
             K.stat_add("join_gather")
             check(_lib.load().nvt_join_gather(idx.data_ptr(), m, _cols_desc(jobs), len(jobs), K.stream_ptr()),
@@ -230,7 +230,7 @@ def join_frame(left, on: List[str], ix: ExternalIndex, how: str, ext_names: List
     if n == 0:
         out = left.copy()
         for name, col in payload:
-            out[name] = DeviceColumn(col.data[:0], None, None, None, col.strings)
+            out[name] = col.like(col.data[:0])
         return out
     stream = K.stream_ptr()
     keys, alive = key_descs([left[c] for c in on], ix.modes)
@@ -243,7 +243,7 @@ def join_frame(left, on: List[str], ix: ExternalIndex, how: str, ext_names: List
             for name, col in payload[i0: i0 + _lib.JOIN_MAX_COLS]:
                 dst, dst_valid = _alloc(col.data, n, True, dev)
                 jobs.append((col.data, col.valid, dst, dst_valid))
-                out[name] = DeviceColumn(dst, dst_valid, None, None, col.strings)
+                out[name] = col.like(dst, dst_valid)
             K.stat_add("join_probe_gather")
             check(lib.nvt_join_probe_gather(C.byref(ix.struct), keys, ix.nkeys, n, _cols_desc(jobs), len(jobs),
                                             None, stream), "nvt_join_probe_gather")

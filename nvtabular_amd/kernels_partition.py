@@ -174,7 +174,8 @@ def _shuffle_list_column(name, frames, perms, cnt, off, P):
 
         valid = pack_bitmap_device(torch.cat(bits))
     leaves = torch.cat(leaves)
-    big = DeviceFrame({name: DeviceColumn(leaves, valid, torch.cat(offs), None, strings)})
+    big = DeviceFrame({name: DeviceColumn(leaves, valid, torch.cat(offs), None, strings,
+                                            logical=cols[0].logical)})
     out = []
     for p in range(P):
         index = torch.cat([perms[i][int(off[i, p]): int(off[i, p] + cnt[i, p])] + row_base[i]
@@ -258,7 +259,7 @@ def shuffle_frames(frames, keys: Sequence[str], P: int) -> List:
                 dst_valid = None
                 if (p, n) in valid_at:
                     dst_valid = torch.empty(_bitmap_bytes(mp), dtype=torch.uint8, device=dev)
-                out[p][n] = DeviceColumn(dst, dst_valid, None, None, strings)
+                out[p][n] = DeviceColumn(dst, dst_valid, None, None, strings, logical=cols[0].logical)
                 if mp:
                     jobs.append((n, dst, dst_valid))
             for j0 in range(0, len(jobs), _lib.PARTITION_MAX_COLS):

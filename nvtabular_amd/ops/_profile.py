@@ -102,8 +102,8 @@ def merge_ranks(acc: torch.Tensor, is_float) -> torch.Tensor:
 
 class ProfileFit:
     """Streaming state: one accumulator row per profiled column.  A column's dtype is taken from
-    the first partition that holds it; string columns and dtypes outside ``dtypes_taken`` are left
-    out (``dtypes[name]`` stays None)."""
+    the first partition that holds it; string and datetime columns and dtypes outside
+    ``dtypes_taken`` are left out (``dtypes[name]`` stays None)."""
 
     def __init__(self, names, leaves_of_lists=False, dtypes_taken=_PROFILED, device=None):
         self.names = list(names)
@@ -118,7 +118,7 @@ class ProfileFit:
         for n in self.names:
             col = frame[n]
             self.device = col.data.device
-            if col.strings is None and col.data.dtype in self.taken:
+            if col.strings is None and col.logical is None and col.data.dtype in self.taken:
                 self.dtypes[n] = col.data.dtype
         self._allocate()
 

@@ -8,6 +8,8 @@ from .base import Operator
 
 
 class AddMetadata(Operator):
+    accepts_datetime = True
+
     def __init__(self, tags=None, properties=None):
         super().__init__()
         self.tags = tags or []

@@ -47,6 +47,19 @@ class Operator:
     # True: compute_selector reads properties that a fit fills in (DropLowCardinality); Workflow.fit
     # then refreshes the graph's schemas and selectors behind every fit phase
     selector_from_fit = False
+    # False: the operator computes on the numbers of its columns and a datetime column
+    # (DeviceColumn.logical) must be converted first; the Workflow raises instead of handing it
+    # over.  True: it moves, selects, labels or hashes the column and takes the int64 counts.
+    accepts_datetime = False
+
+    def datetime_rejects(self, col_selector, frame):
+        """The input columns this operator must not be given because they are datetimes: what the
+        Workflow's guard raises for ("Datetime columns").  Groupby and JoinExternal
+        accept some uses of a datetime column and override this; JoinGroupby and TargetEncoding add
+        the dependency columns they reduce (``cont_cols``, the targets), which no selector names."""
+        if self.accepts_datetime:
+            return []
+        return [n for n in col_selector.names if n in frame and frame[n].logical is not None]
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

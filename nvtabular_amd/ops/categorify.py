@@ -76,6 +76,8 @@ class _GroupFit:
 class Categorify(StatOperator):
     """Encode categorical columns as contiguous integers (categorify.py:59-343)."""
 
+    accepts_datetime = True
+
     def __init__(
         self,
         freq_threshold=0,

@@ -13,6 +13,8 @@ from .base import Operator
 
 
 class DropLowCardinality(Operator):
+    accepts_datetime = True
+
     selector_from_fit = True
 
     def __init__(self, min_cardinality=4):

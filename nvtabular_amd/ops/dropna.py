@@ -16,6 +16,8 @@ from .base import Operator
 
 
 class Dropna(Operator):
+    accepts_datetime = True
+
     def transform(self, col_selector: ColumnSelector, df):
         from ..kernels_compact import dropna_frame
 

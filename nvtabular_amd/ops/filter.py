@@ -90,6 +90,8 @@ def _device_mask(res, n: int):
 
 
 class Filter(Operator):
+    accepts_datetime = True
+
     def __init__(self, f):
         super().__init__()
         if f is None:

@@ -91,6 +91,13 @@ class Groupby(Operator):
     def dependencies(self):
         return self.groupby_cols
 
+    def datetime_rejects(self, col_selector, frame):
+        # key, sort and list / first / last / count columns move rows or count them; the other
+        # aggregates are reduced in float64 (nvt_seg_aggregate) and would round nanoseconds
+        _, conv = self._agg_dicts(col_selector)
+        return [c for c, aggs in conv.items()
+                if c in frame and frame[c].logical is not None and any(a != "count" for a in aggs)]
+
     def _find_agg(self, col_schema, input_schema):
         mapping = self.column_mapping(ColumnSelector(input_schema.column_names))
         src = mapping[col_schema.name][0]
@@ -175,7 +182,7 @@ class Groupby(Operator):
             if c in col_selector.names:
                 src = frame[c]
                 data = gkeys[j].to(src.data.dtype) if src.strings is None else gkeys[j]
-                out[c] = DeviceColumn(data, None, None, None, src.strings)
+                out[c] = src.like(data)
         for ci, c in enumerate(conts):
             col = cols[c]
             vals = ok = None
@@ -186,13 +193,13 @@ class Groupby(Operator):
                 name = self.name_sep.join([c, a])
                 if a == "list":
                     vb = None if bool(ok.all()) else pack_bitmap_device(ok)
-                    out[name] = DeviceColumn(vals.contiguous(), vb, offsets, None, col.strings)
+                    out[name] = col.like(vals.contiguous(), vb, offsets)
                 else:
                     take_first = (a == "first") == bool(self.ascending)  # groupby.py:287-296
                     pos = offsets[:-1] if take_first else offsets[1:] - 1
                     sel_ok = ok[pos]
                     vb = None if bool(sel_ok.all()) else pack_bitmap_device(sel_ok)
-                    out[name] = DeviceColumn(vals[pos].contiguous(), vb, None, None, col.strings)
+                    out[name] = col.like(vals[pos].contiguous(), vb)
             for a in conv.get(c, []):
                 out[self.name_sep.join([c, a])] = _finish_agg(
                     a, col.data.dtype, count[ci].to(torch.float64), sm[ci],

@@ -21,6 +21,8 @@ from .categorify import _emb_sz_rule
 
 
 class HashBucket(Operator):
+    accepts_datetime = True
+
     def __init__(self, num_buckets: Union[int, Dict[str, int]]):
         if isinstance(num_buckets, (dict, int)):
             self.num_buckets = num_buckets

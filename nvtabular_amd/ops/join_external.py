@@ -162,6 +162,10 @@ class JoinExternal(Operator):
         from .. import kernels_join as KJ
 
         ext = self._external_frame()
+        for c in self.on_ext:
+            if ext[c].logical is not None:
+                raise TypeError(f"JoinExternal: key column '{c}' of the external table is {ext[c].logical}; "
+                                f"a datetime column cannot be a join key, convert it first")
         modes = KJ.key_modes([KJ.key_class(left[c]) for c in self.on],
                              [KJ.key_class(ext[c]) for c in self.on_ext], self.on, self.on_ext)
         payload = tuple(self._payload(left.columns))
@@ -171,6 +175,11 @@ class JoinExternal(Operator):
             ix = self._indexes[key] = KJ.ExternalIndex(ext, self.on_ext, list(payload), modes)
             self.builds += 1
         return ix
+
+    def datetime_rejects(self, col_selector, frame):
+        # carried columns of both sides keep their type; a key is hashed and compared by class
+        # (integer / float / string), which a datetime is none of
+        return [c for c in self.on if c in frame and frame[c].logical is not None]
 
     def transform(self, col_selector: ColumnSelector, df):
         from .. import kernels_join as KJ

@@ -335,6 +335,11 @@ class JoinGroupby(StatOperator):
     def dependencies(self):
         return self.cont_cols  # selector or node: either way an upstream dependency
 
+    def datetime_rejects(self, col_selector, frame):
+        # the cont_cols are dependencies, not selected columns: they are reduced in float64
+        conts = [c for c in self.cont_names.names if c in frame and frame[c].logical is not None]
+        return super().datetime_rejects(col_selector, frame) + conts
+
     def compute_selector(self, input_schema, selector, parents_selector=None,
                          dependencies_selector=None):
         self._validate_matching_cols(input_schema, parents_selector, "computing input selector")

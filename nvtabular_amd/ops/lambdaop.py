@@ -6,7 +6,9 @@ DeviceFrame the column handed over is a ``DeviceSeries`` (series.py): numeric ex
 ``col * df["other"]``) stay in HBM and run as device kernels.  A UDF that needs something only
 pandas offers (``col.str.slice(1, 3)``) raises ``HostFallback`` inside the wrapper and is re-run
 on the host with pandas Series -- the reference's CPU behaviour.  ``last_path`` records which
-route the last ``transform`` took ("device" / "host").
+route the last ``transform`` took ("device" / "host").  A datetime column arrives as a
+``DatetimeSeries`` (``col.dt.hour``, ``col.astype("datetime64[s]")``); a UDF that returns one, on
+either route, yields a datetime column.
 """
 from __future__ import annotations
 
@@ -17,11 +19,13 @@ import torch
 
 from ..device import DeviceColumn, DeviceFrame, as_device_frame
 from ..selector import ColumnSelector
-from ..series import DeviceFrameView, DeviceSeries, HostFallback
+from ..series import DatetimeSeries, DeviceFrameView, DeviceSeries, HostFallback
 from .base import Operator
 
 
 class LambdaOp(Operator):
+    accepts_datetime = True
+
     def __init__(self, f, dtype=None, tags=None, properties=None, dependency=None):
         super().__init__()
         if f is None:
@@ -45,7 +49,7 @@ class LambdaOp(Operator):
         n = len(frame)
         for name in col_selector.names:
             res = self._call(DeviceSeries.from_column(frame[name], name), view)
-            if isinstance(res, DeviceSeries):
+            if isinstance(res, (DeviceSeries, DatetimeSeries)):
                 out[name] = res.to_column()
             elif isinstance(res, torch.Tensor) and res.is_cuda and res.dim() == 1 and res.numel() == n:
                 out[name] = DeviceColumn(res.contiguous())

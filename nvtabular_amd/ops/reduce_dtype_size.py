@@ -20,6 +20,8 @@ from .base import StatOperator
 
 
 class ReduceDtypeSize(StatOperator):
+    accepts_datetime = True
+
     def __init__(self, float_dtype=np.float32):
         super().__init__()
         self.float_dtype = float_dtype

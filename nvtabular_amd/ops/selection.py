@@ -9,6 +9,8 @@ from .base import Operator
 
 
 class ConcatColumns(Operator):
+    accepts_datetime = True
+
     def compute_selector(self, input_schema, selector, parents_selector=None,
                          dependencies_selector=None):
         return (parents_selector or ColumnSelector()) + (dependencies_selector or ColumnSelector())
@@ -21,6 +23,8 @@ class ConcatColumns(Operator):
 
 
 class SubsetColumns(Operator):
+    accepts_datetime = True
+
     def compute_selector(self, input_schema, selector, parents_selector=None,
                          dependencies_selector=None):
         self._validate_matching_cols(input_schema, selector, "computing input selector")
@@ -34,6 +38,8 @@ class SubsetColumns(Operator):
 
 
 class SubtractionOp(Operator):
+    accepts_datetime = True
+
     def __init__(self, selector=None):
         self.removed = selector
 
@@ -54,6 +60,8 @@ class SubtractionOp(Operator):
 
 class Rename(Operator):
     """nvtabular/ops/rename.py: rename columns by function, postfix or single name."""
+
+    accepts_datetime = True
 
     def __init__(self, f=None, postfix=None, name=None):
         if not f and postfix is None and name is None:

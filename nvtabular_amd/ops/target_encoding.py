@@ -448,6 +448,11 @@ class TargetEncoding(StatOperator):
     def dependencies(self):
         return self.dependency
 
+    def datetime_rejects(self, col_selector, frame):
+        # the targets are dependencies, not selected columns: their means are taken in float64
+        targets = [c for c in self.target_columns if c in frame and frame[c].logical is not None]
+        return super().datetime_rejects(col_selector, frame) + targets
+
     def compute_selector(self, input_schema, selector, parents_selector=None,
                          dependencies_selector=None):
         self._validate_matching_cols(input_schema, parents_selector, "computing input selector")

@@ -18,6 +18,9 @@ The file layout (magic, row groups of column chunks of pages, thrift-compact Fil
 footer) is written by hand: parquet-format's PageHeader / FileMetaData structures in the
 thrift compact protocol.  Readers: pyarrow / pandas / the reference's merlin-io read these
 files like any other (tests/test_parquet_plain.py reads them back with pyarrow).
+A datetime column (DeviceColumn.logical, unit ms / us / ns) is an INT64 column whose
+SchemaElement carries the LogicalType TIMESTAMP (isAdjustedToUTC = false) and, for ms / us, the
+converted type; parquet has no seconds unit.
 Anything else (strings, lists, booleans, requested dtype casts) stays with pyarrow's writer.
 """
 from __future__ import annotations
@@ -35,8 +38,22 @@ PAGE_VALUES = 1 << 20          # values per data page (8 MiB of int64)
 ROW_GROUP_ROWS = 1 << 23       # rows per row group
 
 
+# datetime unit -> (TimeUnit union field of LogicalType TIMESTAMP, converted type or None)
+_TS_UNIT = {"ms": (1, 9), "us": (2, 10), "ns": (3, None)}
+_TS_BY_FIELD = {1: "ms", 2: "us", 3: "ns"}
+
+
 def supported_dtype(dt) -> bool:
     return np.dtype(dt) in _PQ_TYPE
+
+
+def timestamp_unit(logical) -> Optional[str]:
+    """"ms" / "us" / "ns" of a datetime64 dtype the PLAIN writer takes, else None."""
+    if logical is None:
+        return None
+    dt = np.dtype(logical)
+    unit = np.datetime_data(dt)[0] if dt.kind == "M" else None
+    return unit if unit in _TS_UNIT else None
 
 
 def _varint(v: int) -> bytes:
@@ -79,6 +96,10 @@ class _Struct:
     def i64(self, fid, v):
         self._head(fid, _CT_I64)
         self.b += _zigzag(int(v))
+        return self
+
+    def bool(self, fid, v):
+        self._head(fid, 1 if v else 2)   # (the value of a boolean field is its type id)
         return self
 
     def binary(self, fid, s):
@@ -128,13 +149,18 @@ class PlainParquetWriter:
     with ``os.pwrite`` (which releases the GIL) while the caller stages the next row group or
     another file."""
 
-    def __init__(self, path: str, names: Sequence[str], dtypes: Sequence, pool=None):
+    def __init__(self, path: str, names: Sequence[str], dtypes: Sequence, pool=None, logical=None):
+        """``logical[j]``: None, or datetime64[ms|us|ns] for an int64 column of such counts."""
         self.path = path
         self.names = list(names)
         self.dtypes = [np.dtype(d) for d in dtypes]
         for d in self.dtypes:
             if d not in _PQ_TYPE:
                 raise TypeError(f"PlainParquetWriter: unsupported dtype {d}")
+        self.logical = [np.dtype(x) if x is not None else None for x in (logical or [None] * len(self.names))]
+        for d, x in zip(self.dtypes, self.logical):
+            if x is not None and (timestamp_unit(x) is None or d != np.dtype("int64")):
+                raise TypeError(f"PlainParquetWriter: logical type {x} on a {d} column (int64 counts in ms, us or ns)")
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
         os.pwrite(self.fd, b"PAR1", 0)
         self.pos = 4
@@ -265,8 +291,15 @@ class PlainParquetWriter:
             f.result()
         self.pending = []
         schema = [_Struct().binary(4, "schema").i32(5, len(self.names)).done()]
-        for name, dt in zip(self.names, self.dtypes):
-            schema.append(_Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, name).done())
+        for name, dt, logical in zip(self.names, self.dtypes, self.logical):
+            el = _Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, name)
+            if logical is not None:
+                field, conv = _TS_UNIT[timestamp_unit(logical)]
+                if conv is not None:
+                    el.i32(6, conv)
+                unit = _Struct().struct(field, _Struct().done()).done()
+                el.struct(10, _Struct().struct(8, _Struct().bool(1, False).struct(2, unit).done()).done())
+            schema.append(el.done())
         groups = [_Struct().list(1, _CT_STRUCT, [self._chunk_struct(c) for c in chunks]).i64(2, total).i64(3, n).done()
                   for chunks, total, n in self.row_groups]
         # column_orders: TYPE_ORDER for every column (min_value / max_value are only defined with it)
@@ -406,13 +439,27 @@ class PlainParquetFile:
         if len(leaves) != root_children or any(e.get(5) for e in leaves):
             self.eligible, self.why = False, "nested schema"
         self.names = [e.get(4, b"").decode() for e in leaves]
-        self.dtypes, self.max_def = [], []
+        self.dtypes, self.max_def, self.units = [], [], []
         for e in leaves:
             ptype, rep = e.get(1), e.get(3, 0)
             conv, logical = e.get(6), e.get(10)
             dt = _PQ_NP.get(ptype)
             if dt is None or rep == 2:
                 self.eligible, self.why = False, f"column {e.get(4)!r}: physical type {ptype} / repetition {rep}"
+            # an INT64 TIMESTAMP (LogicalType union field 8 {1: isAdjustedToUTC, 2: unit}, or the
+            # converted types 9 TIMESTAMP_MILLIS / 10 TIMESTAMP_MICROS of legacy writers) keeps its
+            # bits: the counts are taken as they are and the unit is recorded
+            unit = None
+            if ptype == 2 and isinstance(logical, dict) and len(logical) == 1 and isinstance(logical.get(8), dict):
+                tu = logical[8].get(2)
+                unit = _TS_BY_FIELD.get(next(iter(tu))) if isinstance(tu, dict) and len(tu) == 1 else None
+                if unit is not None and conv not in (None, _TS_UNIT[unit][1]):
+                    unit = None
+            elif ptype == 2 and logical is None and conv in (9, 10):
+                unit = "ms" if conv == 9 else "us"
+            self.units.append(unit)
+            if unit is not None:
+                conv = logical = None
             # converted types that reinterpret the integer: DATE 6, TIME 7-8, TIMESTAMP 9-10,
             # UINT 11-14, DECIMAL 5; INT_8 / INT_16 (15 / 16) on a physical INT32 come back as
             # int8 / int16 from pyarrow (legacy writers without a LogicalType): only INT_32 (17)
@@ -465,10 +512,11 @@ class StagedColumn:
     """One column of a partition in pinned host memory: packed (non-null) values + validity
     bitmap, as nvt_pq_decode_chunk leaves them."""
 
-    __slots__ = ("values", "valid", "rows", "nvalid", "dtype")
+    __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical")
 
-    def __init__(self, values, valid, rows, nvalid, dtype):
+    def __init__(self, values, valid, rows, nvalid, dtype, logical=None):
         self.values, self.valid, self.rows, self.nvalid, self.dtype = values, valid, rows, nvalid, dtype
+        self.logical = logical   # datetime64[ms|us|ns] of a TIMESTAMP column, else None
 
 
 _TLS = None
@@ -565,7 +613,9 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
             READER_CHUNKS["plain"] += 1
             row_at += rows
             val_at += int(v.value)
-        return StagedColumn(vals, valid if (valid is not None and val_at < total) else None, total, val_at, dt)
+        logical = np.dtype(f"datetime64[{pf.units[j]}]") if pf.units[j] is not None else None
+        return StagedColumn(vals, valid if (valid is not None and val_at < total) else None, total, val_at, dt,
+                            logical)
 
     futs = []
     try:

@@ -157,6 +157,8 @@ class Schema:
                     if len(nn) and isinstance(nn.iloc[0], (list, np.ndarray)):
                         is_list = True
                         dt = np.asarray(nn.iloc[0]).dtype if len(nn.iloc[0]) else None
+                if isinstance(dt, pd.DatetimeTZDtype):
+                    dt = np.dtype(f"datetime64[{dt.unit}]")   # (the zone is dropped on the way in)
                 if isinstance(dt, pd.api.extensions.ExtensionDtype):
                     dt = getattr(dt, "numpy_dtype", object)
                 cols.append(ColumnSchema(str(n), dt, is_list=is_list, is_ragged=is_list))
@@ -165,7 +167,7 @@ class Schema:
 
         if isinstance(df, DeviceFrame):
             for n, c in df.items():
-                dt = object if c.strings is not None else c.dtype
+                dt = object if c.strings is not None else (c.logical if c.logical is not None else c.dtype)
                 cols.append(ColumnSchema(n, dt, is_list=c.is_list, is_ragged=c.is_list))
             return Schema(cols)
         import pyarrow as pa
@@ -177,7 +179,7 @@ class Schema:
                 if is_list:
                     t = t.value_type
                 try:
-                    dt = t.to_pandas_dtype()
+                    dt = np.dtype(f"datetime64[{t.unit}]") if pa.types.is_timestamp(t) else t.to_pandas_dtype()
                 except Exception:
                     dt = object
                 cols.append(ColumnSchema(f.name, dt, is_list=is_list, is_ragged=is_list))

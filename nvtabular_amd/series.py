@@ -7,8 +7,15 @@ arithmetic, comparisons, ``astype``, ``fillna``, ``clip``, ``abs``, ``where``, `
 ufuncs (``np.log(col + 1)``) run on the HBM-resident buffer through torch-ROCm elementwise
 kernels (plumbing: a UDF is arbitrary Python, there is no fixed kernel to hand-write), with pandas'
 semantics: an integer column that has nulls behaves as float64 with NaN, ``/`` is float64 true
-division, comparisons against a null are False.  Anything else (``.str``, ``.dt``, ``.map``,
+division, comparisons against a null are False.  Anything else (``.str``, ``.map``,
 ``.apply`` ...) raises ``HostFallback`` and LambdaOp re-runs the UDF on pandas on the host.
+
+A datetime column (``DeviceColumn.logical``) is handed over as a ``DatetimeSeries``: int64 counts
+with a validity mask of their own -- NaN in float64 cannot hold a nanosecond count.  Its calendar
+fields (``col.dt.hour`` ...) are one launch of nvt_dt_field each; ``astype("int64")``,
+``astype("datetime64[u]")``, ``isna`` / ``notna`` and comparisons with a datetime series of the
+same unit stay on the device, everything else (arithmetic, ``.dt.floor``, ``strftime``, ``tz_*``)
+raises ``HostFallback``.
 """
 from __future__ import annotations
 
@@ -37,9 +44,11 @@ class DeviceSeries:
 
     # ---- construction ------------------------------------------------------------------
     @staticmethod
-    def from_column(col: DeviceColumn, name=None) -> "DeviceSeries":
+    def from_column(col: DeviceColumn, name=None):
         if col.is_list or col.strings is not None:
             raise HostFallback("list / string column")
+        if col.logical is not None:
+            return DatetimeSeries.from_column(col, name)
         col = col.materialize()
         t = col.data
         if t.dtype == torch.uint8:
@@ -158,6 +167,9 @@ class DeviceSeries:
     def astype(self, dtype):
         if dtype in (str, "str", object, "object", "string"):
             raise HostFallback("astype(str)")
+        logical = _as_datetime_dtype(dtype)
+        if logical is not None:
+            return DatetimeSeries.from_counts(self._t, logical, self.name)
         try:
             dt = torch_dtype(np.dtype(dtype))
         except Exception:
@@ -237,6 +249,172 @@ class DeviceSeries:
     def __getattr__(self, item):
         # .str / .dt / .map / .apply / anything pandas-only
         raise HostFallback(f"Series.{item}")
+
+
+_INT64_MIN = -(1 << 63)
+
+
+def _as_datetime_dtype(dtype):
+    """numpy's datetime64[s|ms|us|ns] when ``dtype`` names one, else None."""
+    try:
+        dt = np.dtype(dtype)
+    except Exception:
+        return None
+    if dt.kind != "M":
+        return None
+    from .device import DATETIME_UNITS
+
+    if np.datetime_data(dt)[0] not in DATETIME_UNITS or np.datetime_data(dt)[1] != 1:
+        raise HostFallback(f"astype({dtype!r})")
+    return dt
+
+
+class _DtAccessor:
+    """``series.dt``: the calendar fields pandas offers that nvt_dt_field computes."""
+
+    def __init__(self, series):
+        self._s = series
+
+    def __getattr__(self, item):
+        from . import kernels_datetime as KD
+
+        if item not in KD.FIELD_CODE:
+            raise HostFallback(f"Series.dt.{item}")
+        s = self._s
+        out = KD.dt_field(s._t, s.bitmap(), KD.unit_of(s.logical), item)
+        if s._ok is None:
+            return DeviceSeries(out, s.name)       # pandas: int32
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=out.device)
+        return DeviceSeries(torch.where(s._ok, out.to(torch.float64), nan), s.name)   # with a NaT: float64
+
+
+class DatetimeSeries:
+    """A datetime column inside a UDF: int64 counts in the unit of ``logical`` (0 under a null)
+    and ``_ok``, None (no NaT) or the bool mask of the rows that hold a value."""
+
+    __array_priority__ = 1000
+
+    def __init__(self, counts: torch.Tensor, logical, ok=None, name=None, bitmap=None):
+        self._t, self.logical, self._ok, self.name, self._bitmap = counts, np.dtype(logical), ok, name, bitmap
+
+    @staticmethod
+    def from_column(col: DeviceColumn, name=None) -> "DatetimeSeries":
+        t, ok, bitmap = col.data, None, None
+        if col.valid is not None:
+            ok = _unpack_valid(col)
+            if bool(ok.all()):      # (pandas decides the dtype of a field by whether there IS a NaT)
+                ok = None
+            else:
+                t, bitmap = torch.where(ok, t, torch.zeros_like(t)), col.valid
+        return DatetimeSeries(t, col.logical, ok, name, bitmap)
+
+    @staticmethod
+    def from_counts(t: torch.Tensor, logical, name=None) -> "DatetimeSeries":
+        """An integer series as counts in the unit of ``logical`` (pandas: ``astype``); INT64_MIN is NaT."""
+        if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise HostFallback(f"astype({logical}) of a {t.dtype} series")
+        t = t.to(torch.int64)
+        nat = t == _INT64_MIN
+        if bool(nat.any()):
+            return DatetimeSeries(torch.where(nat, torch.zeros_like(t), t), logical, ~nat, name)
+        return DatetimeSeries(t, logical, None, name)
+
+    def bitmap(self):
+        if self._ok is not None and self._bitmap is None:
+            from .device import pack_bitmap_device
+
+            self._bitmap = pack_bitmap_device(self._ok)
+        return self._bitmap
+
+    def to_column(self) -> DeviceColumn:
+        return DeviceColumn(self._t.contiguous(), self.bitmap(), logical=self.logical)
+
+    @property
+    def dtype(self):
+        return self.logical
+
+    @property
+    def dt(self):
+        return _DtAccessor(self)
+
+    def __len__(self):
+        return int(self._t.numel())
+
+    def isna(self):
+        if self._ok is None:
+            return DeviceSeries(torch.zeros_like(self._t, dtype=torch.bool), self.name)
+        return DeviceSeries(~self._ok, self.name)
+
+    isnull = isna
+
+    def notna(self):
+        return DeviceSeries(~self.isna()._t, self.name)
+
+    notnull = notna
+
+    def astype(self, dtype):
+        from . import kernels_datetime as KD
+
+        if dtype in (int, "int", "int64", np.int64) or (isinstance(dtype, np.dtype) and dtype == np.dtype("int64")):
+            t = self._t
+            if self._ok is not None:    # pandas: NaT -> INT64_MIN
+                t = torch.where(self._ok, t, torch.full((), _INT64_MIN, dtype=torch.int64, device=t.device))
+            return DeviceSeries(t, self.name)
+        logical = _as_datetime_dtype(dtype) if not isinstance(dtype, (type, type(None))) else None
+        if logical is None:
+            raise HostFallback(f"astype({dtype!r}) of a datetime series")
+        src = KD.UNIT_PER_SECOND[KD.unit_of(self.logical)]
+        dst = KD.UNIT_PER_SECOND[KD.unit_of(logical)]
+        t = self._t
+        if dst < src:        # coarser: the count is rounded down, as numpy and pandas do
+            t = torch.div(t, src // dst, rounding_mode="floor")
+        elif dst > src:
+            k = dst // src
+            if t.numel() and int(t.abs().max().item()) > ((1 << 63) - 1) // k:
+                raise HostFallback("datetime unit conversion out of bounds")   # (pandas raises there)
+            t = t * k
+        return DatetimeSeries(t, logical, self._ok, self.name, self._bitmap)
+
+    def _cmp(self, other, fn, when_nat: bool):
+        if not isinstance(other, DatetimeSeries) or other.logical != self.logical:
+            raise HostFallback("comparison of a datetime series with anything but one of the same unit")
+        r = fn(self._t, other._t)
+        for ok in (self._ok, other._ok):    # NaT compares False (!=: True), like pandas
+            if ok is not None:
+                r = (r | ~ok) if when_nat else (r & ok)
+        return DeviceSeries(r, self.name)
+
+    def __eq__(self, o): return self._cmp(o, torch.eq, False)  # noqa: E704
+    def __ne__(self, o): return self._cmp(o, torch.ne, True)
+    def __lt__(self, o): return self._cmp(o, torch.lt, False)
+    def __le__(self, o): return self._cmp(o, torch.le, False)
+    def __gt__(self, o): return self._cmp(o, torch.gt, False)
+    def __ge__(self, o): return self._cmp(o, torch.ge, False)
+    __hash__ = None
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        raise HostFallback(f"numpy ufunc {getattr(ufunc, '__name__', ufunc)} on a datetime series")
+
+    def __array__(self, *a, **k):
+        raise HostFallback("conversion to a numpy array")
+
+    def __getattr__(self, item):
+        raise HostFallback(f"Series.{item} on a datetime series")
+
+
+def _datetime_host_only(name):
+    def op(self, *a, **k):
+        raise HostFallback(f"Series.{name} on a datetime series")
+
+    op.__name__ = name
+    return op
+
+
+for _n in ("add", "radd", "sub", "rsub", "mul", "rmul", "truediv", "rtruediv", "floordiv", "rfloordiv", "mod",
+           "rmod", "pow", "rpow", "neg", "pos", "abs", "invert", "and", "rand", "or", "ror", "xor", "rxor",
+           "getitem", "iter"):
+    setattr(DatetimeSeries, f"__{_n}__", _datetime_host_only(f"__{_n}__"))
+del _n
 
 
 class DeviceFrameView:

@@ -111,6 +111,7 @@ class Workflow:
             out = root[node.output_schema.column_names]
         else:
             inp = self._node_input(node, root, cache)
+            _guard_datetime(node, inp)
             with annotate(node.op.range_name("transform")):
                 out = node.op.transform(node.input_columns, inp)
             out, _ = as_device_frame(out)
@@ -225,6 +226,7 @@ class Workflow:
                 with pass_memo():  # one pass over this partition: shared intermediates
                     for n in phase:
                         inp = self._node_input(n, part, cache)
+                        _guard_datetime(n, inp)
                         with annotate(n.op.range_name("fit")):
                             n.op.fit_partition(states[id(n)], n.input_columns, inp)
             # operators whose fit_end only reads a few scalars back (Normalize) go first: their
@@ -348,6 +350,14 @@ class Workflow:
         for node in iter_nodes(self.output_node):
             if isinstance(node.op, StatOperator):
                 node.op.clear()
+
+
+def _guard_datetime(node: Node, inp: DeviceFrame):
+    """An operator that computes on numbers is not handed a datetime column (int64 counts under
+    a logical type): it would normalise, clip or average epoch counts without a word."""
+    for name in node.op.datetime_rejects(node.input_columns, inp):
+        raise TypeError(f"{node.op.label}: column '{name}' is {inp[name].logical}; convert it first, "
+                        f"e.g. ['{name}'] >> LambdaOp(lambda c: c.dt.hour)")
 
 
 def _async_pending(node: Node) -> bool:
