@@ -1153,6 +1153,52 @@ int nvt_list_len_minmax(const nvt_list_len_col *cols, int ncols, void *stream);
 int nvt_difference_lag_many(const nvt_lag_key *keys, int nkeys, const nvt_lag_col *cols, int ncols, uint64_t n,
                             void *stream);
 
+/* ---- parquet list columns: repetition / definition level streams (Dataset.to_parquet) ----
+ * A list column is written as the standard three-level list (max repetition level 1, max
+ * definition level 3).  There are no null lists, so a row of L leaves occupies max(L, 1) SLOTS: an
+ * empty row is one slot (rep 0, def 1), leaf i of a row has rep 0 (first leaf of its row) or 1 and
+ * def 3 (valid) or 2 (null).  `offsets` points at the n + 1 offsets of the rows to write (any row
+ * range of a column); n > 0.
+ * nvt_pqlist_plan: slot_start[r] (n + 1 words) = the exclusive prefix sum of max(len_r, 1), and
+ *   the page table.  Nominal page p starts at the first row r with slot_start[r] >= p * page_slots;
+ *   a page that gets no row is dropped, so a page is never cut inside a row and may exceed
+ *   page_slots by less than one row.  table: NVT_PQLIST_HEADER_WORDS + max_pages *
+ *   NVT_PQLIST_PAGE_WORDS uint64:
+ *     header {pages, slots, rep bytes, def bytes, pack tiles, offsets[0] - origin[0],
+ *             offsets[n] - origin[0], overflow}    (origin: the column's first offset; the two
+ *             differences are the range of the rows' leaves in the column's value buffer)
+ *     page   {first row, rows, first slot, slots, rep offset, def offset, first pack tile, leaves}
+ *   A page's repetition levels are ceil(slots / 8) bytes at `rep offset` of the rep buffer (regions
+ *   are padded to 8 bytes), its definition levels 2 * ceil(slots / 8) bytes at `def offset` of a
+ *   def buffer (padded to 16): the payload of ONE bit-packed run of the RLE / bit-packing hybrid at
+ *   bit width 1 / 2, LSB first, the bits behind the last slot 0.  `overflow` is 1 -- and the pack
+ *   writes nothing -- when there are more than max_pages pages or more than rep_cap / def_cap
+ *   bytes.  ws: nvt_pqlist_ws_bytes(n) bytes, 8-byte aligned.
+ * nvt_pqlist_pack_many: ONE launch per NVT_PQLIST_MAX_COLS descriptors writes rep_out (once) and
+ *   every descriptor's def_out, and counts its non-null leaves per page into nonnull[max_pages]
+ *   (zeroed here; integer atomics).  A descriptor is one definition stream: a leaf bitmap, or NULL
+ *   for every column without one.  Leaf L (a value of `offsets`) is bit bit0 + (L - origin[0]) of
+ *   leaf_valid; a bit at or past nbits is null.  max_slots bounds the slot total (it sizes the
+ *   grid).  Buffers 8-byte aligned.
+ * Every entry is stream-ordered and does not synchronise. */
+#define NVT_PQLIST_MAX_COLS 16
+#define NVT_PQLIST_HEADER_WORDS 8
+#define NVT_PQLIST_PAGE_WORDS 8
+typedef struct nvt_pqlist_col {
+  const uint8_t *leaf_valid; /* leaf bitmap or NULL                              */
+  uint64_t bit0;             /* bit of the leaf that origin[0] names             */
+  uint64_t nbits;            /* bits of leaf_valid that may be read              */
+  uint8_t *def_out;          /* def_cap bytes                                    */
+  uint64_t *nonnull;         /* max_pages counters                               */
+} nvt_pqlist_col;
+int nvt_pqlist_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_pqlist_plan(const int64_t *offsets, const int64_t *origin, uint64_t n, uint64_t page_slots, uint64_t max_pages, uint64_t rep_cap,
+                    uint64_t def_cap, uint64_t *slot_start, uint64_t *table, void *ws, uint64_t ws_bytes,
+                    void *stream);
+int nvt_pqlist_pack_many(const nvt_pqlist_col *cols, int ncols, const int64_t *offsets, const int64_t *origin,
+                         uint64_t n, const uint64_t *slot_start, const uint64_t *table, uint64_t max_pages,
+                         uint64_t max_slots, uint8_t *rep_out, void *stream);
+
 /* ---- exact column medians: ops.FillMedian (MSD radix select) ----
  * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a
  * negative value and the sign bit of the others, integers flip the sign bit.  The two middle

@@ -329,6 +329,19 @@ SIGNATURES.update({
     "nvt_difference_lag_many": [C.POINTER(LagKey), _i32, C.POINTER(LagCol), _i32, _u64, _vp],
 })
 
+class PqListCol(C.Structure):
+    """nvt_pqlist_col: one definition-level stream written by nvt_pqlist_pack_many."""
+    _fields_ = [("leaf_valid", _vp), ("bit0", _u64), ("nbits", _u64), ("def_out", _vp), ("nonnull", _vp)]
+
+
+# include/nvt_hip.h NVT_PQLIST_MAX_COLS / NVT_PQLIST_HEADER_WORDS / NVT_PQLIST_PAGE_WORDS
+PQLIST_MAX_COLS, PQLIST_HEADER_WORDS, PQLIST_PAGE_WORDS = 16, 8, 8
+SIGNATURES.update({
+    "nvt_pqlist_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_pqlist_plan": [_vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
+    "nvt_pqlist_pack_many": [C.POINTER(PqListCol), _i32, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp],
+})
+
 class SelectCol(C.Structure):
     """nvt_select_col: one chunk of one column read by nvt_select_hist_many."""
     _fields_ = [("x", _vp), ("valid", _vp), ("n", _u64), ("dtype", C.c_int32), ("has_fill", C.c_int32),

@@ -336,8 +336,11 @@ class Dataset:
           device, before the copy out); ``Shuffle.PER_WORKER`` additionally permutes each
           output file as a whole (its pieces are held on the host until the end); ``None`` /
           ``False`` keeps the row order.
-        * ``dtypes``: {column: dtype} casts applied on the way out.
-        * ``compression``: ``None`` (default) lets fixed-width numeric frames take the hand-written
+        * ``dtypes``: {column: dtype} casts applied on the way out (an entry that names a list
+          column sends the frame to pyarrow, whose cast does not convert lists).
+        * ``compression``: ``None`` (default) lets fixed-width numeric frames -- flat int32 / int64 /
+          float32 / float64 and datetime columns, and list columns with such number leaves (written
+          as the standard three-level list, levels packed on the device) -- take the hand-written
           PLAIN writer (uncompressed pages, no dictionary, no column statistics: files are larger
           than pyarrow's snappy + dictionary output and carry no min / max for predicate
           pushdown -- the price of writing at tens of GB/s); any codec name (``"snappy"``,
@@ -562,13 +565,17 @@ class StagedPartition:
 PLAIN_WRITE_THREADS = int(os.environ.get("NVT_PARQUET_THREADS", "16"))
 PLAIN_ROW_GROUP = int(os.environ.get("NVT_PARQUET_ROW_GROUP", str(1 << 22)))
 PLAIN_INFLIGHT = int(os.environ.get("NVT_PARQUET_INFLIGHT", "8"))   # row groups being written at once
-LAST_TIMING = {}   # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing
+# seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
+# levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables
+LAST_TIMING = {}
 
 
 def _plain_eligible(frame, dtypes) -> bool:
     """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
-    casts) or a datetime column in ms / us / ns: the hand-written PLAIN writer takes the partition;
-    anything else (datetime64[s] too: parquet has no seconds unit) goes to pyarrow."""
+    casts), a datetime column in ms / us / ns, or a list column on the device whose leaves are
+    int32 / int64 / float32 / float64 numbers: the hand-written PLAIN writer takes the partition;
+    anything else (datetime64[s] too: parquet has no seconds unit; string, bool and 8 / 16-bit
+    leaves; a cast of a list column) goes to pyarrow."""
     import numpy as np
     import torch
 
@@ -578,7 +585,10 @@ def _plain_eligible(frame, dtypes) -> bool:
     if len(frame.columns) == 0:
         return False
     for name, col in frame.items():
-        if col.strings is not None or col.offsets is not None or col.data.dtype not in np_of:
+        if col.strings is not None or col.data.dtype not in np_of:
+            return False
+        if col.offsets is not None and (not col.data.is_cuda or col.logical is not None or
+                                        (dtypes and name in dtypes)):
             return False
         if col.logical is not None and (timestamp_unit(col.logical) is None or (dtypes and name in dtypes)):
             return False
@@ -593,6 +603,11 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
     stream (nulls: values compacted and the validity bitmap re-packed on the device first) while
     the previous row group is written -- all its column chunks at once, by a pool of threads
     calling pwrite at offsets laid out beforehand (PlainParquetWriter).
+    List columns: the repetition / definition levels of a row group are packed on the device
+    (kernels_parquet_list: the columns that share an offsets tensor share one plan and one
+    repetition stream); ONE read-back per row group and offsets tensor brings the page table, the
+    stream sizes and the non-null counts, then the level bytes and the non-null leaves are copied
+    out like the values of a flat column.
     -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -601,13 +616,16 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
     import torch
 
     from . import kernels as K
+    from . import kernels_parquet_list as KPL
+    from . import parquet_plain as PP
     from .device import pack_bitmap_device
-    from .parquet_plain import PlainParquetWriter
+    from .parquet_plain import ListLevels, PlainParquetWriter
 
     import time
 
     t_of = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
-    LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0)
+    LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
+                       levels_s=0.0)
     t_all = time.perf_counter()
     copy_s = None
     writers, names, rows_in = {}, {}, {}
@@ -622,7 +640,7 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
             # the host does not wait for the copies: every column task synchronises with the
             # event itself before it writes.  Only validity bitmaps must be here already (the
             # pages are laid out from their popcounts).
-            if event is not None and any(c[2] is not None for c in cols):
+            if event is not None and any(isinstance(c[2], np.ndarray) for c in cols):
                 event.synchronize()
             ready = event.synchronize if event is not None else None
             t1 = time.perf_counter()
@@ -632,9 +650,10 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                 names[j] = fname(j)
                 w = writers[j] = PlainParquetWriter(
                     os.path.join(output_path, names[j]), [c[0] for c in cols],
-                    [c[1].dtype for c in cols], pool=pool, logical=[c[3] for c in cols])
+                    [c[1].dtype for c in cols], pool=pool, logical=[c[3] for c in cols],
+                    lists=[isinstance(c[2], ListLevels) for c in cols])
             elif w.names != [c[0] for c in cols] or w.dtypes != [c[1].dtype for c in cols] or \
-                    w.logical != [c[3] for c in cols]:
+                    w.logical != [c[3] for c in cols] or w.lists != [isinstance(c[2], ListLevels) for c in cols]:
                 # (pyarrow's ParquetWriter raises on a schema change too; never cast silently)
                 raise ValueError(
                     f"to_parquet: partition schema {[(c[0], str(c[1].dtype)) for c in cols]} differs from "
@@ -664,13 +683,24 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                 if shuffle is not None and n > 1:
                     part = part.take_rows(_device_permutation(n, part))
                 cols = []
+                lists = {}   # list column -> (leaves, bool mask of the leaves or None, offsets, leaf bitmap)
                 for name, col in part.items():
                     col = col.materialize()
+                    if col.offsets is not None:
+                        leaves = col.data.contiguous()
+                        lmask = K.unpack_bitmap(col.valid, leaves.numel()) if col.valid is not None else None
+                        lists[name] = (leaves, lmask, col.offsets.contiguous(), col.valid)
+                        cols.append((name, leaves, None, None))
+                        continue
                     data = col.data
                     if dtypes and name in dtypes:
                         data = data.to(t_of[str(np.dtype(dtypes[name]))])
                     mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
                     cols.append((name, data, mask, col.logical))
+                # list columns that share one offsets tensor share plan, page table and repetition stream
+                groups = {}
+                for name, (_, _, off, _) in lists.items():
+                    groups.setdefault((off.data_ptr(), off.numel()), []).append(name)
                 on_gpu = any(c[1].is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
@@ -689,15 +719,42 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                         t_st = time.perf_counter()
                         ctx = torch.cuda.stream(copy_s) if on_gpu else _nullcontext()
                         with ctx:
+                            levels = {}   # list column -> (LevelTable, host rep bytes, host def bytes, its stream)
+                            if rows > 0 and groups:
+                                t_lv = time.perf_counter()
+                                packed = []
+                                for members in groups.values():
+                                    n_leaves = min(int(lists[m][0].numel()) for m in members)
+                                    packed.append(KPL.pack_levels(lists[members[0]][2], s0, s1,
+                                                                  [lists[m][3] for m in members], n_leaves,
+                                                                  PP.PAGE_VALUES))
+                                for members, dl in zip(groups.values(), packed):
+                                    lt = dl.read_back()   # (the one host synchronisation of this offsets tensor)
+                                    LAST_TIMING["levels_s"] += time.perf_counter() - t_lv
+                                    hrep = _to_host(dl.rep[:lt.rep_bytes])
+                                    hdefs = [_to_host(d[:lt.def_bytes]) for d in dl.defs]
+                                    keep.append((dl, hrep, hdefs))
+                                    for m, st in zip(members, dl.stream_of):
+                                        levels[m] = (lt, hrep.numpy(), hdefs[st].numpy(), st)
+                                    t_lv = time.perf_counter()
                             for name, data, mask, logical in cols:
                                 vals, bm = data[s0:s1], None
-                                if mask is not None:
+                                if name in lists:
+                                    if rows > 0:
+                                        lt, hrep, hdef, st = levels[name]
+                                        vals = data[lt.leaf_lo:lt.leaf_hi]
+                                        if lists[name][1] is not None:
+                                            vals = vals[lists[name][1][lt.leaf_lo:lt.leaf_hi]]
+                                        bm = ListLevels(lt.slots, lt.nonnull[st], hrep, lt.rep_at, hdef, lt.def_at)
+                                    else:
+                                        vals, bm = data[:0], ListLevels([], [], b"", [], b"", [])
+                                elif mask is not None:
                                     m = mask[s0:s1]
                                     vals = vals[m]
                                     bm = pack_bitmap_device(m) if m.is_cuda else torch.from_numpy(
                                         np.packbits(m.numpy(), bitorder="little"))
                                 hv = _to_host(vals)
-                                hb = _to_host(bm) if bm is not None else None
+                                hb = bm if isinstance(bm, ListLevels) else (_to_host(bm) if bm is not None else None)
                                 if statistics:
                                     mm = None
                                     if vals.numel():
@@ -711,7 +768,8 @@ def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False
                                         keep.append((mm,))
                                     stats.append(mm.numpy() if mm is not None else None)
                                 keep.append((vals, bm))
-                                host.append((name, hv.numpy(), hb.numpy() if hb is not None else None, logical))
+                                host.append((name, hv.numpy(), hb if isinstance(hb, ListLevels) else
+                                             (hb.numpy() if hb is not None else None), logical))
                             event = None
                             if on_gpu:
                                 event = torch.cuda.Event()

@@ -21,7 +21,16 @@ files like any other (tests/test_parquet_plain.py reads them back with pyarrow).
 A datetime column (DeviceColumn.logical, unit ms / us / ns) is an INT64 column whose
 SchemaElement carries the LogicalType TIMESTAMP (isAdjustedToUTC = false) and, for ms / us, the
 converted type; parquet has no seconds unit.
-Anything else (strings, lists, booleans, requested dtype casts) stays with pyarrow's writer.
+A list column of such numbers is the standard three-level list: a page is
+
+    thrift PageHeader | repetition levels | definition levels | non-null leaves
+
+with both level streams ONE bit-packed run each (bit width 1 and 2), packed on the device
+(kernels_parquet_list, csrc/nvt_parquet_list.hip) and handed over as ``ListLevels``; a row of L
+leaves is max(L, 1) slots and every page starts at a row ("List columns in the PLAIN
+parquet writer").  The reading half below does not take nested files: they are read with pyarrow.
+Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
+columns) stays with pyarrow's writer.
 """
 from __future__ import annotations
 
@@ -140,17 +149,48 @@ def _def_levels(n: int, valid_bytes: Optional[memoryview]) -> Tuple[bytes, Optio
     return struct.pack("<I", len(head) + groups) + head, valid_bytes[:groups]
 
 
+def _packed_levels(slots: int, width: int) -> bytes:
+    """Prefix of one level stream of a list page: u32 length | header of ONE bit-packed run of
+    ceil(slots / 8) groups; `width` bytes of payload per group follow (bit width 1 or 2)."""
+    groups = (slots + 7) // 8
+    head = _varint((groups << 1) | 1)
+    return struct.pack("<I", len(head) + groups * width) + head
+
+
+class ListLevels:
+    """Repetition / definition levels of one list column chunk, already bit-packed (the device
+    packs them: kernels_parquet_list; tests/pq_list_reference.py restates the layout).
+
+    Page p holds ``slots[p]`` slots (a row of L leaves is max(L, 1) slots) of which ``nonnull[p]``
+    are non-null leaves; its repetition levels are the ceil(slots / 8) bytes at ``rep_at[p]`` of
+    ``rep`` (bit width 1), its definition levels the 2 * ceil(slots / 8) bytes at ``def_at[p]`` of
+    ``dfn`` (bit width 2), LSB first, pad bits 0.  ``rep`` / ``dfn`` are bytes-like (uint8 arrays);
+    like the values they may still be in flight when the row group is laid out, the tables not."""
+
+    __slots__ = ("slots", "nonnull", "rep", "rep_at", "dfn", "def_at")
+
+    def __init__(self, slots, nonnull, rep, rep_at, dfn, def_at):
+        self.slots = [int(x) for x in slots]
+        self.nonnull = [int(x) for x in nonnull]
+        self.rep_at = [int(x) for x in rep_at]
+        self.def_at = [int(x) for x in def_at]
+        self.rep, self.dfn = rep, dfn
+
+
 class PlainParquetWriter:
-    """One parquet file of flat int32 / int64 / float32 / float64 columns, every column OPTIONAL
-    (like pyarrow writes nullable Arrow columns), PLAIN encoding, no compression.
+    """One parquet file of int32 / int64 / float32 / float64 columns, flat or "list of" such leaves,
+    every column OPTIONAL (like pyarrow writes nullable Arrow columns), PLAIN encoding, no
+    compression.  A list column is the standard three-level list (optional group ``name`` (LIST) >
+    repeated group ``list`` > optional ``element``); there are no null lists.
 
     With a thread ``pool`` a row group is written by a pool task: a PLAIN page's size is known
     before it is written, so the row group is laid out first and its pages go to their offsets
     with ``os.pwrite`` (which releases the GIL) while the caller stages the next row group or
     another file."""
 
-    def __init__(self, path: str, names: Sequence[str], dtypes: Sequence, pool=None, logical=None):
-        """``logical[j]``: None, or datetime64[ms|us|ns] for an int64 column of such counts."""
+    def __init__(self, path: str, names: Sequence[str], dtypes: Sequence, pool=None, logical=None, lists=None):
+        """``logical[j]``: None, or datetime64[ms|us|ns] for an int64 column of such counts.
+        ``lists[j]``: True for a list column whose leaves are ``dtypes[j]``."""
         self.path = path
         self.names = list(names)
         self.dtypes = [np.dtype(d) for d in dtypes]
@@ -161,6 +201,11 @@ class PlainParquetWriter:
         for d, x in zip(self.dtypes, self.logical):
             if x is not None and (timestamp_unit(x) is None or d != np.dtype("int64")):
                 raise TypeError(f"PlainParquetWriter: logical type {x} on a {d} column (int64 counts in ms, us or ns)")
+        self.lists = [bool(x) for x in (lists or [False] * len(self.names))]
+        if len(self.lists) != len(self.names):
+            raise ValueError("PlainParquetWriter: names and lists differ in length")
+        if any(l and x is not None for l, x in zip(self.lists, self.logical)):
+            raise TypeError("PlainParquetWriter: list columns of datetime leaves are not written")
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
         os.pwrite(self.fd, b"PAR1", 0)
         self.pos = 4
@@ -210,6 +255,48 @@ class PlainParquetWriter:
                              f"({values.size} values, {done_vals} valid rows)")
         return segs, at - start
 
+    def _plan_list_column(self, values, levels, dt, start):
+        """The same for a list column: page = header | rep levels | def levels | non-null leaves."""
+        values = np.asarray(values)
+        if values.dtype != dt or values.ndim != 1 or not values.flags.c_contiguous:
+            raise TypeError(f"PlainParquetWriter: leaf buffer is {values.dtype} "
+                            f"(contiguous={values.flags.c_contiguous}), the file's column is list of {dt}")
+        vbytes = memoryview(values).cast("B") if values.size else memoryview(b"")
+        rep = memoryview(levels.rep).cast("B") if len(levels.rep) else memoryview(b"")
+        dfn = memoryview(levels.dfn).cast("B") if len(levels.dfn) else memoryview(b"")
+        npages = len(levels.slots)
+        if not (len(levels.nonnull) == len(levels.rep_at) == len(levels.def_at) == npages):
+            raise ValueError("PlainParquetWriter: the page table's columns differ in length")
+        segs, at, done_vals = [], start, 0
+        for p in range(npages):
+            slots, nv = levels.slots[p], levels.nonnull[p]
+            groups = (slots + 7) // 8
+            r0, d0 = levels.rep_at[p], levels.def_at[p]
+            if slots <= 0 or not 0 <= nv <= slots:
+                raise ValueError(f"PlainParquetWriter: page {p} has {slots} slots and {nv} non-null leaves")
+            if r0 < 0 or d0 < 0 or r0 + groups > len(rep) or d0 + 2 * groups > len(dfn):
+                raise ValueError(f"PlainParquetWriter: the level bytes do not match the page table (page {p}: "
+                                 f"{slots} slots at {r0} of {len(rep)} rep bytes, at {d0} of {len(dfn)} def bytes)")
+            payload = vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize]
+            rhead, dhead = _packed_levels(slots, 1), _packed_levels(slots, 2)
+            body = len(rhead) + groups + len(dhead) + 2 * groups + nv * dt.itemsize
+            for buf in (_page_header(slots, body) + rhead, rep[r0: r0 + groups], dhead,
+                        dfn[d0: d0 + 2 * groups], payload):
+                if len(buf):
+                    segs.append((at, buf))
+                    at += len(buf)
+            done_vals += nv
+        if npages == 0:
+            # no rows: one page without slots (both level streams an RLE run of length 0)
+            empty = _varint(0) + b"\x00"
+            body = 2 * (struct.pack("<I", len(empty)) + empty)
+            segs.append((at, _page_header(0, len(body)) + body))
+            at += len(segs[-1][1])
+        if done_vals != values.size:
+            raise ValueError("PlainParquetWriter: the values do not match the page table "
+                             f"({values.size} values, {done_vals} non-null leaves)")
+        return segs, at - start
+
     def _run(self, segs, ready=None):
         if ready is not None:
             ready()   # (e.g. the event behind the device-to-host copy of these buffers)
@@ -222,7 +309,9 @@ class PlainParquetWriter:
     def write_row_group(self, columns, n: int, wait: bool = True, ready=None, stats=None):
         """columns[j] = (values, valid): `values` a 1-D numpy array of the column's dtype holding
         the NON-NULL values in row order, `valid` None or the Arrow validity bitmap (uint8, LSB
-        first, >= ceil(n / 8) bytes) of the n rows.  wait=False (with a pool): returns the
+        first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
+        non-null LEAVES of the n rows in order and their ``ListLevels``.  Argument errors raise
+        before anything of the row group is written.  wait=False (with a pool): returns the
         futures of the column writes instead of waiting for them -- the layout is fixed, so later
         row groups (of this or of other files) can be written meanwhile; the caller keeps the
         buffers alive until the futures are done, close() waits for whatever is left.
@@ -237,15 +326,26 @@ class PlainParquetWriter:
         total = 0
         if len(columns) != len(self.names):
             raise ValueError(f"PlainParquetWriter: {len(columns)} columns for a file of {len(self.names)}")
+        pos = self.pos
         for j, ((values, valid), name, dt) in enumerate(zip(columns, self.names, self.dtypes)):
-            start = self.pos
-            segs, size = self._plan_column(values, valid, n, dt, start)
+            start = pos
+            if self.lists[j] != isinstance(valid, ListLevels):
+                raise TypeError(f"PlainParquetWriter: column '{name}' is a {'list' if self.lists[j] else 'flat'} "
+                                f"column of the file, this row group passes it as the other kind")
+            if self.lists[j]:
+                segs, size = self._plan_list_column(values, valid, dt, start)
+                nv = sum(valid.slots)   # (num_values of a list chunk counts slots, not leaves or rows)
+            else:
+                segs, size = self._plan_column(values, valid, n, dt, start)
+                nv = n
             plans.append(segs)
-            self.pos += size
+            pos += size
             nvalid = int(np.asarray(values).size)
-            chunks.append(dict(name=name, dt=dt, n=n, size=size, start=start, nulls=n - nvalid,
-                               minmax=stats[j] if (stats is not None and nvalid > 0) else None))
+            chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
+                               minmax=stats[j] if (stats is not None and nvalid > 0) else None,
+                               is_list=self.lists[j]))
             total += size
+        self.pos = pos
         futures = []
         if self.pool is not None:
             # ONE task per row group: buffered writes to one file serialise on its inode lock
@@ -280,8 +380,9 @@ class PlainParquetWriter:
         st.i64(3, c["nulls"])
         if hi is not None:
             st.binary(5, hi).binary(6, lo)               # max_value / min_value
+        path = [name, "list", "element"] if c.get("is_list") else [name]
         meta = (_Struct().i32(1, _PQ_TYPE[dt]).list(2, _CT_I32, [_zigzag(0), _zigzag(3)])
-                .list(3, _CT_BINARY, [_varint(len(name.encode())) + name.encode()])
+                .list(3, _CT_BINARY, [_varint(len(x.encode())) + x.encode() for x in path])
                 .i32(4, 0).i64(5, c["n"]).i64(6, c["size"]).i64(7, c["size"]).i64(9, c["start"])
                 .struct(12, st.done()).done())
         return _Struct().i64(2, c["start"]).struct(3, meta).done()
@@ -291,7 +392,14 @@ class PlainParquetWriter:
             f.result()
         self.pending = []
         schema = [_Struct().binary(4, "schema").i32(5, len(self.names)).done()]
-        for name, dt, logical in zip(self.names, self.dtypes, self.logical):
+        for name, dt, logical, is_list in zip(self.names, self.dtypes, self.logical, self.lists):
+            if is_list:
+                # optional group <name> (LIST) { repeated group list { optional <T> element } }
+                schema.append(_Struct().i32(3, 1).binary(4, name).i32(5, 1).i32(6, 3)
+                              .struct(10, _Struct().struct(3, _Struct().done()).done()).done())
+                schema.append(_Struct().i32(3, 2).binary(4, "list").i32(5, 1).done())
+                schema.append(_Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, "element").done())
+                continue
             el = _Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, name)
             if logical is not None:
                 field, conv = _TS_UNIT[timestamp_unit(logical)]
