@@ -696,6 +696,24 @@ int nvt_pq_decode_chunk_codec(const uint8_t *chunk, uint64_t chunk_bytes, int co
                               uint64_t valid_bit_offset, uint8_t *values_out, uint64_t values_cap_bytes,
                               uint8_t *scratch, uint64_t scratch_bytes, uint64_t *rows_out,
                               uint64_t *values_count);
+/* nvt_pq_decode_list_chunk (HOST function, thread-safe): one column chunk of a standard three-level
+ * list column (max repetition level 1; max definition level max_def_level = O + 1 + E with O / E = 1
+ * for an optional outer group / leaf, leaf_level = O + 1), pages and codecs as above.  The levels of
+ * the chunk's expect_slots slots (the chunk's num_values) are APPENDED to the partition's staging
+ * streams at slot `slot_offset`: repetition levels 1 bit per slot in rep_out, definition levels W bits
+ * per slot in def_out (W = 1 for max_def_level 1, else 2), LSB first and continuous over pages, chunks
+ * and row groups (one thread per column: chunks may share a word).  Both buffers hold
+ * ceil(slot_cap * W' / 64) * 8 bytes (W' = 1 / W) and slot_offset + expect_slots <= slot_cap.  The
+ * non-null leaves go packed behind each other into values_out, PLAIN or through the dictionary.
+ * counts[4] = {slots, row starts (rep 0), leaf slots (def >= leaf_level), non-null leaves
+ * (def == max_def_level)} of the chunk.  NVT_EINVAL: the first slot is no row start, slots !=
+ * expect_slots, row starts != expect_rows, a level above its maximum, level runs or values that do
+ * not fit their page.  NVT_EUNSUPPORTED: BIT_PACKED level streams, other codecs / value encodings. */
+int nvt_pq_decode_list_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
+                             int leaf_level, int max_def_level, uint64_t expect_slots, uint64_t expect_rows,
+                             uint8_t *rep_out, uint8_t *def_out, uint64_t slot_offset, uint64_t slot_cap,
+                             uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch,
+                             uint64_t scratch_bytes, uint64_t *counts);
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes);
 int nvt_expand_valid(const void *packed, int type_size, const uint8_t *bitmap, uint64_t n, void *out,
                      void *ws, void *stream);
@@ -1198,6 +1216,19 @@ int nvt_pqlist_plan(const int64_t *offsets, const int64_t *origin, uint64_t n, u
 int nvt_pqlist_pack_many(const nvt_pqlist_col *cols, int ncols, const int64_t *offsets, const int64_t *origin,
                          uint64_t n, const uint64_t *slot_start, const uint64_t *table, uint64_t max_pages,
                          uint64_t max_slots, uint8_t *rep_out, void *stream);
+/* The way back (the parquet reader): the staged level streams of nvt_pq_decode_list_chunk -- rep 1
+ * bit per slot, def `def_width` (1 or 2) bits per slot, n_slots < 2^32 slots, both 8-byte aligned and
+ * ceil(n_slots * width / 64) words long -- become offsets[rows + 1] (offsets[r] = leaf slots in front
+ * of the r-th slot with rep 0, offsets[rows] = leaves; a null or empty list is one slot that is no
+ * leaf, i.e. an empty row) and, when leaf_valid is not NULL, the Arrow validity bitmap of the leaves
+ * (ceil(leaves / 64) words, bit = def == max_def, bits past the last leaf 0).  rows and leaves are the
+ * host decoder's counts: a stream that disagrees with them gives wrong numbers, never a store outside
+ * offsets / leaf_valid.  ws: nvt_pqlist_unpack_ws_bytes(n_slots) bytes, 8-byte aligned.
+ * Stream-ordered, no read-back. */
+int nvt_pqlist_unpack_ws_bytes(uint64_t n_slots, uint64_t *bytes);
+int nvt_pqlist_unpack(const uint8_t *rep, const uint8_t *def, int def_width, uint64_t n_slots, int leaf_level,
+                      int max_def, uint64_t rows, uint64_t leaves, int64_t *offsets, uint8_t *leaf_valid,
+                      void *ws, uint64_t ws_bytes, void *stream);
 
 /* ---- exact column medians: ops.FillMedian (MSD radix select) ----
  * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a

@@ -121,6 +121,8 @@ SIGNATURES = {
     "nvt_pq_decode_chunk": [_vp, _u64, _i32, _i32, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)],
     "nvt_pq_decode_chunk_codec": [_vp, _u64, _i32, _i32, _i32, _u64, _vp, _u64, _vp, _u64, _vp, _u64,
                                   C.POINTER(_u64), C.POINTER(_u64)],
+    "nvt_pq_decode_list_chunk": [_vp, _u64, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _u64,
+                                 _vp, _u64, C.POINTER(_u64)],
     "nvt_expand_valid_ws_bytes": [_u64, C.POINTER(_u64)],
     "nvt_expand_valid": [_vp, _i32, _vp, _u64, _vp, _vp, _vp],
     "nvt_exchange_ranges": [_vp, _i32, _vp, _vp],
@@ -340,6 +342,8 @@ SIGNATURES.update({
     "nvt_pqlist_ws_bytes": [_u64, C.POINTER(_u64)],
     "nvt_pqlist_plan": [_vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
     "nvt_pqlist_pack_many": [C.POINTER(PqListCol), _i32, _vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _vp],
+    "nvt_pqlist_unpack_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_pqlist_unpack": [_vp, _vp, _i32, _u64, _i32, _i32, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
 })
 
 class SelectCol(C.Structure):

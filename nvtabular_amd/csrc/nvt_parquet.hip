@@ -18,7 +18,12 @@
 //     resolved through the chunk's dictionary in the same task, so the staging buffer always holds
 //     packed PLAIN values.
 //
-// Anything else in a chunk (other codecs / encodings, nested columns) is reported as
+//   list columns (the standard three-level list of such leaves): nvt_pq_decode_list_chunk walks the
+//     same pages and appends their repetition / definition levels to two bit streams that are
+//     continuous over the partition (1 and W bits per slot); the device turns them into offsets and
+//     the leaf bitmap (nvt_pqlist_unpack, nvt_parquet_list.hip).
+//
+// Anything else in a chunk (other codecs / encodings, other nesting) is reported as
 // NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -121,7 +126,7 @@ struct PageHead {
   int type = -1;            // 0 data page, 2 dictionary page, 3 data page v2
   int64_t uncompressed = 0, compressed = 0;
   int64_t num_values = 0;   // rows of the page (flat columns)
-  int encoding = -1, def_encoding = -1;
+  int encoding = -1, def_encoding = -1, rep_encoding = -1;
   // v2
   int64_t num_nulls = -1, def_bytes = 0, rep_bytes = 0;
   bool v2_compressed = false;
@@ -142,6 +147,7 @@ bool read_page_header(TReader &r, PageHead &h) {
         if (f2 == 1 && t2 == 5) h.num_values = r.zigzag();
         else if (f2 == 2 && t2 == 5) h.encoding = (int)r.zigzag();
         else if (f2 == 3 && t2 == 5) h.def_encoding = (int)r.zigzag();
+        else if (f2 == 4 && t2 == 5) h.rep_encoding = (int)r.zigzag();
         else r.skip(t2);
       }
     } else if (fid == 7 && type == 12) {  // DictionaryPageHeader
@@ -251,6 +257,120 @@ bool decode_levels(const uint8_t *lv, uint64_t nbytes, uint64_t rows, uint8_t *b
   return true;
 }
 
+// ---- level streams of list columns ------------------------------------------------------------
+// The staging streams hold one level per slot at `bw` bits (1 or 2), LSB first, continuous over the
+// pages, chunks and row groups of a partition: a page's levels land at an arbitrary bit position.
+// They are written 64 bits at a time through the words that hold them (memcpy: no alignment is
+// asked of the buffer, which is ceil(bits / 64) words long).
+inline void put_bits(uint8_t *dst, uint64_t bitpos, uint64_t v, unsigned n) {  // n in 1 .. 64, v < 2^n
+  uint8_t *at = dst + (bitpos >> 6) * 8;
+  const unsigned sh = (unsigned)(bitpos & 63);
+  const uint64_t mask = n == 64 ? ~0ull : ((1ull << n) - 1ull);
+  uint64_t w;
+  memcpy(&w, at, 8);
+  w = (w & ~(mask << sh)) | (v << sh);
+  memcpy(at, &w, 8);
+  if (sh + n > 64) {
+    const uint64_t m2 = (1ull << (sh + n - 64)) - 1ull;
+    memcpy(&w, at + 8, 8);
+    w = (w & ~m2) | (v >> (64 - sh));
+    memcpy(at + 8, &w, 8);
+  }
+}
+
+// levels per value in `nbits` bits of w (its other bits 0): hist[v] += count
+inline void hist_add(uint64_t w, unsigned nbits, unsigned bw, uint64_t hist[4]) {
+  if (bw == 1) {
+    const uint64_t ones = (uint64_t)__builtin_popcountll(w);
+    hist[1] += ones;
+    hist[0] += nbits - ones;
+  } else {
+    const uint64_t lo = w & 0x5555555555555555ull, hi = (w >> 1) & 0x5555555555555555ull;
+    const uint64_t c3 = (uint64_t)__builtin_popcountll(lo & hi);
+    const uint64_t c1 = (uint64_t)__builtin_popcountll(lo) - c3, c2 = (uint64_t)__builtin_popcountll(hi) - c3;
+    hist[1] += c1;
+    hist[2] += c2;
+    hist[3] += c3;
+    hist[0] += nbits / 2 - c1 - c2 - c3;
+  }
+}
+
+// `nbits` bits of src (from its bit 0; ceil(nbits / 8) bytes readable) -> dst at bit `pos`, counted
+inline void bits_copy_count(uint8_t *dst, uint64_t pos, const uint8_t *src, uint64_t nbits, unsigned bw,
+                            uint64_t hist[4]) {
+  uint64_t done = 0;
+  for (; done + 64 <= nbits; done += 64) {
+    uint64_t w;
+    memcpy(&w, src + (done >> 3), 8);
+    hist_add(w, 64, bw, hist);
+    put_bits(dst, pos + done, w, 64);
+  }
+  if (done < nbits) {
+    const unsigned rem = (unsigned)(nbits - done);
+    uint64_t w = 0;
+    memcpy(&w, src + (done >> 3), (rem + 7) / 8);
+    w &= (1ull << rem) - 1ull;
+    hist_add(w, rem, bw, hist);
+    put_bits(dst, pos + done, w, rem);
+  }
+}
+
+inline void bits_fill_value(uint8_t *dst, uint64_t pos, uint64_t nbits, unsigned bw, unsigned v) {
+  const uint64_t pat = bw == 1 ? (v ? ~0ull : 0ull) : (uint64_t)v * 0x5555555555555555ull;
+  uint64_t done = 0;
+  for (; done + 64 <= nbits; done += 64) put_bits(dst, pos + done, pat, 64);  // (64 is a multiple of bw)
+  if (done < nbits) put_bits(dst, pos + done, pat & ((1ull << (nbits - done)) - 1ull), (unsigned)(nbits - done));
+}
+
+// One level stream of a page (RLE / bit-packed hybrid at bit width `bw`, nbytes long, n levels) ->
+// slots [slot, slot + n) of `out`; hist[v] += levels of value v.  A bit-packed run is a shifting bit
+// copy (the padding of its last group is not copied), an RLE run a fill.
+// -> 0, or 1: a run leaves the stream's bytes, 2: a level above max_level
+int decode_levels_wide(const uint8_t *lv, uint64_t nbytes, uint64_t n, unsigned bw, unsigned max_level,
+                       uint8_t *out, uint64_t slot, uint64_t hist[4]) {
+  TReader r{lv, lv + nbytes};
+  uint64_t done = 0;
+  uint64_t h[4] = {0, 0, 0, 0};
+  while (done < n) {
+    const uint64_t head = r.varint();
+    if (!r.ok) return 1;
+    if (head & 1) {
+      const uint64_t groups = head >> 1;
+      if (groups == 0 || groups > (1ull << 40)) return 1;
+      uint64_t take = groups * 8;
+      if (take > n - done) take = n - done;
+      const uint64_t avail = (uint64_t)(r.end - r.p);
+      if (avail < groups * bw && avail * 8 < take * bw) return 1;   // (a writer may cut the last group's padding)
+      bits_copy_count(out, (slot + done) * bw, r.p, take * bw, bw, h);
+      r.skip_bytes(groups * bw < avail ? groups * bw : avail);
+      done += take;
+    } else {
+      uint64_t count = head >> 1;
+      if (count == 0 || r.p >= r.end) return 1;
+      const unsigned v = *r.p++;
+      if (v > max_level) return 2;
+      if (count > n - done) count = n - done;
+      bits_fill_value(out, (slot + done) * bw, count * bw, bw, v);
+      h[v] += count;
+      done += count;
+    }
+  }
+  for (unsigned v = max_level + 1; v < 4; ++v)
+    if (h[v]) return 2;
+  for (int v = 0; v < 4; ++v) hist[v] += h[v];
+  return 0;
+}
+
+// what a list chunk adds to the page walk of pq_decode
+struct ListSink {
+  uint8_t *rep, *def;          // the partition's staging streams
+  uint64_t slot0, slot_cap;    // the chunk's first slot; slots the streams hold
+  unsigned width;              // bits per definition level (1 or 2)
+  unsigned leaf_level, max_def;
+  uint64_t expect_rows;
+  uint64_t starts = 0, leaves = 0;
+};
+
 // ---- snappy, raw block format (what parquet's SNAPPY codec holds per page) --------------------
 // -> uncompressed bytes written, or -1 on malformed input / a block that does not fit `cap`
 int64_t snappy_uncompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap) {
@@ -339,8 +459,8 @@ bool decode_dict_indices(const uint8_t *p, const uint8_t *end, uint64_t count, c
       for (uint64_t i = 0; i < take; ++i, bitpos += bw) {
         const uint64_t byte = bitpos >> 3;
         uint64_t w = 0;   // up to 5 bytes hold a value of <= 32 bits at any bit offset
-        const uint64_t nbv = avail - byte < 8 ? avail - byte : 8;
-        memcpy(&w, q + byte, nbv);
+        if (avail - byte >= 8) memcpy(&w, q + byte, 8);   // (a fixed size: one load)
+        else memcpy(&w, q + byte, avail - byte);
         const uint64_t idx = (w >> (bitpos & 7)) & mask;
         if (idx >= ndict) return false;
         out[done + i] = dict[idx];
@@ -435,11 +555,12 @@ extern "C" {
 static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size, int max_def_level,
                      uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
                      uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch, uint64_t scratch_bytes,
-                     uint64_t *rows_out, uint64_t *values_out_count) {
+                     uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr) {
+  // ls: a list chunk -- `rows` / expect_rows below count SLOTS, the levels go to the sink's streams
   NVT_CHECK_ARG(chunk && values_out && rows_out && values_out_count, "null pointer");
   NVT_CHECK_ARG(type_size == 4 || type_size == 8, "values are 4 or 8 bytes");
-  NVT_CHECK_ARG(max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
-  NVT_CHECK_ARG(max_def_level == 0 || valid_out, "null validity buffer");
+  NVT_CHECK_ARG(ls || max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
+  NVT_CHECK_ARG(ls || max_def_level == 0 || valid_out, "null validity buffer");
   if (codec != 0 && codec != 1) {
     set_error("nvt_pq_decode_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
     return NVT_EUNSUPPORTED;
@@ -532,7 +653,39 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       if (rc) return rc;
       q = u;
       pend = u + h.uncompressed;
-      if (max_def_level == 1) {
+      if (ls) {
+        if (h.rep_encoding != 3 || h.def_encoding != 3) {
+          set_error("nvt_pq_decode_list_chunk: level encodings %d / %d (the RLE hybrid is decoded here)",
+                    h.rep_encoding, h.def_encoding);
+          return NVT_EUNSUPPORTED;
+        }
+        uint64_t hist[4] = {0, 0, 0, 0};
+        for (int pass = 0; pass < 2; ++pass) {   // u32 length | repetition levels, then the same for definition
+          uint32_t lb;
+          if (pend - q < 4) {
+            set_error("nvt_pq_decode_list_chunk: page too short for its level streams");
+            return NVT_EINVAL;
+          }
+          memcpy(&lb, q, 4);
+          q += 4;
+          int bad = (uint64_t)(pend - q) < lb ? 1 : 0;
+          if (!bad && pass == 0) {
+            uint64_t rh[4] = {0, 0, 0, 0};
+            bad = decode_levels_wide(q, lb, prow, 1, 1, ls->rep, ls->slot0 + rows, rh);
+            ls->starts += rh[0];
+          } else if (!bad) {
+            bad = decode_levels_wide(q, lb, prow, ls->width, ls->max_def, ls->def, ls->slot0 + rows, hist);
+          }
+          if (bad) {
+            set_error(bad == 1 ? "nvt_pq_decode_list_chunk: level runs leave their stream"
+                               : "nvt_pq_decode_list_chunk: a level above the column's maximum");
+            return NVT_EINVAL;
+          }
+          q += lb;
+        }
+        pvalid = hist[ls->max_def];
+        for (unsigned v = ls->leaf_level; v <= ls->max_def; ++v) ls->leaves += hist[v];
+      } else if (max_def_level == 1) {
         if (h.def_encoding != 3) {  // RLE (the hybrid)
           set_error("nvt_pq_decode_chunk: definition level encoding %d", h.def_encoding);
           return NVT_EUNSUPPORTED;
@@ -549,28 +702,51 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       }
     } else {  // v2: repetition levels (none for flat columns), then definition levels -- never
               // compressed, no length prefix --, then the values (compressed when the header says so)
-      if (h.rep_bytes != 0) {
+      if (h.rep_bytes != 0 && !ls) {
         set_error("nvt_pq_decode_chunk: repetition levels (nested column)");
         return NVT_EUNSUPPORTED;
       }
-      if (h.def_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes) {
+      // (each length is checked on its own before the sum: both are below 2^31 then)
+      if (h.def_bytes < 0 || h.rep_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
+          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes || (uint64_t)h.compressed < (uint64_t)h.rep_bytes ||
+          (uint64_t)h.uncompressed < (uint64_t)h.rep_bytes ||
+          (uint64_t)h.compressed < (uint64_t)h.def_bytes + (uint64_t)h.rep_bytes ||
+          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes + (uint64_t)h.rep_bytes) {
         set_error("nvt_pq_decode_chunk: definition levels run past the page");
         return NVT_EINVAL;
       }
-      if (max_def_level == 1) {
+      const uint64_t lbytes = (uint64_t)h.rep_bytes + (uint64_t)h.def_bytes;
+      if (ls) {
+        uint64_t rh[4] = {0, 0, 0, 0}, hist[4] = {0, 0, 0, 0};
+        int bad = decode_levels_wide(body, (uint64_t)h.rep_bytes, prow, 1, 1, ls->rep, ls->slot0 + rows, rh);
+        if (!bad)
+          bad = decode_levels_wide(body + h.rep_bytes, (uint64_t)h.def_bytes, prow, ls->width, ls->max_def, ls->def,
+                                   ls->slot0 + rows, hist);
+        if (bad) {
+          set_error(bad == 1 ? "nvt_pq_decode_list_chunk: level runs leave their stream"
+                             : "nvt_pq_decode_list_chunk: a level above the column's maximum");
+          return NVT_EINVAL;
+        }
+        ls->starts += rh[0];
+        pvalid = hist[ls->max_def];
+        for (unsigned v = ls->leaf_level; v <= ls->max_def; ++v) ls->leaves += hist[v];
+      } else if (max_def_level == 1) {
         if (!decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
           set_error("nvt_pq_decode_chunk: malformed definition levels");
           return NVT_EINVAL;
         }
       }
       const uint8_t *u = nullptr;
-      const uint64_t vcomp = (uint64_t)h.compressed - (uint64_t)h.def_bytes;
-      const uint64_t vraw = (uint64_t)h.uncompressed - (uint64_t)h.def_bytes;
-      int rc = inflate(body + h.def_bytes, vcomp, vraw, codec != 0 && h.v2_compressed, &u);
+      const uint64_t vcomp = (uint64_t)h.compressed - lbytes;
+      const uint64_t vraw = (uint64_t)h.uncompressed - lbytes;
+      int rc = inflate(body + lbytes, vcomp, vraw, codec != 0 && h.v2_compressed, &u);
       if (rc) return rc;
       q = u;
       pend = u + vraw;
+    }
+    if (ls && rows == 0 && prow > 0 && ((ls->rep[ls->slot0 >> 3] >> (ls->slot0 & 7)) & 1)) {
+      set_error("nvt_pq_decode_list_chunk: the chunk's first slot continues a row");
+      return NVT_EINVAL;
     }
     if ((vals + pvalid) * (uint64_t)type_size > values_cap_bytes) {
       set_error("nvt_pq_decode_chunk: values buffer too small");
@@ -580,6 +756,10 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       const uint64_t vbytes = pvalid * (uint64_t)type_size;
       if ((uint64_t)(pend - q) < vbytes) {
         set_error("nvt_pq_decode_chunk: page holds fewer values than its levels say");
+        return NVT_EINVAL;
+      }
+      if (ls && (uint64_t)(pend - q) != vbytes) {   // (the levels say how many PLAIN values follow: exactly)
+        set_error("nvt_pq_decode_list_chunk: page holds more values than its levels say");
         return NVT_EINVAL;
       }
       memcpy(values_out + vals * (uint64_t)type_size, q, vbytes);
@@ -603,8 +783,44 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
               (unsigned long long)expect_rows);
     return NVT_EINVAL;
   }
+  if (ls && ls->starts != ls->expect_rows) {
+    set_error("nvt_pq_decode_list_chunk: %llu row starts in the pages, %llu expected", (unsigned long long)ls->starts,
+              (unsigned long long)ls->expect_rows);
+    return NVT_EINVAL;
+  }
   *rows_out = rows;
   *values_out_count = vals;
+  return NVT_OK;
+}
+
+int nvt_pq_decode_list_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
+                             int leaf_level, int max_def_level, uint64_t expect_slots, uint64_t expect_rows,
+                             uint8_t *rep_out, uint8_t *def_out, uint64_t slot_offset, uint64_t slot_cap,
+                             uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch,
+                             uint64_t scratch_bytes, uint64_t *counts) {
+  NVT_CHECK_ARG(rep_out && def_out && counts, "null pointer");
+  NVT_CHECK_ARG(leaf_level == 1 || leaf_level == 2, "leaf_level is 1 or 2 (required / optional outer group)");
+  NVT_CHECK_ARG(max_def_level == leaf_level || max_def_level == leaf_level + 1,
+                "max_def_level is leaf_level (+ 1 for optional leaves)");
+  NVT_CHECK_ARG(slot_offset <= slot_cap && expect_slots <= slot_cap - slot_offset, "the slots do not fit the level streams");
+  NVT_CHECK_ARG(slot_cap < (1ull << 60), "slot_cap too large");
+  ListSink ls;
+  ls.rep = rep_out;
+  ls.def = def_out;
+  ls.slot0 = slot_offset;
+  ls.slot_cap = slot_cap;
+  ls.width = max_def_level == 1 ? 1u : 2u;
+  ls.leaf_level = (unsigned)leaf_level;
+  ls.max_def = (unsigned)max_def_level;
+  ls.expect_rows = expect_rows;
+  uint64_t slots = 0, vals = 0;
+  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_slots, nullptr, 0, values_out,
+                           values_cap_bytes, scratch, scratch_bytes, &slots, &vals, &ls);
+  if (rc) return rc;
+  counts[0] = slots;
+  counts[1] = ls.starts;
+  counts[2] = ls.leaves;
+  counts[3] = vals;
   return NVT_OK;
 }
 

@@ -294,6 +294,123 @@ __global__ __launch_bounds__(kBlock) void pack_kernel(PBatch b, const int64_t *_
   }
 }
 
+// ---- unpack: staged level streams -> offsets + leaf bitmap (the parquet reader) ------------------
+// The streams of nvt_pq_decode_list_chunk: rep 1 bit per slot, def W bits per slot, LSB first.  A slot
+// is a row start when rep == 0, a leaf when def >= leaf_level, a non-null leaf when def == max_def.
+//   count: one wave per tile of 2048 slots, popcounts of whole words -> row starts and leaves per
+//          tile; two exclusive scans (nvt_scan.hpp) give every tile its first row and first leaf.
+//   emit:  one wave per tile walks its 32 groups of 64 slots, one slot per lane: three ballot words
+//          (start, leaf, valid); a lane's row / leaf rank = the wave's running base + the popcount of
+//          the lower lanes.  A start lane stores offsets[row] = leaf rank.  Leaves take one validity
+//          bit each and the other slots none, so a tile's bits start anywhere in a word: the wave
+//          builds them in LDS (atomicOr at rank - first word of the tile), stores the words that lie
+//          wholly inside the tile's leaves and merges the at most two it shares with its neighbours
+//          into the zeroed bitmap with a 64-bit atomicOr (commutative: the result is deterministic).
+constexpr int kUnpackWaves = kBlock / kWave;
+constexpr int kUnpackWords = (int)(kTile / 64) + 2;   // bit string of one tile: 2048 bits at any bit offset
+
+__device__ __forceinline__ uint64_t live_mask(uint64_t slot0, uint64_t n_slots) {
+  return slot0 >= n_slots ? 0ull : (n_slots - slot0 >= 64 ? ~0ull : ((1ull << (n_slots - slot0)) - 1ull));
+}
+// 32 definition levels at 2 bits -> bit 2 i set when level i >= leaf_level (1 or 2)
+__device__ __forceinline__ uint64_t leaf_pairs(uint64_t d, int leaf_level) {
+  return (leaf_level == 1 ? (d | (d >> 1)) : (d >> 1)) & 0x5555555555555555ull;
+}
+
+__global__ __launch_bounds__(kBlock) void unpack_count_kernel(const uint64_t *__restrict__ rep,
+                                                               const uint64_t *__restrict__ def, int width,
+                                                               uint64_t n_slots, int leaf_level, uint64_t ntiles,
+                                                               unsigned *__restrict__ tile_rows,
+                                                               unsigned *__restrict__ tile_leaves) {
+  const unsigned lane = lane_id();
+  const uint64_t t = (uint64_t)blockIdx.x * kUnpackWaves + threadIdx.x / kWave;
+  if (t >= ntiles) return;
+  unsigned starts = 0, leaves = 0;
+  const uint64_t g = t * (kTile / 64) + lane;   // lanes 0 .. 31: one group of 64 slots each
+  const uint64_t live = lane < kTile / 64 ? live_mask(g * 64, n_slots) : 0ull;
+  if (live) {
+    starts = (unsigned)__popcll(~rep[g] & live);
+    if (width == 1) {
+      leaves = (unsigned)__popcll(def[g] & live);
+    } else {
+      leaves = (unsigned)__popcll(leaf_pairs(def[2 * g], leaf_level) & spread_bits((uint32_t)live));
+      if (live >> 32)
+        leaves += (unsigned)__popcll(leaf_pairs(def[2 * g + 1], leaf_level) & spread_bits((uint32_t)(live >> 32)));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    starts += __shfl_down(starts, off, 64);
+    leaves += __shfl_down(leaves, off, 64);
+  }
+  if (lane == 0) {
+    tile_rows[t] = starts;
+    tile_leaves[t] = leaves;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void unpack_emit_kernel(const uint64_t *__restrict__ rep,
+                                                              const uint64_t *__restrict__ def, int width,
+                                                              uint64_t n_slots, int leaf_level, int max_def,
+                                                              uint64_t rows, uint64_t leaves, uint64_t ntiles,
+                                                              const unsigned *__restrict__ tile_rows,
+                                                              const unsigned *__restrict__ tile_leaves,
+                                                              int64_t *__restrict__ offsets,
+                                                              unsigned long long *__restrict__ leaf_valid) {
+  __shared__ unsigned long long sbits[kUnpackWaves][kUnpackWords];
+  const unsigned lane = lane_id(), w = threadIdx.x / kWave;
+  const uint64_t t = (uint64_t)blockIdx.x * kUnpackWaves + w;
+  const bool tile_live = t < ntiles;   // (wave-uniform; every wave of the block reaches the barriers)
+  if (blockIdx.x == 0 && threadIdx.x == 0) offsets[rows] = (int64_t)leaves;
+  for (unsigned k = lane; k < (unsigned)kUnpackWords; k += kWave) sbits[w][k] = 0ull;
+  __syncthreads();
+  uint64_t row_at = tile_live ? tile_rows[t] : 0, leaf_at = tile_live ? tile_leaves[t] : 0;
+  const uint64_t leaf0 = leaf_at, word0 = leaf0 >> 6;
+  const uint64_t lower = (1ull << lane) - 1ull;
+  if (tile_live) {
+    for (unsigned gi = 0; gi < kTile / 64; ++gi) {
+      const uint64_t s0 = t * kTile + (uint64_t)gi * 64;
+      if (s0 >= n_slots) break;   // (uniform)
+      const uint64_t slot = s0 + lane;
+      const bool live = slot < n_slots;
+      unsigned d = 0;
+      bool cont = false;
+      if (live) {
+        cont = (rep[slot >> 6] >> lane) & 1ull;
+        d = width == 1 ? (unsigned)((def[slot >> 6] >> lane) & 1ull)
+                       : (unsigned)((def[slot >> 5] >> ((slot & 31) * 2)) & 3ull);
+      }
+      const bool leaf = live && d >= (unsigned)leaf_level;
+      const uint64_t startw = __ballot(live && !cont);
+      const uint64_t leafw = __ballot(leaf);
+      const uint64_t validw = __ballot(leaf && d == (unsigned)max_def);
+      const uint64_t lrank = leaf_at + (uint64_t)__popcll(leafw & lower);
+      if (live && !cont) {
+        const uint64_t row = row_at + (uint64_t)__popcll(startw & lower);
+        if (row < rows) offsets[row] = (int64_t)lrank;
+      }
+      if (leaf_valid != nullptr && ((validw >> lane) & 1ull) && lrank < leaves) {
+        const uint64_t k = (lrank >> 6) - word0;   // < kUnpackWords: lrank - leaf0 < kTile
+        if (k < (uint64_t)kUnpackWords) atomicOr(&sbits[w][k], 1ull << (lrank & 63));
+      }
+      row_at += (uint64_t)__popcll(startw);
+      leaf_at += (uint64_t)__popcll(leafw);
+    }
+  }
+  __syncthreads();
+  if (tile_live && leaf_valid != nullptr) {
+    const uint64_t nwords = (leaves + 63) / 64;
+    const uint64_t leaf1 = leaf_at < leaves ? leaf_at : leaves;   // the tile's leaves: [leaf0, leaf1)
+    for (unsigned k = lane; k < (unsigned)kUnpackWords; k += kWave) {
+      const uint64_t wi = word0 + k;
+      const unsigned long long v = sbits[w][k];
+      if (wi >= nwords || wi * 64 >= leaf1) continue;
+      if (wi * 64 >= leaf0 && (wi + 1) * 64 <= leaf1) leaf_valid[wi] = v;   // no other tile has a bit here
+      else if (v != 0ull) atomicOr(&leaf_valid[wi], v);                      // shared with a neighbour tile
+    }
+  }
+}
+
 }  // namespace
 }  // namespace nvt
 
@@ -367,6 +484,59 @@ int nvt_pqlist_pack_many(const nvt_pqlist_col *cols, int ncols, const int64_t *o
                                         i0 == 0 ? reinterpret_cast<uint64_t *>(rep_out) : nullptr);
     NVT_CHECK_LAUNCH();
   }
+  return NVT_OK;
+}
+
+static uint64_t unpack_tile_bytes(uint64_t ntiles) { return (ntiles * 4 + 255) & ~255ull; }
+
+int nvt_pqlist_unpack_ws_bytes(uint64_t n_slots, uint64_t *bytes) {
+  NVT_CHECK_ARG(bytes, "null output");
+  const uint64_t nt = ntiles_of(n_slots);
+  *bytes = 2 * unpack_tile_bytes(nt) + scan_chunks(nt) * 8 + 256;
+  return NVT_OK;
+}
+
+int nvt_pqlist_unpack(const uint8_t *rep, const uint8_t *def, int def_width, uint64_t n_slots, int leaf_level,
+                      int max_def, uint64_t rows, uint64_t leaves, int64_t *offsets, uint8_t *leaf_valid,
+                      void *ws, uint64_t ws_bytes, void *stream) {
+  NVT_CHECK_ARG(offsets, "null offsets");
+  NVT_CHECK_ARG(def_width == 1 || def_width == 2, "def_width is 1 or 2");
+  NVT_CHECK_ARG(leaf_level == 1 || leaf_level == 2, "leaf_level is 1 or 2");
+  NVT_CHECK_ARG(max_def == leaf_level || max_def == leaf_level + 1, "max_def is leaf_level (+ 1 for optional leaves)");
+  NVT_CHECK_ARG((max_def == 1) == (def_width == 1), "def_width 1 goes with max_def 1");
+  NVT_CHECK_ARG(n_slots < (1ull << 32), "fewer than 2^32 slots");
+  NVT_CHECK_ARG(rows <= n_slots && leaves <= n_slots, "more rows or leaves than slots");
+  NVT_CHECK_ARG((reinterpret_cast<uintptr_t>(offsets) & 7) == 0 && (reinterpret_cast<uintptr_t>(leaf_valid) & 7) == 0,
+                "offsets / leaf_valid must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (leaf_valid != nullptr && leaves > 0) NVT_CHECK_HIP(hipMemsetAsync(leaf_valid, 0, ((leaves + 63) / 64) * 8, s));
+  if (n_slots == 0) {   // no slots: every row (there should be none) is empty
+    NVT_CHECK_HIP(hipMemsetAsync(offsets, 0, (rows + 1) * 8, s));
+    return NVT_OK;
+  }
+  NVT_CHECK_ARG(rep && def && ws, "null pointer");
+  NVT_CHECK_ARG(((reinterpret_cast<uintptr_t>(rep) | reinterpret_cast<uintptr_t>(def) |
+                  reinterpret_cast<uintptr_t>(ws)) & 7) == 0, "rep / def / ws must be 8-byte aligned");
+  const uint64_t nt = ntiles_of(n_slots);
+  NVT_CHECK_ARG(ws_bytes >= 2 * unpack_tile_bytes(nt) + scan_chunks(nt) * 8 + 256,
+                "workspace smaller than nvt_pqlist_unpack_ws_bytes(n_slots)");
+  unsigned *tile_rows = reinterpret_cast<unsigned *>(ws);
+  unsigned *tile_leaves = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ws) + unpack_tile_bytes(nt));
+  unsigned long long *chunk_tot =
+      reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(ws) + 2 * unpack_tile_bytes(nt));
+  const uint64_t *r64 = reinterpret_cast<const uint64_t *>(rep), *d64 = reinterpret_cast<const uint64_t *>(def);
+  NVT_PROF("pqlist_unpack", n_slots * (1 + def_width) / 8 + (rows + 1) * 8 + leaves / 8, s);
+  const unsigned grid = (unsigned)((nt + kUnpackWaves - 1) / kUnpackWaves);
+  unpack_count_kernel<<<grid, kBlock, 0, s>>>(r64, d64, def_width, n_slots, leaf_level, nt, tile_rows, tile_leaves);
+  NVT_CHECK_LAUNCH();
+  int rc = exclusive_scan_u32(tile_rows, nt, chunk_tot, s);
+  if (rc) return rc;
+  rc = exclusive_scan_u32(tile_leaves, nt, chunk_tot, s);
+  if (rc) return rc;
+  unpack_emit_kernel<<<grid, kBlock, 0, s>>>(r64, d64, def_width, n_slots, leaf_level, max_def, rows, leaves, nt,
+                                             tile_rows, tile_leaves, offsets,
+                                             reinterpret_cast<unsigned long long *>(leaf_valid));
+  NVT_CHECK_LAUNCH();
   return NVT_OK;
 }
 

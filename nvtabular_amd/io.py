@@ -126,8 +126,9 @@ class Dataset:
         if self._schema is None:
             self._schema = Schema.from_frame(pq.ParquetFile(files[0]).schema_arrow)
 
-        # files the hand-written reader takes (flat numeric columns; PLAIN or dictionary-encoded
-        # values, uncompressed or snappy: parquet_plain.PlainParquetFile); everything else is
+        # files the hand-written reader takes (flat numeric columns and three-level lists of such
+        # leaves; PLAIN or dictionary-encoded values, uncompressed or snappy:
+        # parquet_plain.PlainParquetFile.readable); everything else is
         # decoded by pyarrow and counted in parquet_plain.READER_CHUNKS
         plain_files = {}
 
@@ -139,7 +140,7 @@ class Dataset:
                         from .parquet_plain import PlainParquetFile
 
                         pf = PlainParquetFile(f)
-                        if not pf.eligible:
+                        if not pf.readable:
                             pf = None
                     except Exception:
                         pf = None
@@ -540,11 +541,15 @@ class StagedPartition:
 
         device = device or default_device()
         out = {}
+        unpacked = {}   # list column -> (offsets, leaf bitmap): one unpack per distinct level streams
         for name, sc in self.columns.items():
             tdt = sc.values.dtype
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
                 raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
             packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
+            if getattr(sc, "rep", None) is not None:
+                out[name] = self._list_to_device(name, sc, packed, device, unpacked)
+                continue
             if sc.valid is None:
                 out[name] = DeviceColumn(packed, logical=sc.logical)
                 continue
@@ -562,6 +567,39 @@ class StagedPartition:
                                              data.data_ptr(), ws.data_ptr(), K.stream_ptr()), "nvt_expand_valid")
             out[name] = DeviceColumn(data, bitmap, logical=sc.logical)
         return DeviceFrame(out)
+
+    def _list_to_device(self, name, sc, packed, device, unpacked):
+        """A list column: its level streams become offsets and the leaf bitmap on the device
+        (nvt_pqlist_unpack; columns with byte-equal streams share both tensors), then the non-null
+        leaves are expanded to one slot per leaf like a flat column's rows."""
+        import ctypes as C
+
+        import torch
+
+        from . import kernels as K
+        from . import kernels_parquet_list as KPL
+        from .device import DeviceColumn
+
+        key = sc.same_as if sc.same_as in unpacked else name
+        if key not in unpacked:
+            rep = sc.rep[: ((sc.slots + 63) // 64) * 8].to(device, non_blocking=True)
+            dfn = sc.dfn[: ((sc.slots * sc.width + 63) // 64) * 8].to(device, non_blocking=True)
+            unpacked[key] = KPL.unpack_levels(rep, dfn, sc.width, sc.slots, sc.leaf_level, sc.max_def, sc.rows,
+                                              sc.leaves, sc.nvalid < sc.leaves)
+        offsets, bitmap = unpacked[key]
+        if bitmap is None:
+            return DeviceColumn(packed, None, offsets)
+        if sc.nvalid == 0:
+            data = torch.zeros(sc.leaves, dtype=packed.dtype, device=device)
+        else:
+            data = torch.empty(sc.leaves, dtype=packed.dtype, device=device)
+            need = C.c_uint64()
+            lib = K._lib.load()
+            K.check(lib.nvt_expand_valid_ws_bytes(sc.leaves, C.byref(need)), "nvt_expand_valid_ws_bytes")
+            ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+            K.check(lib.nvt_expand_valid(packed.data_ptr(), sc.dtype.itemsize, bitmap.data_ptr(), sc.leaves,
+                                         data.data_ptr(), ws.data_ptr(), K.stream_ptr()), "nvt_expand_valid")
+        return DeviceColumn(data, bitmap, offsets)
 PLAIN_WRITE_THREADS = int(os.environ.get("NVT_PARQUET_THREADS", "16"))
 PLAIN_ROW_GROUP = int(os.environ.get("NVT_PARQUET_ROW_GROUP", str(1 << 22)))
 PLAIN_INFLIGHT = int(os.environ.get("NVT_PARQUET_INFLIGHT", "8"))   # row groups being written at once

@@ -9,7 +9,10 @@ the group's one host synchronisation and brings the page table, the stream sizes
 counts of every stream back together -- the writer lays the pages out from them while the level
 bytes and the values are still being copied.  Part of the host driver of the C ABI, with the
 facade's conventions: launches under ``kernels.LAUNCH_LOCK`` on torch's current stream, errors
-through ``_lib.check``, workspace from torch's allocator."""
+through ``_lib.check``, workspace from torch's allocator.
+
+``unpack_levels`` is the opposite direction, behind the parquet reader: level streams staged by the
+host decoder -> offsets and leaf bitmap ("List columns in the parquet reader")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -122,3 +125,38 @@ def pack_levels(offsets: torch.Tensor, r0: int, r1: int, bitmaps: Sequence[Optio
               "nvt_pqlist_pack_many")
     return DeviceLevels(meta, rep, list(defs), stream_of, max_pages, (meta_raw, rep_raw, list(defs_raw)),
                         (ws, slot_start, offsets, streams))
+
+
+def unpack_levels(rep: torch.Tensor, dfn: torch.Tensor, width: int, n_slots: int, leaf_level: int, max_def: int,
+                  rows: int, leaves: int, want_valid: bool, guard: int = 0):
+    """The way back (the parquet reader, ``io.StagedPartition.to_device``): enqueue
+    ``nvt_pqlist_unpack`` on the staged level streams of one list column (uint8 on the device, 8-byte
+    aligned: 1 and ``width`` bits per slot) -> (offsets int64[rows + 1], leaf validity bitmap of
+    ceil(leaves / 64) words or None when ``want_valid`` is False).  ``rows`` and ``leaves`` are the
+    host decoder's counts, so nothing is read back.  ``guard``: bytes left untouched in front of and
+    behind both outputs (tests); the raw buffers are returned as a third element then."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = rep.device
+    assert rep.dtype == torch.uint8 and dfn.dtype == torch.uint8 and guard % 16 == 0
+    assert rep.numel() >= ((n_slots + 63) // 64) * 8 and dfn.numel() >= ((n_slots * width + 63) // 64) * 8
+
+    def buffer(nbytes):
+        raw = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev) if guard else \
+            torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return raw, raw[guard: guard + nbytes]
+
+    with K.LAUNCH_LOCK:
+        need = C.c_uint64()
+        check(lib.nvt_pqlist_unpack_ws_bytes(n_slots, C.byref(need)), "nvt_pqlist_unpack_ws_bytes")
+        ws = torch.empty(need.value // 8, dtype=torch.int64, device=dev)
+        off_raw, off8 = buffer((rows + 1) * 8)
+        offsets = off8.view(torch.int64)
+        valid_raw = valid = None
+        if want_valid:
+            valid_raw, valid = buffer(((leaves + 63) // 64) * 8)
+        K.stat_add("pqlist_unpack")
+        check(lib.nvt_pqlist_unpack(K.ptr(rep), K.ptr(dfn), width, n_slots, leaf_level, max_def, rows, leaves,
+                                    offsets.data_ptr(), K.ptr(valid), ws.data_ptr(), ws.numel() * 8, K.stream_ptr()),
+              "nvt_pqlist_unpack")
+    return (offsets, valid, (off_raw, valid_raw)) if guard else (offsets, valid)

@@ -28,7 +28,8 @@ A list column of such numbers is the standard three-level list: a page is
 with both level streams ONE bit-packed run each (bit width 1 and 2), packed on the device
 (kernels_parquet_list, csrc/nvt_parquet_list.hip) and handed over as ``ListLevels``; a row of L
 leaves is max(L, 1) slots and every page starts at a row ("List columns in the PLAIN
-parquet writer").  The reading half below does not take nested files: they are read with pyarrow.
+parquet writer").  The reading half below takes such lists too, from any writer ("List
+columns in the parquet reader"); other nested files are read with pyarrow.
 Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
 columns) stays with pyarrow's writer.
 """
@@ -523,8 +524,16 @@ class PlainParquetFile:
     converted / logical type that changes the meaning of the bits (dates, decimals, unsigned),
     codec UNCOMPRESSED or SNAPPY, values PLAIN or dictionary-encoded (what pandas / pyarrow / cuDF
     write by default), encodings within {PLAIN, PLAIN_DICTIONARY, RLE, BIT_PACKED, RLE_DICTIONARY}.
-    ``eligible`` says whether EVERY column of every row group qualifies; otherwise the caller
-    reads the file with pyarrow."""
+    ``eligible`` says whether EVERY column of every row group qualifies as such a flat column.
+    ``readable`` is the wider verdict the reader goes by: every top-level column is such a flat
+    column or the standard three-level list of such leaves (a group annotated LIST, optional or
+    required, holding one repeated group, holding one primitive leaf, optional or required; the two
+    inner names are not looked at), and no chunk of a list column announces BIT_PACKED levels.
+    ``columns[j]`` describes top-level column j: ``kind`` ("flat" / "list"), ``outer_optional``,
+    ``elem_optional``, ``max_def`` (lists: O + 1 + E), ``leaf_level`` (O + 1) and ``leaf_dtype``.  For
+    a readable file ``names`` / ``dtypes`` / ``max_def`` / ``units`` are per top-level column.
+    Otherwise ``why_not`` says what keeps the file with pyarrow (legacy two-level lists, lists of
+    lists, maps, structs, string / bool / narrow / TIMESTAMP leaves, other codecs)."""
 
     def __init__(self, path: str):
         self.path = path
@@ -548,7 +557,9 @@ class PlainParquetFile:
             self.eligible, self.why = False, "nested schema"
         self.names = [e.get(4, b"").decode() for e in leaves]
         self.dtypes, self.max_def, self.units = [], [], []
-        for e in leaves:
+        self._leaf_why = {}
+        for at, e in enumerate(leaves):
+            why_before = self.why
             ptype, rep = e.get(1), e.get(3, 0)
             conv, logical = e.get(6), e.get(10)
             dt = _PQ_NP.get(ptype)
@@ -583,6 +594,9 @@ class PlainParquetFile:
                     self.eligible, self.why = False, f"column {e.get(4)!r}: logical type {logical}"
             self.dtypes.append(dt)
             self.max_def.append(0 if rep == 0 else 1)
+            if self.why is not why_before:   # (assigned in this round: every message is a new string)
+                self._leaf_why[at + 1] = self.why   # (what disqualifies schema element at + 1 as a leaf)
+        self._top_level(schema, root_children)
         self.row_groups = []
         for rg in meta.get(4, []):
             cols = []
@@ -596,6 +610,9 @@ class PlainParquetFile:
                 if not ok:
                     self.eligible, self.why = False, (f"chunk of {md.get(3)}: codec {md.get(4)}, encodings "
                                                       f"{sorted(enc)}")
+                    self._not_readable(self.why)
+                if len(md.get(3, [])) > 1 and 4 in enc:
+                    self._not_readable(f"chunk of {md.get(3)}: BIT_PACKED level streams")
                 first = int(md.get(9, 0))
                 dpo = md.get(11)
                 if dpo is not None and 0 < int(dpo) < first:
@@ -607,9 +624,80 @@ class PlainParquetFile:
                 if not (0 <= cols[-1]["offset"] and 0 <= cols[-1]["size"] and
                         cols[-1]["offset"] + cols[-1]["size"] <= size):
                     self.eligible, self.why = False, f"chunk of {md.get(3)} lies outside the file"
+                    self._not_readable(self.why)
             if [c["path"] for c in cols] != [[n] for n in self.names]:
                 self.eligible, self.why = False, "column chunks do not follow the schema order"
+            # the wider rule: the chunks follow the top-level columns, a list chunk's path has three parts
+            if [(c["path"][:1], len(c["path"])) for c in cols] != \
+                    [([col["name"]], 3 if col["kind"] == "list" else 1) for col in self.columns]:
+                self._not_readable("column chunks do not follow the schema order")
             self.row_groups.append(dict(num_rows=int(rg.get(3, 0)), columns=cols))
+        if self.readable and not self.eligible:
+            # (an eligible file has these per top-level column already)
+            self.names = [c["name"] for c in self.columns]
+            self.dtypes = [c["leaf_dtype"] for c in self.columns]
+            self.max_def = [c["max_def"] for c in self.columns]
+            self.units = [c["unit"] for c in self.columns]
+
+    def _not_readable(self, why):
+        self.readable, self.why_not = False, why
+
+    def _top_level(self, schema, root_children):
+        """``columns`` and the ``readable`` verdict from the schema tree (a depth-first list of
+        SchemaElements: 1 physical type, 3 repetition {0 required, 1 optional, 2 repeated}, 4 name,
+        5 children, 6 converted type, 10 LogicalType)."""
+        self.readable, self.why_not, self.columns = True, "", []
+
+        def behind(i, depth=0):   # index behind the subtree at i
+            kids = int(schema[i].get(5) or 0) if (i < len(schema) and depth < 64) else 0
+            i += 1
+            for _ in range(kids):
+                i = behind(i, depth + 1)
+            return i
+
+        at = 1
+        for _ in range(root_children):
+            if at >= len(schema):
+                self._not_readable("schema shorter than its root says")
+                break
+            e, end = schema[at], behind(at)
+            name = e.get(4, b"").decode()
+            col = dict(name=name, kind="flat", outer_optional=False, elem_optional=False, max_def=0, leaf_level=0,
+                       leaf_dtype=None, unit=None)
+            if not e.get(5):
+                col.update(outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1,
+                           leaf_dtype=self.dtypes[at - 1], unit=self.units[at - 1])
+                if at in self._leaf_why:
+                    self._not_readable(self._leaf_why[at])
+            else:
+                col["kind"] = "list"
+                logical = e.get(10)
+                is_list = e.get(6) == 3 or (isinstance(logical, dict) and 3 in logical)
+                mid = schema[at + 1] if at + 1 < len(schema) else {}
+                leaf = schema[at + 2] if at + 2 < len(schema) else {}
+                if not is_list:
+                    kind = "map" if (e.get(6) in (1, 2) or (isinstance(logical, dict) and 2 in logical)) else "struct"
+                    self._not_readable(f"column {name!r}: a {kind}")
+                elif e.get(3, 0) == 2 or int(e.get(5)) != 1 or mid.get(3, 0) != 2:
+                    self._not_readable(f"column {name!r}: not the standard three-level list")
+                elif not mid.get(5):
+                    self._not_readable(f"column {name!r}: legacy two-level list (a repeated primitive)")
+                elif int(mid.get(5)) != 1 or leaf.get(5):
+                    self._not_readable(f"column {name!r}: list of lists or of structs")
+                elif leaf.get(3, 0) == 2:
+                    self._not_readable(f"column {name!r}: a repeated leaf")
+                elif (at + 2) in self._leaf_why:
+                    self._not_readable(f"column {name!r}: list leaves: {self._leaf_why[at + 2]}")
+                elif self.units[at + 1] is not None:
+                    self._not_readable(f"column {name!r}: list of TIMESTAMP leaves")
+                else:
+                    O, E = int(e.get(3, 0) == 1), int(leaf.get(3, 0) == 1)
+                    col.update(outer_optional=bool(O), elem_optional=bool(E), max_def=O + 1 + E, leaf_level=O + 1,
+                               leaf_dtype=self.dtypes[at + 1])
+            self.columns.append(col)
+            at = end
+        if self.readable and at != len(schema):
+            self._not_readable("schema longer than its root says")
 
     @property
     def num_row_groups(self):
@@ -618,13 +706,28 @@ class PlainParquetFile:
 
 class StagedColumn:
     """One column of a partition in pinned host memory: packed (non-null) values + validity
-    bitmap, as nvt_pq_decode_chunk leaves them."""
+    bitmap, as nvt_pq_decode_chunk leaves them.
 
-    __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical")
+    A list column (``rep`` is not None) is staged as nvt_pq_decode_list_chunk leaves it: ``values``
+    the ``nvalid`` non-null LEAVES, ``rep`` / ``dfn`` the level streams of its ``slots`` slots (1 and
+    ``width`` bits per slot, continuous over the partition), ``leaves`` the leaf slots among them,
+    ``leaf_level`` / ``max_def`` the level arithmetic; ``rows`` stays the row count.  ``same_as``: the
+    name of an earlier list column of the partition whose level streams are byte-equal (they share
+    one unpack and one offsets tensor on the device), else None."""
 
-    def __init__(self, values, valid, rows, nvalid, dtype, logical=None):
+    __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical", "rep", "dfn", "width", "leaf_level",
+                 "max_def", "slots", "leaves", "same_as")
+
+    def __init__(self, values, valid, rows, nvalid, dtype, logical=None, rep=None, dfn=None, width=0, leaf_level=0,
+                 max_def=0, slots=0, leaves=0):
         self.values, self.valid, self.rows, self.nvalid, self.dtype = values, valid, rows, nvalid, dtype
         self.logical = logical   # datetime64[ms|us|ns] of a TIMESTAMP column, else None
+        self.rep, self.dfn, self.width, self.leaf_level, self.max_def = rep, dfn, width, leaf_level, max_def
+        self.slots, self.leaves, self.same_as = slots, leaves, None
+
+    @property
+    def is_list(self):
+        return self.rep is not None
 
 
 _TLS = None
@@ -664,10 +767,11 @@ READER_CHUNKS = {"plain": 0, "pyarrow": 0}
 
 
 def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True):
-    """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of an eligible
+    """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of a readable
     file.  One task per column: pread of a chunk into a scratch buffer, then nvt_pq_decode_chunk
     (ctypes: GIL released) moves its values and validity bits to their place in the partition's
-    (pinned) staging buffers."""
+    (pinned) staging buffers; a list column's chunks go through nvt_pq_decode_list_chunk, which
+    appends their levels to the column's two level streams instead."""
     import ctypes as C
 
     import torch
@@ -680,11 +784,60 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
     pinned = bool(pin) and torch.cuda.is_available()   # (host-only processes stage in pageable memory)
     fd = os.open(pf.path, os.O_RDONLY)
 
+    def read_chunk(cc, n):
+        buf = _scratch(cc["size"])   # (per thread, reused: a fresh 30 MB bytearray is zero-filled
+        got, mv = 0, memoryview(buf)  #  and page-faulted in for every chunk)
+        while got < cc["size"]:
+            k = os.preadv(fd, [mv[got:cc["size"]]], cc["offset"] + got)
+            if k <= 0:
+                raise IOError(f"{pf.path}: short read of column chunk {n}")
+            got += k
+        cbuf = (C.c_uint8 * len(buf)).from_buffer(buf)
+        sbuf, sbytes = None, 0
+        if cc.get("codec", 0) != 0 or cc.get("dictionary"):
+            sbytes = 2 * max(cc.get("raw_size", 0), cc["size"]) + 64
+            sraw = _scratch2(sbytes)
+            sbuf = (C.c_uint8 * len(sraw)).from_buffer(sraw)
+        return cbuf, sbuf, sbytes
+
+    def list_task(n, j):
+        """One list column: the non-null leaves of its chunks behind each other, their levels
+        appended to ONE repetition and ONE definition stream (a thread per column: chunks share words)."""
+        col, dt = pf.columns[j], pf.dtypes[j]
+        width = 1 if col["max_def"] == 1 else 2
+        slots = sum(pf.row_groups[g]["columns"][j]["num_values"] for g in groups if pf.row_groups[g]["num_rows"])
+        vals = torch.empty(slots, dtype=getattr(torch, dt.name), pin_memory=pinned)
+        rep = torch.zeros(((slots + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
+        dfn = torch.zeros(((slots * width + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
+        slot_at = val_at = leaves = 0
+        counts = (C.c_uint64 * 4)()
+        for g in groups:
+            cc = pf.row_groups[g]["columns"][j]
+            rows = pf.row_groups[g]["num_rows"]
+            if rows == 0:
+                continue
+            cbuf, sbuf, sbytes = read_chunk(cc, n)
+            rc = lib.nvt_pq_decode_list_chunk(cbuf, cc["size"], cc.get("codec", 0), dt.itemsize, col["leaf_level"],
+                                              col["max_def"], cc["num_values"], rows, rep.data_ptr(), dfn.data_ptr(),
+                                              slot_at, slots, vals.data_ptr() + val_at * dt.itemsize,
+                                              (slots - val_at) * dt.itemsize, sbuf, sbytes, counts)
+            if rc != 0:
+                raise _lib.NvtHipError(f"nvt_pq_decode_list_chunk({pf.path}, {n}, row group {g}): "
+                                       f"{lib.nvt_last_error().decode()} (rc {rc})")
+            READER_CHUNKS["plain"] += 1
+            slot_at += int(counts[0])
+            leaves += int(counts[2])
+            val_at += int(counts[3])
+        return StagedColumn(vals, None, total, val_at, dt, None, rep=rep, dfn=dfn, width=width,
+                            leaf_level=col["leaf_level"], max_def=col["max_def"], slots=slot_at, leaves=leaves)
+
     def task(n):
         """One column: its chunks of the row groups one after the other -- packed values behind
         each other, validity bits at the partition's row positions (a thread per COLUMN: two row
         groups may share a bitmap byte)."""
         j = pf.names.index(n)
+        if getattr(pf, "columns", None) and pf.columns[j]["kind"] == "list":
+            return list_task(n, j)
         dt = pf.dtypes[j]
         vals = torch.empty(total, dtype=getattr(torch, dt.name), pin_memory=pinned)
         valid = None
@@ -696,20 +849,8 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
             rows = pf.row_groups[g]["num_rows"]
             if rows == 0:
                 continue
-            buf = _scratch(cc["size"])   # (per thread, reused: a fresh 30 MB bytearray is zero-filled
-            got, mv = 0, memoryview(buf)  #  and page-faulted in for every chunk)
-            while got < cc["size"]:
-                k = os.preadv(fd, [mv[got:cc["size"]]], cc["offset"] + got)
-                if k <= 0:
-                    raise IOError(f"{pf.path}: short read of column chunk {n}")
-                got += k
-            cbuf = (C.c_uint8 * len(buf)).from_buffer(buf)
+            cbuf, sbuf, sbytes = read_chunk(cc, n)
             r, v = C.c_uint64(), C.c_uint64()
-            sbuf, sbytes = None, 0
-            if cc.get("codec", 0) != 0 or cc.get("dictionary"):
-                sbytes = 2 * max(cc.get("raw_size", 0), cc["size"]) + 64
-                sraw = _scratch2(sbytes)
-                sbuf = (C.c_uint8 * len(sraw)).from_buffer(sraw)
             rc = lib.nvt_pq_decode_chunk_codec(cbuf, cc["size"], cc.get("codec", 0), dt.itemsize, pf.max_def[j],
                                                rows, valid.data_ptr() if valid is not None else None, row_at,
                                                vals.data_ptr() + val_at * dt.itemsize,
@@ -741,4 +882,18 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
             if not f.cancelled():
                 f.exception()
         os.close(fd)
+    # list columns whose level streams are byte-equal (what ops.Groupby's "list" aggregates of one
+    # frame are) share one unpack on the device: 3 bits per slot to compare
+    lists = []
+    for n, sc in zip(names, cols):
+        if not sc.is_list:
+            continue
+        key = (sc.slots, sc.width, sc.leaf_level, sc.max_def)
+        for m, other in lists:
+            if key == (other.slots, other.width, other.leaf_level, other.max_def) and \
+                    torch.equal(sc.rep, other.rep) and torch.equal(sc.dfn, other.dfn):
+                sc.same_as = m
+                break
+        else:
+            lists.append((n, sc))
     return dict(zip(names, cols))
