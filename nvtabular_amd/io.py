@@ -3,8 +3,10 @@ merlin.io.Dataset the hot path touches: SURVEY section 8(b) "Dataset").
 
 Sources: pandas DataFrame, DeviceFrame, pyarrow Table, parquet path(s) or a list
 of already-partitioned frames.  ``to_iter()`` yields HBM-resident DeviceFrames;
-parquet row groups are decoded by pyarrow straight into Arrow buffers and copied
-to the device without going through pandas.
+parquet row groups are decoded by the hand-written reader where it takes the file
+(parquet_plain.py: ``PlainParquetFile.readable``, ``StagedPartition``), else by pyarrow
+straight into Arrow buffers, and copied to the device without going through pandas.
+``to_parquet`` hands frames to the PLAIN write driver (parquet_write.py) or to pyarrow.
 """
 from __future__ import annotations
 
@@ -15,6 +17,8 @@ from typing import Iterable, List, Optional
 import pandas as pd
 
 from .device import DeviceFrame, as_device_frame
+from .parquet_plain import READER_CHUNKS, PlainParquetFile, StagedPartition, read_row_groups_staged
+from .parquet_write import LAST_TIMING, device_permutation, plain_eligible, write_plain  # noqa: F401
 from .schema import Schema
 
 
@@ -137,8 +141,6 @@ class Dataset:
                 pf = None
                 if PLAIN_PARQUET_READ:
                     try:
-                        from .parquet_plain import PlainParquetFile
-
                         pf = PlainParquetFile(f)
                         if not pf.readable:
                             pf = None
@@ -151,8 +153,6 @@ class Dataset:
             f, groups = piece
             pf = plain_file(f)
             if pf is not None:
-                from .parquet_plain import read_row_groups_staged
-
                 try:
                     return StagedPartition(read_row_groups_staged(pf, groups, columns, pool=_plain_read_pool()))
                 except Exception as e:  # (a page kind the footer did not announce: pyarrow reads it)
@@ -161,8 +161,6 @@ class Dataset:
                     if not isinstance(e, _lib.NvtHipError):
                         raise
                     plain_files[f] = None
-            from .parquet_plain import READER_CHUNKS
-
             table = pq.ParquetFile(f).read_row_groups(groups, columns=columns)
             READER_CHUNKS["pyarrow"] += table.num_columns * len(groups)   # (counted: never silent)
             return table
@@ -355,151 +353,155 @@ class Dataset:
           ``_metadata.json`` (file stats + cats / conts / labels) next to the data files.
         """
         import itertools
-        import json
 
-        import numpy as np
-        import pyarrow as pa
         import pyarrow.parquet as pq
 
         from . import dist
 
         shuffle = Shuffle.coerce(shuffle)
-        pq_kw = {} if compression is None else {"compression": compression}
         os.makedirs(str(output_path), exist_ok=True)
         output_path = str(output_path)
         rank, world = dist.rank(), dist.world_size()
         k = int(out_files_per_proc) if out_files_per_proc else None
-        rng = np.random.default_rng()
-        writers, held, names, rows_in = {}, {}, {}, {}
-        touched = set()
-        collector = []
 
         def fname(j):
             return f"part_{(rank * k + j) if k else (j * world + rank)}{suffix}"
 
-        # Parquet encoding (dictionary + compression) is host work that pyarrow does with the
-        # GIL released: file j is always written by lane j % NLANES, in order, so up to NLANES
-        # files are encoded at once while the next partition is transformed and copied out.
-        import threading
-        from concurrent.futures import ThreadPoolExecutor
-
-        NLANES = 4
-        lanes = [ThreadPoolExecutor(max_workers=1) for _ in range(NLANES)]
-        inflight = threading.BoundedSemaphore(2 * NLANES)  # bounds the host memory queued up
-        pending = []
-
-        def write(j, table):
-            try:
-                w = writers.get(j)
-                if w is None:
-                    names[j] = fname(j)
-                    w = writers[j] = pq.ParquetWriter(os.path.join(output_path, names[j]),
-                                                      table.schema, metadata_collector=collector,
-                                                      **pq_kw)
-                w.write_table(table)
-                rows_in[j] = rows_in.get(j, 0) + table.num_rows
-            finally:
-                inflight.release()
-
-        def emit(j, table):
-            if shuffle == Shuffle.PER_WORKER and k:
-                held.setdefault(j, []).append(table)
-                return
-            inflight.acquire()
-            pending.append(lanes[j % NLANES].submit(write, j, table))
-
-        def drain():
-            for f in pending:
-                f.result()  # re-raises a writer's exception here
-            pending.clear()
-
-        shard = (rank, world) if world > 1 else None
-        parts_iter = iter(self.to_iter(shard=shard))
-        first = next(parts_iter, None)
-        plain = None
-        if first is not None and PLAIN_PARQUET and compression is None and _plain_eligible(first, dtypes) and \
+        parts = iter(self.to_iter(shard=(rank, world) if world > 1 else None))
+        first = next(parts, None)
+        parts = itertools.chain([first], parts) if first is not None else iter(())
+        if first is not None and PLAIN_PARQUET and compression is None and plain_eligible(first, dtypes) and \
                 not (shuffle == Shuffle.PER_WORKER and k):
             # fixed-width numeric columns: PLAIN pages written straight from pinned column
-            # buffers (parquet_plain.py) -- no dictionary pass, no compression, no statistics
-            plain = _write_plain(itertools.chain([first], parts_iter), output_path, fname, k, shuffle, dtypes,
-                                 statistics=bool(statistics))
-            parts_iter, first = iter(()), None
-        rest = itertools.chain([first], parts_iter) if first is not None else iter(())
-        for i, part in enumerate(rest):
-            n = len(part)
-            if shuffle is not None and n > 1:
-                part = part.take_rows(_device_permutation(n, part))
-            table = part.to_arrow()  # pinned async copies, no pandas round trip
-            if dtypes:
-                for c, t in dtypes.items():
-                    if c in table.column_names:
-                        ci = table.column_names.index(c)  # NOT `i`: that is the partition index
-                        table = table.set_column(ci, c, table.column(c).cast(pa.from_numpy_dtype(np.dtype(t))))
-            if k is None:
-                emit(i, table)
-                continue
-            bounds = [(n * j) // k for j in range(k + 1)]
-            for j in range(k):
-                if bounds[j + 1] > bounds[j] or j not in touched:
-                    touched.add(j)
-                    emit(j, table.slice(bounds[j], bounds[j + 1] - bounds[j]))
-        drain()
-        for ex in lanes:
-            ex.shutdown(wait=True)
-        for j, pieces in sorted(held.items()):
-            table = pa.concat_tables(pieces)
-            if table.num_rows > 1:
-                table = table.take(pa.array(rng.permutation(table.num_rows)))
-            names[j] = fname(j)
-            w = writers[j] = pq.ParquetWriter(os.path.join(output_path, names[j]), table.schema,
-                                              metadata_collector=collector, **pq_kw)
-            w.write_table(table)
-            rows_in[j] = table.num_rows
-        schema = None
-        order = sorted(writers)
-        for j in order:
-            schema = schema or writers[j].schema
-            writers[j].close()
-        # every ParquetWriter appended its FileMetaData on close, in closing order
+            # buffers (parquet_write.py) -- no dictionary pass, no compression, no statistics
+            names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
+                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS)
+            collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
+            schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
+        else:
+            names, rows, order, schema, collector = _write_pyarrow(
+                parts, output_path, fname, k, shuffle, dtypes, {} if compression is None else {"compression": compression})
         for md, j in zip(collector, order):
             md.set_file_path(names[j])
-        if plain is not None:
-            names, rows_in, order = plain
-            collector = []
-            for j in order:
-                md = pq.read_metadata(os.path.join(output_path, names[j]))
-                md.set_file_path(names[j])
-                collector.append(md)
-            schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
-        if world > 1:
-            gathered = [None] * world
-            import torch.distributed as td
-
-            td.all_gather_object(gathered, [(names[j], rows_in.get(j, 0)) for j in order])
-            td.barrier()
-            files = [x for g in gathered for x in g]
-        else:
-            files = [(names[j], rows_in.get(j, 0)) for j in order]
-        if rank == 0 and schema is not None:
-            if world > 1:  # summary over every rank's files
-                collector = []
-                for name, _ in files:
-                    md = pq.read_metadata(os.path.join(output_path, name))
-                    md.set_file_path(name)
-                    collector.append(md)
-            pq.write_metadata(schema, os.path.join(output_path, "_metadata"),
-                              metadata_collector=collector)
-            with open(os.path.join(output_path, "_file_list.txt"), "w") as f:
-                f.write(str(len(files)) + "\n")
-                for name, _ in files:
-                    f.write(name + "\n")
-            cols = schema.names
-            pick = lambda lst: [{"col_name": c, "index": cols.index(c)} for c in (lst or []) if c in cols]
-            meta = {"file_stats": [{"file_name": name, "num_rows": int(nr)} for name, nr in files],
-                    "cats": pick(cats), "conts": pick(conts), "labels": pick(labels)}
-            with open(os.path.join(output_path, "_metadata.json"), "w") as f:
-                json.dump(meta, f)
+        _write_summary(output_path, [(names[j], rows.get(j, 0)) for j in order], schema, collector,
+                       cats, conts, labels)
         return None
+
+
+def _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw):
+    """Dataset.to_parquet with pyarrow's writer (strings, bools, a codec, Shuffle.PER_WORKER with
+    ``k`` files ...): partition i goes to file i, or with ``k`` is cut into k pieces for files
+    0 .. k-1.  -> (names {file index: name}, rows {file index: rows}, file indices in order, the
+    files' Arrow schema, their FileMetaData in that order)."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    rng = np.random.default_rng()
+    writers, held, names, rows_in = {}, {}, {}, {}
+    touched = set()
+    collector = []
+    # Parquet encoding (dictionary + compression) is host work that pyarrow does with the
+    # GIL released: file j is always written by lane j % NLANES, in order, so up to NLANES
+    # files are encoded at once while the next partition is transformed and copied out.
+    NLANES = 4
+    lanes = [ThreadPoolExecutor(max_workers=1) for _ in range(NLANES)]
+    inflight = threading.BoundedSemaphore(2 * NLANES)  # bounds the host memory queued up
+    pending = []
+
+    def write(j, table):
+        try:
+            w = writers.get(j)
+            if w is None:
+                names[j] = fname(j)
+                w = writers[j] = pq.ParquetWriter(os.path.join(output_path, names[j]), table.schema,
+                                                  metadata_collector=collector, **pq_kw)
+            w.write_table(table)
+            rows_in[j] = rows_in.get(j, 0) + table.num_rows
+        finally:
+            inflight.release()
+
+    def emit(j, table):
+        if shuffle == Shuffle.PER_WORKER and k:
+            held.setdefault(j, []).append(table)
+            return
+        inflight.acquire()
+        pending.append(lanes[j % NLANES].submit(write, j, table))
+
+    for i, part in enumerate(parts):
+        n = len(part)
+        if shuffle is not None and n > 1:
+            part = part.take_rows(device_permutation(n, part))
+        table = part.to_arrow()  # pinned async copies, no pandas round trip
+        for c, t in (dtypes or {}).items():
+            if c in table.column_names:
+                ci = table.column_names.index(c)  # NOT `i`: that is the partition index
+                table = table.set_column(ci, c, table.column(c).cast(pa.from_numpy_dtype(np.dtype(t))))
+        if k is None:
+            emit(i, table)
+            continue
+        bounds = [(n * j) // k for j in range(k + 1)]
+        for j in range(k):
+            if bounds[j + 1] > bounds[j] or j not in touched:
+                touched.add(j)
+                emit(j, table.slice(bounds[j], bounds[j + 1] - bounds[j]))
+    for f in pending:
+        f.result()  # re-raises a writer's exception here
+    for ex in lanes:
+        ex.shutdown(wait=True)
+    for j, pieces in sorted(held.items()):
+        table = pa.concat_tables(pieces)
+        if table.num_rows > 1:
+            table = table.take(pa.array(rng.permutation(table.num_rows)))
+        inflight.acquire()
+        write(j, table)
+    schema = None
+    order = sorted(writers)
+    for j in order:   # (every ParquetWriter appends its FileMetaData to the collector on close)
+        schema = schema or writers[j].schema
+        writers[j].close()
+    return names, rows_in, order, schema, collector
+
+
+def _write_summary(output_path, files, schema, collector, cats, conts, labels):
+    """``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and ``_metadata.json``
+    next to the data files.  ``files``: this rank's [(name, rows)]; ``collector``: their
+    FileMetaData with the file paths set.  Under torch.distributed rank 0 writes for every rank."""
+    import json
+
+    import pyarrow.parquet as pq
+
+    from . import dist
+
+    if dist.world_size() > 1:
+        import torch.distributed as td
+
+        gathered = [None] * dist.world_size()
+        td.all_gather_object(gathered, files)
+        td.barrier()
+        files = [x for g in gathered for x in g]
+    if dist.rank() != 0 or schema is None:
+        return
+    if dist.world_size() > 1:  # summary over every rank's files
+        collector = []
+        for name, _ in files:
+            md = pq.read_metadata(os.path.join(output_path, name))
+            md.set_file_path(name)
+            collector.append(md)
+    pq.write_metadata(schema, os.path.join(output_path, "_metadata"), metadata_collector=collector)
+    with open(os.path.join(output_path, "_file_list.txt"), "w") as f:
+        f.write(str(len(files)) + "\n")
+        for name, _ in files:
+            f.write(name + "\n")
+    cols = schema.names
+    pick = lambda lst: [{"col_name": c, "index": cols.index(c)} for c in (lst or []) if c in cols]
+    meta = {"file_stats": [{"file_name": name, "num_rows": int(nr)} for name, nr in files],
+            "cats": pick(cats), "conts": pick(conts), "labels": pick(labels)}
+    with open(os.path.join(output_path, "_metadata.json"), "w") as f:
+        json.dump(meta, f)
 
 
 PLAIN_PARQUET = os.environ.get("NVT_PLAIN_PARQUET", "1") != "0"
@@ -517,341 +519,10 @@ def _plain_read_pool():
     return _PLAIN_READ_POOL
 
 
-class StagedPartition:
-    """A partition as the hand-written parquet reader leaves it on the host: per column the
-    packed non-null values and the validity bitmap in pinned memory
-    (parquet_plain.read_row_groups_staged).  ``to_device`` enqueues the copies on the CURRENT
-    stream (the prefetcher's side stream) and expands columns with nulls to one slot per row on
-    the device (nvt_expand_valid)."""
-
-    def __init__(self, columns):
-        self.columns = columns
-
-    @property
-    def num_rows(self):
-        return next(iter(self.columns.values())).rows if self.columns else 0
-
-    def to_device(self, device=None):
-        import ctypes as C
-
-        import torch
-
-        from . import kernels as K
-        from .device import DeviceColumn, DeviceFrame, default_device
-
-        device = device or default_device()
-        out = {}
-        unpacked = {}   # list column -> (offsets, leaf bitmap): one unpack per distinct level streams
-        for name, sc in self.columns.items():
-            tdt = sc.values.dtype
-            if device.type != "cuda":   # (host-only use: tests of the reader itself)
-                raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
-            packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
-            if getattr(sc, "rep", None) is not None:
-                out[name] = self._list_to_device(name, sc, packed, device, unpacked)
-                continue
-            if sc.valid is None:
-                out[name] = DeviceColumn(packed, logical=sc.logical)
-                continue
-            nb = ((sc.rows + 63) // 64) * 8
-            bitmap = sc.valid[:nb].to(device, non_blocking=True)
-            if sc.nvalid == 0:
-                data = torch.zeros(sc.rows, dtype=tdt, device=device)
-            else:
-                data = torch.empty(sc.rows, dtype=tdt, device=device)
-                need = C.c_uint64()
-                lib = K._lib.load()
-                K.check(lib.nvt_expand_valid_ws_bytes(sc.rows, C.byref(need)), "nvt_expand_valid_ws_bytes")
-                ws = torch.empty(need.value, dtype=torch.uint8, device=device)
-                K.check(lib.nvt_expand_valid(packed.data_ptr(), sc.dtype.itemsize, bitmap.data_ptr(), sc.rows,
-                                             data.data_ptr(), ws.data_ptr(), K.stream_ptr()), "nvt_expand_valid")
-            out[name] = DeviceColumn(data, bitmap, logical=sc.logical)
-        return DeviceFrame(out)
-
-    def _list_to_device(self, name, sc, packed, device, unpacked):
-        """A list column: its level streams become offsets and the leaf bitmap on the device
-        (nvt_pqlist_unpack; columns with byte-equal streams share both tensors), then the non-null
-        leaves are expanded to one slot per leaf like a flat column's rows."""
-        import ctypes as C
-
-        import torch
-
-        from . import kernels as K
-        from . import kernels_parquet_list as KPL
-        from .device import DeviceColumn
-
-        key = sc.same_as if sc.same_as in unpacked else name
-        if key not in unpacked:
-            rep = sc.rep[: ((sc.slots + 63) // 64) * 8].to(device, non_blocking=True)
-            dfn = sc.dfn[: ((sc.slots * sc.width + 63) // 64) * 8].to(device, non_blocking=True)
-            unpacked[key] = KPL.unpack_levels(rep, dfn, sc.width, sc.slots, sc.leaf_level, sc.max_def, sc.rows,
-                                              sc.leaves, sc.nvalid < sc.leaves)
-        offsets, bitmap = unpacked[key]
-        if bitmap is None:
-            return DeviceColumn(packed, None, offsets)
-        if sc.nvalid == 0:
-            data = torch.zeros(sc.leaves, dtype=packed.dtype, device=device)
-        else:
-            data = torch.empty(sc.leaves, dtype=packed.dtype, device=device)
-            need = C.c_uint64()
-            lib = K._lib.load()
-            K.check(lib.nvt_expand_valid_ws_bytes(sc.leaves, C.byref(need)), "nvt_expand_valid_ws_bytes")
-            ws = torch.empty(need.value, dtype=torch.uint8, device=device)
-            K.check(lib.nvt_expand_valid(packed.data_ptr(), sc.dtype.itemsize, bitmap.data_ptr(), sc.leaves,
-                                         data.data_ptr(), ws.data_ptr(), K.stream_ptr()), "nvt_expand_valid")
-        return DeviceColumn(data, bitmap, offsets)
+# the PLAIN writer (parquet_write.write_plain): pwrite threads, rows per row group, row groups being written at once
 PLAIN_WRITE_THREADS = int(os.environ.get("NVT_PARQUET_THREADS", "16"))
 PLAIN_ROW_GROUP = int(os.environ.get("NVT_PARQUET_ROW_GROUP", str(1 << 22)))
-PLAIN_INFLIGHT = int(os.environ.get("NVT_PARQUET_INFLIGHT", "8"))   # row groups being written at once
-# seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
-# levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables
-LAST_TIMING = {}
-
-
-def _plain_eligible(frame, dtypes) -> bool:
-    """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
-    casts), a datetime column in ms / us / ns, or a list column on the device whose leaves are
-    int32 / int64 / float32 / float64 numbers: the hand-written PLAIN writer takes the partition;
-    anything else (datetime64[s] too: parquet has no seconds unit; string, bool and 8 / 16-bit
-    leaves; a cast of a list column) goes to pyarrow."""
-    import numpy as np
-    import torch
-
-    from .parquet_plain import supported_dtype, timestamp_unit
-
-    np_of = {torch.int32: "int32", torch.int64: "int64", torch.float32: "float32", torch.float64: "float64"}
-    if len(frame.columns) == 0:
-        return False
-    for name, col in frame.items():
-        if col.strings is not None or col.data.dtype not in np_of:
-            return False
-        if col.offsets is not None and (not col.data.is_cuda or col.logical is not None or
-                                        (dtypes and name in dtypes)):
-            return False
-        if col.logical is not None and (timestamp_unit(col.logical) is None or (dtypes and name in dtypes)):
-            return False
-        if dtypes and name in dtypes and not supported_dtype(np.dtype(dtypes[name])):
-            return False
-    return True
-
-
-def _write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics=False):
-    """Dataset.to_parquet for fixed-width numeric frames: every partition is cut into row groups
-    of PLAIN_ROW_GROUP rows; a row group's columns are copied into pinned host buffers on a side
-    stream (nulls: values compacted and the validity bitmap re-packed on the device first) while
-    the previous row group is written -- all its column chunks at once, by a pool of threads
-    calling pwrite at offsets laid out beforehand (PlainParquetWriter).
-    List columns: the repetition / definition levels of a row group are packed on the device
-    (kernels_parquet_list: the columns that share an offsets tensor share one plan and one
-    repetition stream); ONE read-back per row group and offsets tensor brings the page table, the
-    stream sizes and the non-null counts, then the level bytes and the non-null leaves are copied
-    out like the values of a flat column.
-    -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
-    from collections import deque
-    from concurrent.futures import ThreadPoolExecutor
-
-    import numpy as np
-    import torch
-
-    from . import kernels as K
-    from . import kernels_parquet_list as KPL
-    from . import parquet_plain as PP
-    from .device import pack_bitmap_device
-    from .parquet_plain import ListLevels, PlainParquetWriter
-
-    import time
-
-    t_of = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
-    LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
-                       levels_s=0.0)
-    t_all = time.perf_counter()
-    copy_s = None
-    writers, names, rows_in = {}, {}, {}
-    staged = deque()
-    inflight = deque()   # (futures, host buffers) of row groups whose column writes are still running
-    touched = set()
-
-    with ThreadPoolExecutor(max_workers=PLAIN_WRITE_THREADS) as pool:
-        def flush_one():
-            j, cols, rows, event, keep, stats = staged.popleft()
-            t0 = time.perf_counter()
-            # the host does not wait for the copies: every column task synchronises with the
-            # event itself before it writes.  Only validity bitmaps must be here already (the
-            # pages are laid out from their popcounts).
-            if event is not None and any(isinstance(c[2], np.ndarray) for c in cols):
-                event.synchronize()
-            ready = event.synchronize if event is not None else None
-            t1 = time.perf_counter()
-            LAST_TIMING["wait_copy_s"] += t1 - t0
-            w = writers.get(j)
-            if w is None:
-                names[j] = fname(j)
-                w = writers[j] = PlainParquetWriter(
-                    os.path.join(output_path, names[j]), [c[0] for c in cols],
-                    [c[1].dtype for c in cols], pool=pool, logical=[c[3] for c in cols],
-                    lists=[isinstance(c[2], ListLevels) for c in cols])
-            elif w.names != [c[0] for c in cols] or w.dtypes != [c[1].dtype for c in cols] or \
-                    w.logical != [c[3] for c in cols] or w.lists != [isinstance(c[2], ListLevels) for c in cols]:
-                # (pyarrow's ParquetWriter raises on a schema change too; never cast silently)
-                raise ValueError(
-                    f"to_parquet: partition schema {[(c[0], str(c[1].dtype)) for c in cols]} differs from "
-                    f"the schema {list(zip(w.names, map(str, w.dtypes)))} of {names[j]}")
-            # the column writes of this row group go to the pool and are NOT waited for: row
-            # groups of other files (other inodes: buffered writes to ONE file serialise on its
-            # inode lock, ~10 GB/s) and the next copies proceed meanwhile
-            futs = w.write_row_group([(c[1], c[2]) for c in cols], rows, wait=False, ready=ready, stats=stats)
-            inflight.append((futs, cols, keep))
-            while len(inflight) > PLAIN_INFLIGHT:
-                for f in inflight.popleft()[0]:
-                    f.result()
-            LAST_TIMING["write_s"] += time.perf_counter() - t1
-            rows_in[j] = rows_in.get(j, 0) + rows
-
-        parts = iter(parts)
-        i = -1
-        try:
-            while True:
-                t_in = time.perf_counter()
-                part = next(parts, None)
-                LAST_TIMING["input_s"] += time.perf_counter() - t_in
-                if part is None:
-                    break
-                i += 1
-                n = len(part)
-                if shuffle is not None and n > 1:
-                    part = part.take_rows(_device_permutation(n, part))
-                cols = []
-                lists = {}   # list column -> (leaves, bool mask of the leaves or None, offsets, leaf bitmap)
-                for name, col in part.items():
-                    col = col.materialize()
-                    if col.offsets is not None:
-                        leaves = col.data.contiguous()
-                        lmask = K.unpack_bitmap(col.valid, leaves.numel()) if col.valid is not None else None
-                        lists[name] = (leaves, lmask, col.offsets.contiguous(), col.valid)
-                        cols.append((name, leaves, None, None))
-                        continue
-                    data = col.data
-                    if dtypes and name in dtypes:
-                        data = data.to(t_of[str(np.dtype(dtypes[name]))])
-                    mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
-                    cols.append((name, data, mask, col.logical))
-                # list columns that share one offsets tensor share plan, page table and repetition stream
-                groups = {}
-                for name, (_, _, off, _) in lists.items():
-                    groups.setdefault((off.data_ptr(), off.numel()), []).append(name)
-                on_gpu = any(c[1].is_cuda for c in cols)
-                if on_gpu and copy_s is None:
-                    copy_s = torch.cuda.Stream()
-                if on_gpu:
-                    copy_s.wait_stream(torch.cuda.current_stream())
-                pieces = [(i, 0, n)] if k is None else [
-                    (j, (n * j) // k, (n * (j + 1)) // k) for j in range(k)]
-                for j, a, b in pieces:
-                    if b <= a and j in touched:
-                        continue
-                    touched.add(j)
-                    for s0 in (range(a, b, PLAIN_ROW_GROUP) if b > a else [a]):
-                        s1 = min(b, s0 + PLAIN_ROW_GROUP)
-                        rows = s1 - s0
-                        host, keep, stats = [], [], ([] if statistics else None)
-                        t_st = time.perf_counter()
-                        ctx = torch.cuda.stream(copy_s) if on_gpu else _nullcontext()
-                        with ctx:
-                            levels = {}   # list column -> (LevelTable, host rep bytes, host def bytes, its stream)
-                            if rows > 0 and groups:
-                                t_lv = time.perf_counter()
-                                packed = []
-                                for members in groups.values():
-                                    n_leaves = min(int(lists[m][0].numel()) for m in members)
-                                    packed.append(KPL.pack_levels(lists[members[0]][2], s0, s1,
-                                                                  [lists[m][3] for m in members], n_leaves,
-                                                                  PP.PAGE_VALUES))
-                                for members, dl in zip(groups.values(), packed):
-                                    lt = dl.read_back()   # (the one host synchronisation of this offsets tensor)
-                                    LAST_TIMING["levels_s"] += time.perf_counter() - t_lv
-                                    hrep = _to_host(dl.rep[:lt.rep_bytes])
-                                    hdefs = [_to_host(d[:lt.def_bytes]) for d in dl.defs]
-                                    keep.append((dl, hrep, hdefs))
-                                    for m, st in zip(members, dl.stream_of):
-                                        levels[m] = (lt, hrep.numpy(), hdefs[st].numpy(), st)
-                                    t_lv = time.perf_counter()
-                            for name, data, mask, logical in cols:
-                                vals, bm = data[s0:s1], None
-                                if name in lists:
-                                    if rows > 0:
-                                        lt, hrep, hdef, st = levels[name]
-                                        vals = data[lt.leaf_lo:lt.leaf_hi]
-                                        if lists[name][1] is not None:
-                                            vals = vals[lists[name][1][lt.leaf_lo:lt.leaf_hi]]
-                                        bm = ListLevels(lt.slots, lt.nonnull[st], hrep, lt.rep_at, hdef, lt.def_at)
-                                    else:
-                                        vals, bm = data[:0], ListLevels([], [], b"", [], b"", [])
-                                elif mask is not None:
-                                    m = mask[s0:s1]
-                                    vals = vals[m]
-                                    bm = pack_bitmap_device(m) if m.is_cuda else torch.from_numpy(
-                                        np.packbits(m.numpy(), bitorder="little"))
-                                hv = _to_host(vals)
-                                hb = bm if isinstance(bm, ListLevels) else (_to_host(bm) if bm is not None else None)
-                                if statistics:
-                                    mm = None
-                                    if vals.numel():
-                                        if vals.dtype.is_floating_point:   # (NaN is no minimum / maximum)
-                                            nan = torch.isnan(vals)
-                                            lo = torch.where(nan, torch.full_like(vals, float("inf")), vals).amin()
-                                            hi = torch.where(nan, torch.full_like(vals, float("-inf")), vals).amax()
-                                        else:
-                                            lo, hi = torch.aminmax(vals)
-                                        mm = _to_host(torch.stack([lo, hi]))
-                                        keep.append((mm,))
-                                    stats.append(mm.numpy() if mm is not None else None)
-                                keep.append((vals, bm))
-                                host.append((name, hv.numpy(), hb if isinstance(hb, ListLevels) else
-                                             (hb.numpy() if hb is not None else None), logical))
-                            event = None
-                            if on_gpu:
-                                event = torch.cuda.Event()
-                                event.record(copy_s)
-                        LAST_TIMING["stage_s"] += time.perf_counter() - t_st
-                        staged.append((j, host, rows, event, keep, stats))
-                        flush_one()
-            while staged:
-                flush_one()
-            t_cl = time.perf_counter()
-            for w in writers.values():
-                w.close()
-            LAST_TIMING["close_s"] = time.perf_counter() - t_cl
-        except BaseException:
-            # no fds leaked, no truncated footer-less part files left behind
-            for futs, _, _ in inflight:
-                for f in futs:
-                    try:
-                        f.result()
-                    except Exception:
-                        pass
-            for w in writers.values():
-                w.abort()
-            raise
-    LAST_TIMING["total_s"] = time.perf_counter() - t_all
-    return names, rows_in, sorted(writers)
-
-
-class _nullcontext:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-def _to_host(t):
-    import torch
-
-    if not t.is_cuda:
-        return t.contiguous()
-    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    h.copy_(t, non_blocking=True)
-    return h
+PLAIN_INFLIGHT = int(os.environ.get("NVT_PARQUET_INFLIGHT", "8"))
 
 
 class Shuffle:
@@ -872,16 +543,6 @@ class Shuffle:
         if value == Shuffle.FULL:
             return Shuffle.PER_WORKER
         raise ValueError(f"unknown shuffle option {value!r}")
-
-
-def _device_permutation(n: int, frame):
-    import torch
-
-    dev = None
-    for _, col in frame.items():
-        dev = col.data.device
-        break
-    return torch.randperm(n, device=dev)
 
 
 def _prefetch_frames(host_parts, cols, depth: int = 2):

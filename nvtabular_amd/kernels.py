@@ -1881,6 +1881,23 @@ def unpack_bitmap(valid: torch.Tensor, n: int) -> torch.Tensor:
     return bits.reshape(-1)[:n].to(torch.bool)
 
 
+def expand_valid(packed: torch.Tensor, bitmap: torch.Tensor, n: int) -> torch.Tensor:
+    """The non-null values ``packed`` (in order) under an Arrow validity bitmap -> one slot for each
+    of the ``n`` positions (nvt_expand_valid); no values at all: zeros.  Enqueued on the current
+    stream with a workspace of its own, so the parquet prefetcher's thread calls it without
+    LAUNCH_LOCK, as it always has."""
+    if packed.numel() == 0:
+        return torch.zeros(n, dtype=packed.dtype, device=packed.device)
+    lib = _lib.load()
+    out = torch.empty(n, dtype=packed.dtype, device=packed.device)
+    need = C.c_uint64()
+    check(lib.nvt_expand_valid_ws_bytes(n, C.byref(need)), "nvt_expand_valid_ws_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=packed.device)
+    check(lib.nvt_expand_valid(packed.data_ptr(), packed.element_size(), bitmap.data_ptr(), n, out.data_ptr(),
+                               ws.data_ptr(), stream_ptr()), "nvt_expand_valid")
+    return out
+
+
 def popcount(valid: Optional[torch.Tensor], n: int) -> int:
     if valid is None:
         return n

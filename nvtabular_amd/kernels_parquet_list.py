@@ -1,5 +1,5 @@
 """Parquet level streams of list columns on the device: the host driver of ``nvt_pqlist_*``
-(include/nvt_hip.h), behind ``Dataset.to_parquet`` (``io._write_plain``).
+(include/nvt_hip.h), behind ``Dataset.to_parquet`` (``parquet_write.write_plain``).
 
 For one row range of a partition, the list columns whose ``offsets`` are the same tensor (what
 ``ops.Groupby`` hands over and ``ops.ListSlice`` keeps) are planned ONCE: one slot prefix sum, one
@@ -26,6 +26,15 @@ from . import kernels as K
 from ._lib import check
 
 HDR, PG = _lib.PQLIST_HEADER_WORDS, _lib.PQLIST_PAGE_WORDS
+
+
+def _buffer(nbytes, guard, dev):
+    """(raw, view) of an output buffer of nbytes on ``dev``; ``guard`` bytes of 0xA5 in front of and
+    behind the view (tests check that they stay)."""
+    assert guard % 16 == 0
+    raw = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev) if guard else \
+        torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return raw, raw[guard: guard + nbytes]
 
 
 class LevelTable:
@@ -91,12 +100,6 @@ def pack_levels(offsets: torch.Tensor, r0: int, r1: int, bitmaps: Sequence[Optio
             streams.append(bm)
         stream_of.append(keys[key])
 
-    def buffer(nbytes):
-        assert guard % 16 == 0
-        raw = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev) if guard else \
-            torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return raw, raw[guard: guard + nbytes]
-
     with K.LAUNCH_LOCK:
         stream = K.stream_ptr()
         need = C.c_uint64()
@@ -104,10 +107,10 @@ def pack_levels(offsets: torch.Tensor, r0: int, r1: int, bitmaps: Sequence[Optio
         ws = torch.empty(need.value // 8, dtype=torch.int64, device=dev)
         slot_start = torch.empty(n + 1, dtype=torch.int64, device=dev)
         words = HDR + max_pages * PG + len(streams) * max_pages
-        meta_raw, meta8 = buffer(words * 8)
+        meta_raw, meta8 = _buffer(words * 8, guard, dev)
         meta = meta8.view(torch.int64)
-        rep_raw, rep = buffer(rep_cap)
-        defs_raw, defs = zip(*[buffer(def_cap) for _ in streams])
+        rep_raw, rep = _buffer(rep_cap, guard, dev)
+        defs_raw, defs = zip(*[_buffer(def_cap, guard, dev) for _ in streams])
         off_ptr = offsets.data_ptr() + 8 * r0
         K.stat_add("pqlist_plan")
         check(lib.nvt_pqlist_plan(off_ptr, offsets.data_ptr(), n, int(page_slots), max_pages, rep_cap, def_cap, slot_start.data_ptr(),
@@ -129,7 +132,7 @@ def pack_levels(offsets: torch.Tensor, r0: int, r1: int, bitmaps: Sequence[Optio
 
 def unpack_levels(rep: torch.Tensor, dfn: torch.Tensor, width: int, n_slots: int, leaf_level: int, max_def: int,
                   rows: int, leaves: int, want_valid: bool, guard: int = 0):
-    """The way back (the parquet reader, ``io.StagedPartition.to_device``): enqueue
+    """The way back (the parquet reader, ``parquet_plain.StagedPartition.to_device``): enqueue
     ``nvt_pqlist_unpack`` on the staged level streams of one list column (uint8 on the device, 8-byte
     aligned: 1 and ``width`` bits per slot) -> (offsets int64[rows + 1], leaf validity bitmap of
     ceil(leaves / 64) words or None when ``want_valid`` is False).  ``rows`` and ``leaves`` are the
@@ -138,23 +141,18 @@ def unpack_levels(rep: torch.Tensor, dfn: torch.Tensor, width: int, n_slots: int
     _lib.require_gpu()
     lib = _lib.load()
     dev = rep.device
-    assert rep.dtype == torch.uint8 and dfn.dtype == torch.uint8 and guard % 16 == 0
+    assert rep.dtype == torch.uint8 and dfn.dtype == torch.uint8
     assert rep.numel() >= ((n_slots + 63) // 64) * 8 and dfn.numel() >= ((n_slots * width + 63) // 64) * 8
-
-    def buffer(nbytes):
-        raw = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev) if guard else \
-            torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return raw, raw[guard: guard + nbytes]
 
     with K.LAUNCH_LOCK:
         need = C.c_uint64()
         check(lib.nvt_pqlist_unpack_ws_bytes(n_slots, C.byref(need)), "nvt_pqlist_unpack_ws_bytes")
         ws = torch.empty(need.value // 8, dtype=torch.int64, device=dev)
-        off_raw, off8 = buffer((rows + 1) * 8)
+        off_raw, off8 = _buffer((rows + 1) * 8, guard, dev)
         offsets = off8.view(torch.int64)
         valid_raw = valid = None
         if want_valid:
-            valid_raw, valid = buffer(((leaves + 63) // 64) * 8)
+            valid_raw, valid = _buffer(((leaves + 63) // 64) * 8, guard, dev)
         K.stat_add("pqlist_unpack")
         check(lib.nvt_pqlist_unpack(K.ptr(rep), K.ptr(dfn), width, n_slots, leaf_level, max_def, rows, leaves,
                                     offsets.data_ptr(), K.ptr(valid), ws.data_ptr(), ws.numel() * 8, K.stream_ptr()),

@@ -32,18 +32,20 @@ parquet writer").  The reading half below takes such lists too, from any writer 
 columns in the parquet reader"); other nested files are read with pyarrow.
 Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
 columns) stays with pyarrow's writer.
+parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver in front of the writer.
 """
 from __future__ import annotations
 
 import os
 import struct
+import threading
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-# parquet physical types / thrift compact type ids
-_PQ_TYPE = {np.dtype("int32"): 1, np.dtype("int64"): 2, np.dtype("float32"): 4, np.dtype("float64"): 5}
-_CT_BOOL_TRUE, _CT_I32, _CT_I64, _CT_BINARY, _CT_LIST, _CT_STRUCT = 1, 5, 6, 8, 9, 12
+from .parquet_thrift import _CT_BINARY, _CT_I32, _CT_STRUCT, _Struct, _TReader, _varint, _zigzag
+
+_PQ_TYPE = {np.dtype("int32"): 1, np.dtype("int64"): 2, np.dtype("float32"): 4, np.dtype("float64"): 5}   # physical types
 PAGE_VALUES = 1 << 20          # values per data page (8 MiB of int64)
 ROW_GROUP_ROWS = 1 << 23       # rows per row group
 
@@ -64,75 +66,6 @@ def timestamp_unit(logical) -> Optional[str]:
     dt = np.dtype(logical)
     unit = np.datetime_data(dt)[0] if dt.kind == "M" else None
     return unit if unit in _TS_UNIT else None
-
-
-def _varint(v: int) -> bytes:
-    out = bytearray()
-    while True:
-        b = v & 0x7F
-        v >>= 7
-        if v:
-            out.append(b | 0x80)
-        else:
-            out.append(b)
-            return bytes(out)
-
-
-def _zigzag(v: int) -> bytes:
-    return _varint((v << 1) ^ (v >> 63))
-
-
-class _Struct:
-    """Minimal thrift compact-protocol struct writer (fields must be added in ascending id)."""
-
-    def __init__(self):
-        self.b = bytearray()
-        self.last = 0
-
-    def _head(self, fid: int, ctype: int):
-        d = fid - self.last
-        if 0 < d <= 15:
-            self.b.append((d << 4) | ctype)
-        else:
-            self.b.append(ctype)
-            self.b += _zigzag(fid)
-        self.last = fid
-
-    def i32(self, fid, v):
-        self._head(fid, _CT_I32)
-        self.b += _zigzag(int(v))
-        return self
-
-    def i64(self, fid, v):
-        self._head(fid, _CT_I64)
-        self.b += _zigzag(int(v))
-        return self
-
-    def bool(self, fid, v):
-        self._head(fid, 1 if v else 2)   # (the value of a boolean field is its type id)
-        return self
-
-    def binary(self, fid, s):
-        s = s.encode() if isinstance(s, str) else bytes(s)
-        self._head(fid, _CT_BINARY)
-        self.b += _varint(len(s)) + s
-        return self
-
-    def struct(self, fid, body: bytes):
-        self._head(fid, _CT_STRUCT)
-        self.b += body
-        return self
-
-    def list(self, fid, etype: int, items: Sequence[bytes]):
-        self._head(fid, _CT_LIST)
-        n = len(items)
-        self.b += bytes([(n << 4) | etype]) if n < 15 else bytes([0xF0 | etype]) + _varint(n)
-        for it in items:
-            self.b += it
-        return self
-
-    def done(self) -> bytes:
-        return bytes(self.b) + b"\x00"
 
 
 def _page_header(num_values: int, page_bytes: int) -> bytes:
@@ -442,98 +375,121 @@ class PlainParquetWriter:
 # ================================================================================================
 # reading side: footer (thrift compact FileMetaData) + column chunks of PLAIN / uncompressed pages
 # ================================================================================================
-class _TReader:
-    """Minimal thrift compact-protocol reader: a struct comes back as {field id: value}, nested
-    structs as dicts, lists as Python lists, binaries as bytes."""
-
-    def __init__(self, buf, pos=0):
-        self.b, self.p = buf, pos
-
-    def varint(self) -> int:
-        v = sh = 0
-        while True:
-            c = self.b[self.p]
-            self.p += 1
-            v |= (c & 0x7F) << sh
-            if not c & 0x80:
-                return v
-            sh += 7
-
-    def zigzag(self) -> int:
-        v = self.varint()
-        return (v >> 1) ^ -(v & 1)
-
-    def value(self, t):
-        if t == 1:
-            return True
-        if t == 2:
-            return False
-        if t == 3:
-            self.p += 1
-            return self.b[self.p - 1]
-        if t in (4, 5, 6):
-            return self.zigzag()
-        if t == 7:
-            self.p += 8
-            return struct.unpack("<d", bytes(self.b[self.p - 8:self.p]))[0]
-        if t == 8:
-            n = self.varint()
-            self.p += n
-            return bytes(self.b[self.p - n:self.p])
-        if t in (9, 10):
-            h = self.b[self.p]
-            self.p += 1
-            n = h >> 4
-            if n == 15:
-                n = self.varint()
-            et = h & 0x0F
-            if et in (1, 2):   # list<bool>: one byte per element
-                out = [self.b[self.p + i] == 1 for i in range(n)]
-                self.p += n
-                return out
-            return [self.value(et) for _ in range(n)]
-        if t == 11:
-            n = self.varint()
-            if n == 0:
-                return {}
-            kv = self.b[self.p]
-            self.p += 1
-            return {self.value(kv >> 4): self.value(kv & 0x0F) for _ in range(n)}
-        if t == 12:
-            return self.struct()
-        raise ValueError(f"thrift compact: unknown type {t}")
-
-    def struct(self) -> dict:
-        out, fid = {}, 0
-        while True:
-            h = self.b[self.p]
-            self.p += 1
-            if h == 0:
-                return out
-            d, t = h >> 4, h & 0x0F
-            fid = fid + d if d else self.zigzag()
-            out[fid] = self.value(t)
-
-
 _PQ_NP = {1: np.dtype("int32"), 2: np.dtype("int64"), 4: np.dtype("float32"), 5: np.dtype("float64")}
 
 
+def _judge_leaf(e):
+    """(dtype, unit, reason or None) of a primitive SchemaElement (1 physical type, 3 repetition
+    {0 required, 1 optional, 2 repeated}, 4 name, 6 converted type, 10 LogicalType): the rule for
+    flat columns and for list leaves.  ``unit``: "ms" / "us" / "ns" of an INT64 TIMESTAMP."""
+    ptype, conv, logical = e.get(1), e.get(6), e.get(10)
+    dt, who = _PQ_NP.get(ptype), f"column {e.get(4)!r}"
+    # an INT64 TIMESTAMP (LogicalType union field 8 {1: isAdjustedToUTC, 2: unit}, or the
+    # converted types 9 TIMESTAMP_MILLIS / 10 TIMESTAMP_MICROS of legacy writers) keeps its
+    # bits: the counts are taken as they are and the unit is recorded
+    unit = None
+    if ptype == 2 and isinstance(logical, dict) and len(logical) == 1 and isinstance(logical.get(8), dict):
+        tu = logical[8].get(2)
+        unit = _TS_BY_FIELD.get(next(iter(tu))) if isinstance(tu, dict) and len(tu) == 1 else None
+        if unit is not None and conv not in (None, _TS_UNIT[unit][1]):
+            unit = None
+    elif ptype == 2 and logical is None and conv in (9, 10):
+        unit = "ms" if conv == 9 else "us"
+    if unit is not None:
+        conv = logical = None
+    # the most specific annotation is the one reported.  LogicalType union: 10 = INTEGER
+    # {1: bitWidth, 2: isSigned}.  Converted types that reinterpret the integer: DATE 6, TIME 7-8,
+    # TIMESTAMP 9-10, UINT 11-14, DECIMAL 5; INT_8 / INT_16 (15 / 16) on a physical INT32 come back
+    # as int8 / int16 from pyarrow (legacy writers without a LogicalType): only INT_32 (17) on INT32
+    # and INT_64 (18) on INT64 keep dtype AND bits -- the same rule as for the LogicalType INTEGER;
+    # everything else is left to the pyarrow reader
+    integer = logical.get(10) if isinstance(logical, dict) else None
+    if logical is not None and not (integer is not None and integer.get(2, True) and len(logical) == 1 and
+                                    integer.get(1, 0) == (32 if ptype == 1 else 64)):
+        return dt, unit, f"{who}: logical type {logical}"
+    if conv is not None and conv != {1: 17, 2: 18}.get(ptype):
+        return dt, unit, f"{who}: converted type {conv}"
+    if dt is None or e.get(3, 0) == 2:
+        return dt, unit, f"{who}: physical type {ptype} / repetition {e.get(3, 0)}"
+    return dt, unit, None
+
+
+def _judge_column(schema, at):
+    """(``columns`` entry, reason or None) of the top-level column whose subtree starts at
+    schema[at]: a flat column, or the standard three-level list of number leaves."""
+    e = schema[at]
+    name, logical = e.get(4, b"").decode(), e.get(10)
+    col = dict(name=name, kind="flat", outer_optional=False, elem_optional=False, max_def=0, leaf_level=0,
+               leaf_dtype=None, unit=None)
+    if not e.get(5):
+        dt, unit, why = _judge_leaf(e)
+        col.update(outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1, leaf_dtype=dt, unit=unit)
+        return col, why
+    col["kind"] = "list"
+    mid = schema[at + 1] if at + 1 < len(schema) else {}
+    leaf = schema[at + 2] if at + 2 < len(schema) else {}
+    if not (e.get(6) == 3 or (isinstance(logical, dict) and 3 in logical)):
+        kind = "map" if (e.get(6) in (1, 2) or (isinstance(logical, dict) and 2 in logical)) else "struct"
+        return col, f"column {name!r}: a {kind}"
+    if e.get(3, 0) == 2 or int(e.get(5)) != 1 or mid.get(3, 0) != 2:
+        return col, f"column {name!r}: not the standard three-level list"
+    if not mid.get(5):
+        return col, f"column {name!r}: legacy two-level list (a repeated primitive)"
+    if int(mid.get(5)) != 1 or leaf.get(5):
+        return col, f"column {name!r}: list of lists or of structs"
+    if leaf.get(3, 0) == 2:
+        return col, f"column {name!r}: a repeated leaf"
+    dt, unit, why = _judge_leaf(leaf)
+    if why is not None:
+        return col, f"column {name!r}: list leaves: {why}"
+    if unit is not None:
+        return col, f"column {name!r}: list of TIMESTAMP leaves"
+    O, E = int(e.get(3, 0) == 1), int(leaf.get(3, 0) == 1)
+    col.update(outer_optional=bool(O), elem_optional=bool(E), max_def=O + 1 + E, leaf_level=O + 1, leaf_dtype=dt)
+    return col, None
+
+
+def _judge_chunk(cc, col, file_size):
+    """(row_groups[g]["columns"] entry, reason or None) of one ColumnChunk that stands where
+    top-level column ``col`` (None: there is no such column) has its chunk."""
+    md = cc.get(3) or {}
+    enc = set(md.get(2, []))
+    first = int(md.get(9, 0))   # (the chunk starts at its dictionary page when it has one)
+    dpo = md.get(11)
+    if dpo is not None and 0 < int(dpo) < first:
+        first = int(dpo)
+    path = [x.decode() for x in md.get(3, [])]
+    c = dict(offset=first, size=int(md.get(7, 0)), num_values=int(md.get(5, 0)), codec=int(md.get(4, 0)),
+             raw_size=int(md.get(6, 0)), dictionary=bool(dpo is not None or (enc & {2, 8})), path=path)
+    # codec 0 UNCOMPRESSED / 1 SNAPPY; encodings PLAIN 0, PLAIN_DICTIONARY 2, RLE 3, BIT_PACKED 4,
+    # RLE_DICTIONARY 8 (nvt_pq_decode_chunk_codec)
+    if not (md.get(4) in (0, 1) and enc <= {0, 2, 3, 4, 8} and cc.get(1) in (None, b"")):
+        return c, f"chunk of {md.get(3)}: codec {md.get(4)}, encodings {sorted(enc)}"
+    if len(path) > 1 and 4 in enc:
+        return c, f"chunk of {md.get(3)}: BIT_PACKED level streams"
+    if not (0 <= c["offset"] and 0 <= c["size"] and c["offset"] + c["size"] <= file_size):
+        return c, f"chunk of {md.get(3)} lies outside the file"
+    # the chunks follow the top-level columns, a list chunk's path has three parts
+    if col is None or path[:1] != [col["name"]] or len(path) != (3 if col["kind"] == "list" else 1):
+        return c, "column chunks do not follow the schema order"
+    return c, None
+
+
 class PlainParquetFile:
-    """Footer of one parquet file and, per row group, the column chunks the hand-written reader
-    can take: flat columns (no nesting), physical type INT32 / INT64 / FLOAT / DOUBLE without a
-    converted / logical type that changes the meaning of the bits (dates, decimals, unsigned),
-    codec UNCOMPRESSED or SNAPPY, values PLAIN or dictionary-encoded (what pandas / pyarrow / cuDF
-    write by default), encodings within {PLAIN, PLAIN_DICTIONARY, RLE, BIT_PACKED, RLE_DICTIONARY}.
-    ``eligible`` says whether EVERY column of every row group qualifies as such a flat column.
-    ``readable`` is the wider verdict the reader goes by: every top-level column is such a flat
-    column or the standard three-level list of such leaves (a group annotated LIST, optional or
+    """Footer of one parquet file and the verdict on whether the hand-written reader takes it.
+    ``readable``: every top-level column is a flat column (physical type INT32 / INT64 / FLOAT /
+    DOUBLE without a converted / logical type that changes the meaning of the bits: dates, decimals,
+    unsigned) or the standard three-level list of such leaves (a group annotated LIST, optional or
     required, holding one repeated group, holding one primitive leaf, optional or required; the two
-    inner names are not looked at), and no chunk of a list column announces BIT_PACKED levels.
+    inner names are not looked at), and every column chunk follows its column, with codec
+    UNCOMPRESSED or SNAPPY, values PLAIN or dictionary-encoded (what pandas / pyarrow / cuDF write by
+    default), encodings within {PLAIN, PLAIN_DICTIONARY, RLE, BIT_PACKED, RLE_DICTIONARY} and no
+    BIT_PACKED levels on a list chunk.  Otherwise ``why_not`` is the FIRST thing found that keeps
+    the file with pyarrow (legacy two-level lists, lists of lists, maps, structs, string / bool /
+    narrow / TIMESTAMP leaves, other codecs).  ``eligible``: readable and all columns flat.
     ``columns[j]`` describes top-level column j: ``kind`` ("flat" / "list"), ``outer_optional``,
-    ``elem_optional``, ``max_def`` (lists: O + 1 + E), ``leaf_level`` (O + 1) and ``leaf_dtype``.  For
-    a readable file ``names`` / ``dtypes`` / ``max_def`` / ``units`` are per top-level column.
-    Otherwise ``why_not`` says what keeps the file with pyarrow (legacy two-level lists, lists of
-    lists, maps, structs, string / bool / narrow / TIMESTAMP leaves, other codecs)."""
+    ``elem_optional``, ``max_def`` (lists: O + 1 + E), ``leaf_level`` (O + 1), ``leaf_dtype`` and
+    ``unit``; ``names`` / ``dtypes`` / ``max_def`` / ``units`` are the same per top-level column."""
 
     def __init__(self, path: str):
         self.path = path
@@ -550,105 +506,9 @@ class PlainParquetFile:
             meta = _TReader(f.read(flen)).struct()
         schema = meta.get(2, [])
         self.num_rows = int(meta.get(3, 0))
-        self.eligible, self.why = True, ""
-        root_children = int(schema[0].get(5, 0)) if schema else 0
-        leaves = schema[1:]
-        if len(leaves) != root_children or any(e.get(5) for e in leaves):
-            self.eligible, self.why = False, "nested schema"
-        self.names = [e.get(4, b"").decode() for e in leaves]
-        self.dtypes, self.max_def, self.units = [], [], []
-        self._leaf_why = {}
-        for at, e in enumerate(leaves):
-            why_before = self.why
-            ptype, rep = e.get(1), e.get(3, 0)
-            conv, logical = e.get(6), e.get(10)
-            dt = _PQ_NP.get(ptype)
-            if dt is None or rep == 2:
-                self.eligible, self.why = False, f"column {e.get(4)!r}: physical type {ptype} / repetition {rep}"
-            # an INT64 TIMESTAMP (LogicalType union field 8 {1: isAdjustedToUTC, 2: unit}, or the
-            # converted types 9 TIMESTAMP_MILLIS / 10 TIMESTAMP_MICROS of legacy writers) keeps its
-            # bits: the counts are taken as they are and the unit is recorded
-            unit = None
-            if ptype == 2 and isinstance(logical, dict) and len(logical) == 1 and isinstance(logical.get(8), dict):
-                tu = logical[8].get(2)
-                unit = _TS_BY_FIELD.get(next(iter(tu))) if isinstance(tu, dict) and len(tu) == 1 else None
-                if unit is not None and conv not in (None, _TS_UNIT[unit][1]):
-                    unit = None
-            elif ptype == 2 and logical is None and conv in (9, 10):
-                unit = "ms" if conv == 9 else "us"
-            self.units.append(unit)
-            if unit is not None:
-                conv = logical = None
-            # converted types that reinterpret the integer: DATE 6, TIME 7-8, TIMESTAMP 9-10,
-            # UINT 11-14, DECIMAL 5; INT_8 / INT_16 (15 / 16) on a physical INT32 come back as
-            # int8 / int16 from pyarrow (legacy writers without a LogicalType): only INT_32 (17)
-            # on INT32 and INT_64 (18) on INT64 keep dtype AND bits -- the same rule as the
-            # LogicalType INTEGER below; everything else is left to the pyarrow reader
-            if conv is not None and conv != {1: 17, 2: 18}.get(ptype):
-                self.eligible, self.why = False, f"column {e.get(4)!r}: converted type {conv}"
-            if logical is not None:
-                # LogicalType union: 10 = INTEGER {1: bitWidth, 2: isSigned}
-                integer = logical.get(10) if isinstance(logical, dict) else None
-                if not (integer is not None and integer.get(2, True) and
-                        integer.get(1, 0) == (32 if ptype == 1 else 64) and len(logical) == 1):
-                    self.eligible, self.why = False, f"column {e.get(4)!r}: logical type {logical}"
-            self.dtypes.append(dt)
-            self.max_def.append(0 if rep == 0 else 1)
-            if self.why is not why_before:   # (assigned in this round: every message is a new string)
-                self._leaf_why[at + 1] = self.why   # (what disqualifies schema element at + 1 as a leaf)
-        self._top_level(schema, root_children)
-        self.row_groups = []
-        for rg in meta.get(4, []):
-            cols = []
-            for cc in rg.get(1, []):
-                md = cc.get(3) or {}
-                enc = set(md.get(2, []))
-                # codec 0 UNCOMPRESSED / 1 SNAPPY; encodings PLAIN 0, PLAIN_DICTIONARY 2, RLE 3,
-                # BIT_PACKED 4, RLE_DICTIONARY 8 (nvt_pq_decode_chunk_codec); the chunk starts at its
-                # dictionary page when it has one
-                ok = (md.get(4) in (0, 1) and enc <= {0, 2, 3, 4, 8} and cc.get(1) in (None, b""))
-                if not ok:
-                    self.eligible, self.why = False, (f"chunk of {md.get(3)}: codec {md.get(4)}, encodings "
-                                                      f"{sorted(enc)}")
-                    self._not_readable(self.why)
-                if len(md.get(3, [])) > 1 and 4 in enc:
-                    self._not_readable(f"chunk of {md.get(3)}: BIT_PACKED level streams")
-                first = int(md.get(9, 0))
-                dpo = md.get(11)
-                if dpo is not None and 0 < int(dpo) < first:
-                    first = int(dpo)
-                cols.append(dict(offset=first, size=int(md.get(7, 0)), num_values=int(md.get(5, 0)),
-                                 codec=int(md.get(4, 0)), raw_size=int(md.get(6, 0)),
-                                 dictionary=bool(dpo is not None or (enc & {2, 8})),
-                                 path=[x.decode() for x in md.get(3, [])]))
-                if not (0 <= cols[-1]["offset"] and 0 <= cols[-1]["size"] and
-                        cols[-1]["offset"] + cols[-1]["size"] <= size):
-                    self.eligible, self.why = False, f"chunk of {md.get(3)} lies outside the file"
-                    self._not_readable(self.why)
-            if [c["path"] for c in cols] != [[n] for n in self.names]:
-                self.eligible, self.why = False, "column chunks do not follow the schema order"
-            # the wider rule: the chunks follow the top-level columns, a list chunk's path has three parts
-            if [(c["path"][:1], len(c["path"])) for c in cols] != \
-                    [([col["name"]], 3 if col["kind"] == "list" else 1) for col in self.columns]:
-                self._not_readable("column chunks do not follow the schema order")
-            self.row_groups.append(dict(num_rows=int(rg.get(3, 0)), columns=cols))
-        if self.readable and not self.eligible:
-            # (an eligible file has these per top-level column already)
-            self.names = [c["name"] for c in self.columns]
-            self.dtypes = [c["leaf_dtype"] for c in self.columns]
-            self.max_def = [c["max_def"] for c in self.columns]
-            self.units = [c["unit"] for c in self.columns]
-
-    def _not_readable(self, why):
-        self.readable, self.why_not = False, why
-
-    def _top_level(self, schema, root_children):
-        """``columns`` and the ``readable`` verdict from the schema tree (a depth-first list of
-        SchemaElements: 1 physical type, 3 repetition {0 required, 1 optional, 2 repeated}, 4 name,
-        5 children, 6 converted type, 10 LogicalType)."""
         self.readable, self.why_not, self.columns = True, "", []
 
-        def behind(i, depth=0):   # index behind the subtree at i
+        def behind(i, depth=0):   # index behind the subtree at i of the depth-first schema list
             kids = int(schema[i].get(5) or 0) if (i < len(schema) and depth < 64) else 0
             i += 1
             for _ in range(kids):
@@ -656,48 +516,44 @@ class PlainParquetFile:
             return i
 
         at = 1
-        for _ in range(root_children):
+        for _ in range(int(schema[0].get(5, 0)) if schema else 0):
             if at >= len(schema):
-                self._not_readable("schema shorter than its root says")
+                self._fail("schema shorter than its root says")
                 break
-            e, end = schema[at], behind(at)
-            name = e.get(4, b"").decode()
-            col = dict(name=name, kind="flat", outer_optional=False, elem_optional=False, max_def=0, leaf_level=0,
-                       leaf_dtype=None, unit=None)
-            if not e.get(5):
-                col.update(outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1,
-                           leaf_dtype=self.dtypes[at - 1], unit=self.units[at - 1])
-                if at in self._leaf_why:
-                    self._not_readable(self._leaf_why[at])
-            else:
-                col["kind"] = "list"
-                logical = e.get(10)
-                is_list = e.get(6) == 3 or (isinstance(logical, dict) and 3 in logical)
-                mid = schema[at + 1] if at + 1 < len(schema) else {}
-                leaf = schema[at + 2] if at + 2 < len(schema) else {}
-                if not is_list:
-                    kind = "map" if (e.get(6) in (1, 2) or (isinstance(logical, dict) and 2 in logical)) else "struct"
-                    self._not_readable(f"column {name!r}: a {kind}")
-                elif e.get(3, 0) == 2 or int(e.get(5)) != 1 or mid.get(3, 0) != 2:
-                    self._not_readable(f"column {name!r}: not the standard three-level list")
-                elif not mid.get(5):
-                    self._not_readable(f"column {name!r}: legacy two-level list (a repeated primitive)")
-                elif int(mid.get(5)) != 1 or leaf.get(5):
-                    self._not_readable(f"column {name!r}: list of lists or of structs")
-                elif leaf.get(3, 0) == 2:
-                    self._not_readable(f"column {name!r}: a repeated leaf")
-                elif (at + 2) in self._leaf_why:
-                    self._not_readable(f"column {name!r}: list leaves: {self._leaf_why[at + 2]}")
-                elif self.units[at + 1] is not None:
-                    self._not_readable(f"column {name!r}: list of TIMESTAMP leaves")
-                else:
-                    O, E = int(e.get(3, 0) == 1), int(leaf.get(3, 0) == 1)
-                    col.update(outer_optional=bool(O), elem_optional=bool(E), max_def=O + 1 + E, leaf_level=O + 1,
-                               leaf_dtype=self.dtypes[at + 1])
+            col, why = _judge_column(schema, at)
             self.columns.append(col)
-            at = end
-        if self.readable and at != len(schema):
-            self._not_readable("schema longer than its root says")
+            self._fail(why)
+            at = behind(at)
+        else:   # (every column was there)
+            self._fail("schema longer than its root says" if at != len(schema) else None)
+        self.names = [c["name"] for c in self.columns]
+        self.dtypes = [c["leaf_dtype"] for c in self.columns]
+        self.max_def = [c["max_def"] for c in self.columns]
+        self.units = [c["unit"] for c in self.columns]
+        self.row_groups = []
+        for rg in meta.get(4, []):
+            cols = []
+            for j, cc in enumerate(rg.get(1, [])):
+                c, why = _judge_chunk(cc, self.columns[j] if j < len(self.columns) else None, size)
+                cols.append(c)
+                self._fail(why)
+            if len(cols) != len(self.columns):
+                self._fail("column chunks do not follow the schema order")
+            self.row_groups.append(dict(num_rows=int(rg.get(3, 0)), columns=cols))
+
+    def _fail(self, why):
+        if why is not None and self.readable:   # (the first reason stays)
+            self.readable, self.why_not = False, why
+
+    @property
+    def eligible(self):
+        return self.readable and all(c["kind"] == "flat" for c in self.columns)
+
+    @property
+    def why(self):
+        """What keeps the file from being ``eligible``."""
+        return self.why_not or next((f"column {c['name']!r}: a list column" for c in self.columns
+                                     if c["kind"] == "list"), "")
 
     @property
     def num_row_groups(self):
@@ -730,34 +586,64 @@ class StagedColumn:
         return self.rep is not None
 
 
-_TLS = None
+class StagedPartition:
+    """A partition as ``read_row_groups_staged`` leaves it on the host: {column: StagedColumn}.
+    ``to_device`` enqueues the copies on the CURRENT stream (the prefetcher's side stream) and
+    expands columns with nulls to one slot per row on the device (kernels.expand_valid)."""
+
+    def __init__(self, columns):
+        self.columns = columns
+
+    @property
+    def num_rows(self):
+        return next(iter(self.columns.values())).rows if self.columns else 0
+
+    def to_device(self, device=None):
+        from . import kernels as K
+        from . import kernels_parquet_list as KPL
+        from .device import DeviceColumn, DeviceFrame, default_device
+
+        device = device or default_device()
+        out = {}
+        unpacked = {}   # list column -> (offsets, leaf bitmap): one unpack per distinct level streams
+        for name, sc in self.columns.items():
+            if device.type != "cuda":   # (host-only use: tests of the reader itself)
+                raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
+            packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
+            if sc.is_list:
+                # the level streams become offsets and the leaf bitmap on the device (columns with
+                # byte-equal streams share both tensors); the non-null leaves are then expanded to
+                # one slot per leaf like a flat column's rows
+                key = sc.same_as if sc.same_as in unpacked else name
+                if key not in unpacked:
+                    rep = sc.rep[: ((sc.slots + 63) // 64) * 8].to(device, non_blocking=True)
+                    dfn = sc.dfn[: ((sc.slots * sc.width + 63) // 64) * 8].to(device, non_blocking=True)
+                    unpacked[key] = KPL.unpack_levels(rep, dfn, sc.width, sc.slots, sc.leaf_level, sc.max_def,
+                                                      sc.rows, sc.leaves, sc.nvalid < sc.leaves)
+                offsets, bitmap = unpacked[key]
+                data = packed if bitmap is None else K.expand_valid(packed, bitmap, sc.leaves)
+                out[name] = DeviceColumn(data, bitmap, offsets)
+            elif sc.valid is None:
+                out[name] = DeviceColumn(packed, logical=sc.logical)
+            else:
+                bitmap = sc.valid[: ((sc.rows + 63) // 64) * 8].to(device, non_blocking=True)
+                out[name] = DeviceColumn(K.expand_valid(packed, bitmap, sc.rows), bitmap, logical=sc.logical)
+        return DeviceFrame(out)
 
 
-def _scratch(nbytes: int) -> bytearray:
-    """This thread's read buffer, grown in powers of two."""
-    global _TLS
-    if _TLS is None:
-        import threading
+_TLS = threading.local()
 
-        _TLS = threading.local()
-    buf = getattr(_TLS, "buf", None)
+
+def _scratch(slot: str, nbytes: int) -> bytearray:
+    """This thread's buffer ``slot`` ("read": one column chunk as it is in the file; "codec": a
+    dictionary + one decompressed page), grown in powers of two."""
+    buf = getattr(_TLS, slot, None)
     if buf is None or len(buf) < nbytes:
         cap = 1 << 20
         while cap < nbytes:
             cap <<= 1
-        buf = _TLS.buf = bytearray(cap)
-    return buf
-
-
-def _scratch2(nbytes: int) -> bytearray:
-    """This thread's decompression scratch (dictionary + one page), grown in powers of two."""
-    _scratch(1)   # (creates _TLS)
-    buf = getattr(_TLS, "buf2", None)
-    if buf is None or len(buf) < nbytes:
-        cap = 1 << 20
-        while cap < nbytes:
-            cap <<= 1
-        buf = _TLS.buf2 = bytearray(cap)
+        buf = bytearray(cap)
+        setattr(_TLS, slot, buf)
     return buf
 
 
@@ -784,21 +670,31 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
     pinned = bool(pin) and torch.cuda.is_available()   # (host-only processes stage in pageable memory)
     fd = os.open(pf.path, os.O_RDONLY)
 
-    def read_chunk(cc, n):
-        buf = _scratch(cc["size"])   # (per thread, reused: a fresh 30 MB bytearray is zero-filled
-        got, mv = 0, memoryview(buf)  #  and page-faulted in for every chunk)
-        while got < cc["size"]:
-            k = os.preadv(fd, [mv[got:cc["size"]]], cc["offset"] + got)
-            if k <= 0:
-                raise IOError(f"{pf.path}: short read of column chunk {n}")
-            got += k
-        cbuf = (C.c_uint8 * len(buf)).from_buffer(buf)
-        sbuf, sbytes = None, 0
-        if cc.get("codec", 0) != 0 or cc.get("dictionary"):
-            sbytes = 2 * max(cc.get("raw_size", 0), cc["size"]) + 64
-            sraw = _scratch2(sbytes)
-            sbuf = (C.c_uint8 * len(sraw)).from_buffer(sraw)
-        return cbuf, sbuf, sbytes
+    def chunks(n, j):
+        """(row group, chunk, rows, chunk bytes, codec scratch, its size) of column j's chunks in
+        the row groups that have rows, each read into this thread's buffers."""
+        for g in groups:
+            cc, rows = pf.row_groups[g]["columns"][j], pf.row_groups[g]["num_rows"]
+            if rows == 0:
+                continue
+            buf = _scratch("read", cc["size"])   # (per thread, reused: a fresh 30 MB bytearray is
+            got, mv = 0, memoryview(buf)         #  zero-filled and page-faulted in for every chunk)
+            while got < cc["size"]:
+                k = os.preadv(fd, [mv[got:cc["size"]]], cc["offset"] + got)
+                if k <= 0:
+                    raise IOError(f"{pf.path}: short read of column chunk {n}")
+                got += k
+            sbuf, sbytes = None, 0
+            if cc.get("codec", 0) != 0 or cc.get("dictionary"):
+                sbytes = 2 * max(cc.get("raw_size", 0), cc["size"]) + 64
+                sraw = _scratch("codec", sbytes)
+                sbuf = (C.c_uint8 * len(sraw)).from_buffer(sraw)
+            yield g, cc, rows, (C.c_uint8 * len(buf)).from_buffer(buf), sbuf, sbytes
+
+    def decoded(fn, rc, n, g):
+        if rc != 0:
+            raise _lib.NvtHipError(f"{fn}({pf.path}, {n}, row group {g}): {lib.nvt_last_error().decode()} (rc {rc})")
+        READER_CHUNKS["plain"] += 1
 
     def list_task(n, j):
         """One list column: the non-null leaves of its chunks behind each other, their levels
@@ -811,20 +707,12 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         dfn = torch.zeros(((slots * width + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         slot_at = val_at = leaves = 0
         counts = (C.c_uint64 * 4)()
-        for g in groups:
-            cc = pf.row_groups[g]["columns"][j]
-            rows = pf.row_groups[g]["num_rows"]
-            if rows == 0:
-                continue
-            cbuf, sbuf, sbytes = read_chunk(cc, n)
+        for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
             rc = lib.nvt_pq_decode_list_chunk(cbuf, cc["size"], cc.get("codec", 0), dt.itemsize, col["leaf_level"],
                                               col["max_def"], cc["num_values"], rows, rep.data_ptr(), dfn.data_ptr(),
                                               slot_at, slots, vals.data_ptr() + val_at * dt.itemsize,
                                               (slots - val_at) * dt.itemsize, sbuf, sbytes, counts)
-            if rc != 0:
-                raise _lib.NvtHipError(f"nvt_pq_decode_list_chunk({pf.path}, {n}, row group {g}): "
-                                       f"{lib.nvt_last_error().decode()} (rc {rc})")
-            READER_CHUNKS["plain"] += 1
+            decoded("nvt_pq_decode_list_chunk", rc, n, g)
             slot_at += int(counts[0])
             leaves += int(counts[2])
             val_at += int(counts[3])
@@ -836,7 +724,7 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         each other, validity bits at the partition's row positions (a thread per COLUMN: two row
         groups may share a bitmap byte)."""
         j = pf.names.index(n)
-        if getattr(pf, "columns", None) and pf.columns[j]["kind"] == "list":
+        if pf.columns[j]["kind"] == "list":
             return list_task(n, j)
         dt = pf.dtypes[j]
         vals = torch.empty(total, dtype=getattr(torch, dt.name), pin_memory=pinned)
@@ -844,22 +732,14 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if pf.max_def[j]:
             valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         row_at = val_at = 0
-        for g in groups:
-            cc = pf.row_groups[g]["columns"][j]
-            rows = pf.row_groups[g]["num_rows"]
-            if rows == 0:
-                continue
-            cbuf, sbuf, sbytes = read_chunk(cc, n)
+        for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
             r, v = C.c_uint64(), C.c_uint64()
             rc = lib.nvt_pq_decode_chunk_codec(cbuf, cc["size"], cc.get("codec", 0), dt.itemsize, pf.max_def[j],
                                                rows, valid.data_ptr() if valid is not None else None, row_at,
                                                vals.data_ptr() + val_at * dt.itemsize,
                                                (total - val_at) * dt.itemsize, sbuf, sbytes,
                                                C.byref(r), C.byref(v))
-            if rc != 0:
-                raise _lib.NvtHipError(f"nvt_pq_decode_chunk_codec({pf.path}, {n}, row group {g}): "
-                                       f"{lib.nvt_last_error().decode()} (rc {rc})")
-            READER_CHUNKS["plain"] += 1
+            decoded("nvt_pq_decode_chunk_codec", rc, n, g)
             row_at += rows
             val_at += int(v.value)
         logical = np.dtype(f"datetime64[{pf.units[j]}]") if pf.units[j] is not None else None

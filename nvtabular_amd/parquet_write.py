@@ -1,0 +1,306 @@
+"""The PLAIN write driver behind ``Dataset.to_parquet``: partitions on the device -> row groups
+staged in pinned host memory -> ``parquet_plain.PlainParquetWriter``.
+
+Every partition is cut into row groups; a row group's columns are copied into pinned host buffers
+on a side stream (nulls: values compacted and the validity bitmap re-packed on the device first)
+while the previous row group is written -- all its column chunks at once, by a pool of threads
+calling pwrite at offsets laid out beforehand.
+List columns: the repetition / definition levels of a row group are packed on the device
+(kernels_parquet_list: the columns that share an offsets tensor share one plan and one repetition
+stream); ONE read-back per row group and offsets tensor brings the page table, the stream sizes and
+the non-null counts, then the level bytes and the non-null leaves are copied out like the values of
+a flat column ("List columns in the PLAIN parquet writer")."""
+from __future__ import annotations
+
+import os
+import time
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+from contextlib import nullcontext
+from typing import Any, NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from . import kernels_parquet_list as KPL
+from . import parquet_plain as PP
+from .device import pack_bitmap_device
+from .parquet_plain import ListLevels, PlainParquetWriter
+
+# seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
+# levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables
+LAST_TIMING = {}
+_TORCH_OF = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
+
+
+class _Column(NamedTuple):
+    """One column of a partition as it goes out (after the requested cast)."""
+    name: str
+    data: torch.Tensor                       # the rows' values; a list column: its leaves
+    mask: Optional[torch.Tensor]             # bool per row (list column: per leaf), None: no nulls
+    logical: Any                             # datetime64 dtype of a flat column, or None
+    offsets: Optional[torch.Tensor] = None   # of a list column
+    bitmap: Optional[torch.Tensor] = None    # leaf bitmap of a list column (what `mask` unpacks)
+
+
+class _HostColumn(NamedTuple):
+    """One column of a staged row group, as PlainParquetWriter.write_row_group takes it."""
+    name: str
+    values: np.ndarray   # the non-null values / leaves (pinned; may still be in flight)
+    valid: Any           # None, the rows' validity bitmap (uint8 array) or a list column's ListLevels
+    logical: Any
+
+
+class _RowGroup(NamedTuple):
+    file: int        # index of the part file
+    columns: list    # of _HostColumn
+    rows: int
+    event: Any       # recorded behind the copies on the side stream (None: host frames)
+    keep: list       # device tensors and pinned buffers the copies and the writes still use
+    stats: Optional[list]   # per column: {min, max} as a 2-element array (in flight) or None
+
+
+def plain_eligible(frame, dtypes) -> bool:
+    """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
+    casts), a datetime column in ms / us / ns, or a list column on the device whose leaves are
+    int32 / int64 / float32 / float64 numbers: the hand-written PLAIN writer takes the partition;
+    anything else (datetime64[s] too: parquet has no seconds unit; string, bool and 8 / 16-bit
+    leaves; a cast of a list column) goes to pyarrow."""
+    if len(frame.columns) == 0:
+        return False
+    for name, col in frame.items():
+        if col.strings is not None or col.data.dtype not in _TORCH_OF.values():
+            return False
+        if col.offsets is not None and (not col.data.is_cuda or col.logical is not None or
+                                        (dtypes and name in dtypes)):
+            return False
+        if col.logical is not None and (PP.timestamp_unit(col.logical) is None or (dtypes and name in dtypes)):
+            return False
+        if dtypes and name in dtypes and not PP.supported_dtype(np.dtype(dtypes[name])):
+            return False
+    return True
+
+
+def device_permutation(n: int, frame):
+    return torch.randperm(n, device=next((col.data.device for _, col in frame.items()), None))
+
+
+def _to_host(t):
+    if not t.is_cuda:
+        return t.contiguous()
+    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    h.copy_(t, non_blocking=True)
+    return h
+
+
+def _prepare(part, n, dtypes):
+    """-> ([_Column] of a partition of n rows, [[list columns that share one offsets tensor]]: they share
+    plan, page table and repetition stream)."""
+    cols, groups = [], {}
+    for name, col in part.items():
+        col = col.materialize()
+        if col.offsets is not None:
+            leaves = col.data.contiguous()
+            mask = K.unpack_bitmap(col.valid, leaves.numel()) if col.valid is not None else None
+            cols.append(_Column(name, leaves, mask, None, col.offsets.contiguous(), col.valid))
+            groups.setdefault((cols[-1].offsets.data_ptr(), cols[-1].offsets.numel()), []).append(cols[-1])
+            continue
+        data = col.data
+        if dtypes and name in dtypes:
+            data = data.to(_TORCH_OF[str(np.dtype(dtypes[name]))])
+        mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
+        cols.append(_Column(name, data, mask, col.logical))
+    return cols, list(groups.values())
+
+
+def _pack_levels(groups, s0, s1, keep):
+    """Rows [s0, s1) of the list columns: {name: (their ListLevels, the slice of their leaves)}.
+    All groups are enqueued first; each read-back is the one host synchronisation of its offsets
+    tensor.  The level bytes are in flight when this returns (``keep`` holds their buffers)."""
+    levels = {}
+    t_lv = time.perf_counter()
+    packed = [KPL.pack_levels(members[0].offsets, s0, s1, [c.bitmap for c in members],
+                              min(int(c.data.numel()) for c in members), PP.PAGE_VALUES) for members in groups]
+    for members, dl in zip(groups, packed):
+        lt = dl.read_back()
+        LAST_TIMING["levels_s"] += time.perf_counter() - t_lv
+        hrep = _to_host(dl.rep[:lt.rep_bytes])
+        hdefs = [_to_host(d[:lt.def_bytes]) for d in dl.defs]
+        keep.append((dl, hrep, hdefs))
+        for c, st in zip(members, dl.stream_of):
+            levels[c.name] = (ListLevels(lt.slots, lt.nonnull[st], hrep.numpy(), lt.rep_at, hdefs[st].numpy(),
+                                         lt.def_at), slice(lt.leaf_lo, lt.leaf_hi))
+        t_lv = time.perf_counter()
+    return levels
+
+
+def _min_max(vals):
+    """{min, max} of the values on their way to a pinned 2-element tensor; no values: None."""
+    if not vals.numel():
+        return None
+    if vals.dtype.is_floating_point:   # (NaN is no minimum / maximum)
+        nan = torch.isnan(vals)
+        lo = torch.where(nan, torch.full_like(vals, float("inf")), vals).amin()
+        hi = torch.where(nan, torch.full_like(vals, float("-inf")), vals).amax()
+    else:
+        lo, hi = torch.aminmax(vals)
+    return _to_host(torch.stack([lo, hi]))
+
+
+def _stage_column(c: _Column, s0, s1, levels, statistics, keep):
+    """Rows [s0, s1) of one column on their way to the host -> (_HostColumn, min / max or None)."""
+    vals, valid = c.data[s0:s1], None
+    if c.offsets is not None and s1 > s0:
+        valid, leaves = levels[c.name]
+        vals = c.data[leaves] if c.mask is None else c.data[leaves][c.mask[leaves]]
+    elif c.offsets is not None:
+        vals, valid = c.data[:0], ListLevels([], [], b"", [], b"", [])
+    elif c.mask is not None:
+        m = c.mask[s0:s1]
+        vals = vals[m]
+        valid = pack_bitmap_device(m) if m.is_cuda else torch.from_numpy(np.packbits(m.numpy(), bitorder="little"))
+    hv = _to_host(vals)
+    hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
+    mm = _min_max(vals) if statistics else None
+    keep.append((vals, valid, mm))
+    return _HostColumn(c.name, hv.numpy(), hb, c.logical), (mm.numpy() if mm is not None else None)
+
+
+def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
+    """Enqueue everything that brings rows [s0, s1) to the host, on ``copy_s`` (None: the frame is
+    on the host already), and record one event behind it."""
+    host, keep, stats = [], [], ([] if statistics else None)
+    t_st = time.perf_counter()
+    with torch.cuda.stream(copy_s) if copy_s is not None else nullcontext():
+        levels = _pack_levels(groups, s0, s1, keep) if (s1 > s0 and groups) else {}
+        for c in cols:
+            hc, mm = _stage_column(c, s0, s1, levels, statistics, keep)
+            host.append(hc)
+            if statistics:
+                stats.append(mm)
+        event = None
+        if copy_s is not None:
+            event = torch.cuda.Event()
+            event.record(copy_s)
+    LAST_TIMING["stage_s"] += time.perf_counter() - t_st
+    return _RowGroup(j, host, s1 - s0, event, keep, stats)
+
+
+class _PartFiles:
+    """The part files of one to_parquet call: file j is opened by its first row group, which sets
+    its schema.  ``pool`` runs the column writes, at most ``max_inflight`` row groups at a time."""
+
+    def __init__(self, output_path, fname, pool, max_inflight):
+        self.output_path, self.fname, self.pool, self.max_inflight = output_path, fname, pool, max_inflight
+        self.writers, self.names, self.rows = {}, {}, {}
+        self.inflight = deque()   # (futures, row group) of row groups whose column writes are still running
+
+    def flush(self, rg: _RowGroup):
+        t0 = time.perf_counter()
+        # the host does not wait for the copies: every column task synchronises with the event
+        # itself before it writes.  Only validity bitmaps must be here already (the pages are
+        # laid out from their popcounts).
+        if rg.event is not None and any(isinstance(c.valid, np.ndarray) for c in rg.columns):
+            rg.event.synchronize()
+        ready = rg.event.synchronize if rg.event is not None else None
+        t1 = time.perf_counter()
+        LAST_TIMING["wait_copy_s"] += t1 - t0
+        schema = ([c.name for c in rg.columns], [c.values.dtype for c in rg.columns],
+                  [c.logical for c in rg.columns], [isinstance(c.valid, ListLevels) for c in rg.columns])
+        w = self.writers.get(rg.file)
+        if w is None:
+            self.names[rg.file] = self.fname(rg.file)
+            w = self.writers[rg.file] = PlainParquetWriter(
+                os.path.join(self.output_path, self.names[rg.file]), schema[0], schema[1], pool=self.pool,
+                logical=schema[2], lists=schema[3])
+        elif (w.names, w.dtypes, w.logical, w.lists) != schema:
+            # (pyarrow's ParquetWriter raises on a schema change too; never cast silently)
+            raise ValueError(
+                f"to_parquet: partition schema {[(c.name, str(c.values.dtype)) for c in rg.columns]} differs from "
+                f"the schema {list(zip(w.names, map(str, w.dtypes)))} of {self.names[rg.file]}")
+        # the column writes of this row group go to the pool and are NOT waited for: row groups
+        # of other files (other inodes: buffered writes to ONE file serialise on its inode lock,
+        # ~10 GB/s) and the next copies proceed meanwhile
+        futs = w.write_row_group([(c.values, c.valid) for c in rg.columns], rg.rows, wait=False, ready=ready,
+                                 stats=rg.stats)
+        self.inflight.append((futs, rg))
+        while len(self.inflight) > self.max_inflight:
+            for f in self.inflight.popleft()[0]:
+                f.result()
+        LAST_TIMING["write_s"] += time.perf_counter() - t1
+        self.rows[rg.file] = self.rows.get(rg.file, 0) + rg.rows
+
+    def close(self):
+        t_cl = time.perf_counter()
+        for w in self.writers.values():
+            w.close()
+        LAST_TIMING["close_s"] = time.perf_counter() - t_cl
+
+    def abort(self):
+        """No fds leaked, no truncated footer-less part files left behind."""
+        for futs, _ in self.inflight:
+            for f in futs:
+                try:
+                    f.result()
+                except Exception:
+                    pass
+        for w in self.writers.values():
+            w.abort()
+
+
+def _timed_input(parts):
+    """The partitions; the time spent waiting for each (the upstream transform) goes to input_s."""
+    parts = iter(parts)
+    while True:
+        t_in = time.perf_counter()
+        part = next(parts, None)
+        LAST_TIMING["input_s"] += time.perf_counter() - t_in
+        if part is None:
+            return
+        yield part
+
+
+def _row_ranges(i, n, k, row_group, touched):
+    """(file index, first row, row behind the last) of the row groups that partition i of n rows is
+    cut into.  A piece without rows is still a row group if its file has none yet (``touched``)."""
+    pieces = [(i, 0, n)] if k is None else [(j, (n * j) // k, (n * (j + 1)) // k) for j in range(k)]
+    for j, a, b in pieces:
+        if b <= a and j in touched:
+            continue
+        touched.add(j)
+        for s0 in (range(a, b, row_group) if b > a else [a]):
+            yield j, s0, min(b, s0 + row_group)
+
+
+def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads):
+    """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
+    with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
+    ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
+    -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
+    LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
+                       levels_s=0.0)
+    t_all = time.perf_counter()
+    copy_s = None
+    touched = set()
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        files = _PartFiles(output_path, fname, pool, max_inflight)
+        try:
+            for i, part in enumerate(_timed_input(parts)):
+                n = len(part)
+                if shuffle is not None and n > 1:
+                    part = part.take_rows(device_permutation(n, part))
+                cols, groups = _prepare(part, n, dtypes)
+                on_gpu = any(c.data.is_cuda for c in cols)
+                if on_gpu and copy_s is None:
+                    copy_s = torch.cuda.Stream()
+                if on_gpu:
+                    copy_s.wait_stream(torch.cuda.current_stream())
+                for j, s0, s1 in _row_ranges(i, n, k, row_group, touched):
+                    files.flush(_stage_row_group(j, cols, groups, s0, s1, copy_s if on_gpu else None, statistics))
+            files.close()
+        except BaseException:
+            files.abort()
+            raise
+    LAST_TIMING["total_s"] = time.perf_counter() - t_all
+    return files.names, files.rows, sorted(files.writers)

@@ -272,6 +272,24 @@ def test_to_parquet_list_columns_end_to_end(tmp_path, monkeypatch, rows, k, shuf
     _assert_same(_columns(back, by="id"), exp)
 
 
+@pytest.mark.parametrize("change", ["dtype", "list_column_gone"])
+def test_schema_change_between_partitions_leaves_no_file(tmp_path, change):
+    """Two partitions of 100 rows go to part_0; the second does not have the file's schema (int32 for
+    int64, or a list column missing): its flush raises and the footer-less file is removed."""
+    import nvtabular_amd as nvt
+    from nvtabular_amd.device import DeviceColumn, DeviceFrame
+
+    t = lambda v: torch.from_numpy(v).to(dev())
+    first = {"a": DeviceColumn(t(np.arange(100, dtype=np.int64)))}
+    second = {"a": DeviceColumn(t(np.arange(100, dtype=np.int32 if change == "dtype" else np.int64)))}
+    if change == "list_column_gone":
+        first["l"] = DeviceColumn(t(np.arange(200, dtype=np.int64)), None, t(_offsets([2] * 100)))
+    out = str(tmp_path / "out")
+    with pytest.raises(ValueError, match="differs from the schema"):
+        nvt.Dataset([DeviceFrame(first), DeviceFrame(second)]).to_parquet(out, out_files_per_proc=1)
+    assert not [f for f in os.listdir(out) if f.endswith(".parquet")]
+
+
 def test_statistics_of_list_columns(tmp_path):
     """min / max over the non-null leaves, null_count = slots - non-null leaves."""
     import nvtabular_amd as nvt

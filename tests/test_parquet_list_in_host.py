@@ -78,6 +78,8 @@ def test_nested_files_left_to_pyarrow(tmp_path, kind):
     pf = PP.PlainParquetFile(path)
     assert not pf.readable and pf.why_not
     assert not pf.eligible and pf.why
+    # the first reason found stays: the column and what it is, or the codec of the first chunk
+    assert ("codec 2" if kind == "gzip" else "'c'") in pf.why_not, pf.why_not
 
 
 def test_flat_files_keep_both_verdicts(tmp_path):
