@@ -307,7 +307,9 @@ uint64_t *nvt_gb_state_ptr(nvt_gb_table *t);
 int nvt_gb_update_ws_bytes(uint64_t n, uint64_t *bytes);
 int nvt_gb_set_workspace(nvt_gb_table *t, void *ws, uint64_t bytes);
 int nvt_gb_clear(nvt_gb_table *t, void *stream);
-/* keys[k]: int64 device column, key_valid[k]: bitmap or NULL; vals[j]: column of vdtype[j] */
+/* keys[k]: int64 device column, key_valid[k]: bitmap or NULL; vals[j]: column of vdtype[j].
+ * Values of every dtype are reduced as float64 (here and in nvt_seg_aggregate), so int64 values
+ * are exact up to +-2^53 and round beyond. */
 int nvt_gb_update(nvt_gb_table *t, const int64_t *const *keys, const uint8_t *const *key_valid,
                   const void *const *vals, const int *vdtypes, const uint8_t *const *val_valid,
                   uint64_t n, void *stream);
@@ -321,7 +323,11 @@ int nvt_gb_merge(nvt_gb_table *t, const int64_t *const *keys, const uint8_t *key
 int nvt_gb_state(nvt_gb_table *t, uint64_t *host_state, void *stream);
 /* compact groups: out_keys[k][g], out_null_mask[g] (bit k = component k is null),
  * out_size/out_count[g], out_sum/sumsq/min/max[j][g]; any out pointer may be NULL.
- * *out_n (device) = number of groups */
+ * *out_n (device) = number of groups.
+ * min / max of a group without a non-null value are NaN.  The table keeps no per-column value
+ * count: "no value seen" is the initial +inf in min (-inf in max) itself, so a group whose
+ * non-null values are ALL +inf reports min NaN, and one whose values are all -inf max NaN
+ * (nvt_seg_aggregate returns a count per column and leaves that decision to its caller). */
 int nvt_gb_compact(nvt_gb_table *t, int64_t *const *out_keys, uint8_t *out_null_mask,
                    int64_t *out_size, int64_t *out_count, double *const *out_sum,
                    double *const *out_sumsq, double *const *out_min, double *const *out_max,
@@ -334,7 +340,12 @@ int nvt_gb_lookup(nvt_gb_table *t, const int64_t *const *keys, const uint8_t *co
                   uint64_t n, int64_t *out_group, void *stream);
 /* ---- Groupby operator (groupby.py:236-263): row order by (group, sort columns) + aggregates.
  * nvt_sort_key_u64: order-preserving 64-bit image of a column (nulls / NaN last in either
- * direction, pandas na_position="last").  nvt_order_rows: stable refinement of a row order by
+ * direction, pandas na_position="last"; -0.0 and +0.0 share one image).  The largest image
+ * is reserved for nulls, so the value that would map to it takes the image next to it: the two
+ * values at that end of the order -- INT64_MAX and INT64_MAX - 1 ascending, INT64_MIN and
+ * INT64_MIN + 1 descending -- tie and keep their row order.  Only int64 columns reach it:
+ * int32 / uint8 are widened first, and the float images of that end are NaN bit patterns
+ * (-inf and -DBL_MAX order exactly).  nvt_order_rows: stable refinement of a row order by
  * such a key (two 32-bit radix passes) or by group id (-1 = null key, sorted last); perm
  * entries are 64-bit words whose LOW 32 bits are the row index (after a gid refinement the high
  * half is the group id: exactly the `words` nvt_seg_aggregate takes).  nvt_seg_aggregate:

@@ -540,6 +540,9 @@ __device__ __forceinline__ uint64_t sortable_bits<uint8_t>(uint8_t v) {
 }
 template <>
 __device__ __forceinline__ uint64_t sortable_bits<double>(double v) {
+  // -0.0 == +0.0 for every comparison sort (numpy, pandas): ONE image, so that a stable sort
+  // keeps the two in row order (float32 columns come through here too)
+  if (v == 0.0) v = 0.0;
   const uint64_t b = (uint64_t)__double_as_longlong(v);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
@@ -1234,8 +1237,8 @@ int nvt_order_rows_ws_bytes(uint64_t n, uint64_t *bytes) {
 // perm_in / perm_out: uint64 row indices (may alias).  ws: nvt_order_rows_ws_bytes(n).
 int nvt_order_rows(const uint64_t *key64, const int64_t *gid, uint64_t ngroups,
                    const uint64_t *perm_in, uint64_t n, uint64_t *perm_out, void *ws, void *stream) {
+  if (n == 0) return NVT_OK;  // (first: the columns of an empty frame have no address)
   NVT_CHECK_ARG((key64 != nullptr) != (gid != nullptr), "exactly one of key64 / gid");
-  if (n == 0) return NVT_OK;
   NVT_CHECK_ARG(perm_out && ws, "null pointer");
   NVT_CHECK_ARG(n < (1ull << 30) && ngroups < (1ull << 31), "at most 2^30-1 rows");
   hipStream_t s = (hipStream_t)stream;
