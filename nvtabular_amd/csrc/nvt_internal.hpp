@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nvt_hip.h"
+
 namespace nvt {
 
 // nvt_util.hip: per-device pools of internal streams that batched calls fork onto from / join
@@ -36,6 +38,34 @@ int sort_words_bits(uint64_t *data, uint64_t n, int bit_lo, int bit_hi, void *tm
 // [rb, 64) without writing the unsorted words out first; *result = a buffer inside tmp
 int sort_packed_keys(const void *keys, int key_dtype, int64_t key_bias, const uint8_t *fold, int rb,
                      uint64_t n, void *tmp, uint64_t **result, hipStream_t stream);
+
+// nvt_hot_sample.hip: the sample in front of the hot filter (paths 1 / 2 / 3 | NVT_PATH_HOT) and of
+// the range path; one launch, one workgroup per column, ncols <= kHotBatch
+struct HotSampleCol {
+  const int32_t *keys;
+  const uint8_t *valid;
+  uint64_t n;
+  int32_t *image;
+  int nb_log2;  // > 0: also derive the key ranges of the range path (image[NVT_RANGE_AUX_*])
+  int pieces;   // range path: also decide on the piecewise map (NVT_PATH_PIECES: after an overflow)
+};
+constexpr int kHotBatch = 32;
+struct HotSampleBatch {
+  HotSampleCol c[kHotBatch];
+};
+int hot_sample_launch(const HotSampleBatch &batch, int ncols, hipStream_t s);
+
+// nvt_count_lds.hip: paths 0 / 6 / 7 of nvt_dense_count_* (`kind`) for a column the driver
+// (nvt_dense_count.hip) has checked, n > 0; K = int32_t or int64_t as c.key_bytes says
+uint64_t lds_count_ws_bytes(int kind, int key_bytes, bool weighted);
+template <typename K>
+int lds_count(const nvt_count_col &c, int kind, hipStream_t s);
+
+// nvt_count_part.hip: paths 1 / 2 / 3, with the hot filter in front when `hot` (c.hot_image = the
+// column's sampled image, or nullptr: sampled here into the workspace)
+uint64_t part_count_ws_bytes(int kind, bool hot, int key_bytes, bool weighted, uint64_t n);
+template <typename K>
+int part_count(const nvt_count_col &c, int kind, bool hot, hipStream_t s);
 
 // nvt_range_count.hip: path NVT_PATH_RANGE of nvt_dense_count_* (aux = hot image + range
 // parameters written by hot_sample_kernel + class histogram)

@@ -1,6 +1,6 @@
 // Categorify.fit groupby-size, path 9 ("range path"): int32 keys, unweighted, ~11 k .. ~6.5 M
 // distinct keys.  Replaces categorify.py:955-1051 (_top_level_groupby, size only) like the
-// hash-partitioned paths 1-3 of nvt_dense_count.hip, with two differences that matter:
+// hash-partitioned paths 1-3 of nvt_count_part.hip, with two differences that matter:
 //
 //   * ONE pass over the column instead of histogram + scan + 1-2 scatter passes: every
 //     workgroup keeps a small write-combining bin per bucket in LDS and flushes whole 64-byte
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(kRpBS) void rp_partition_kernel(
 }
 
 // totals per hot slot = column sums of the per-workgroup counters (64 slots per workgroup x 16
-// row groups, every load of a thread in flight; cf. hot_reduce_kernel of nvt_dense_count.hip)
+// row groups, every load of a thread in flight; cf. hot_reduce_kernel of nvt_count_part.hip)
 constexpr int kTotGroups = 16;
 __global__ __launch_bounds__(64 * kTotGroups) void hot_totals_kernel(
     const unsigned *__restrict__ hot_cnt, int nblocks, unsigned *__restrict__ hot_tot) {

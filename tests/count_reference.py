@@ -1,7 +1,7 @@
 """Plain numpy references of Categorify's counting step (groupby-size of a key column, the
 weighted merge of partial lists, and what the one-pass vocabulary ordering reads from a count
-list), for the kernel-level tests of csrc/nvt_dense_count.hip, nvt_range_count.hip,
-nvt_sort_count.hip and nvt_count.hip (test_gpu_count_kernels.py).  test_count_reference.py pins
+list), for the kernel-level tests of csrc/nvt_count_lds.hip, nvt_count_part.hip, nvt_hot_sample.hip,
+nvt_range_count.hip, nvt_sort_count.hip and nvt_count.hip (test_gpu_count_kernels.py).  test_count_reference.py pins
 them to the pandas oracle on the CPU.  Nothing here shares code with the device side: the counts
 are ``np.unique`` + ``np.add.at`` on uint64, checked against 2^63 so that the reference itself
 cannot wrap.

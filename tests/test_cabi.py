@@ -204,6 +204,97 @@ def test_count_entry_points_refuse_bad_arguments_before_any_launch():
         assert lib.nvt_dense_count_ws_bytes(4, 1000, path, 0, C.byref(nbytes)) == 0 and nbytes.value > 0
 
 
+_WS_N = (0, 1, 8191, 8192, 8193, 65536, 1 << 20, 2**32 - 1)
+# (key_bytes, path, weighted) -> nvt_dense_count_ws_bytes for every n of _WS_N, as returned by the
+# library before the counting driver was split into units (profiles/dense_count_split_notes.md).
+# path: 0x10 = NVT_PATH_HOT, 0x609 / 0xa09 = range path with 64 / 1024 buckets, 0x10000 =
+# NVT_PATH_PIECES, 0xa = sort path
+_WS_BYTES = {
+    (4, 0x0, 0): (38011968, 38011968, 38011968, 38011968, 38011968, 38011968, 38011968, 38011968),
+    (4, 0x0, 1): (19137600, 19137600, 19137600, 19137600, 19137600, 19137600, 19137600, 19137600),
+    (8, 0x0, 0): (25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056),
+    (8, 0x0, 1): (25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056),
+    (4, 0x6, 0): (38011968, 38011968, 38011968, 38011968, 38011968, 38011968, 38011968, 38011968),
+    (4, 0x6, 1): (19137600, 19137600, 19137600, 19137600, 19137600, 19137600, 19137600, 19137600),
+    (8, 0x6, 0): (25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056),
+    (8, 0x6, 1): (25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056, 25429056),
+    (4, 0x7, 0): (76023872, 76023872, 76023872, 76023872, 76023872, 76023872, 76023872, 76023872),
+    (4, 0x7, 1): (38275136, 38275136, 38275136, 38275136, 38275136, 38275136, 38275136, 38275136),
+    (8, 0x7, 0): (50858048, 50858048, 50858048, 50858048, 50858048, 50858048, 50858048, 50858048),
+    (8, 0x7, 1): (50858048, 50858048, 50858048, 50858048, 50858048, 50858048, 50858048, 50858048),
+    (4, 0x1, 0): (34704640, 34705728, 34869504, 34869504, 34870592, 36760928, 67605760, 89491541200),
+    (4, 0x1, 1): (34557184, 34558304, 34853120, 34853120, 34854240, 37293408, 78337280, 156701068496),
+    (8, 0x1, 0): (34606336, 34607424, 34869504, 34869504, 34870592, 37203296, 76158208, 140024515792),
+    (8, 0x1, 1): (34606336, 34607456, 35000576, 35000576, 35001696, 38251872, 92935424, 208743992528),
+    (4, 0x2, 0): (34483456, 34484544, 34648320, 34648320, 34649408, 35876144, 56766592, 91306134736),
+    (4, 0x2, 1): (34557184, 34558304, 34853120, 34853120, 34854240, 37072176, 74797184, 164857449680),
+    (8, 0x2, 0): (34508032, 34509120, 34771200, 34771200, 34772288, 36711728, 69767296, 144456355024),
+    (8, 0x2, 1): (34606336, 34607456, 35000576, 35000576, 35001696, 37956912, 88215680, 219618282704),
+    (4, 0x3, 0): (34557184, 34558272, 34722048, 34722048, 34723136, 36023600, 58019968, 96137972944),
+    (4, 0x3, 1): (34557184, 34558304, 34853120, 34853120, 34854240, 37072176, 74797184, 164857449680),
+    (8, 0x3, 0): (34606336, 34607424, 34869504, 34869504, 34870592, 36908336, 71438464, 150898805968),
+    (8, 0x3, 1): (34606336, 34607456, 35000576, 35000576, 35001696, 37956912, 88215680, 219618282704),
+    (4, 0x11, 0): (43126016, 43128128, 43291904, 43291904, 43294016, 45190496, 76158208, 90036833488),
+    (4, 0x12, 0): (42904832, 42906944, 43070720, 43070720, 43072832, 44305712, 65319040, 91851427024),
+    (4, 0x13, 0): (42978560, 42980672, 43144448, 43144448, 43146560, 44453168, 66572416, 96683265232),
+    (4, 0x609, 0): (12681856, 12681856, 12681856, 12681856, 12681856, 13730432, 21070464, 34372420224),
+    (4, 0xa09, 0): (76587136, 76587136, 76587136, 76587136, 76587136, 76587136, 93364352, 34436325504),
+    (4, 0x10609, 0): (12681856, 12681856, 12681856, 12681856, 12681856, 13730432, 21070464, 34372420224),
+    (4, 0x10a09, 0): (76587136, 76587136, 76587136, 76587136, 76587136, 76587136, 93364352, 34436325504),
+    (4, 0xa, 0): (1053504, 1058368, 1155904, 1155904, 1160768, 1872704, 14161728, 53692339008),
+}
+
+
+@pytest.mark.parametrize("key_bytes, path, weighted", sorted(_WS_BYTES))
+def test_count_workspace_sizes_are_unchanged(key_bytes, path, weighted):
+    """The workspace of every counting path, byte for byte what the unsplit driver asked for."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    nbytes = C.c_uint64()
+    for n, want in zip(_WS_N, _WS_BYTES[key_bytes, path, weighted]):
+        assert lib.nvt_dense_count_ws_bytes(key_bytes, n, path, weighted, C.byref(nbytes)) == 0
+        assert nbytes.value == want, (n, nbytes.value, want)
+
+
+def test_count_workspace_refuses_the_paths_the_launch_refuses():
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    nbytes = C.c_uint64()
+    for path in (4, 5, 4 | 16, 5 | 16):
+        for key_bytes in (4, 8):
+            assert lib.nvt_dense_count_ws_bytes(key_bytes, 1000, path, 0, C.byref(nbytes)) == _lib.NVT_EINVAL
+            assert b"path must be" in lib.nvt_last_error()
+
+
+@pytest.mark.parametrize("bad", [dict(key_bytes=3), dict(path=12)])
+def test_count_many_checks_every_column_before_the_first_launch(bad):
+    """A valid column in front of a bad one: NVT_EINVAL naming column 1.  The buffers are host memory
+    and there is no device, so a call that had started on column 0 would return a HIP error."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    raw = (C.c_uint8 * 8192)()
+    base = (C.addressof(raw) + 63) & ~63
+    keys, outk, outc, state, ws = (base + 512 * i for i in range(5))
+    d = (_lib.CountCol * 2)()
+    for i in range(2):
+        d[i].keys, d[i].n, d[i].key_bytes, d[i].path, d[i].ws = keys, 8, 4, 0, ws
+        d[i].out_keys, d[i].out_counts, d[i].out_capacity, d[i].state = outk, outc, 9, state + 128 * i
+    for name, v in bad.items():
+        setattr(d[1], name, v)
+    assert lib.nvt_dense_count_many(d, 2, None) == _lib.NVT_EINVAL, lib.nvt_last_error()
+    msg = lib.nvt_last_error()
+    assert b"column 1" in msg and (b"key_bytes" if "key_bytes" in bad else b"path must be") in msg, msg
+
+
 @pytest.mark.parametrize("n, n_big", [(1, 0), (1, 1), (4096, 0), (4097, 2), (4097, 4097), (1 << 20, 16385),
                                       ((1 << 30) - 1, 0)])
 def test_vocab_order_workspace_layout(n, n_big):

@@ -4,16 +4,19 @@
 numpy references of count_reference.py (which test_count_reference.py pins to the pandas oracle on
 the CPU).  Nothing is approximate here: every comparison is exact.
 
-Path id -> kernels (csrc/nvt_dense_count.hip unless named otherwise):
+Path id -> kernels (csrc/; nvt_dense_count.hip is the driver that decodes the path and checks the
+arguments):
 
-    6 / 0 / 7   LDS-resident: lds_stage_kernel<K, u32 | u64, 16384 | 8192> (one / one / two key
-                classes per row slab; 6 replicates hot keys per 8-lane group) + range_merge_kernel
-    1 / 2 / 3   partitioned: part_hist_kernel -> scan -> part_scatter_kernel<LEVEL 1 (, 2)> ->
-                part_count_kernel -> part_offsets / part_copy / part_merge_kernel
+    6 / 0 / 7   LDS-resident, nvt_count_lds.hip: lds_stage_kernel<K, u32 | u64, 16384 | 8192> (one /
+                one / two key classes per row slab; 6 replicates hot keys per 8-lane group) +
+                range_merge_kernel
+    1 / 2 / 3   partitioned, nvt_count_part.hip: part_hist_kernel -> scan -> part_scatter_kernel<LEVEL
+                1 (, 2)> -> part_count_kernel -> part_offsets / part_copy / part_merge_kernel
                 (256 / 64 x 64 / 64 x 256 buckets)
-    1|16 ..     the same behind the hot-key filter (int32 keys, no weights): hot_sample_kernel,
-                part_hist_hot_kernel (cold bitmap) ... hot_reduce_kernel
-    9           range path, nvt_range_count.hip: hot_sample_kernel (range map), rp_partition_kernel,
+    1|16 ..     the same behind the hot-key filter (int32 keys, no weights): hot_sample_kernel
+                (nvt_hot_sample.hip), part_hist_hot_kernel (cold bitmap) ... hot_reduce_kernel
+    9           range path, nvt_range_count.hip: hot_sample_kernel (range map, nvt_hot_sample.hip),
+                rp_partition_kernel,
                 hot_totals_kernel, rp_count_kernel; key-ordered list, class histogram, dumped table
     10          sort path, nvt_sort_count.hip: sc_pack, s32_hist / s32_base / s32_scatter (radix
                 passes), sc_rle_kernel, sc_counts_kernel; key-ordered list, class histogram
@@ -39,6 +42,9 @@ Weighted: rows i0 = slab * 1024 + thread, stride 256 * 1024 = 262 144, four in f
 8 / 7 + 1)), and the hot sample reads 64 blocks of 1024 rows, the whole column up to 65 536 rows;
 part_hist_hot_kernel walks the tiles with kHotBlocks = 256 workgroups, each with hot counters of its
 own that hot_reduce_kernel adds up: 257 * 8192 + 5 rows give every workgroup a tile and one two.
+The per-tile histogram (256 counters per tile on path 1) is scanned by one scan_small_kernel launch
+up to kScanSmallMax = 131 072 counters and by scan_chunk_kernel + scan_totals_kernel beyond: 513 *
+8192 + 3 rows are 514 tiles.
 Range path: one round of a partition workgroup is kRpBS * NVT_RANGE_U = 2048 vectors = 8192 rows,
 256 workgroups: 2 097 152 rows are one full round each; 2 * 2 097 152 + 5003 three rounds with a
 ragged end.  Sort path: tiles of kS32Tile = 8192 words (radix passes) and kScTile = 4096 (run
@@ -378,6 +384,17 @@ def test_partitioned_paths_split_a_bucket_inflated_by_one_key(K, path, dtype, we
     assert np.unique(keys[valid]).size >= 50_000
     w = weights_for(keys, rng) if weighted else None
     part(K, path, hot, keys, valid, w, f"{path} {dtype} skewed bucket", hint=70_000)
+
+
+def test_partitioned_path_scans_a_tile_histogram_of_more_than_one_block(K):
+    """Path 1 keeps 256 counters per scatter tile.  Beyond kScanSmallMax = 131 072 counters (512
+    tiles) their exclusive scan is scan_chunk_kernel + scan_totals_kernel with the last step left to
+    the level-1 scatter, below it one scan_small_kernel launch: 514 tiles, the last one of 3 rows."""
+    n = 513 * 8192 + 3
+    rng = np.random.default_rng(seed_of("scan", n))
+    keys = column("scrambled", n, 20_000, "int32", rng)
+    valid = rng.random(n) >= 0.1
+    part(K, 1, False, poison(keys, valid, "int32", rng), valid, None, "1 int32 chunked scan")
 
 
 @pytest.mark.parametrize("bits", [8, 9, 10])
