@@ -30,6 +30,7 @@
  *   nvtabular/ops/normalize.py:150-186     NormalizeMinMax      -> nvt_minmax, nvt_fill_normalize
  *   nvtabular/ops/join_groupby.py:175-217  JoinGroupby.transform-> nvt_gb_lookup + nvt_gather_f64
  *   nvtabular/ops/target_encoding.py:301-384 _op_group_logic    -> nvt_gb_lookup + nvt_te_apply
+ *   nvtabular/ops/groupby.py:236-263       Groupby.transform    -> nvt_order_rows + nvt_seg_aggregate, nvt_seg_nunique
  *   nvtabular/ops/data_stats.py:52-92      DataStats.fit        -> nvt_col_profile_many (+ nvt_dense_count_many)
  *   nvtabular/ops/reduce_dtype_size.py:40-56 ReduceDtypeSize    -> nvt_col_profile_many, nvt_cast_many
  *   cpp/nvtabular/inference/categorify.cc:145-252, fill.cc:91-102 (serving-time
@@ -362,6 +363,26 @@ int nvt_seg_aggregate(const uint64_t *words, uint64_t n, uint64_t ngroups, const
                       const int *vdtypes, const uint8_t *const *val_valid, int nvals,
                       uint64_t *out_size, uint64_t *out_count, double *out_sum, double *out_sumsq,
                       double *out_min, double *out_max, void *stream);
+/* Groupby nunique (groupby.py:190-198): out[c][g] = number of distinct values of column c among
+ * the rows of group g, pandas groupby(...).nunique() with dropna=True.  `words`: the n words
+ * nvt_seg_aggregate takes (group << 32 | row, ordered by group, rows of a group in any order;
+ * words of a group >= ngroups -- the rows of null keys -- are ignored).  vals[c]: device column
+ * of vdtypes[c] (NVT_F32 / F64 / I32 / I64 / U8), indexed by row; val_valid: NULL, or per column
+ * a bitmap or NULL.  An entry counts when it is valid and not NaN; two entries are one value when
+ * == says so on the column's own type: -0.0 and +0.0 are one value, +-inf are ordinary values,
+ * and every int64 value is its own (INT64_MAX and INT64_MAX - 1 included: the image the rows
+ * are ordered by is injective, unlike nvt_sort_key_u64's, because nulls leave through the group
+ * id and need no image).  out: uint64[ncols][ngroups], zeroed by the caller; a group without a
+ * counting entry keeps 0.  ncols 0..8.  n == 0 or ngroups == 0 returns NVT_OK without a launch;
+ * otherwise null pointers, ncols outside 0..8 and an unknown dtype are NVT_EINVAL before any
+ * launch.  ws: nvt_seg_nunique_ws_bytes(n) bytes.  Per column: the rows are refined by value
+ * inside their groups (stable radix sorts of 32-bit key chunks, then of the group id) and the
+ * value changes are summed per group by a wave-level segmented reduction -- the cost of a sort,
+ * whatever the group sizes; work on `stream` only, no read-back. */
+int nvt_seg_nunique_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_seg_nunique(const uint64_t *words, uint64_t n, uint64_t ngroups, const void *const *vals,
+                    const int *vdtypes, const uint8_t *const *val_valid, int ncols, uint64_t *out,
+                    void *ws, void *stream);
 /* out[i] = group[i] >= 0 ? src[group[i]] : miss   (stat columns joined back onto rows) */
 int nvt_gather_f64(const double *src, const int64_t *group, uint64_t n, double miss, void *out,
                    int out_dtype, void *stream);

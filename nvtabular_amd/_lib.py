@@ -94,6 +94,8 @@ SIGNATURES = {
     "nvt_order_rows": [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp],
     "nvt_seg_aggregate": [_vp, _u64, _u64, _pp, C.POINTER(C.c_int), _pp, _i32, _vp, _vp, _vp, _vp,
                           _vp, _vp, _vp],
+    "nvt_seg_nunique_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_seg_nunique": [_vp, _u64, _u64, _pp, C.POINTER(C.c_int), _pp, _i32, _vp, _vp, _vp],
     "nvt_gather_f64": [_vp, _vp, _u64, _dbl, _vp, _i32, _vp],
     "nvt_te_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _i32, _vp],
     "nvt_te_apply_folds": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _i32, _vp],

@@ -1981,7 +1981,7 @@ EAGER_IMAGES = os.environ.get("NVT_EAGER_IMAGES", "1") != "0"
 
 # ---- the rest of the driver lives beside this file; the facade re-exports it ---------------------
 from .kernels_groupby import (  # noqa: E402,F401
-    GroupbyTable, sorted_groupby_eligible, sorted_groupby, flat_index_for, te_apply_folds, _order_ws, order_rows, seg_aggregate, gather, te_apply,
+    GroupbyTable, sorted_groupby_eligible, sorted_groupby, flat_index_for, te_apply_folds, _order_ws, order_rows, seg_aggregate, seg_nunique, gather, te_apply,
 )
 from .kernels_lookup import (  # noqa: E402,F401
     FlatIndex, _value_bits, LookupConsumer, image_pack, JG_KINDS, jg_image, jg_image_part, te_image_part, te_image,

@@ -403,6 +403,46 @@ def seg_aggregate(words: torch.Tensor, ngroups: int, vals, val_valid, sumsq=Fals
     return size, count, sm, sq, mn, mx
 
 
+SEG_NUNIQUE_MAX_COLS = 8   # include/nvt_hip.h nvt_seg_nunique
+
+
+def seg_nunique(words: torch.Tensor, ngroups: int, vals, val_valid) -> torch.Tensor:
+    """int64[V, G]: distinct non-null values per group and column (pandas nunique, dropna=True)
+    over rows ordered by group (``words`` from order_rows with gid).  nvt_seg_nunique, at most 8
+    columns per call; bool columns go as their uint8 view, int8 / int16 as int32 and float16 as
+    float32 (exact widenings: the distinct values stay distinct).  No read-back."""
+    lib = _lib.load()
+    dev = words.device
+    nv, n = len(vals), int(words.numel())
+    out = torch.zeros(nv, ngroups, dtype=torch.int64, device=dev)
+    if nv == 0 or n == 0 or ngroups == 0:
+        return out
+
+    def kernel_view(v):
+        if v.dtype == torch.bool:
+            v = v.view(torch.uint8)
+        elif v.dtype in (torch.int8, torch.int16):
+            v = v.to(torch.int32)
+        elif v.dtype in (torch.float16, torch.bfloat16):
+            v = v.to(torch.float32)
+        return K.aligned(v)
+
+    vals = [kernel_view(v) for v in vals]
+    need = C.c_uint64()
+    check(lib.nvt_seg_nunique_ws_bytes(n, C.byref(need)), "nvt_seg_nunique_ws_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    for lo in range(0, nv, SEG_NUNIQUE_MAX_COLS):
+        chunk = vals[lo:lo + SEG_NUNIQUE_MAX_COLS]
+        vd = (C.c_int * len(chunk))(*[K.dtype_code(v.dtype) for v in chunk])
+        check(lib.nvt_seg_nunique(words.data_ptr(), n, int(ngroups),
+                                  _lib.ptr_array([v.data_ptr() for v in chunk]), vd,
+                                  _lib.ptr_array([K.ptr(v) for v in val_valid[lo:lo + len(chunk)]]),
+                                  len(chunk), out[lo:].data_ptr(), ws.data_ptr(), K.stream_ptr()),
+              "nvt_seg_nunique")
+        K.stat_add("seg_nunique_calls")
+    return out
+
+
 def gather(src: torch.Tensor, group: torch.Tensor, miss: float, out_dtype: torch.dtype):
     _lib.require_gpu()
     src = src.to(torch.float64).contiguous()

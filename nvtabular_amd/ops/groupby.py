@@ -1,6 +1,6 @@
 """Groupby (reference: nvtabular/ops/groupby.py:27-330): collapse the rows of each key group
 into one row -- list / first / last aggregations in ``sort_cols`` order plus the conventional
-count / sum / mean / min / max / std / var.
+count / nunique / sum / mean / min / max / std / var.
 
 Row -> group assignment runs on the multi-key hash tables of the JoinGroupby path
 (``nvt_gb_update`` / ``nvt_gb_index_build`` / ``nvt_gb_lookup``); ordering the rows inside the
@@ -23,7 +23,8 @@ from .base import Operator
 
 _FLOAT32_AGGS = ("mean", "median", "std", "var", "sum")
 _INT32_AGGS = ("count", "nunique")
-_SUPPORTED = ("list", "first", "last", "count", "sum", "mean", "min", "max", "std", "var")
+_SUPPORTED = ("list", "first", "last", "count", "nunique", "sum", "mean", "min", "max", "std", "var")
+_ROW_AGGS = ("count", "nunique")   # count rows or their values: nothing is computed on the numbers
 
 
 def is_list_agg(agg, custom=False):
@@ -92,11 +93,11 @@ class Groupby(Operator):
         return self.groupby_cols
 
     def datetime_rejects(self, col_selector, frame):
-        # key, sort and list / first / last / count columns move rows or count them; the other
-        # aggregates are reduced in float64 (nvt_seg_aggregate) and would round nanoseconds
+        # key, sort and list / first / last / count / nunique columns move rows or count them; the
+        # other aggregates are reduced in float64 (nvt_seg_aggregate) and would round nanoseconds
         _, conv = self._agg_dicts(col_selector)
         return [c for c, aggs in conv.items()
-                if c in frame and frame[c].logical is not None and any(a != "count" for a in aggs)]
+                if c in frame and frame[c].logical is not None and any(a not in _ROW_AGGS for a in aggs)]
 
     def _find_agg(self, col_schema, input_schema):
         mapping = self.column_mapping(ColumnSelector(input_schema.column_names))
@@ -153,7 +154,9 @@ class Groupby(Operator):
             k, v = key_view(frame[c].materialize())
             keys.append(k)
             valids.append(v)
-        gid = index.lookup(keys, valids)  # row -> rank of its group, -1 for a null key
+        # row -> rank of its group, -1 for a null key (the columns of an empty partition, such as
+        # shuffle_by_keys leaves when it has more partitions than keys, have no address)
+        gid = index.lookup(keys, valids) if n else torch.empty(0, dtype=torch.int64, device=dev)
         # 2. row order: sort_cols (stable, nulls last), then stable by group -- the stable radix
         #    sort of nvt_sort.hip over (key32 << 32 | row) words (nvt_order_rows); rows of null
         #    keys sort behind the last group and are cut off
@@ -168,10 +171,18 @@ class Groupby(Operator):
             if col.is_list:
                 raise NotImplementedError("Groupby over list columns")
         want = {a for c in conv for a in conv[c]}
+        # (int8 / int16 columns are reduced as int32: the kernels take no narrower integers)
+        red = {c: col.data.to(torch.int32) if col.data.dtype in (torch.int8, torch.int16) else col.data
+               for c, col in cols.items()}
         # 3. every conventional aggregate from ONE segmented reduction over the ordered rows
         size, count, sm, sq, mn, mx = K.seg_aggregate(
-            words, ngroups, [cols[c].data for c in conts], [cols[c].valid for c in conts],
+            words, ngroups, [red[c] for c in conts], [cols[c].valid for c in conts],
             sumsq=bool(want & {"std", "var"}), minmax=bool(want & {"min", "max"}))
+        #    and the distinct values per group of the columns that ask for them: rows refined by
+        #    value inside the groups, value changes counted (nvt_seg_nunique; strings by surrogate)
+        uniq_cols = [c for c in conts if "nunique" in conv.get(c, [])]
+        nuniq = K.seg_nunique(words, ngroups, [red[c] for c in uniq_cols],
+                              [cols[c].valid for c in uniq_cols]) if uniq_cols else None
         offsets = torch.zeros(ngroups + 1, dtype=torch.int64, device=dev)
         torch.cumsum(size, 0, out=offsets[1:])
         n_valid = int(offsets[-1].item())
@@ -201,6 +212,10 @@ class Groupby(Operator):
                     vb = None if bool(sel_ok.all()) else pack_bitmap_device(sel_ok)
                     out[name] = col.like(vals[pos].contiguous(), vb)
             for a in conv.get(c, []):
+                if a == "nunique":  # a group of nulls is 0, as in pandas: no bitmap
+                    out[self.name_sep.join([c, a])] = DeviceColumn(
+                        nuniq[uniq_cols.index(c)].to(torch.int32))
+                    continue
                 out[self.name_sep.join([c, a])] = _finish_agg(
                     a, col.data.dtype, count[ci].to(torch.float64), sm[ci],
                     sq[ci] if sq is not None else None, mn[ci] if mn is not None else None,
