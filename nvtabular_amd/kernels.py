@@ -3,14 +3,19 @@
 torch is used here only as the device allocator / stream provider ("plumbing");
 every O(rows) computation below is a hand-written gfx950 kernel reached through
 ``libnvt_hip.so``.  Nothing in this module has a CPU code path.
+
+This file is the facade of the host driver: the subjects with a module of their own
+(``kernels_count.py``: Categorify's counting driver and its path policy; ``kernels_groupby.py``,
+``kernels_lookup.py``, ``kernels_exchange.py``) are re-exported at the bottom, and the switches
+that tests, bench.py or a tool assign live here -- those modules read them as ``K.<NAME>`` when
+they are called.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import threading
-import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional
 
 import torch
 
@@ -276,9 +281,6 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-MIN_COUNT_CAPACITY = 1 << 16
-
-
 def next_pow2(x: int) -> int:
     return 1 << max(6, (int(x) - 1).bit_length())
 
@@ -292,673 +294,23 @@ def _key_suffix(keys: torch.Tensor) -> str:
 
 
 # --------------------------------------------------------------------------
-# Categorify.fit: count tables
+# Categorify.fit counting (kernels_count.py): what tests, bench.py and tools set on the facade
 # --------------------------------------------------------------------------
-class CountTable:
-    """Open-addressing (key -> count) table in HBM for one column (group)."""
-
-    def __init__(self, key_dtype: torch.dtype, capacity: int, device=None):
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.key_dtype = key_dtype
-        self.key_bytes = 4 if key_dtype == torch.int32 else 8
-        self.suffix = "i32" if self.key_bytes == 4 else "i64"
-        self.capacity = next_pow2(capacity)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        nbytes = C.c_uint64()
-        check(self.lib.nvt_count_table_bytes(self.key_bytes, self.capacity, C.byref(nbytes)))
-        self.table = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        self.state = torch.zeros(_lib.STATE_WORDS, dtype=torch.int64, device=self.device)
-        self.clear()
-
-    def clear(self):
-        with _timed("count_clear", 0):
-            check(
-                self.lib.nvt_count_clear(
-                    self.table.data_ptr(), self.key_bytes, self.capacity, self.state.data_ptr(),
-                    stream_ptr(),
-                ),
-                "nvt_count_clear",
-            )
-
-    def update(self, keys: torch.Tensor, valid: Optional[torch.Tensor]):
-        assert keys.dtype == self.key_dtype
-        keys = aligned(keys)
-        fn = getattr(self.lib, f"nvt_count_{self.suffix}")
-        with _timed(f"count_{self.suffix}", keys.numel() * self.key_bytes):
-            check(
-                fn(keys.data_ptr(), ptr(valid), keys.numel(), self.table.data_ptr(),
-                   self.capacity, self.state.data_ptr(), stream_ptr()),
-                f"nvt_count_{self.suffix}",
-            )
-
-    def merge(self, keys: torch.Tensor, counts: torch.Tensor):
-        assert keys.dtype == self.key_dtype and counts.dtype == torch.int64
-        fn = getattr(self.lib, f"nvt_count_merge_{self.suffix}")
-        check(
-            fn(keys.contiguous().data_ptr(), counts.contiguous().data_ptr(), keys.numel(),
-               self.table.data_ptr(), self.capacity, self.state.data_ptr(), stream_ptr()),
-            f"nvt_count_merge_{self.suffix}",
-        )
-
-    def read_state(self) -> List[int]:
-        return self.state.cpu().tolist()  # synchronises the stream
-
-    def compact(self, occupied: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Dense (keys, counts[int64]) in arbitrary order, sentinel-key rows included."""
-        st = self.read_state()
-        occ = st[_lib.ST_OCCUPIED] if occupied is None else occupied
-        out_k = torch.empty(occ + 1, dtype=self.key_dtype, device=self.device)
-        out_c = torch.empty(occ + 1, dtype=torch.int64, device=self.device)
-        out_n = torch.zeros(1, dtype=torch.int64, device=self.device)
-        fn = getattr(self.lib, f"nvt_count_compact_{self.suffix}")
-        with _timed("count_compact", 0):
-            check(
-                fn(self.table.data_ptr(), self.capacity, out_k.data_ptr(), out_c.data_ptr(),
-                   out_n.data_ptr(), stream_ptr()),
-                f"nvt_count_compact_{self.suffix}",
-            )
-        n = occ
-        if st[_lib.ST_SENTINEL] > 0:
-            # rows whose key equals the empty-slot sentinel are counted on the side
-            out_k[n] = INT32_MIN if self.key_bytes == 4 else INT64_MIN
-            out_c[n] = st[_lib.ST_SENTINEL]
-            n += 1
-        return out_k[:n], out_c[:n]
-
-
-def count_into_new_table(
-    keys_list: Sequence[torch.Tensor],
-    valid_list: Sequence[Optional[torch.Tensor]],
-    hint: int,
-    max_tries: int = 8,
-) -> Tuple[CountTable, List[int]]:
-    """Groupby-size of one partition's column(s) into a fresh table sized from
-    ``hint`` (expected distinct keys); regrows and recounts on overflow, which
-    is safe because the table only holds this partition."""
-    total = sum(int(k.numel()) for k in keys_list)
-    # never below 2^16 slots: a tiny table puts every block's end-of-kernel flush on the
-    # same few memory channels (measured: 36 keys in a 128-slot table cost 340 us of
-    # serialised atomics; spread over 512 KiB they cost ~10 us)
-    cap = next_pow2(max(MIN_COUNT_CAPACITY, 2 * min(max(hint, 32), max(total, 32))))
-    for _ in range(max_tries):
-        tab = CountTable(keys_list[0].dtype, cap)
-        for k, v in zip(keys_list, valid_list):
-            tab.update(k, v)
-        st = tab.read_state()
-        if not st[_lib.ST_OVERFLOW] and st[_lib.ST_OCCUPIED] * 10 <= tab.capacity * 7:
-            return tab, st
-        cap = next_pow2(max(16 * cap, 3 * st[_lib.ST_OCCUPIED]))
-    raise _lib.NvtHipError("count table kept overflowing; cardinality estimate diverged")
-
-
-# --------------------------------------------------------------------------
-# Categorify.fit, atomic-free: dense (key, count) lists
-# --------------------------------------------------------------------------
-PATH_S_MAX_DISTINCT = int(os.environ.get("NVT_S_MAX", 11000))          # path 0 (int32 keys, unweighted): 16384-slot LDS tables
-PATH_S_MAX_WEIGHTED = 5000          # path 0 for weighted merges / int64 keys: 8192 slots
-# Path 7 = path 0 with 2 key classes per row slab (column read twice): 350 us against 420 us on
-# path 1 for 12-21 k distinct keys.
-# escalation order when a path's LDS tables overflow (C-ABI path ids, include/nvt_hip.h)
-PATH_ORDER = [6, 0, 7, 1, 2, 3]
-_S_CLASSES = {6: 1, 0: 1, 7: 2}
-PATH_S2_FACTOR = 1.95               # path 7: path 0 with 2 key classes per row slab (column read twice)
 PATH_TINY_MAX = 64                  # path 6: path 0 with hot keys replicated per lane group
-PATH_P1_MAX_DISTINCT = int(os.environ.get("NVT_P1_MAX", 2_400_000))    # path 1: ONE level, 256 buckets x 16384-slot tables (int32)
-PATH_P1_MAX_SMALL = 1_100_000       #         ... 8192-slot tables (int64 keys / weighted merges)
-PATH_P2_MAX_DISTINCT = 9_000_000    # path 2: 64 x 64 buckets, 4096-slot tables
-PATH_P2_MAX_WEIGHTED = 18_000_000   #         weighted: 8192-slot tables
-# path 3: 64 x 256 = 16384 buckets, 8192-slot tables that may fill to 6144: at 60 M distinct keys a
-# bucket holds 3662 +- 60 of them (Poisson), 40 % headroom -- Criteo-1TB's largest columns
-# (C1 / C10 / C20 / C22: 38.5-40.0 M uniques, dask-nvtabular-criteo-benchmark.py:360-366) stay on
-# the atomic-free path whether they arrive as one partition or as a merge of partial lists
-PATH_P3_MAX_DISTINCT = 60_000_000
-
-# path 9 (range path, include/nvt_hip.h NVT_PATH_RANGE): int32 keys without weights; ONE partition
-# pass by key range + per-bucket tables emitted in key order.  Buckets are sized for <= ~5000
-# distinct keys (16384-slot tables addressed by a monotone function of the key want a low load).
-PATH_RANGE = 9
-PATH_PIECES = 0x10000   # include/nvt_hip.h NVT_PATH_PIECES
-USE_PIECES = os.environ.get("NVT_RANGE_PIECES", "1") != "0"
-RANGE_AUX_WORDS, RANGE_AUX_HIST = 13600 + 256, 8208   # include/nvt_hip.h NVT_RANGE_AUX_*
-RANGE_AUX_PW, RANGE_PIECES = 13600, 64   # include/nvt_hip.h NVT_RANGE_AUX_PW, nvt_range.hpp kRpPieces
-# distinct keys per bucket the bucket count (256 / 512 / 1024) is chosen for.  Round 6: 10000 (load
-# 0.61 of the 16384-slot tables) instead of 5000: fewer bins in the partition pass and range tables
-# of half the size -- count 3.90 -> 3.66 ms, ordering 0.87 -> 0.76 ms on cfg2.  A bucket holds at
-# most 12288 keys (NVT_OVF_FULL); a column whose keys are not spread evenly enough for that is
-# relaunched with all 1024 buckets and REMEMBERED (info["range_bits_floor"] -> Categorify).
-RANGE_KEYS_PER_BUCKET = int(os.environ.get("NVT_RANGE_KEYS_PER_BUCKET", "10000"))
+# most distinct keys the range path (path 9) is started on; beyond: the sort path
 PATH_RANGE_MAX_DISTINCT = int(os.environ.get("NVT_RANGE_MAX", 6_500_000))
-USE_RANGE = os.environ.get("NVT_RANGE", "1") != "0"
-
-# path 10 (sort path, NVT_PATH_SORT): int32 keys without weights beyond the range path -- radix sort
-# of the rows + run lengths, key-sorted output (Criteo-1TB's 38-40 M-unique columns)
-PATH_SORT = 10
-USE_SORT = os.environ.get("NVT_SORT_PATH", "1") != "0"
+RANGE_PIECES = 64   # nvt_range.hpp kRpPieces: pieces of the piecewise range map (range_splitters)
 USE_FLAT_TABLE = os.environ.get("NVT_FLAT_TABLE", "1") != "0"
-
-_ws_cache = {}
 _check_streams = {}   # device index -> side stream of the read-backs that must not wait for work queued later
-_RT_BYTES = {}   # range_bits -> nvt_range_table_bytes
-_WS_BYTES = {}   # (key_bytes, n, path, weighted) -> nvt_dense_count_ws_bytes
-
-
 # Columns of one nvt_dense_count_many call that are given different workspaces run on different
 # internal streams (include/nvt_hip.h); COUNT_STREAMS workspaces are kept per device.
 COUNT_STREAMS = max(1, min(3, int(os.environ.get("NVT_COUNT_STREAMS", "3"))))
 # columns that need no hot-key sample start the counting streams (they run under the sample launch)
 HEAD_START = os.environ.get("NVT_COUNT_HEAD_START", "1") != "0"
-PATH_HOT, HOT_IMAGE_WORDS = 16, 8192   # include/nvt_hip.h NVT_PATH_HOT, NVT_HOT_IMAGE_WORDS
-HOT_FILTER = os.environ.get("NVT_HOT_FILTER", "1") != "0"
-_PATH_COST = {6: 0.5, 0: 0.7, 7: 1.7, 9: 2.0, 1: 2.5, 2: 3.2, 3: 3.5, 10: 6.0}
-
-
-def _workspace(nbytes: int, device, slot: int = 0) -> torch.Tensor:
-    key = (device.type, device.index, slot)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = None
-        _ws_cache.pop(key, None)
-        buf = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-    return buf
-
-
-def _path_for(hint: int, small_tables: bool = False, allow_range: bool = True) -> int:
-    s_max = PATH_S_MAX_WEIGHTED if small_tables else PATH_S_MAX_DISTINCT
-    if 0 < hint <= PATH_TINY_MAX:
-        return 6
-    if hint <= s_max:
-        return 0
-    if hint <= PATH_S2_FACTOR * s_max and (small_tables or not HOT_FILTER):
-        return 7  # (with the hot-key filter path 1 is faster there: 241 against 307 us)
-    if USE_RANGE and HOT_FILTER and allow_range and not small_tables and hint <= PATH_RANGE_MAX_DISTINCT:
-        return PATH_RANGE
-    if USE_SORT and not small_tables and hint > PATH_RANGE_MAX_DISTINCT:
-        return PATH_SORT
-    if USE_SORT and USE_RANGE and HOT_FILTER and not small_tables and not allow_range:
-        # a column the range path gave up on (keys that cluster in their range): the sort path
-        # keeps its per-partition lists KEY-ORDERED, which is what the partition merge and the
-        # one-pass vocabulary ordering live on; the hash paths would hand back unordered lists
-        return PATH_SORT
-    if hint <= (PATH_P1_MAX_SMALL if small_tables else PATH_P1_MAX_DISTINCT):
-        return 1
-    if hint <= PATH_P2_MAX_DISTINCT:
-        return 2
-    if hint <= PATH_P3_MAX_DISTINCT:
-        return 3
-    return -1  # global-table fallback
-
-
-class DenseCountJob:
-    """One column's groupby-size, launched asynchronously; ``dense_count_many`` reads all
-    jobs' state words back with a single device->host copy."""
-
-    def __init__(self, keys, valid, weights=None, hint: int = 0, allow_range: bool = True,
-                 pieces=None, min_range_bits: int = 8):
-        _lib.require_gpu()
-        self.want_table = True    # range path: also dump the count tables as the encode table
-        self.range_table = None
-        self.allow_range = allow_range  # False: the range path overflowed on this column before
-        self.range_failed = False
-        self.range_fail_bits = 0
-        # range path with a piecewise map (NVT_PATH_PIECES): `pieces` = int32[65] splitters
-        # (range_splitters) of a column whose keys are not spread over their range
-        self.pieces = pieces if USE_PIECES else None
-        # (a column that overflowed its buckets in an earlier fit starts with the bucket count
-        # that held it: the caller remembers info["range_bits_floor"])
-        self.min_range_bits = max(8, min(10, int(min_range_bits)))
-        self.lib = _lib.load()
-        self.keys = aligned(keys)
-        self.valid = valid
-        self.weights = weights.contiguous() if weights is not None else None
-        self.n = int(self.keys.numel())
-        self.dev = self.keys.device
-        self.suffix = _key_suffix(self.keys)
-        self.kb = 4 if self.suffix == "i32" else 8
-        self.hint = hint
-        self.path = _path_for(hint, small_tables=(weights is not None or self.kb == 8),
-                              allow_range=allow_range)
-        self.cap_guess = max(1 << 16, 2 * max(hint, 1))
-        self.state = None  # device uint64[STATE_WORDS] view, assigned by dense_count_many
-        self.result = None
-        self.hot = None    # None: HOT_FILTER decides; True / False: forced (tests, probes)
-
-    def range_bits(self) -> int:
-        """log2 of the bucket count of the range path: 256 .. 1024 buckets."""
-        want = max(1, -(-max(self.hint, 1) // RANGE_KEYS_PER_BUCKET))
-        return max(self.min_range_bits, min(10, max(8, (want - 1).bit_length())))
-
-    def _launch_path_of(self, path: int) -> int:
-        if path == PATH_RANGE:
-            return PATH_RANGE | (self.range_bits() << 8) | (PATH_PIECES if self.pieces is not None else 0)
-        eligible = path in (1, 2, 3) and self.kb == 4 and self.weights is None
-        hot = HOT_FILTER if self.hot is None else self.hot
-        return path | PATH_HOT if (eligible and hot) else path
-
-    def _launch_path(self) -> int:
-        """The `path` argument of the C call: partitioned paths of int32 keys without weights
-        get the hot-key filter in front (include/nvt_hip.h, NVT_PATH_HOT)."""
-        return self._launch_path_of(self.path)
-
-    def prepare(self, desc: "_lib.CountCol") -> int:
-        """Allocate this attempt's output list and fill one nvt_count_col descriptor; returns
-        the workspace bytes the path needs (the caller shares ONE workspace per call)."""
-        n, path = self.n, self.path
-        out_cap = min(self.cap_guess, n) + 1
-        if path in _S_CLASSES:
-            # stage 2 has 256 workgroups per key class, each emitting <= 384 keys
-            out_cap = min(out_cap, _S_CLASSES[path] * 256 * 384 + 1)
-        self.out_k = torch.empty(out_cap + 1, dtype=self.keys.dtype, device=self.dev)
-        self.out_c = torch.empty(out_cap + 1, dtype=torch.int64, device=self.dev)
-        lpath = self._launch_path()
-        key = (self.kb, n, lpath, self.weights is not None)
-        nbytes = _WS_BYTES.get(key)
-        if nbytes is None:
-            out = C.c_uint64()
-            check(self.lib.nvt_dense_count_ws_bytes(self.kb, n, lpath,
-                                                    0 if self.weights is None else 1, C.byref(out)))
-            nbytes = _WS_BYTES[key] = out.value
-        desc.keys = self.keys.data_ptr()
-        desc.valid = ptr(self.valid)
-        desc.weights = ptr(self.weights)
-        desc.n = n
-        desc.key_bytes = self.kb
-        desc.path = lpath
-        desc.out_keys = self.out_k.data_ptr()
-        desc.out_counts = self.out_c.data_ptr()
-        desc.out_capacity = out_cap
-        desc.state = self.state.data_ptr()
-        desc.hot_image = None
-        desc.range_table = None
-        if path == PATH_SORT:
-            # uint32[256] block that receives the histogram of min(count, 255)
-            self.hot_image = torch.empty(256, dtype=torch.int32, device=self.dev)
-            desc.hot_image = self.hot_image.data_ptr()
-        elif path == PATH_RANGE:
-            # aux block: hot image + range parameters (sample kernel) + class histogram
-            self.hot_image = torch.empty(RANGE_AUX_WORDS, dtype=torch.int32, device=self.dev)
-            if self.pieces is not None:
-                self.hot_image[RANGE_AUX_PW:RANGE_AUX_PW + RANGE_PIECES + 1] = self.pieces
-            desc.hot_image = self.hot_image.data_ptr()
-            if self.want_table:
-                # the per-bucket count tables, dumped: the column's encode table (range table)
-                bits = self.range_bits()
-                rt_bytes = _RT_BYTES.get(bits)
-                if rt_bytes is None:
-                    rt_out = C.c_uint64()
-                    check(self.lib.nvt_range_table_bytes(bits, C.byref(rt_out)))
-                    rt_bytes = _RT_BYTES[bits] = rt_out.value
-                self.range_table = torch.empty(rt_bytes, dtype=torch.uint8, device=self.dev)
-                self.table_bits = bits
-                desc.range_table = self.range_table.data_ptr()
-        elif lpath & PATH_HOT:
-            # the column's own hot-key table image: sampled for all columns by one launch
-            self.hot_image = torch.empty(HOT_IMAGE_WORDS, dtype=torch.int32, device=self.dev)
-            desc.hot_image = self.hot_image.data_ptr()
-        return nbytes
-
-    def resolve(self, st) -> bool:
-        """Inspect the state words read back for this job; False = relaunch needed."""
-        ovf = st[_lib.ST_OVERFLOW]
-        if ovf & 1:
-            order = PATH_ORDER
-            if self.path == PATH_SORT:  # (no LDS tables to overflow)
-                raise _lib.NvtHipError("dense count: the sort path reported a table overflow")
-            if self.path == PATH_RANGE and self.range_bits() < 10:
-                # more distinct keys than the hint promised (cold start): all 1024 buckets first
-                self.min_range_bits = 10
-                self.cap_guess = max(self.cap_guess, 1 << 22)
-                return False
-            # (the range path assumes keys spread over their range; a hash path does not)
-            nxt = order.index(1) if self.path == PATH_RANGE else order.index(self.path) + 1
-            if self.path == PATH_RANGE and not self.range_failed:
-                self.range_fail_bits = int(ovf)  # NVT_OVF_*: region / probe / full (diagnostic)
-            self.range_failed = self.range_failed or self.path == PATH_RANGE
-            if (self.path == 0 and USE_RANGE and HOT_FILTER and self.allow_range and self.kb == 4
-                    and self.weights is None and not self.range_failed):
-                # LDS tables too small: the range path comes next for int32 keys
-                self.path = PATH_RANGE
-                self.cap_guess = max(self.cap_guess, 1 << 20)
-                return False
-            if nxt >= len(order):
-                self._fallback()
-                return True
-            self.path = order[nxt]
-            if self.path == 7 and self._launch_path_of(1) & PATH_HOT:
-                self.path = 1  # the filtered path 1 beats two key classes (see _path_for)
-            if self.path == 1 and self.range_failed and USE_SORT and self.kb == 4 and self.weights is None:
-                # the range path gave up at 1024 buckets: more keys than it holds, or keys that
-                # are not spread over their range -- the sort path copes with both in one go
-                # (the next fit picks its path from the distinct count found here)
-                self.path = PATH_SORT
-            elif self.path == 1 and self.hint > PATH_P1_MAX_DISTINCT:
-                self.path = 2 if self.hint <= PATH_P2_MAX_DISTINCT else 3
-            self.cap_guess = max(self.cap_guess, _PATH_MAX[self.path])
-            return False
-        if ovf & 2:
-            if self.cap_guess > self.n:
-                raise _lib.NvtHipError("dense count: output list overflowed at full capacity")
-            need = st[_lib.ST_NEED] if self.path in (PATH_RANGE, PATH_SORT) else 0
-            # (the range path reports the exact size; the hash paths only that it was too small)
-            self.cap_guess = need + 64 if need > self.cap_guess else max(4 * self.cap_guess, 1 << 20)
-            return False
-        m = st[_lib.ST_OCCUPIED]
-        max_count = st[_lib.ST_MAXCOUNT]
-        if self.path == PATH_SORT:
-            self.result = (self.out_k[:m], self.out_c[:m], st[_lib.ST_NULLS],
-                           dict(path=self.path, distinct=m, max_count=max_count,
-                                rows=st[_lib.ST_ROWS], sorted_by_key=True, cls_hist=self.hot_image,
-                                n_big=st[_lib.ST_BIG], range_failed=self.range_failed,
-                                range_fail_bits=self.range_fail_bits,
-                                range_pieces=self.pieces is not None))
-            return True
-        if self.path == PATH_RANGE:
-            # key-ordered list (the sentinel key, smallest int32, already leads it) + what the
-            # one-pass vocabulary ordering needs: histogram of min(count, 255), entries >= 255
-            self.result = (self.out_k[:m], self.out_c[:m], st[_lib.ST_NULLS],
-                           dict(path=self.path, distinct=m, max_count=max_count,
-                                rows=st[_lib.ST_ROWS], sorted_by_key=True,
-                                cls_hist=self.hot_image[RANGE_AUX_HIST:RANGE_AUX_HIST + 256],
-                                n_big=st[_lib.ST_BIG], range_aux=self.hot_image,
-                                range_table=self.range_table,
-                                range_bits=self.table_bits if self.range_table is not None else 0,
-                                range_pieces=self.pieces is not None,
-                                range_fail_bits=self.range_fail_bits,
-                                range_bits_floor=self.min_range_bits))
-            return True
-        if st[_lib.ST_SENTINEL] > 0:
-            self.out_k[m] = INT32_MIN if self.kb == 4 else INT64_MIN
-            self.out_c[m] = st[_lib.ST_SENTINEL]
-            max_count = max(max_count, st[_lib.ST_SENTINEL])
-            m += 1
-        self.result = (self.out_k[:m], self.out_c[:m], st[_lib.ST_NULLS],
-                       dict(path=self.path, distinct=m, max_count=max_count, rows=st[_lib.ST_ROWS],
-                            range_failed=self.range_failed, range_fail_bits=self.range_fail_bits))
-        return True
-
-    def _fallback(self):
-        """Last resort: one global open-addressing table (device atomics)."""
-        if self.weights is None:
-            tab, st = count_into_new_table([self.keys], [self.valid], max(self.hint, 1 << 20))
-        else:
-            keys, weights, null_weight = self.keys, self.weights, 0
-            if self.valid is not None:
-                # nvt_count_merge_* takes a (key, count) list, no bitmap: the null rows leave here
-                # (torch plumbing for a rare path, as unpack_bitmap) and their weights are the nulls
-                ok = unpack_bitmap(self.valid, self.n)
-                null_weight = int(weights[~ok].sum().item())
-                keys, weights = keys[ok].contiguous(), weights[ok].contiguous()
-            # int32 tables keep uint32 counts (include/nvt_hip.h): weighted sums may pass 2^32, so
-            # int32 keys go through an int64 table, where the smallest int32 is a key like any other
-            tab = CountTable(torch.int64, 2 * max(int(keys.numel()), 1))   # (rows left after the nulls)
-            if keys.numel():
-                tab.merge(keys.to(torch.int64), weights)
-            st = tab.read_state()
-            st[_lib.ST_NULLS] += null_weight
-        k, c = tab.compact()
-        k = k.to(self.keys.dtype)   # (the int64 table of int32 keys: every key came from an int32, exact)
-        mx = int(c.max().item()) if c.numel() else 0
-        self.result = (k, c, st[_lib.ST_NULLS],
-                       dict(path=-1, distinct=int(k.numel()), max_count=mx, rows=self.n))
-
-
-SAMPLE_ROWS = 1 << 18               # cold start: distinct keys of this many leading rows ...
-SAMPLE_MIN_ROWS = 8 * SAMPLE_ROWS   # ... when the column is at least this long
-# distinct keys each path is sized for (output-capacity guess when a path is entered by escalation)
-_PATH_MAX = {6: 1024, 0: 98304, 7: 196608, 9: PATH_RANGE_MAX_DISTINCT, 10: 1 << 30, 1: PATH_P1_MAX_DISTINCT,
-             2: PATH_P2_MAX_DISTINCT, 3: PATH_P3_MAX_DISTINCT}
-
-
-def _estimate_distinct(d: int, m: int, n: int) -> int:
-    """Distinct keys expected in n rows given d distinct among the first m (uniform-draw
-    model d = D (1 - exp(-m / D)), tripled for the heavy tails of real categorical data).
-    Only steers the first path choice: an underestimate costs one cheap failed attempt."""
-    if m <= 0 or d <= 0:
-        return 1
-    r = d / m
-    if r < 0.02:
-        D = float(d)
-    elif r > 0.999:
-        D = float(n)
-    else:
-        lo, hi = 1e-6, 60.0  # x = m / D, (1 - exp(-x)) / x decreases from 1 to 0
-        for _ in range(60):
-            mid = 0.5 * (lo + hi)
-            if (1.0 - math.exp(-mid)) / mid > r:
-                lo = mid
-            else:
-                hi = mid
-        D = m / (0.5 * (lo + hi))
-    return int(min(n, 3.0 * D + 64))
-
-
 STATS = {"count_relaunches": 0, "presampled_columns": 0}  # diagnostics (bench.py cold step)
 PRESAMPLE_SKETCH = os.environ.get("NVT_PRESAMPLE_EXACT", "0") != "1"
 
 
-def _presample(jobs):
-    """Jobs with no cardinality hint (first partition of a fit) start on a path chosen from
-    the distinct count of a 256 K-row prefix instead of climbing PATH_ORDER from the bottom:
-    the cold fit of the 45 M-row Criteo frame drops from 74 ms to under 30 ms."""
-    cand = [j for j in jobs if j.result is None and j.hint <= 0 and j.weights is None
-            and j.n >= SAMPLE_MIN_ROWS]
-    if not cand:
-        return
-    if PRESAMPLE_SKETCH:
-        # ONE launch: a HyperLogLog sketch of every column's prefix (nvt_prefix_distinct); the exact
-        # count below went through ~11 launches per column for numbers that are tripled anyway
-        descs = (_lib.PrefixCol * len(cand))()
-        for d, j in zip(descs, cand):
-            d.keys, d.valid = j.keys.data_ptr(), ptr(j.valid)
-            d.n, d.key_bytes = min(SAMPLE_ROWS, j.n), j.kb
-        out = torch.empty((len(cand), 2), dtype=torch.int64, device=cand[0].dev)
-        check(cand[0].lib.nvt_prefix_distinct(descs, len(cand), out.data_ptr(), stream_ptr()),
-              "nvt_prefix_distinct")
-        res = [(None, None, 0, dict(distinct=int(d), rows=int(r))) for d, r in read_back(out).tolist()]
-    else:
-        samples = []
-        for j in cand:
-            valid = None if j.valid is None else j.valid[: SAMPLE_ROWS // 8]
-            sj = DenseCountJob(j.keys[:SAMPLE_ROWS], valid, None, hint=SAMPLE_ROWS)
-            sj.path, sj.cap_guess = 1, SAMPLE_ROWS
-            samples.append(sj)
-        res = _run_jobs(samples)
-    for j, (_, _, nulls, info) in zip(cand, res):
-        est = _estimate_distinct(info["distinct"], info["rows"] - nulls, j.n)
-        j.hint = est
-        stat_add("presampled_columns")
-        # an estimate, not a hint: the range path starts with all its buckets (a column with more
-        # keys than estimated would overflow 256 / 512 buckets and be counted twice) -- unless the
-        # prefix shows every key >= 10 times on average: the estimate (3 x the uniform model) then
-        # sizes the buckets.  (Heavy tails defeat any extrapolation from 0.6 % of the rows: a
-        # Criteo column with 6.2 M keys shows 98 k in the prefix and is estimated at 322 k, Chao1
-        # says 550 k; such columns show most prefix keys once or twice and keep 1024 buckets.)
-        seen_rows = max(int(info["rows"]) - int(nulls), 1)
-        j.min_range_bits = max(j.min_range_bits, 10 if int(info["distinct"]) * 10 >= seen_rows else 8)
-        j.path = _path_for(est, small_tables=(j.kb == 8), allow_range=j.allow_range)
-        # ... and a roomy output list (a sixth of the rows): a relaunch costs a full recount
-        j.cap_guess = max(1 << 16, 2 * est, j.n // 6 if j.path not in _S_CLASSES else 0)
-
-
-class CountBatch:
-    """Every column's groupby-size of one partition, enqueued by ONE C call
-    (nvt_dense_count_many); ``results()`` performs the single device->host read of all the
-    state words and relaunches the (rare, once hints are learned) columns whose LDS tables or
-    output lists overflowed.  Launch and read-back are separate so that the caller can queue
-    other work (Normalize's moments, the next partition's copies) before synchronising."""
-
-    def __init__(self, jobs):
-        self.jobs = list(jobs)
-        self._results = None
-        _presample(self.jobs)
-        for j in self.jobs:
-            if j.n == 0:
-                j.result = (torch.empty(0, dtype=j.keys.dtype, device=j.dev),
-                            torch.empty(0, dtype=torch.int64, device=j.dev), 0,
-                            dict(path=0, distinct=0, max_count=0, rows=0))
-        for j in self.jobs:
-            if j.result is None and j.path < 0:
-                j._fallback()
-        self.pending = [j for j in self.jobs if j.result is None]
-        self.states = None
-        self._launch()
-
-    def _launch(self):
-        pending = self.pending
-        if not pending:
-            return
-        if COUNT_STREAMS > 1 and len(pending) >= 2 and HEAD_START:
-            # The C call launches the columns in the order of the descriptors, each on the stream of
-            # its workspace, and a stream waits for the hot-key samples in front of its first
-            # FILTERED column.  In column order every stream began with a range-path column: 243
-            # CUs idled for the ~110 us of the sample launch.  COUNT_STREAMS columns that need no
-            # sample (LDS-resident: paths 0 / 6 / 7) go first -- they land on different streams
-            # (longest-processing-time assignment below: equal loads at that point) and run
-            # under the sample.
-            free = [j for j in pending if j.path in _S_CLASSES][:COUNT_STREAMS]
-            if free and len(free) < len(pending):
-                ids = {id(j) for j in free}
-                pending = self.pending = free + [j for j in pending if id(j) not in ids]
-        dev = pending[0].dev
-        self.states = torch.empty(len(pending), _lib.STATE_WORDS, dtype=torch.int64, device=dev)
-        descs = (_lib.CountCol * len(pending))()
-        need = 0
-        for i, j in enumerate(pending):
-            j.state = self.states[i]
-            need = max(need, j.prepare(descs[i]))
-        if COUNT_STREAMS == 1 or len(pending) < 2:
-            wp = _workspace(need, dev).data_ptr()  # shared: the columns are ordered on one stream
-            for d in descs:
-                d.ws = wp
-        else:
-            # longest-processing-time assignment of the columns to COUNT_STREAMS workspaces
-            load = [0.0] * COUNT_STREAMS
-            wps = [_workspace(need, dev, k).data_ptr() for k in range(COUNT_STREAMS)]
-            order = sorted(range(len(pending)),
-                           key=lambda i: -_PATH_COST.get(pending[i].path, 1.0) * pending[i].n)
-            head = 0
-            if HEAD_START:   # (the head-start columns: one per stream, whatever their cost)
-                while head < min(COUNT_STREAMS, len(pending)) and pending[head].path in _S_CLASSES \
-                        and pending[-1].path not in _S_CLASSES:
-                    head += 1
-                if head < COUNT_STREAMS:
-                    head = 0
-            for i in range(head):
-                load[i] += _PATH_COST.get(pending[i].path, 1.0) * pending[i].n
-                descs[i].ws = wps[i]
-            for i in order:
-                if i < head:
-                    continue
-                k = load.index(min(load))
-                load[k] += _PATH_COST.get(pending[i].path, 1.0) * pending[i].n
-                descs[i].ws = wps[k]
-        check(_lib.load().nvt_dense_count_many(descs, len(pending), stream_ptr()),
-              "nvt_dense_count_many")
-        # what results() waits for: THIS call's kernels, not whatever is queued behind them (the
-        # next partition's counting is launched before this one is read back)
-        self._done = torch.cuda.Event()
-        self._done.record()
-
-    def _read_states(self):
-        dev = self.states.device
-        side = _check_streams.get(dev.index)
-        if side is None:
-            side = _check_streams[dev.index] = torch.cuda.Stream(device=dev)
-        side.wait_event(self._done)
-        with torch.cuda.stream(side):
-            return read_back(self.states).tolist()
-
-    def results(self):
-        if self._results is None:
-            while self.pending:
-                host = self._read_states()  # the single synchronisation point
-                self.pending = [j for i, j in enumerate(self.pending) if not j.resolve(host[i])]
-                stat_add("count_relaunches", len(self.pending))
-                self._launch()
-            self._results = [j.result for j in self.jobs]
-        return self._results
-
-
-def dense_count_many(jobs):
-    """Launch every job (one C call), then ONE readback for all their state words."""
-    return CountBatch(jobs).results()
-
-
-def _run_jobs(jobs):
-    batch = CountBatch.__new__(CountBatch)
-    batch.jobs = list(jobs)
-    batch._results = None
-    for j in batch.jobs:
-        if j.n == 0:
-            j.result = (torch.empty(0, dtype=j.keys.dtype, device=j.dev),
-                        torch.empty(0, dtype=torch.int64, device=j.dev), 0,
-                        dict(path=0, distinct=0, max_count=0, rows=0))
-    for j in batch.jobs:
-        if j.result is None and j.path < 0:
-            j._fallback()
-    batch.pending = [j for j in batch.jobs if j.result is None]
-    batch.states = None
-    batch._launch()
-    return batch.results()
-
-
-def dense_count(
-    keys: torch.Tensor,
-    valid: Optional[torch.Tensor],
-    weights: Optional[torch.Tensor] = None,
-    hint: int = 0,
-):
-    """Groupby-size (or weighted sum) of a key column -> (keys, counts[int64], nulls, info).
-
-    ``hint`` = expected number of distinct keys (0 = unknown).  Picks the LDS /
-    partitioned path from it and escalates when a kernel reports that its LDS
-    tables filled up; the last resort is the global-table kernel of nvt_count_*.
-    info = dict(path, distinct, max_count, rows) so callers can remember the hint."""
-    return dense_count_many([DenseCountJob(keys, valid, weights, hint)])[0]
-
-
-def merge_dense(lists, hint: int = 0):
-    """Tree-merge step (_mid_level_groupby): sum the counts of equal keys across
-    several dense (keys, counts) lists."""
-    lists = [(t[0], t[1]) + tuple(t[2:]) for t in lists if t[0].numel()]
-    if not lists:
-        return None
-    if len(lists) == 1:
-        return lists[0] if len(lists[0]) == 3 else (lists[0][0], lists[0][1], 0)
-    lists = [(t[0], t[1]) for t in lists]
-    dt = torch.int64 if any(k.dtype == torch.int64 for k, _ in lists) else torch.int32
-    keys = torch.cat([k.to(dt) for k, _ in lists])
-    counts = torch.cat([c for _, c in lists])
-    k, c, _, info = dense_count(keys, None, counts,
-                                hint=hint or max(int(x[0].numel()) for x in lists))
-    return k, c, info["max_count"]
-
-
-def merge_dense_many(groups, hints=None):
-    """merge_dense for several groups with ONE nvt_dense_count_many call (and one read-back):
-    groups[j] = the (keys, counts[, max_count]) lists of group j -> [(keys, counts, max_count)]."""
-    jobs, slots, out = [], [], [None] * len(groups)
-    for j, lists in enumerate(groups):
-        lists = [(t[0], t[1]) for t in lists if t[0].numel()]
-        if not lists:
-            continue
-        if len(lists) == 1:
-            out[j] = (lists[0][0], lists[0][1], int(groups[j][0][2]) if len(groups[j][0]) > 2 else 0)
-            continue
-        dt = torch.int64 if any(k.dtype == torch.int64 for k, _ in lists) else torch.int32
-        keys = torch.cat([k.to(dt) for k, _ in lists])
-        counts = torch.cat([c for _, c in lists])
-        hint = (hints[j] if hints else 0) or max(int(x[0].numel()) for x in lists)
-        jobs.append(DenseCountJob(keys, None, counts, hint))
-        slots.append(j)
-    if jobs:
-        for j, (k, c, _, info) in zip(slots, dense_count_many(jobs)):
-            out[j] = (k, c, info["max_count"])
-    return out
-
-
-MERGE_SORTED = os.environ.get("NVT_MERGE_SORTED", "1") != "0"
 MERGE_SORTED_MAX_TOTAL = (1 << 31) - 1   # include/nvt_hip.h nvt_merge_sorted_many: na + nb < 2^31
 
 
@@ -1988,4 +1340,12 @@ from .kernels_lookup import (  # noqa: E402,F401
 )
 from .kernels_exchange import (  # noqa: E402,F401
     ExchangeBatch, exchange_unpack, merge_counts_sorted,
+)
+from .kernels_count import (  # noqa: E402,F401
+    MIN_COUNT_CAPACITY, CountTable, count_into_new_table,
+    PATH_S_MAX_DISTINCT, PATH_S_MAX_WEIGHTED, PATH_ORDER, _S_CLASSES, PATH_S2_FACTOR, PATH_P1_MAX_DISTINCT, PATH_P1_MAX_SMALL,
+    PATH_P2_MAX_DISTINCT, PATH_P2_MAX_WEIGHTED, PATH_P3_MAX_DISTINCT, PATH_RANGE, PATH_PIECES, PATH_SORT, PATH_HOT,
+    RANGE_AUX_WORDS, RANGE_AUX_HIST, RANGE_AUX_PW, RANGE_KEYS_PER_BUCKET, HOT_IMAGE_WORDS, SAMPLE_ROWS, SAMPLE_MIN_ROWS,
+    _path_for, _path_max, CountPolicy, escalate, _launch_path_of, assign_streams, DenseCountJob, _estimate_distinct,
+    _presample, CountBatch, dense_count_many, dense_count, merge_dense, merge_dense_many, CountMemory,
 )

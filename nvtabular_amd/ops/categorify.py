@@ -48,7 +48,6 @@ def _pick(opt, name, default=None):
 
 MERGE_FAN_IN = 8
 LAZY_FINALIZE = os.environ.get("NVT_LAZY_FINALIZE", "1") != "0"
-PIPELINE_COUNTS = os.environ.get("NVT_PIPELINE_COUNTS", "1") != "0"
 # (opt-in: measured 12.44 vs 12.15 ms per Criteo step -- the ordering kernels and the LDS-resident
 # encodes slow each other down by more than the overlap buys; profiles/r04_notes.md)
 SPLIT_FINALIZE = os.environ.get("NVT_SPLIT_FINALIZE", "0") == "1"
@@ -163,7 +162,7 @@ class Categorify(StatOperator):
             )
         # device-side state: storage_name -> encoder (built at fit_end or lazily from parquet)
         self._encoders: Dict[str, object] = {}
-        self._cap_hints: Dict[str, int] = {}
+        self._memory = K.CountMemory()   # what counting learned of each column (hints, range path)
         self._pending_counts: Dict[int, tuple] = {}  # id(fit state) -> (CountBatch, owners)
         # Engine extension (not in the reference): with defer_artifacts=True the
         # unique.*/meta.*.parquet files are written by flush_artifacts() /
@@ -179,14 +178,8 @@ class Categorify(StatOperator):
             raise ValueError("tie_break must be 'value' or 'reference'")
         self.tie_break = tie_break
         self._pending: Dict[str, dict] = {}
-        self._last_paths: Dict[str, int] = {}  # counting path of each column's last partition
-        self._no_range = set()                 # columns on which the range path overflowed
-        self._range_failures = []              # (column, NVT_OVF_* bits, distinct) of each overflow
-        self._range_oks: Dict[str, int] = {}   # partitions each column counted on the range path
         self._flat_unchecked: List[str] = []   # flat range tables whose displacement is still unread
         self._no_flat = set()                  # vocabularies whose keys cluster: hashed tables
-        self._range_pieces: Dict[str, object] = {}   # column -> int32[65] splitters (NVT_PATH_PIECES)
-        self._range_bits_floor: Dict[str, int] = {}  # column -> log2 buckets that held it after an overflow
         self._lazy_finalize = None  # (groups, options, base) of a fit whose ordering is deferred
         self._writer_cache: Dict[str, bool] = {}
         self.vocabs = {}
@@ -199,6 +192,13 @@ class Categorify(StatOperator):
     # them -- a few hundred microseconds for the 26 Criteo columns -- while the moments kernel
     # that was queued behind the counting still runs, instead of after it
     fit_end_priority = -1
+
+    # the containers of the counting memory that bench.py, tests and tools read
+    _cap_hints = property(lambda self: self._memory.cap_hints)
+    _last_paths = property(lambda self: self._memory.last_paths)
+    _no_range = property(lambda self: self._memory.no_range)
+    _range_failures = property(lambda self: self._memory.range_failures)
+    _range_pieces = property(lambda self: self._memory.range_pieces)
 
     def range_name(self, kind: str) -> str:
         return "Categorify_fit" if kind == "fit" else "Categorify_transform"  # categorify.py:345,477
@@ -263,11 +263,7 @@ class Categorify(StatOperator):
             # every column's count kernels are enqueued by ONE C call (top_level_groupby,
             # categorify.py:955); the one readback of all state words happens in
             # _absorb_pending (next partition / fit_end)
-            jobs = [K.DenseCountJob(k, v, None, hint=self._cap_hints.get(hkey, 0),
-                                    allow_range=hkey not in self._no_range,
-                                    pieces=self._range_pieces.get(hkey),
-                                    min_range_bits=self._range_bits_floor.get(hkey, 8))
-                    for _, hkey, k, v in specs]
+            jobs = [K.DenseCountJob(k, v, None, **self._memory.job_args(hkey)) for _, hkey, k, v in specs]
             with K.annotate("top_level_groupby"):
                 return K.CountBatch(jobs), [(g, hkey) for g, hkey, _, _ in specs]
 
@@ -277,7 +273,7 @@ class Categorify(StatOperator):
         # next without waiting for the host to digest the results in between (0.5 ms per
         # partition on the Criteo workload).  A fresh fit reads first: it has no hints to launch on.
         ahead = None
-        if specs and PIPELINE_COUNTS and id(state) in self._pending_counts and \
+        if specs and id(state) in self._pending_counts and \
                 all(hkey in self._cap_hints for _, hkey, _, _ in specs):
             ahead = launch()
         # the previous partition's counts are read back only now: its kernels (and whatever
@@ -295,40 +291,7 @@ class Categorify(StatOperator):
         batch, owners = item
         per_group = {}
         for (g, hkey), (dk, dc, nulls, info) in zip(owners, batch.results()):
-            old_hint = self._cap_hints.get(hkey, 0)
-            self._cap_hints[hkey] = max(64, info["distinct"])
-            self._last_paths[hkey] = info["path"]
-            if (info.get("range_bits_floor", 8) > self._range_bits_floor.get(hkey, 8)
-                    and old_hint > 0 and info["distinct"] <= old_hint + old_hint // 4):
-                # the buckets a GOOD hint asked for overflowed (keys not spread evenly): the next
-                # partitions / fits of this column start with the bucket count that held it.  (A
-                # launch without a hint, or with one the column outgrew, escalates for itself only.)
-                self._range_bits_floor[hkey] = info["range_bits_floor"]
-            if info.get("range_failed"):
-                # one overflow does not condemn a column: the hot-key sample is a heuristic (a
-                # frequent key that loses the race for its image bucket floods one region of the
-                # partition pass -- about one 45 M-row partition in a hundred on the Criteo-shaped
-                # columns).  Keys that are NOT spread over their range fail every time: banned
-                # after two overflows making up more than a fifth of the attempts.
-                self._range_failures.append((hkey, info.get("range_fail_bits", 0), info["distinct"]))
-                fails = sum(1 for h, _, _ in self._range_failures if h == hkey)
-                if fails >= 2 and 4 * fails > self._range_oks.get(hkey, 0):
-                    self._no_range.add(hkey)
-            elif info["path"] == K.PATH_RANGE:
-                self._range_oks[hkey] = self._range_oks.get(hkey, 0) + 1
-            if info.get("range_failed") and info.get("sorted_by_key") and K.USE_PIECES \
-                    and dk.dtype == torch.int32:
-                # the linear range map overflowed (keys not spread over their range: dense /
-                # frequency-ordered ids) and the sort path delivered the exact key-ordered list:
-                # splitters of a piecewise map from it; the column's next partitions / fits take
-                # the range path with them, and the overflow is not held against the column
-                sp = None if info.get("range_pieces") else K.range_splitters(dk, dc)
-                if info.get("range_pieces"):
-                    self._range_pieces.pop(hkey, None)   # overflowed WITH splitters: counts as a failure
-                if sp is not None:
-                    self._range_pieces[hkey] = sp
-                    self._no_range.discard(hkey)
-                    self._range_failures = [f for f in self._range_failures if f[0] != hkey]
+            self._memory.learn(hkey, dk, dc, nulls, info)
             srt = bool(info.get("sorted_by_key")) and dk.dtype == torch.int32
             g.nulls += nulls
             g.valid_rows += info["rows"] - nulls
@@ -376,7 +339,7 @@ class Categorify(StatOperator):
             if len(lists) == 1:
                 self._adopt(g, lists[0])
                 continue
-            if (K.MERGE_SORTED and all(t[3] and t[0].dtype == torch.int32 for t in lists)
+            if (all(t[3] and t[0].dtype == torch.int32 for t in lists)
                     and sum(int(t[0].numel()) for t in lists) <= K.MERGE_SORTED_MAX_TOTAL):
                 sorted_jobs.append((g, lists))
             else:

@@ -258,9 +258,8 @@ def test_small_vocabulary_encode_at_the_table_boundaries(tmp_path, vocab, num_bu
 
 def test_multi_partition_fit_on_the_filtered_partitioned_path(tmp_path):
     """Three partitions of a 150 k-key power-law column: every partition is counted on a
-    partitioned path behind its own sampled hot set (the range path, or path 1 | NVT_PATH_HOT
-    with NVT_RANGE=0), the per-partition lists are merged by the
-    weighted count -- vocabulary and labels equal the oracle's on the whole frame."""
+    partitioned path behind its own sampled hot set (the range path), the per-partition lists
+    are merged by the weighted count -- vocabulary and labels equal the oracle's on the whole frame."""
     import nvtabular_amd as nvt
     from nvtabular_amd import kernels as K, ops
 
@@ -272,8 +271,7 @@ def test_multi_partition_fit_on_the_filtered_partitioned_path(tmp_path):
     df.loc[rng.random(n) < 0.02, "c"] = pd.NA
     parts = [df.iloc[i * 400_000:(i + 1) * 400_000].reset_index(drop=True) for i in range(3)]
     host = _host_view(df)
-    # (a partitioned path: the range path by default, the filtered hash path 1 with NVT_RANGE=0)
-    assert K._path_for(host["c"].nunique()) in (1, K.PATH_RANGE) and K.HOT_FILTER
+    assert K._path_for(host["c"].nunique()) == K.PATH_RANGE
     wf = nvt.Workflow(["c"] >> ops.Categorify(out_path=str(tmp_path / "gpu")))
     wf.fit(nvt.Dataset(parts))
     out = wf.transform(nvt.Dataset(df)).to_ddf().compute()

@@ -49,16 +49,15 @@ def test_path_selection_thresholds():
     assert K._path_for(0) == 0                      # unknown: start on the plain LDS-table path
     assert K._path_for(3) == 6 and K._path_for(64) == 6
     assert K._path_for(65) == 0 and K._path_for(K.PATH_S_MAX_DISTINCT) == 0
-    # 11-21 k int32 keys: two key classes (path 7) only without the hot-key filter
+    # 11-21 k keys: two key classes (path 7) only for int64 keys / weighted merges
     # int32 keys without weights: the range path (9) from the end of the LDS-table path up to
     # ~6.5 M distinct keys, hash partitions beyond
-    rng_on = K.USE_RANGE and K.HOT_FILTER
-    assert K._path_for(K.PATH_S_MAX_DISTINCT + 1) == (9 if rng_on else 1 if K.HOT_FILTER else 7)
-    assert K._path_for(int(K.PATH_S2_FACTOR * K.PATH_S_MAX_DISTINCT) + 1) == (9 if rng_on else 1)
-    assert K._path_for(K.PATH_P1_MAX_DISTINCT + 1) == (9 if rng_on else 2)
+    assert K._path_for(K.PATH_S_MAX_DISTINCT + 1) == 9
+    assert K._path_for(int(K.PATH_S2_FACTOR * K.PATH_S_MAX_DISTINCT) + 1) == 9
+    assert K._path_for(K.PATH_P1_MAX_DISTINCT + 1) == 9
     # beyond the range path: the sort path (int32 keys without weights), hash partitions otherwise
-    assert K._path_for(K.PATH_RANGE_MAX_DISTINCT + 1) == (K.PATH_SORT if K.USE_SORT else 2)
-    assert K._path_for(K.PATH_P2_MAX_DISTINCT + 1) == (K.PATH_SORT if K.USE_SORT else 3)
+    assert K._path_for(K.PATH_RANGE_MAX_DISTINCT + 1) == K.PATH_SORT
+    assert K._path_for(K.PATH_P2_MAX_DISTINCT + 1) == K.PATH_SORT
     assert K._path_for(K.PATH_P2_MAX_DISTINCT + 1, small_tables=True) == 3
     j = K.DenseCountJob.__new__(K.DenseCountJob)
     j.min_range_bits = 8
@@ -70,7 +69,7 @@ def test_path_selection_thresholds():
         assert j.range_bits() == bits, (hint, j.range_bits())
     # (int32 keys without weights never reach the global-table fallback: the sort path has no
     # capacity limit below 2^30 rows)
-    assert K._path_for(K.PATH_P3_MAX_DISTINCT + 1) == (K.PATH_SORT if K.USE_SORT else -1)
+    assert K._path_for(K.PATH_P3_MAX_DISTINCT + 1) == K.PATH_SORT
     assert K._path_for(K.PATH_P3_MAX_DISTINCT + 1, small_tables=True) == -1   # global-table fallback
     # int64 keys / weighted merges use the smaller tables
     assert K._path_for(K.PATH_S_MAX_WEIGHTED + 1, small_tables=True) == 7
@@ -78,7 +77,123 @@ def test_path_selection_thresholds():
     assert K._path_for(K.PATH_P1_MAX_SMALL + 1, small_tables=True) == 2
     assert K._path_for(K.PATH_P2_MAX_DISTINCT + 1, small_tables=True) == 3
     # escalation order covers every automatic path exactly once
-    assert sorted(K.PATH_ORDER) == [0, 1, 2, 3, 6, 7] and set(K._PATH_MAX) >= set(K.PATH_ORDER)
+    assert sorted(K.PATH_ORDER) == [0, 1, 2, 3, 6, 7] and set(K._path_max()) >= set(K.PATH_ORDER)
+
+
+def test_count_escalation_replays_the_recorded_grid():
+    """kernels_count.escalate + _launch_path_of against tests/golden/count_escalation_v1.json: what
+    DenseCountJob.resolve did with every overflow word before the policy became a pure function
+    (grid and origin: profiles/count_driver_notes.md).  Every row, every field."""
+    import json
+    import os
+
+    from nvtabular_amd import _lib, kernels as K
+    from nvtabular_amd.kernels_count import DONE, FALLBACK
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "count_escalation_v1.json")) as f:
+        doc = json.load(f)
+    fields = doc["fields"]
+    assert fields[:-2] == list(K.CountPolicy._fields) and fields[-2:] == ["ovf", "need"]
+    assert doc["outcome"] == ["verdict", "path", "cap_guess", "min_range_bits", "range_failed",
+                              "range_fail_bits", "launch"]
+    assert len(doc["rows"]) > 2000
+    for row in doc["rows"]:
+        args = dict(zip(fields, row))
+        ovf, need = args.pop("ovf"), args.pop("need")
+        args["pieces"] = object() if args["pieces"] else None
+        try:
+            nxt = K.escalate(K.CountPolicy(**args), ovf, need)
+        except _lib.NvtHipError as e:
+            got = ["error: " + str(e)] + [None] * 6
+        else:
+            assert nxt is not DONE, row
+            got = ["fallback"] + [None] * 6 if nxt is FALLBACK else [
+                "relaunch", nxt.path, nxt.cap_guess, nxt.min_range_bits, nxt.range_failed,
+                nxt.range_fail_bits, K._launch_path_of(nxt, nxt.path)]
+        assert got == row[len(fields):], (row, got)
+    assert K.escalate(K.CountPolicy(path=9, kb=4, weighted=False, hint=0, n=10), 0, 0) is DONE
+
+
+def test_count_stream_assignment():
+    """kernels_count.assign_streams: launch order and workspace slot per column.  The expected
+    values are what the loop inside CountBatch._launch produced for these inputs before it was
+    lifted out (profiles/count_driver_notes.md)."""
+    from nvtabular_amd import kernels as K
+
+    paths = [9, 9, 0, 6, 9, 0, 7]
+    ns = [4_000_000, 1_000_000, 3_000_000, 500_000, 2_500_000, 3_500_000, 700_000]
+    cases = [
+        (paths, ns, 1, True, [0, 1, 2, 3, 4, 5, 6], [0, 0, 0, 0, 0, 0, 0]),
+        # (the LDS-resident columns go first; an LDS-resident LAST column takes the head start away)
+        (paths, ns, 3, True, [2, 3, 5, 0, 1, 4, 6], [2, 1, 2, 0, 2, 1, 1]),
+        (paths, ns, 3, False, [0, 1, 2, 3, 4, 5, 6], [0, 2, 2, 1, 1, 2, 1]),
+        # two LDS-resident columns for three streams: they go first, without a head start
+        ([9, 0, 9, 6, 1], [900, 800, 700, 600, 500], 3, True, [1, 3, 0, 2, 4], [2, 1, 0, 1, 2]),
+        ([0, 6, 7], [100, 200, 300], 3, True, [0, 1, 2], [2, 1, 0]),          # nothing to run ahead of
+        ([9], [1000], 3, True, [0], [0]),
+        ([10, 9, 0, 6], [5000, 4000, 3000, 2000], 2, True, [2, 3, 0, 1], [0, 1, 1, 0]),
+        ([0, 0, 0, 9, 0], [500, 400, 300, 200, 100], 3, True, [0, 1, 2, 3, 4], [1, 2, 2, 0, 1]),
+        # a head start: three LDS-resident columns, one stream each whatever their cost
+        (paths + [9], ns + [2_000_000], 3, True, [2, 3, 5, 0, 1, 4, 6, 7], [0, 1, 2, 1, 2, 0, 0, 2]),
+        (paths + [9], ns + [2_000_000], 3, False, [0, 1, 2, 3, 4, 5, 6, 7], [0, 2, 1, 0, 1, 2, 1, 2]),
+    ]
+    for p, n, streams, head_start, order, slots in cases:
+        got_order, got_slots = K.assign_streams(p, n, streams, head_start)
+        assert (list(got_order), list(got_slots)) == (order, slots), (p, streams, head_start)
+        assert sorted(got_order) == list(range(len(p))) and len(got_slots) == len(p)
+        assert all(0 <= k < streams for k in got_slots)
+    order, slots = K.assign_streams(paths + [9], ns + [2_000_000], 3, True)
+    assert all(paths[i] in (0, 6, 7) for i in order[:3]) and sorted(slots[:3]) == [0, 1, 2]
+
+
+def test_count_memory_learn():
+    """kernels_count.CountMemory.learn on synthetic info dicts.  (The branch that adopts splitters
+    from a sort-path list calls range_splitters, a device function: tests/test_gpu_range_path.py
+    covers it.)"""
+    import torch
+
+    from nvtabular_amd import kernels as K
+
+    k32 = torch.empty(0, dtype=torch.int32)
+    ok = dict(path=K.PATH_RANGE, distinct=100_000, max_count=9, rows=10**6, sorted_by_key=True,
+              range_fail_bits=0, range_bits_floor=8, range_pieces=False)
+    fail = dict(path=1, distinct=100_000, max_count=9, rows=10**6, range_failed=True, range_fail_bits=33)
+    m = K.CountMemory()
+    assert m.job_args("c") == dict(hint=0, allow_range=True, pieces=None, min_range_bits=8)
+    m.learn("c", k32, None, 0, dict(path=0, distinct=7, max_count=3, rows=50))
+    assert m.cap_hints["c"] == 64 and m.last_paths["c"] == 0 and m.range_oks == {}   # max(64, distinct)
+    m.learn("c", k32, None, 0, ok)
+    assert m.cap_hints["c"] == 100_000 and m.range_oks == {"c": 1} and m.last_paths["c"] == 9
+    m.learn("c", k32, None, 0, dict(ok, path=K.PATH_SORT))       # a success counts on path 9 only
+    assert m.range_oks == {"c": 1}
+    # the bucket floor: only a good hint raises it
+    m = K.CountMemory()
+    m.learn("c", k32, None, 0, dict(ok, range_bits_floor=10))     # no hint before
+    assert m.range_bits_floor == {}
+    m.learn("c", k32, None, 0, dict(ok, distinct=125_001, range_bits_floor=10))   # outgrew 100 000 + a quarter
+    assert m.range_bits_floor == {}
+    m.learn("c", k32, None, 0, dict(ok, distinct=125_001 + 31_250, range_bits_floor=10))   # within a quarter
+    assert m.range_bits_floor == {"c": 10} and m.job_args("c")["min_range_bits"] == 10
+    # the ban: two overflows that make up more than a fifth of the attempts
+    m = K.CountMemory()
+    m.learn("c", k32, None, 0, fail)
+    assert m.range_failures == [("c", 33, 100_000)] and not m.no_range and m.job_args("c")["allow_range"]
+    m.learn("c", k32, None, 0, fail)
+    assert m.no_range == {"c"} and not m.job_args("c")["allow_range"]
+    m = K.CountMemory()
+    m.range_oks["c"] = 8
+    m.learn("c", k32, None, 0, fail)
+    m.learn("c", k32, None, 0, fail)
+    assert len(m.range_failures) == 2 and not m.no_range           # 4 * 2 fails <= 8 successes
+    m.learn("d", k32, None, 0, fail)                               # (another column's failures do not count)
+    m.range_oks["c"] = 7
+    m.learn("c", k32, None, 0, fail)
+    assert m.no_range == {"c"}
+    # an overflow WITH splitters (sort-path list back): the splitters go, the failure stays
+    m = K.CountMemory()
+    m.range_pieces["c"] = object()
+    m.learn("c", k32, None, 0, dict(fail, path=K.PATH_SORT, sorted_by_key=True, range_pieces=True))
+    assert m.range_pieces == {} and m.job_args("c")["pieces"] is None and len(m.range_failures) == 1
 
 
 def test_shuffle_option_coercion():
