@@ -746,6 +746,67 @@ int nvt_pq_decode_list_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int cod
                              uint8_t *rep_out, uint8_t *def_out, uint64_t slot_offset, uint64_t slot_cap,
                              uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch,
                              uint64_t scratch_bytes, uint64_t *counts);
+/* ---- parquet in: string columns (flat BYTE_ARRAY annotated UTF8 / STRING) ----
+ * A string column is not expanded on the host.  Per partition and column the decoder fills a STAGE:
+ *   entries  an Arrow string table in the layout nvt_str_hash takes: offsets[entries_cap + 1] (int64,
+ *            offsets[0] = 0) and chars[chars_cap] (chars_cap a multiple of 4; the bytes up to the
+ *            4-byte boundary behind the last char are zeroed).  The values of a dictionary page are
+ *            appended as they are, every value of a PLAIN data page as a fresh entry; nothing is
+ *            deduplicated.
+ *   runs     the run table: runs_cap records of 4 uint32 {start, kind | width << 8, a, b}, in value
+ *            order, `start` the position of the run's first value among the column's non-null values
+ *            of the partition.  A run ends where the next record starts; no run is empty; the record
+ *            behind the last run is the closing one {total, NVT_PQ_RUN_END, 0, 0}.
+ *              NVT_PQ_RUN_REPEAT    every value is entry a (an RLE run; bit width 0)
+ *              NVT_PQ_RUN_PACKED    value k is entry a + (the width-bit number at bit k * width,
+ *                                   LSB first, of the bytes from packed[4 * b] on); width 1 .. 32,
+ *                                   a = the chunk's first dictionary entry
+ *              NVT_PQ_RUN_SEQUENCE  value k is entry a + k (the values of PLAIN pages)
+ *            A repeat run whose index lies outside its dictionary has a = 0xFFFFFFFF.
+ *   packed   packed_cap bytes: the bytes of the bit-packed runs as the file holds them, each run's on
+ *            a 4-byte boundary and clipped to the values its page still owes, 8 zero bytes behind
+ *            the last.
+ * entries / nchars / nruns (without the closing record) / npacked / nvalues say how far the stage is
+ * filled; zero them for a new partition.
+ *
+ * nvt_pq_decode_str_chunk (HOST function, no GPU call, thread-safe; one thread per stage): appends
+ * one column chunk (pages, codecs and definition levels as nvt_pq_decode_chunk_codec; values PLAIN
+ * or dictionary indices, also mixed in one chunk) to `stage` and writes the rows' validity bits at
+ * valid_bit_offset.  scratch: the largest page uncompressed (total_uncompressed_size of the chunk
+ * suffices); may be null for codec 0.  The stage advances on NVT_OK only.  NVT_PQ_STR_GROW: a
+ * staging buffer is too small -- need[4] = {entries, chars, runs, packed} holds, for that buffer,
+ * a capacity that reaches further (0 for the others); the caller enlarges it, keeps the filled part
+ * and calls again with the same chunk.  NVT_EINVAL: a length prefix or run past its page, a
+ * dictionary count that does not fit its page, a bit width above 32, row counts that do not add up.
+ * NVT_EUNSUPPORTED: other codecs / encodings / page kinds, 2^31 - 1 or more entries or values.
+ *
+ * nvt_pq_expand_runs (device): out[q] = the entry id of non-null value q for q < nvalues, from the
+ * run table (device memory, 16-byte aligned, nruns records + the closing one) and the packed bytes
+ * (device memory, 4-byte aligned, packed_bytes readable, 8 of them behind the last run).  An id
+ * outside [0, entries) is written as -1 and counted: *bad += their number (a device word the caller
+ * zeroes; one atomic per wave).  Every read is bounded by nruns / packed_bytes whatever the table
+ * says.  closing: the closing record in HOST memory; NVT_EINVAL before any launch when it does not
+ * say nvalues, or on a null pointer.  nvalues == 0: NVT_OK without a launch.  nvalues < 2^32 - 2048.
+ * No read-back; works on `stream` only. */
+#define NVT_PQ_RUN_REPEAT 0u
+#define NVT_PQ_RUN_PACKED 1u
+#define NVT_PQ_RUN_SEQUENCE 2u
+#define NVT_PQ_RUN_END 3u
+#define NVT_PQ_STR_GROW 1
+typedef struct nvt_pq_str_stage {
+  int64_t *offsets;
+  uint8_t *chars;
+  uint32_t *runs;
+  uint8_t *packed;
+  uint64_t entries_cap, chars_cap, runs_cap, packed_cap;
+  uint64_t entries, nchars, nruns, npacked, nvalues;
+} nvt_pq_str_stage;
+int nvt_pq_decode_str_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
+                            uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                            nvt_pq_str_stage *stage, uint8_t *scratch, uint64_t scratch_bytes, uint64_t *need);
+int nvt_pq_expand_runs(const uint32_t *runs, uint64_t nruns, const uint32_t *closing, const uint8_t *packed,
+                       uint64_t packed_bytes, uint64_t entries, uint64_t nvalues, int32_t *out, uint32_t *bad,
+                       void *stream);
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes);
 int nvt_expand_valid(const void *packed, int type_size, const uint8_t *bitmap, uint64_t n, void *out,
                      void *ws, void *stream);

@@ -125,6 +125,8 @@ SIGNATURES = {
                                   C.POINTER(_u64), C.POINTER(_u64)],
     "nvt_pq_decode_list_chunk": [_vp, _u64, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _u64,
                                  _vp, _u64, C.POINTER(_u64)],
+    "nvt_pq_decode_str_chunk": [_vp, _u64, _i32, _i32, _u64, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64)],
+    "nvt_pq_expand_runs": [_vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp],
     "nvt_expand_valid_ws_bytes": [_u64, C.POINTER(_u64)],
     "nvt_expand_valid": [_vp, _i32, _vp, _u64, _vp, _vp, _vp],
     "nvt_exchange_ranges": [_vp, _i32, _vp, _vp],
@@ -188,6 +190,18 @@ class MergeCol(C.Structure):
     _fields_ = [("a_keys", _vp), ("a_counts", _vp), ("na", _u64), ("b_keys", _vp),
                 ("b_counts", _vp), ("nb", _u64), ("out_keys", _vp), ("out_counts", _vp),
                 ("src_a", _vp), ("src_b", _vp), ("out_n", _vp)]
+
+
+class PqStrStage(C.Structure):
+    """nvt_pq_str_stage: the staging buffers of one string column of a partition and how far they
+    are filled (nvt_pq_decode_str_chunk)."""
+    _fields_ = [("offsets", _vp), ("chars", _vp), ("runs", _vp), ("packed", _vp),
+                ("entries_cap", _u64), ("chars_cap", _u64), ("runs_cap", _u64), ("packed_cap", _u64),
+                ("entries", _u64), ("nchars", _u64), ("nruns", _u64), ("npacked", _u64), ("nvalues", _u64)]
+
+
+PQ_RUN_REPEAT, PQ_RUN_PACKED, PQ_RUN_SEQUENCE, PQ_RUN_END = 0, 1, 2, 3   # include/nvt_hip.h NVT_PQ_RUN_*
+PQ_STR_GROW = 1
 
 
 class ImagePart(C.Structure):

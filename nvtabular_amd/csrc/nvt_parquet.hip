@@ -23,6 +23,11 @@
 //     continuous over the partition (1 and W bits per slot); the device turns them into offsets and
 //     the leaf bitmap (nvt_pqlist_unpack, nvt_parquet_list.hip).
 //
+//   string columns (flat BYTE_ARRAY annotated UTF8 / STRING): nvt_pq_decode_str_chunk walks the same
+//     pages but expands nothing: dictionary and PLAIN values become entries of an Arrow string table,
+//     the index streams a run table plus the bytes of their bit-packed runs; the device expands the
+//     runs to entry ids (nvt_pq_expand_runs, nvt_parquet_str.hip) and hashes every entry once.
+//
 // Anything else in a chunk (other codecs / encodings, other nesting) is reported as
 // NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
 #include <hip/hip_runtime.h>
@@ -839,6 +844,340 @@ int nvt_pq_decode_chunk_codec(const uint8_t *chunk, uint64_t chunk_bytes, int co
                               uint64_t *values_out_count) {
   return pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out, valid_bit_offset,
                    values_out, values_cap_bytes, scratch, scratch_bytes, rows_out, values_out_count);
+}
+
+// ---- string columns: entries + run table + packed bytes ("String columns in the parquet
+// reader") ------------------------------------------------------------------------------------------
+namespace {
+
+// the fill state of a nvt_pq_str_stage during one chunk: committed to the stage on NVT_OK only, so a
+// chunk that asked for larger buffers is decoded again from its first byte
+struct StrFill {
+  nvt_pq_str_stage *st;
+  uint64_t entries, nchars, nruns, npacked, nvalues;
+  uint64_t *need;
+  // -> NVT_OK, or NVT_PQ_STR_GROW with need[which] = the least capacity that would have sufficed here
+  int room(int which, uint64_t want, uint64_t cap) {
+    if (want <= cap) return NVT_OK;
+    need[which] = want;
+    set_error("nvt_pq_decode_str_chunk: staging buffer %d holds %llu, %llu needed", which, (unsigned long long)cap,
+              (unsigned long long)want);
+    return NVT_PQ_STR_GROW;
+  }
+  // one record [start = nvalues, kind | width << 8, a, b]; a repeat run that continues the last
+  // record's entry, or a sequence that continues its entries, adds nothing: a run ends where the next
+  // record starts
+  int run(unsigned kind, unsigned width, uint32_t a, uint32_t b, uint64_t count) {
+    if (count == 0) return NVT_OK;
+    uint32_t *rec = st->runs + 4 * nruns;
+    bool merged = false;
+    if (nruns > 0) {
+      const uint32_t *last = rec - 4;
+      if (kind == NVT_PQ_RUN_REPEAT && last[1] == NVT_PQ_RUN_REPEAT && last[2] == a) merged = true;
+      if (kind == NVT_PQ_RUN_SEQUENCE && last[1] == NVT_PQ_RUN_SEQUENCE &&
+          (uint64_t)last[2] + (nvalues - last[0]) == (uint64_t)a)
+        merged = true;
+    }
+    if (!merged) {
+      const int rc = room(2, nruns + 2, st->runs_cap);   // (this record and the closing one)
+      if (rc) return rc;
+      rec[0] = (uint32_t)nvalues;
+      rec[1] = kind | (width << 8);
+      rec[2] = a;
+      rec[3] = b;
+      ++nruns;
+    }
+    nvalues += count;
+    return NVT_OK;
+  }
+};
+
+// `count` PLAIN BYTE_ARRAY values (u32 length | bytes, each) in [q, pend) -> appended entries
+int str_append_plain(StrFill &f, const uint8_t *q, const uint8_t *pend, uint64_t count) {
+  int rc = f.room(0, f.entries + count, f.st->entries_cap);
+  if (rc) return rc;
+  for (uint64_t i = 0; i < count; ++i) {
+    if ((uint64_t)(pend - q) < 4) {
+      set_error("nvt_pq_decode_str_chunk: a length prefix past its page");
+      return NVT_EINVAL;
+    }
+    uint32_t len;
+    memcpy(&len, q, 4);
+    q += 4;
+    if ((uint64_t)(pend - q) < len) {
+      set_error("nvt_pq_decode_str_chunk: a value of %u bytes runs past its page", len);
+      return NVT_EINVAL;
+    }
+    if ((rc = f.room(1, ((f.nchars + len + 3) & ~3ull), f.st->chars_cap))) return rc;
+    memcpy(f.st->chars + f.nchars, q, len);
+    q += len;
+    f.nchars += len;
+    f.st->offsets[++f.entries] = (int64_t)f.nchars;
+  }
+  return NVT_OK;
+}
+
+// the dictionary indices of one page (`count` non-null values; one byte bit width, then the RLE /
+// bit-packed hybrid) -> run records; the bytes of bit-packed runs go to the packed staging buffer,
+// each run's on a 4-byte boundary
+int str_index_runs(StrFill &f, const uint8_t *p, const uint8_t *end, uint64_t count, uint64_t base,
+                   uint64_t ndict) {
+  if (count == 0) return NVT_OK;
+  if (p >= end) {
+    set_error("nvt_pq_decode_str_chunk: an index page without its bit width");
+    return NVT_EINVAL;
+  }
+  const unsigned bw = *p++;
+  if (bw > 32) {
+    set_error("nvt_pq_decode_str_chunk: dictionary indices of bit width %u", bw);
+    return NVT_EINVAL;
+  }
+  const uint32_t kBadId = 0xFFFFFFFFu;   // (entries stay below 2^31: the device counts this id as bad)
+  if (bw == 0)   // a one-entry dictionary: every value is its entry, whatever runs the page spells out
+    return f.run(NVT_PQ_RUN_REPEAT, 0, ndict ? (uint32_t)base : kBadId, 0, count);
+  const uint64_t mask = bw == 32 ? 0xFFFFFFFFull : ((1ull << bw) - 1ull);
+  TReader r{p, end};
+  uint64_t done = 0;
+  while (done < count) {
+    const uint64_t head = r.varint();
+    if (!r.ok) {
+      set_error("nvt_pq_decode_str_chunk: the index runs end before the page's values");
+      return NVT_EINVAL;
+    }
+    const uint64_t avail = (uint64_t)(r.end - r.p);
+    if (head & 1) {   // bit-packed: (head >> 1) groups of 8 values, `bw` bits each, LSB first
+      const uint64_t groups = head >> 1;
+      if (groups > (1ull << 40)) {
+        set_error("nvt_pq_decode_str_chunk: a bit-packed run of %llu groups", (unsigned long long)groups);
+        return NVT_EINVAL;
+      }
+      uint64_t take = groups * 8;
+      if (take > count - done) take = count - done;   // (the last group is padded)
+      const uint64_t nb = (take * bw + 7) / 8;        // the bytes the values need
+      if (avail < nb) {
+        set_error("nvt_pq_decode_str_chunk: a bit-packed run past its page");
+        return NVT_EINVAL;
+      }
+      if (take) {
+        const uint64_t at = (f.npacked + 3) & ~3ull;
+        int rc = f.room(3, at + nb + 8, f.st->packed_cap);
+        if (rc) return rc;
+        if (at / 4 > 0xFFFFFFFFull || base > 0x7FFFFFFFull) {
+          set_error("nvt_pq_decode_str_chunk: more than 16 GiB of packed indices in one partition");
+          return NVT_EUNSUPPORTED;
+        }
+        memset(f.st->packed + f.npacked, 0, at - f.npacked);
+        memcpy(f.st->packed + at, r.p, nb);
+        f.npacked = at + nb;
+        if ((rc = f.run(NVT_PQ_RUN_PACKED, bw, (uint32_t)base, (uint32_t)(at / 4), take))) return rc;
+      }
+      r.skip_bytes(groups * bw < avail ? groups * bw : avail);   // (a writer may cut the padding)
+      done += take;
+    } else {   // RLE: (head >> 1) times the value in the next ceil(bw / 8) bytes
+      uint64_t n = head >> 1;
+      const unsigned vb = (bw + 7) / 8;
+      if (avail < vb) {
+        set_error("nvt_pq_decode_str_chunk: a repeat run past its page");
+        return NVT_EINVAL;
+      }
+      uint64_t idx = 0;
+      memcpy(&idx, r.p, vb);
+      r.p += vb;
+      idx &= mask;
+      if (n > count - done) n = count - done;
+      const int rc = f.run(NVT_PQ_RUN_REPEAT, 0, idx < ndict ? (uint32_t)(base + idx) : kBadId, 0, n);
+      if (rc) return rc;
+      done += n;
+    }
+  }
+  return NVT_OK;
+}
+
+}  // namespace
+
+int nvt_pq_decode_str_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
+                            uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                            nvt_pq_str_stage *stage, uint8_t *scratch, uint64_t scratch_bytes, uint64_t *need) {
+  NVT_CHECK_ARG(chunk && stage && need, "null pointer");
+  NVT_CHECK_ARG(stage->offsets && stage->chars && stage->runs && stage->packed, "null staging buffer");
+  NVT_CHECK_ARG(max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
+  NVT_CHECK_ARG(max_def_level == 0 || valid_out, "null validity buffer");
+  NVT_CHECK_ARG(stage->runs_cap >= 1 && stage->nruns < stage->runs_cap && stage->packed_cap >= 8 &&
+                    stage->npacked <= stage->packed_cap - 8 && stage->entries <= stage->entries_cap &&
+                    stage->nchars <= stage->chars_cap && (stage->chars_cap & 3) == 0,
+                "the stage's fill state does not fit its capacities");
+  if (codec != 0 && codec != 1) {
+    set_error("nvt_pq_decode_str_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
+    return NVT_EUNSUPPORTED;
+  }
+  need[0] = need[1] = need[2] = need[3] = 0;
+  StrFill f{stage, stage->entries, stage->nchars, stage->nruns, stage->npacked, stage->nvalues, need};
+  if (f.entries == 0) stage->offsets[0] = 0;
+  // page body -> `want` uncompressed bytes: the body itself, or the scratch buffer (a string chunk
+  // keeps nothing between pages: the dictionary's values are appended to the entries at once)
+  auto inflate = [&](const uint8_t *src, uint64_t nsrc, uint64_t want, bool compressed, const uint8_t **out) -> int {
+    if (!compressed) {
+      if (nsrc != want) {
+        set_error("nvt_pq_decode_str_chunk: an uncompressed page of %llu bytes that says %llu",
+                  (unsigned long long)nsrc, (unsigned long long)want);
+        return NVT_EINVAL;
+      }
+      *out = src;
+      return NVT_OK;
+    }
+    if (scratch == nullptr || scratch_bytes < want) {
+      set_error("nvt_pq_decode_str_chunk: scratch too small for a page of %llu bytes", (unsigned long long)want);
+      return NVT_EINVAL;
+    }
+    if (snappy_uncompress(src, nsrc, scratch, want) != (int64_t)want) {
+      set_error("nvt_pq_decode_str_chunk: malformed snappy block");
+      return NVT_EINVAL;
+    }
+    *out = scratch;
+    return NVT_OK;
+  };
+  const uint8_t *p = chunk, *end = chunk + chunk_bytes;
+  uint64_t rows = 0;
+  bool have_dict = false;
+  uint64_t base = 0, ndict = 0;   // the chunk's dictionary: entries [base, base + ndict)
+  while (p < end && rows < expect_rows) {
+    TReader r{p, end};
+    PageHead h;
+    if (!read_page_header(r, h)) {
+      set_error("nvt_pq_decode_str_chunk: malformed page header at byte %llu", (unsigned long long)(p - chunk));
+      return NVT_EINVAL;
+    }
+    const uint8_t *body = r.p;
+    if (h.compressed < 0 || h.uncompressed < 0 || (uint64_t)(end - body) < (uint64_t)h.compressed) {
+      set_error("nvt_pq_decode_str_chunk: page of %lld bytes runs past the chunk", (long long)h.compressed);
+      return NVT_EINVAL;
+    }
+    if (h.type == 1) {  // index page: nothing for us
+      p = body + h.compressed;
+      continue;
+    }
+    if (h.type == 2) {  // dictionary page: PLAIN values (encoding 0; 2 = PLAIN_DICTIONARY, the old name)
+      if (have_dict || (h.dict_encoding != 0 && h.dict_encoding != 2)) {
+        set_error("nvt_pq_decode_str_chunk: dictionary page (encoding %d, second %d)", h.dict_encoding, (int)have_dict);
+        return NVT_EUNSUPPORTED;
+      }
+      const uint8_t *d = nullptr;
+      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &d);
+      if (rc) return rc;
+      // every value holds a 4-byte length: compared by division, a count of 2^61 must not wrap
+      if (h.dict_values < 0 || (uint64_t)h.dict_values > (uint64_t)h.uncompressed / 4) {
+        set_error("nvt_pq_decode_str_chunk: dictionary page holds fewer values than it says");
+        return NVT_EINVAL;
+      }
+      have_dict = true;
+      base = f.entries;
+      ndict = (uint64_t)h.dict_values;
+      if ((rc = str_append_plain(f, d, d + h.uncompressed, ndict))) return rc;
+      p = body + h.compressed;
+      continue;
+    }
+    if (h.type != 0 && h.type != 3) {
+      set_error("nvt_pq_decode_str_chunk: page type %d", h.type);
+      return NVT_EUNSUPPORTED;
+    }
+    const bool by_dict = h.encoding == 2 || h.encoding == 8;   // PLAIN_DICTIONARY / RLE_DICTIONARY
+    if (h.encoding != 0 && !by_dict) {
+      set_error("nvt_pq_decode_str_chunk: value encoding %d (PLAIN and dictionary indices are decoded here)",
+                h.encoding);
+      return NVT_EUNSUPPORTED;
+    }
+    if (by_dict && !have_dict) {
+      set_error("nvt_pq_decode_str_chunk: dictionary indices without a dictionary page");
+      return NVT_EINVAL;
+    }
+    const uint64_t prow = (uint64_t)h.num_values;
+    if (h.num_values < 0 || prow > expect_rows - rows) {
+      set_error("nvt_pq_decode_str_chunk: more rows than the row group holds");
+      return NVT_EINVAL;
+    }
+    const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
+    uint64_t pvalid = prow;
+    if (h.type == 0) {   // v1: levels and values are compressed together
+      const uint8_t *u = nullptr;
+      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
+      if (rc) return rc;
+      q = u;
+      pend = u + h.uncompressed;
+      if (max_def_level == 1) {
+        if (h.def_encoding != 3) {  // RLE (the hybrid)
+          set_error("nvt_pq_decode_str_chunk: definition level encoding %d", h.def_encoding);
+          return NVT_EUNSUPPORTED;
+        }
+        uint32_t lb = 0;
+        if (pend - q >= 4) memcpy(&lb, q, 4);
+        if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb ||
+            !decode_levels(q + 4, lb, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
+          set_error("nvt_pq_decode_str_chunk: malformed definition levels");
+          return NVT_EINVAL;
+        }
+        q += 4 + (uint64_t)lb;
+      }
+    } else {  // v2: definition levels uncompressed in front, no length prefix
+      if (h.rep_bytes != 0) {
+        set_error("nvt_pq_decode_str_chunk: repetition levels (nested column)");
+        return NVT_EUNSUPPORTED;
+      }
+      if (h.def_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
+          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes) {
+        set_error("nvt_pq_decode_str_chunk: definition levels run past the page");
+        return NVT_EINVAL;
+      }
+      if (max_def_level == 1 &&
+          !decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
+        set_error("nvt_pq_decode_str_chunk: malformed definition levels");
+        return NVT_EINVAL;
+      }
+      const uint8_t *u = nullptr;
+      const uint64_t lbytes = (uint64_t)h.def_bytes;
+      int rc = inflate(body + lbytes, (uint64_t)h.compressed - lbytes, (uint64_t)h.uncompressed - lbytes,
+                       codec != 0 && h.v2_compressed, &u);
+      if (rc) return rc;
+      q = u;
+      pend = u + ((uint64_t)h.uncompressed - lbytes);
+    }
+    if (pvalid > prow) {
+      set_error("nvt_pq_decode_str_chunk: more valid rows than rows");
+      return NVT_EINVAL;
+    }
+    int rc;
+    if (by_dict) {
+      rc = str_index_runs(f, q, pend, pvalid, base, ndict);
+    } else {
+      const uint64_t first = f.entries;
+      rc = str_append_plain(f, q, pend, pvalid);
+      if (!rc) rc = f.run(NVT_PQ_RUN_SEQUENCE, 0, (uint32_t)first, 0, pvalid);
+    }
+    if (rc) return rc;
+    if (f.entries > 0x7FFFFFFEull || f.nvalues > 0x7FFFFFFEull) {
+      set_error("nvt_pq_decode_str_chunk: more than 2^31 - 2 entries or values in one partition");
+      return NVT_EUNSUPPORTED;
+    }
+    rows += prow;
+    p = body + h.compressed;
+  }
+  if (rows != expect_rows) {
+    set_error("nvt_pq_decode_str_chunk: %llu rows in the pages, %llu expected", (unsigned long long)rows,
+              (unsigned long long)expect_rows);
+    return NVT_EINVAL;
+  }
+  // the closing record (the next chunk writes over it) and the 8 readable bytes behind the packed runs
+  uint32_t *close = stage->runs + 4 * f.nruns;
+  close[0] = (uint32_t)f.nvalues;
+  close[1] = NVT_PQ_RUN_END;
+  close[2] = close[3] = 0;
+  memset(stage->packed + f.npacked, 0, 8);
+  memset(stage->chars + f.nchars, 0, ((f.nchars + 3) & ~3ull) - f.nchars);
+  stage->entries = f.entries;
+  stage->nchars = f.nchars;
+  stage->nruns = f.nruns;
+  stage->npacked = f.npacked;
+  stage->nvalues = f.nvalues;
+  return NVT_OK;
 }
 
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes) {

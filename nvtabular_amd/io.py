@@ -4,7 +4,7 @@ merlin.io.Dataset the hot path touches: SURVEY section 8(b) "Dataset").
 Sources: pandas DataFrame, DeviceFrame, pyarrow Table, parquet path(s) or a list
 of already-partitioned frames.  ``to_iter()`` yields HBM-resident DeviceFrames;
 parquet row groups are decoded by the hand-written reader where it takes the file
-(parquet_plain.py: ``PlainParquetFile.readable``, ``StagedPartition``), else by pyarrow
+(parquet_plain.py: ``PlainParquetFile.decodable``, ``StagedPartition``), else by pyarrow
 straight into Arrow buffers, and copied to the device without going through pandas.
 ``to_parquet`` hands frames to the PLAIN write driver (parquet_write.py) or to pyarrow.
 """
@@ -130,9 +130,9 @@ class Dataset:
         if self._schema is None:
             self._schema = Schema.from_frame(pq.ParquetFile(files[0]).schema_arrow)
 
-        # files the hand-written reader takes (flat numeric columns and three-level lists of such
-        # leaves; PLAIN or dictionary-encoded values, uncompressed or snappy:
-        # parquet_plain.PlainParquetFile.readable); everything else is
+        # files the hand-written reader takes (flat numeric columns, three-level lists of such
+        # leaves and flat string columns; PLAIN or dictionary-encoded values, uncompressed or snappy:
+        # parquet_plain.PlainParquetFile.decodable); everything else is
         # decoded by pyarrow and counted in parquet_plain.READER_CHUNKS
         plain_files = {}
 
@@ -142,7 +142,7 @@ class Dataset:
                 if PLAIN_PARQUET_READ:
                     try:
                         pf = PlainParquetFile(f)
-                        if not pf.readable:
+                        if not pf.decodable:
                             pf = None
                     except Exception:
                         pf = None

@@ -32,6 +32,10 @@ parquet writer").  The reading half below takes such lists too, from any writer 
 columns in the parquet reader"); other nested files are read with pyarrow.
 Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
 columns) stays with pyarrow's writer.
+The reading half also takes flat STRING columns (any writer's dictionary / PLAIN pages): their
+dictionary entries and index runs are staged as the file holds them and expanded, hashed and
+gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "String columns in
+the parquet reader").  Binary columns, lists of strings and DELTA encodings stay with pyarrow.
 parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver in front of the writer.
 """
 from __future__ import annotations
@@ -414,13 +418,29 @@ def _judge_leaf(e):
     return dt, unit, None
 
 
+def _is_string_leaf(e):
+    """A BYTE_ARRAY (physical type 6) annotated as a string: converted type UTF8 (0) and / or the
+    LogicalType STRING (union field 1) -- what pyarrow writes for ``string`` and ``large_string``.
+    Plain binary (no annotation), JSON / BSON / ENUM / DECIMAL byte arrays are not."""
+    conv, logical = e.get(6), e.get(10)
+    if e.get(1) != 6:
+        return False
+    if logical is not None:
+        return isinstance(logical, dict) and list(logical) == [1] and conv in (None, 0)
+    return conv == 0
+
+
 def _judge_column(schema, at):
     """(``columns`` entry, reason or None) of the top-level column whose subtree starts at
-    schema[at]: a flat column, or the standard three-level list of number leaves."""
+    schema[at]: a flat number column, a flat string column, or the standard three-level list of
+    number leaves."""
     e = schema[at]
     name, logical = e.get(4, b"").decode(), e.get(10)
     col = dict(name=name, kind="flat", outer_optional=False, elem_optional=False, max_def=0, leaf_level=0,
                leaf_dtype=None, unit=None)
+    if not e.get(5) and _is_string_leaf(e):
+        col.update(kind="string", outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1)
+        return col, (f"column {name!r}: a repeated string" if e.get(3, 0) == 2 else None)
     if not e.get(5):
         dt, unit, why = _judge_leaf(e)
         col.update(outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1, leaf_dtype=dt, unit=unit)
@@ -472,22 +492,29 @@ def _judge_chunk(cc, col, file_size):
     # the chunks follow the top-level columns, a list chunk's path has three parts
     if col is None or path[:1] != [col["name"]] or len(path) != (3 if col["kind"] == "list" else 1):
         return c, "column chunks do not follow the schema order"
+    if col["kind"] == "string" and not 0 <= c["raw_size"] < (1 << 32):
+        return c, f"chunk of {md.get(3)}: {c['raw_size']} uncompressed bytes"
     return c, None
 
 
 class PlainParquetFile:
     """Footer of one parquet file and the verdict on whether the hand-written reader takes it.
-    ``readable``: every top-level column is a flat column (physical type INT32 / INT64 / FLOAT /
+    ``decodable``: every top-level column is a flat column (physical type INT32 / INT64 / FLOAT /
     DOUBLE without a converted / logical type that changes the meaning of the bits: dates, decimals,
-    unsigned) or the standard three-level list of such leaves (a group annotated LIST, optional or
+    unsigned), a flat string column (BYTE_ARRAY annotated UTF8 / STRING, ``kind`` "string": DESIGN.md,
+    "String columns in the parquet reader") or the standard three-level list of such number leaves (a group annotated LIST, optional or
     required, holding one repeated group, holding one primitive leaf, optional or required; the two
     inner names are not looked at), and every column chunk follows its column, with codec
     UNCOMPRESSED or SNAPPY, values PLAIN or dictionary-encoded (what pandas / pyarrow / cuDF write by
     default), encodings within {PLAIN, PLAIN_DICTIONARY, RLE, BIT_PACKED, RLE_DICTIONARY} and no
-    BIT_PACKED levels on a list chunk.  Otherwise ``why_not`` is the FIRST thing found that keeps
-    the file with pyarrow (legacy two-level lists, lists of lists, maps, structs, string / bool /
-    narrow / TIMESTAMP leaves, other codecs).  ``eligible``: readable and all columns flat.
-    ``columns[j]`` describes top-level column j: ``kind`` ("flat" / "list"), ``outer_optional``,
+    BIT_PACKED levels on a list chunk.  Otherwise ``why_pyarrow`` is the FIRST thing found that keeps
+    the file with pyarrow (legacy two-level lists, lists of lists, maps, structs, binary / fixed-length
+    binary columns, string / bool / narrow / TIMESTAMP list leaves, DELTA encodings, other codecs).
+    ``readable`` / ``why_not`` keep the meaning they had before the reader knew strings: decodable
+    AND no string column (number columns and lists of numbers only); a string column is their first
+    reason like any other.  The reader goes by ``decodable``.
+    ``eligible``: readable and all columns flat number columns.
+    ``columns[j]`` describes top-level column j: ``kind`` ("flat" / "string" / "list"), ``outer_optional``,
     ``elem_optional``, ``max_def`` (lists: O + 1 + E), ``leaf_level`` (O + 1), ``leaf_dtype`` and
     ``unit``; ``names`` / ``dtypes`` / ``max_def`` / ``units`` are the same per top-level column."""
 
@@ -507,6 +534,7 @@ class PlainParquetFile:
         schema = meta.get(2, [])
         self.num_rows = int(meta.get(3, 0))
         self.readable, self.why_not, self.columns = True, "", []
+        self.decodable, self.why_pyarrow = True, ""
 
         def behind(i, depth=0):   # index behind the subtree at i of the depth-first schema list
             kids = int(schema[i].get(5) or 0) if (i < len(schema) and depth < 64) else 0
@@ -523,6 +551,8 @@ class PlainParquetFile:
             col, why = _judge_column(schema, at)
             self.columns.append(col)
             self._fail(why)
+            if col["kind"] == "string":
+                self._fail(f"column {col['name']!r}: a string column", strings=True)
             at = behind(at)
         else:   # (every column was there)
             self._fail("schema longer than its root says" if at != len(schema) else None)
@@ -541,9 +571,12 @@ class PlainParquetFile:
                 self._fail("column chunks do not follow the schema order")
             self.row_groups.append(dict(num_rows=int(rg.get(3, 0)), columns=cols))
 
-    def _fail(self, why):
+    def _fail(self, why, strings=False):
+        """strings: a reason that keeps the file from ``readable`` only (the reader takes it)."""
         if why is not None and self.readable:   # (the first reason stays)
             self.readable, self.why_not = False, why
+        if why is not None and self.decodable and not strings:
+            self.decodable, self.why_pyarrow = False, why
 
     @property
     def eligible(self):
@@ -569,10 +602,13 @@ class StagedColumn:
     ``width`` bits per slot, continuous over the partition), ``leaves`` the leaf slots among them,
     ``leaf_level`` / ``max_def`` the level arithmetic; ``rows`` stays the row count.  ``same_as``: the
     name of an earlier list column of the partition whose level streams are byte-equal (they share
-    one unpack and one offsets tensor on the device), else None."""
+    one unpack and one offsets tensor on the device), else None.
+
+    A string column (``strs`` is not None) has no ``values``: ``strs`` (StagedStrings) holds its
+    entries, run table and packed index bytes, ``nvalid`` counts its non-null rows."""
 
     __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical", "rep", "dfn", "width", "leaf_level",
-                 "max_def", "slots", "leaves", "same_as")
+                 "max_def", "slots", "leaves", "same_as", "strs")
 
     def __init__(self, values, valid, rows, nvalid, dtype, logical=None, rep=None, dfn=None, width=0, leaf_level=0,
                  max_def=0, slots=0, leaves=0):
@@ -580,10 +616,87 @@ class StagedColumn:
         self.logical = logical   # datetime64[ms|us|ns] of a TIMESTAMP column, else None
         self.rep, self.dfn, self.width, self.leaf_level, self.max_def = rep, dfn, width, leaf_level, max_def
         self.slots, self.leaves, self.same_as = slots, leaves, None
+        self.strs = None
 
     @property
     def is_list(self):
         return self.rep is not None
+
+
+_MAX_STR_CHARS = (1 << 32) - 2   # kernels_strings._MAX_CHARS: the dict's strings are gathered with 32-bit sums
+
+
+class StagedStrings:
+    """The staging buffers of one string column of a partition, as nvt_pq_decode_str_chunk fills them
+    (include/nvt_hip.h, nvt_pq_str_stage): ``offsets`` (int64) / ``chars`` the entries, ``runs`` the run
+    table (int32 words, 4 per record, the closing record behind the ``nruns`` runs), ``packed`` the
+    bytes of the bit-packed runs.  Sized from the footer and enlarged when the decoder asks for it.
+    ``where`` names file and column for error messages."""
+
+    def __init__(self, entries_cap, chars_cap, runs_cap, packed_cap, pinned, where):
+        import torch
+
+        from . import _lib
+
+        self.pinned, self.where = pinned, where
+        self.offsets = torch.empty(entries_cap + 1, dtype=torch.int64, pin_memory=pinned)
+        self.chars = torch.empty((chars_cap + 7) & ~7, dtype=torch.uint8, pin_memory=pinned)
+        self.runs = torch.empty(4 * runs_cap, dtype=torch.int32, pin_memory=pinned)
+        self.packed = torch.empty(((packed_cap + 7) & ~7) + 8, dtype=torch.uint8, pin_memory=pinned)
+        self.offsets[0] = 0
+        self.c = _lib.PqStrStage()
+        self._bind()
+
+    def _bind(self):
+        c = self.c
+        c.offsets, c.chars, c.runs, c.packed = (self.offsets.data_ptr(), self.chars.data_ptr(), self.runs.data_ptr(),
+                                                self.packed.data_ptr())
+        c.entries_cap, c.chars_cap = self.offsets.numel() - 1, self.chars.numel()
+        c.runs_cap, c.packed_cap = self.runs.numel() // 4, self.packed.numel()
+
+    def grow(self, need):
+        """Enlarges the buffers named by ``need`` = (entries, chars, runs, packed), 0 = large enough,
+        keeping what is filled."""
+        import torch
+
+        from . import _lib
+
+        c = self.c
+        for which, want in enumerate(need):
+            if not want:
+                continue
+            name, used, unit, extra = (("offsets", c.entries + 1, 1, 1), ("chars", c.nchars, 8, 0),
+                                       ("runs", 4 * (c.nruns + 1), 4, 0), ("packed", c.npacked + 8, 8, 0))[which]
+            old = getattr(self, name)
+            if which == 1 and want > _MAX_STR_CHARS + 2:
+                raise _lib.NvtHipError(f"{self.where}: more than {_MAX_STR_CHARS} bytes of strings in one partition")
+            size = max(int(want) * (4 if which == 2 else 1), 2 * old.numel())
+            if which == 1:
+                size = min(size, _MAX_STR_CHARS + 2)
+            new = torch.empty(((size + unit - 1) // unit) * unit + extra, dtype=old.dtype, pin_memory=self.pinned)
+            new[:used] = old[:used]
+            setattr(self, name, new)
+        self._bind()
+
+    @property
+    def entries(self):
+        return int(self.c.entries)
+
+    @property
+    def nchars(self):
+        return int(self.c.nchars)
+
+    @property
+    def nruns(self):
+        return int(self.c.nruns)
+
+    @property
+    def npacked(self):
+        return int(self.c.npacked)
+
+    @property
+    def nvalues(self):
+        return int(self.c.nvalues)
 
 
 class StagedPartition:
@@ -609,6 +722,13 @@ class StagedPartition:
         for name, sc in self.columns.items():
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
                 raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
+            if sc.strs is not None:
+                # entries, run table and packed index bytes travel as the file holds them: the ids are
+                # expanded, the entries hashed and the dict built on the device
+                from . import kernels_parquet_str as KPS
+
+                out[name] = KPS.column_from_staged(sc, device)
+                continue
             packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
             if sc.is_list:
                 # the level streams become offsets and the leaf bitmap on the device (columns with
@@ -653,11 +773,12 @@ READER_CHUNKS = {"plain": 0, "pyarrow": 0}
 
 
 def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True):
-    """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of a readable
+    """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of a decodable
     file.  One task per column: pread of a chunk into a scratch buffer, then nvt_pq_decode_chunk
     (ctypes: GIL released) moves its values and validity bits to their place in the partition's
     (pinned) staging buffers; a list column's chunks go through nvt_pq_decode_list_chunk, which
-    appends their levels to the column's two level streams instead."""
+    appends their levels to the column's two level streams instead, a string column's through
+    nvt_pq_decode_str_chunk, which appends entries, index runs and packed bytes to a StagedStrings."""
     import ctypes as C
 
     import torch
@@ -719,6 +840,37 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         return StagedColumn(vals, None, total, val_at, dt, None, rep=rep, dfn=dfn, width=width,
                             leaf_level=col["leaf_level"], max_def=col["max_def"], slots=slot_at, leaves=leaves)
 
+    def str_task(n, j):
+        """One string column: the chunks' entries, index runs and packed bytes appended to ONE
+        StagedStrings (nvt_pq_decode_str_chunk), validity bits at the partition's row positions."""
+        ccs = [pf.row_groups[g]["columns"][j] for g in groups if pf.row_groups[g]["num_rows"]]
+        nv = sum(cc["num_values"] for cc in ccs)
+        raw = sum(max(cc.get("raw_size", 0), cc["size"]) for cc in ccs)
+        # from the footer: every entry holds a 4-byte length and every run 2 bytes or more of its
+        # page, pyarrow's runs 8 values or more; a footer that understates them makes the decoder ask
+        st = StagedStrings(min(nv, raw // 4) + 16, min(raw, _MAX_STR_CHARS) + 8, min(raw // 2, nv // 8) + 1024,
+                           raw + nv // 64 + 4096, pinned, f"{pf.path}: column {n!r}")
+        valid = None
+        if pf.max_def[j]:
+            valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
+        row_at = 0
+        need = (C.c_uint64 * 4)()
+        for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
+            while True:
+                rc = lib.nvt_pq_decode_str_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
+                                                 valid.data_ptr() if valid is not None else None, row_at,
+                                                 C.addressof(st.c), sbuf, sbytes, need)
+                if rc != _lib.PQ_STR_GROW:
+                    break
+                st.grow(tuple(int(x) for x in need))
+            decoded("nvt_pq_decode_str_chunk", rc, n, g)
+            if st.nchars > _MAX_STR_CHARS:
+                raise _lib.NvtHipError(f"{st.where}: more than {_MAX_STR_CHARS} bytes of strings in one partition")
+            row_at += rows
+        sc = StagedColumn(None, valid if (valid is not None and st.nvalues < total) else None, total, st.nvalues, None)
+        sc.strs = st
+        return sc
+
     def task(n):
         """One column: its chunks of the row groups one after the other -- packed values behind
         each other, validity bits at the partition's row positions (a thread per COLUMN: two row
@@ -726,6 +878,8 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         j = pf.names.index(n)
         if pf.columns[j]["kind"] == "list":
             return list_task(n, j)
+        if pf.columns[j]["kind"] == "string":
+            return str_task(n, j)
         dt = pf.dtypes[j]
         vals = torch.empty(total, dtype=getattr(torch, dt.name), pin_memory=pinned)
         valid = None
