@@ -1323,6 +1323,36 @@ int nvt_pqlist_unpack(const uint8_t *rep, const uint8_t *def, int def_width, uin
                       int max_def, uint64_t rows, uint64_t leaves, int64_t *offsets, uint8_t *leaf_valid,
                       void *ws, uint64_t ws_bytes, void *stream);
 
+/* ---- parquet dictionary pages: Dataset.to_parquet(use_dictionary=...) ----
+ * One column chunk's n NON-NULL values (NVT_I32 / NVT_I64; every bit pattern is a value) become a
+ * dictionary -- their distinct values in ascending signed order -- and RLE_DICTIONARY index pages.
+ * nvt_pq_dict_build: dict receives the d distinct values (room for min(n, max_entries) entries),
+ *   state[NVT_PQ_DICT_STATE_WORDS] = {d, overflow, internal, 0}.  More than max_entries distinct
+ *   values set overflow (bit 0): d and dict mean nothing then, dict holds no more than max_entries
+ *   entries, and the work that grows with d stops.  1 <= max_entries <= NVT_PQ_DICT_MAX_ENTRIES.
+ *   The value -> rank table stays in ws for the pack: an open-addressing table of
+ *   2 * next_pow2(min(n, max_entries)) slots (at least 16), the home slot of a value v is the top
+ *   log2(slots) bits of (v ^ sign bit, zero-extended to 64 bits) * 0x9E3779B97F4A7C15, probing is
+ *   linear.  n = 0 clears state and does nothing else.
+ * nvt_pq_dict_pack: the same values and n / max_entries, and page_start[npages + 1] on the device:
+ *   page p holds values [page_start[p], page_start[p + 1]).  W = max(1, bit_length(d - 1)) is
+ *   derived from state on the device.  Page p's indices are ONE bit-packed run's payload --
+ *   W * ceil(nv_p / 8) bytes, LSB first, pad bits 0 -- at byte 16 * sum_{q<p} ceil(W *
+ *   ceil(nv_q / 8) / 16) of out; the bytes up to the next 16-byte boundary are written as 0.
+ *   Nothing is written when overflow is set; a page_start that is negative, descending or past n,
+ *   or an out_cap smaller than the total, sets overflow bit 1 and writes nothing either.
+ *   out 16-byte aligned.
+ * ws: nvt_pq_dict_ws_bytes(n, max_entries, npages) bytes, 16-byte aligned, the same buffer for both
+ * calls (build alone: npages = 0).  Stream-ordered, no allocation, no synchronisation. */
+#define NVT_PQ_DICT_MAX_ENTRIES (1u << 20)
+#define NVT_PQ_DICT_STATE_WORDS 4
+int nvt_pq_dict_ws_bytes(uint64_t n, uint64_t max_entries, uint64_t npages, uint64_t *bytes);
+int nvt_pq_dict_build(const void *values, int dtype, uint64_t n, uint64_t max_entries, void *dict,
+                      uint64_t *state, void *ws, uint64_t ws_bytes, void *stream);
+int nvt_pq_dict_pack(const void *values, int dtype, uint64_t n, uint64_t max_entries,
+                     const int64_t *page_start, uint64_t npages, uint64_t *state, uint8_t *out,
+                     uint64_t out_cap, void *ws, uint64_t ws_bytes, void *stream);
+
 /* ---- exact column medians: ops.FillMedian (MSD radix select) ----
  * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a
  * negative value and the sign bit of the others, integers flip the sign bit.  The two middle

@@ -362,6 +362,14 @@ SIGNATURES.update({
     "nvt_pqlist_unpack": [_vp, _vp, _i32, _u64, _i32, _i32, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
 })
 
+# include/nvt_hip.h NVT_PQ_DICT_MAX_ENTRIES / NVT_PQ_DICT_STATE_WORDS
+PQ_DICT_MAX_ENTRIES, PQ_DICT_STATE_WORDS = 1 << 20, 4
+SIGNATURES.update({
+    "nvt_pq_dict_ws_bytes": [_u64, _u64, _u64, C.POINTER(_u64)],
+    "nvt_pq_dict_build": [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
+    "nvt_pq_dict_pack": [_vp, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp],
+})
+
 class SelectCol(C.Structure):
     """nvt_select_col: one chunk of one column read by nvt_select_hist_many."""
     _fields_ = [("x", _vp), ("valid", _vp), ("n", _u64), ("dtype", C.c_int32), ("has_fill", C.c_int32),

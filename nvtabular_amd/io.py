@@ -18,7 +18,7 @@ import pandas as pd
 
 from .device import DeviceFrame, as_device_frame
 from .parquet_plain import READER_CHUNKS, PlainParquetFile, StagedPartition, read_row_groups_staged
-from .parquet_write import LAST_TIMING, device_permutation, plain_eligible, write_plain  # noqa: F401
+from .parquet_write import LAST_TIMING, device_permutation, dictionary_columns, plain_eligible, write_plain  # noqa: F401
 from .schema import Schema
 
 
@@ -323,7 +323,7 @@ class Dataset:
 
     def to_parquet(self, output_path, shuffle=None, out_files_per_proc=None, dtypes=None,
                    cats=None, conts=None, labels=None, preserve_files=False, suffix=".parquet",
-                   num_threads=0, compression=None, statistics=False, **_):
+                   num_threads=0, compression=None, statistics=False, use_dictionary=None, **_):
         """Write the (transformed) dataset as parquet (merlin.io.Dataset.to_parquet; contract in
         tests/unit/workflow/test_workflow.py:171-187,363-396,444-500 and
         bench/datasets/tools/nvt_etl.py:154-171 of the reference).
@@ -349,6 +349,20 @@ class Dataset:
         * ``statistics=True``: the PLAIN writer also records min / max of every column chunk
           (computed on the device next to the copy out); the null count of every chunk is always
           written.  pyarrow's writer always writes statistics.
+        * ``use_dictionary`` (pyarrow's name and value shapes): ``None`` / ``False`` (default) write
+          exactly the PLAIN pages described above.  ``True`` offers every flat int32 / int64 column
+          (after a ``dtypes`` cast), every datetime column and every list column of int32 / int64
+          leaves to the PLAIN writer's dictionary encoding, which runs on the device (columns of a
+          frame on the host are not offered); float columns stay PLAIN silently (repeated floats
+          are not dictionary-encoded).  A list of column names offers only those; a
+          name that is no column, or no such column, raises ``ValueError`` before any file is
+          created.  An offered column chunk gets a dictionary page (its distinct values, ascending)
+          and ``RLE_DICTIONARY`` data pages whose indices are bit-packed on the device, but only when
+          that makes the chunk smaller and it has at most 2^20 distinct values -- otherwise that
+          chunk stays PLAIN, so the option never makes a file larger ("Dictionary pages
+          in the PLAIN parquet writer").  When the frame goes to pyarrow's writer anyway (strings, a
+          codec, ``Shuffle.PER_WORKER`` with ``out_files_per_proc``, ``NVT_PLAIN_PARQUET=0``), a
+          value other than ``None`` is handed to pyarrow as its own ``use_dictionary``.
         * writes ``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and
           ``_metadata.json`` (file stats + cats / conts / labels) next to the data files.
         """
@@ -374,13 +388,16 @@ class Dataset:
                 not (shuffle == Shuffle.PER_WORKER and k):
             # fixed-width numeric columns: PLAIN pages written straight from pinned column
             # buffers (parquet_write.py) -- no dictionary pass, no compression, no statistics
+            offered = dictionary_columns(first, dtypes, use_dictionary)   # (raises before any file exists)
             names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
-                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS)
+                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered)
             collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
             schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
         else:
-            names, rows, order, schema, collector = _write_pyarrow(
-                parts, output_path, fname, k, shuffle, dtypes, {} if compression is None else {"compression": compression})
+            pq_kw = {} if compression is None else {"compression": compression}
+            if use_dictionary is not None:
+                pq_kw["use_dictionary"] = use_dictionary
+            names, rows, order, schema, collector = _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw)
         for md, j in zip(collector, order):
             md.set_file_path(names[j])
         _write_summary(output_path, [(names[j], rows.get(j, 0)) for j in order], schema, collector,

@@ -32,6 +32,13 @@ parquet writer").  The reading half below takes such lists too, from any writer 
 columns in the parquet reader"); other nested files are read with pyarrow.
 Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
 columns) stays with pyarrow's writer.
+With ``to_parquet(use_dictionary=...)`` an int32 / int64 column chunk (datetime counts and list leaves
+too) may instead be a dictionary page -- its distinct non-null values, ascending -- followed by data
+pages of the same cut whose values are ``W | ONE bit-packed run of indices`` (encoding
+RLE_DICTIONARY), handed over as ``DictPages``: dictionary and indices are made on the device
+(kernels_parquet_dict, csrc/nvt_parquet_dict.hip), and ``dict_pays`` keeps a chunk PLAIN unless
+the dictionary makes it smaller ("Dictionary pages in the PLAIN parquet writer").  Not
+done: float, string and bool dictionaries, RLE runs inside the index stream, DELTA encodings.
 The reading half also takes flat STRING columns (any writer's dictionary / PLAIN pages): their
 dictionary entries and index runs are staged as the file holds them and expanded, hashed and
 gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "String columns in
@@ -72,9 +79,15 @@ def timestamp_unit(logical) -> Optional[str]:
     return unit if unit in _TS_UNIT else None
 
 
-def _page_header(num_values: int, page_bytes: int) -> bytes:
-    dph = _Struct().i32(1, num_values).i32(2, 0).i32(3, 3).i32(4, 3).done()  # PLAIN, RLE, RLE
+def _page_header(num_values: int, page_bytes: int, encoding: int = 0) -> bytes:
+    dph = _Struct().i32(1, num_values).i32(2, encoding).i32(3, 3).i32(4, 3).done()  # PLAIN / RLE_DICTIONARY, RLE, RLE
     return _Struct().i32(1, 0).i32(2, page_bytes).i32(3, page_bytes).struct(5, dph).done()
+
+
+def _dict_page_header(d: int, page_bytes: int) -> bytes:
+    """PageHeader of a DICTIONARY_PAGE (type 2) of d PLAIN values."""
+    return (_Struct().i32(1, 2).i32(2, page_bytes).i32(3, page_bytes)
+            .struct(7, _Struct().i32(1, d).i32(2, 0).done()).done())
 
 
 def _def_levels(n: int, valid_bytes: Optional[memoryview]) -> Tuple[bytes, Optional[memoryview]]:
@@ -115,6 +128,83 @@ class ListLevels:
         self.rep, self.dfn = rep, dfn
 
 
+DICT_MAX_ENTRIES = 1 << 20     # distinct values of a dictionary-encoded chunk (an 8 MiB int64 dictionary page)
+
+
+def dict_index_width(d: int) -> int:
+    """Bits per index of a dictionary of d entries: max(1, bit_length(d - 1))."""
+    return max(1, (int(d) - 1).bit_length())
+
+
+def dict_page_offsets(nv, W: int):
+    """(byte offset of every page's indices in ``DictPages.packed``, total bytes): page p's
+    ``W * ceil(nv[p] / 8)`` bytes start at ``16 * sum_{q<p} ceil(W * ceil(nv[q] / 8) / 16)``."""
+    at, pos = [], 0
+    for x in nv:
+        at.append(pos)
+        pos += 16 * (-(-(W * ((int(x) + 7) // 8)) // 16))
+    return at, pos
+
+
+def dict_index_bytes(nv, W: int) -> int:
+    """Bytes the index streams of the data pages take: per page the width byte and, when the page
+    has values, the header and the payload of ONE bit-packed run."""
+    return sum(1 + (len(_varint((((int(x) + 7) // 8) << 1) | 1)) + W * ((int(x) + 7) // 8) if x else 0) for x in nv)
+
+
+def dict_pays(d: int, nv, itemsize: int) -> bool:
+    """The chunk rule: a chunk of sum(nv) non-null values with d distinct ones is dictionary-encoded
+    iff it has values, d <= DICT_MAX_ENTRIES and dictionary + indices are SMALLER than the values."""
+    m = sum(int(x) for x in nv)
+    return m > 0 and d <= DICT_MAX_ENTRIES and \
+        d * itemsize + dict_index_bytes(nv, dict_index_width(d)) < m * itemsize
+
+
+class DictPages:
+    """One dictionary-encoded column chunk, as ``write_row_group`` takes it in the place of the
+    values: ``dictionary`` (the d distinct non-null values, ascending, the column's dtype),
+    ``packed`` (bytes-like: page p's indices -- the payload of ONE bit-packed run at ``W`` bits, LSB
+    first, pad bits 0 -- at ``dict_page_offsets(nv, W)[0][p]``) and ``nv[p]``, the non-null values of
+    data page p (the pages are cut where a PLAIN chunk's are).  The device packs them
+    (kernels_parquet_dict; tests/pq_dict_reference.py restates the layout).  Like the values,
+    ``dictionary`` and ``packed`` may still be in flight when the row group is laid out."""
+
+    __slots__ = ("dictionary", "packed", "W", "nv", "at")
+
+    def __init__(self, dictionary, packed, W, nv):
+        self.dictionary, self.packed, self.W = dictionary, packed, int(W)
+        self.nv = [int(x) for x in nv]
+        d = int(np.asarray(dictionary).size)
+        if d < 1 or self.W != dict_index_width(d):
+            raise ValueError(f"DictPages: index width {self.W} for a dictionary of {d} entries")
+        self.at, total = dict_page_offsets(self.nv, self.W)
+        if len(packed) < total:
+            raise ValueError(f"DictPages: {len(packed)} packed bytes, the pages take {total}")
+
+    @property
+    def dtype(self):
+        return np.asarray(self.dictionary).dtype
+
+    def prologue(self, dt, at):
+        """([(offset, bytes-like)] of the dictionary page laid out from ``at``, the offset behind it)."""
+        dic = np.asarray(self.dictionary)
+        if dic.dtype != dt or dic.ndim != 1 or not dic.flags.c_contiguous:
+            raise TypeError(f"PlainParquetWriter: dictionary is {dic.dtype}, the file's column is {dt}")
+        head = _dict_page_header(dic.size, dic.size * dt.itemsize)
+        return [(at, head), (at + len(head), memoryview(dic).cast("B"))], at + len(head) + dic.size * dt.itemsize
+
+    def indices(self, p, nv):
+        """[bytes-like] of data page p's value section: the width byte, then the run."""
+        if not 0 <= p < len(self.nv) or self.nv[p] != nv:
+            raise ValueError(f"PlainParquetWriter: page {p} has {nv} non-null values, its DictPages say "
+                             f"{self.nv[p] if 0 <= p < len(self.nv) else 'nothing'}")
+        if nv == 0:
+            return [bytes([self.W])]
+        groups = (nv + 7) // 8
+        return [bytes([self.W]) + _varint((groups << 1) | 1),
+                memoryview(self.packed).cast("B")[self.at[p]: self.at[p] + groups * self.W]]
+
+
 class PlainParquetWriter:
     """One parquet file of int32 / int64 / float32 / float64 columns, flat or "list of" such leaves,
     every column OPTIONAL (like pyarrow writes nullable Arrow columns), PLAIN encoding, no
@@ -153,7 +243,10 @@ class PlainParquetWriter:
         self.pending = []
 
     def _plan_column(self, values, valid, n, dt, start):
-        """[(offset, bytes-like)] of one column chunk laid out from `start`, and its size."""
+        """[(offset, bytes-like)] of one column chunk laid out from `start`, its size and the
+        offset of its first data page."""
+        if isinstance(values, DictPages):
+            return self._plan_dict_column(values, valid, n, dt, start)
         values = np.asarray(values)
         if values.dtype != dt or not values.flags.c_contiguous:
             # never cast here: the buffer may still be the target of an asynchronous device-to-host
@@ -191,11 +284,42 @@ class PlainParquetWriter:
         if done_vals != values.size:
             raise ValueError("PlainParquetWriter: the values do not match the validity bitmap "
                              f"({values.size} values, {done_vals} valid rows)")
-        return segs, at - start
+        return segs, at - start, start
+
+    def _plan_dict_column(self, dp, valid, n, dt, start):
+        """A flat chunk of dictionary pages: dictionary page | data pages (header | def levels | W | run)."""
+        vb = memoryview(np.ascontiguousarray(valid)).cast("B") if valid is not None else None
+        segs, at = dp.prologue(dt, start)
+        first = at
+        done_rows, p = 0, 0
+        while True:
+            rows = min(PAGE_VALUES, n - done_rows)
+            if vb is not None:
+                page_valid = vb[done_rows // 8: (done_rows + rows + 7) // 8]
+                nv = int(np.unpackbits(np.frombuffer(page_valid, dtype=np.uint8),
+                                       bitorder="little")[:rows].sum()) if rows else 0
+            else:
+                page_valid, nv = None, rows
+            prefix, bitmap = _def_levels(rows, page_valid)
+            bufs = [bitmap] + dp.indices(p, nv)
+            body = len(prefix) + sum(len(b) for b in bufs if b is not None)
+            for buf in [_page_header(rows, body, 8) + prefix] + bufs:
+                if buf is not None and len(buf):
+                    segs.append((at, buf))
+                    at += len(buf)
+            done_rows += rows
+            p += 1
+            if done_rows >= n:
+                break
+        if p != len(dp.nv):
+            raise ValueError(f"PlainParquetWriter: {p} data pages, the DictPages hold {len(dp.nv)}")
+        return segs, at - start, first
 
     def _plan_list_column(self, values, levels, dt, start):
-        """The same for a list column: page = header | rep levels | def levels | non-null leaves."""
-        values = np.asarray(values)
+        """The same for a list column: page = header | rep levels | def levels | non-null leaves
+        (a DictPages in the place of the values: ... | W | run of indices)."""
+        dp = values if isinstance(values, DictPages) else None
+        values = np.asarray(values if dp is None else dp.dictionary)
         if values.dtype != dt or values.ndim != 1 or not values.flags.c_contiguous:
             raise TypeError(f"PlainParquetWriter: leaf buffer is {values.dtype} "
                             f"(contiguous={values.flags.c_contiguous}), the file's column is list of {dt}")
@@ -206,6 +330,11 @@ class PlainParquetWriter:
         if not (len(levels.nonnull) == len(levels.rep_at) == len(levels.def_at) == npages):
             raise ValueError("PlainParquetWriter: the page table's columns differ in length")
         segs, at, done_vals = [], start, 0
+        if dp is not None:
+            segs, at = dp.prologue(dt, start)
+            if len(dp.nv) != npages:
+                raise ValueError(f"PlainParquetWriter: {npages} data pages, the DictPages hold {len(dp.nv)}")
+        first = at
         for p in range(npages):
             slots, nv = levels.slots[p], levels.nonnull[p]
             groups = (slots + 7) // 8
@@ -215,11 +344,12 @@ class PlainParquetWriter:
             if r0 < 0 or d0 < 0 or r0 + groups > len(rep) or d0 + 2 * groups > len(dfn):
                 raise ValueError(f"PlainParquetWriter: the level bytes do not match the page table (page {p}: "
                                  f"{slots} slots at {r0} of {len(rep)} rep bytes, at {d0} of {len(dfn)} def bytes)")
-            payload = vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize]
+            payload = [vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize]] if dp is None else \
+                dp.indices(p, nv)
             rhead, dhead = _packed_levels(slots, 1), _packed_levels(slots, 2)
-            body = len(rhead) + groups + len(dhead) + 2 * groups + nv * dt.itemsize
-            for buf in (_page_header(slots, body) + rhead, rep[r0: r0 + groups], dhead,
-                        dfn[d0: d0 + 2 * groups], payload):
+            body = len(rhead) + groups + len(dhead) + 2 * groups + sum(len(b) for b in payload)
+            for buf in [_page_header(slots, body, 0 if dp is None else 8) + rhead, rep[r0: r0 + groups], dhead,
+                        dfn[d0: d0 + 2 * groups]] + payload:
                 if len(buf):
                     segs.append((at, buf))
                     at += len(buf)
@@ -230,10 +360,10 @@ class PlainParquetWriter:
             body = 2 * (struct.pack("<I", len(empty)) + empty)
             segs.append((at, _page_header(0, len(body)) + body))
             at += len(segs[-1][1])
-        if done_vals != values.size:
+        if dp is None and done_vals != values.size:
             raise ValueError("PlainParquetWriter: the values do not match the page table "
                              f"({values.size} values, {done_vals} non-null leaves)")
-        return segs, at - start
+        return segs, at - start, first
 
     def _run(self, segs, ready=None):
         if ready is not None:
@@ -248,7 +378,8 @@ class PlainParquetWriter:
         """columns[j] = (values, valid): `values` a 1-D numpy array of the column's dtype holding
         the NON-NULL values in row order, `valid` None or the Arrow validity bitmap (uint8, LSB
         first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
-        non-null LEAVES of the n rows in order and their ``ListLevels``.  Argument errors raise
+        non-null LEAVES of the n rows in order and their ``ListLevels``.  A dictionary-encoded chunk
+        (of either kind): a ``DictPages`` in the place of ``values``.  Argument errors raise
         before anything of the row group is written.  wait=False (with a pool): returns the
         futures of the column writes instead of waiting for them -- the layout is fixed, so later
         row groups (of this or of other files) can be written meanwhile; the caller keeps the
@@ -271,17 +402,18 @@ class PlainParquetWriter:
                 raise TypeError(f"PlainParquetWriter: column '{name}' is a {'list' if self.lists[j] else 'flat'} "
                                 f"column of the file, this row group passes it as the other kind")
             if self.lists[j]:
-                segs, size = self._plan_list_column(values, valid, dt, start)
+                segs, size, first = self._plan_list_column(values, valid, dt, start)
                 nv = sum(valid.slots)   # (num_values of a list chunk counts slots, not leaves or rows)
             else:
-                segs, size = self._plan_column(values, valid, n, dt, start)
+                segs, size, first = self._plan_column(values, valid, n, dt, start)
                 nv = n
             plans.append(segs)
             pos += size
-            nvalid = int(np.asarray(values).size)
+            is_dict = isinstance(values, DictPages)
+            nvalid = sum(values.nv) if is_dict else int(np.asarray(values).size)
             chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
                                minmax=stats[j] if (stats is not None and nvalid > 0) else None,
-                               is_list=self.lists[j]))
+                               is_list=self.lists[j], first_data=first if is_dict else None))
             total += size
         self.pos = pos
         futures = []
@@ -319,10 +451,17 @@ class PlainParquetWriter:
         if hi is not None:
             st.binary(5, hi).binary(6, lo)               # max_value / min_value
         path = [name, "list", "element"] if c.get("is_list") else [name]
-        meta = (_Struct().i32(1, _PQ_TYPE[dt]).list(2, _CT_I32, [_zigzag(0), _zigzag(3)])
+        # a dictionary chunk: encodings PLAIN, RLE, RLE_DICTIONARY; data_page_offset (9) is its first
+        # data page, dictionary_page_offset (11) the chunk's start; the sizes include the dictionary
+        first = c.get("first_data")
+        meta = (_Struct().i32(1, _PQ_TYPE[dt])
+                .list(2, _CT_I32, [_zigzag(0), _zigzag(3)] + ([_zigzag(8)] if first is not None else []))
                 .list(3, _CT_BINARY, [_varint(len(x.encode())) + x.encode() for x in path])
-                .i32(4, 0).i64(5, c["n"]).i64(6, c["size"]).i64(7, c["size"]).i64(9, c["start"])
-                .struct(12, st.done()).done())
+                .i32(4, 0).i64(5, c["n"]).i64(6, c["size"]).i64(7, c["size"])
+                .i64(9, c["start"] if first is None else first))
+        if first is not None:
+            meta.i64(11, c["start"])
+        meta = meta.struct(12, st.done()).done()
         return _Struct().i64(2, c["start"]).struct(3, meta).done()
 
     def close(self):

@@ -9,7 +9,13 @@ List columns: the repetition / definition levels of a row group are packed on th
 (kernels_parquet_list: the columns that share an offsets tensor share one plan and one repetition
 stream); ONE read-back per row group and offsets tensor brings the page table, the stream sizes and
 the non-null counts, then the level bytes and the non-null leaves are copied out like the values of
-a flat column ("List columns in the PLAIN parquet writer")."""
+a flat column ("List columns in the PLAIN parquet writer").
+Dictionary pages (``use_dictionary``): the non-null values of every OFFERED column of a row group
+go through kernels_parquet_dict (dictionary build + index pack, enqueued for all of them first);
+ONE read-back per row group brings their state records {d, overflow} and page starts, the chunk
+rule (``parquet_plain.dict_pays``) is applied on the host, and each chunk then copies out what it
+really needs: dictionary + packed indices, or the plain values ("Dictionary pages in
+the PLAIN parquet writer")."""
 from __future__ import annotations
 
 import os
@@ -23,13 +29,15 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from . import kernels_parquet_dict as KPD
 from . import kernels_parquet_list as KPL
 from . import parquet_plain as PP
 from .device import pack_bitmap_device
-from .parquet_plain import ListLevels, PlainParquetWriter
+from .parquet_plain import DictPages, ListLevels, PlainParquetWriter
 
 # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
-# levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables
+# levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables;
+# dict_s (a part of stage_s): enqueueing dictionary build + pack and waiting for the state records
 LAST_TIMING = {}
 _TORCH_OF = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
 
@@ -42,12 +50,13 @@ class _Column(NamedTuple):
     logical: Any                             # datetime64 dtype of a flat column, or None
     offsets: Optional[torch.Tensor] = None   # of a list column
     bitmap: Optional[torch.Tensor] = None    # leaf bitmap of a list column (what `mask` unpacks)
+    offered: bool = False                    # its chunks are dictionary-encoded where that pays
 
 
 class _HostColumn(NamedTuple):
     """One column of a staged row group, as PlainParquetWriter.write_row_group takes it."""
     name: str
-    values: np.ndarray   # the non-null values / leaves (pinned; may still be in flight)
+    values: Any          # the non-null values / leaves (pinned; may still be in flight), or a DictPages
     valid: Any           # None, the rows' validity bitmap (uint8 array) or a list column's ListLevels
     logical: Any
 
@@ -82,6 +91,38 @@ def plain_eligible(frame, dtypes) -> bool:
     return True
 
 
+def _dict_eligible(col, dtypes, name) -> bool:
+    """A column of a plain-eligible frame whose chunks can be dictionary-encoded: int32 / int64 (after
+    the requested cast; datetime counts are int64), flat or as list leaves, on the device."""
+    dt = np.dtype(dtypes[name]) if (dtypes and name in dtypes) else None
+    is_int = (dt in (np.dtype("int32"), np.dtype("int64"))) if dt is not None else \
+        col.data.dtype in (torch.int32, torch.int64)
+    return bool(is_int and col.strings is None and col.data.is_cuda)
+
+
+def dictionary_columns(frame, dtypes, use_dictionary):
+    """``to_parquet(use_dictionary=...)`` for a frame ``plain_eligible`` takes -> the names of the
+    columns offered for dictionary encoding.  None / False: none; True: every eligible column (float
+    columns stay PLAIN silently); a list of names: those -- a name that is no column or no eligible
+    column raises ValueError."""
+    if use_dictionary is None or use_dictionary is False:
+        return frozenset()
+    eligible = [name for name, col in frame.items() if _dict_eligible(col, dtypes, name)]
+    if use_dictionary is True:
+        return frozenset(eligible)
+    if isinstance(use_dictionary, (str, bytes)):
+        raise ValueError(f"to_parquet: use_dictionary takes None, a bool or a list of column names, not {use_dictionary!r}")
+    names = list(use_dictionary)
+    cols = [name for name, _ in frame.items()]
+    for name in names:
+        if name not in cols:
+            raise ValueError(f"to_parquet: use_dictionary names '{name}', which is no column of {cols}")
+        if name not in eligible:
+            raise ValueError(f"to_parquet: use_dictionary names '{name}': only int32 / int64 and datetime columns "
+                             f"and lists of int32 / int64 on the device are dictionary-encoded (these: {eligible})")
+    return frozenset(names)
+
+
 def device_permutation(n: int, frame):
     return torch.randperm(n, device=next((col.data.device for _, col in frame.items()), None))
 
@@ -94,23 +135,26 @@ def _to_host(t):
     return h
 
 
-def _prepare(part, n, dtypes):
+def _prepare(part, n, dtypes, offered=frozenset()):
     """-> ([_Column] of a partition of n rows, [[list columns that share one offsets tensor]]: they share
-    plan, page table and repetition stream)."""
+    plan, page table and repetition stream).  ``offered``: names of the columns whose chunks may be
+    dictionary-encoded."""
     cols, groups = [], {}
     for name, col in part.items():
         col = col.materialize()
         if col.offsets is not None:
             leaves = col.data.contiguous()
             mask = K.unpack_bitmap(col.valid, leaves.numel()) if col.valid is not None else None
-            cols.append(_Column(name, leaves, mask, None, col.offsets.contiguous(), col.valid))
+            cols.append(_Column(name, leaves, mask, None, col.offsets.contiguous(), col.valid,
+                                name in offered and leaves.is_cuda and leaves.dtype in (torch.int32, torch.int64)))
             groups.setdefault((cols[-1].offsets.data_ptr(), cols[-1].offsets.numel()), []).append(cols[-1])
             continue
         data = col.data
         if dtypes and name in dtypes:
             data = data.to(_TORCH_OF[str(np.dtype(dtypes[name]))])
         mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
-        cols.append(_Column(name, data, mask, col.logical))
+        cols.append(_Column(name, data, mask, col.logical, offered=name in offered and data.is_cuda and
+                            data.dtype in (torch.int32, torch.int64)))
     return cols, list(groups.values())
 
 
@@ -148,9 +192,10 @@ def _min_max(vals):
     return _to_host(torch.stack([lo, hi]))
 
 
-def _stage_column(c: _Column, s0, s1, levels, statistics, keep):
-    """Rows [s0, s1) of one column on their way to the host -> (_HostColumn, min / max or None)."""
-    vals, valid = c.data[s0:s1], None
+def _column_values(c: _Column, s0, s1, levels):
+    """Rows [s0, s1) of one column, still where the column is -> (the non-null values / leaves, None or the
+    rows' validity bitmap or the list column's ListLevels, the rows' bool mask of a flat column or None)."""
+    vals, valid, m = c.data[s0:s1], None, None
     if c.offsets is not None and s1 > s0:
         valid, leaves = levels[c.name]
         vals = c.data[leaves] if c.mask is None else c.data[leaves][c.mask[leaves]]
@@ -160,11 +205,44 @@ def _stage_column(c: _Column, s0, s1, levels, statistics, keep):
         m = c.mask[s0:s1]
         vals = vals[m]
         valid = pack_bitmap_device(m) if m.is_cuda else torch.from_numpy(np.packbits(m.numpy(), bitorder="little"))
-    hv = _to_host(vals)
+    return vals, valid, m
+
+
+def _page_start(vals, valid, m, rows):
+    """int64[pages + 1] on the device: the positions in ``vals`` (the non-null values) at which the data
+    pages of the chunk start -- a list column: from the non-null counts of its page table; a flat column:
+    from the per-page popcounts of the row mask, or by arithmetic when there is no mask."""
+    dev = vals.device
+    if isinstance(valid, ListLevels):
+        ps = np.concatenate([[0], np.cumsum(valid.nonnull)]).astype(np.int64)
+        return torch.from_numpy(ps).to(dev)
+    npages = max(1, -(-rows // PP.PAGE_VALUES))
+    if m is None:
+        return torch.clamp(torch.arange(npages + 1, device=dev, dtype=torch.int64) * PP.PAGE_VALUES, max=rows)
+    padded = torch.zeros(npages * PP.PAGE_VALUES, dtype=torch.bool, device=dev)
+    padded[:rows] = m
+    counts = padded.view(npages, PP.PAGE_VALUES).sum(dim=1, dtype=torch.int64)
+    return torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+
+
+def _stage_column(c: _Column, vals, valid, encoded, statistics, keep):
+    """One column of a row group on its way to the host -> (_HostColumn, min / max or None).
+    ``encoded``: None, or (DeviceDict, d, overflow, page starts) of an offered column after the read-back."""
+    hv = None
+    if encoded is not None:
+        dd, d, overflow, ps = encoded
+        nv = np.diff(ps)
+        if not overflow and PP.dict_pays(d, nv, vals.element_size()):
+            W = PP.dict_index_width(d)
+            hd, hp = _to_host(dd.dictionary[:d]), _to_host(dd.packed[:PP.dict_page_offsets(nv, W)[1]])
+            hv = DictPages(hd.numpy(), hp.numpy(), W, nv)
+            keep.append((dd, hd, hp))
+    if hv is None:
+        hv = _to_host(vals).numpy()
     hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
     mm = _min_max(vals) if statistics else None
-    keep.append((vals, valid, mm))
-    return _HostColumn(c.name, hv.numpy(), hb, c.logical), (mm.numpy() if mm is not None else None)
+    keep.append((vals, valid, mm, hv))
+    return _HostColumn(c.name, hv, hb, c.logical), (mm.numpy() if mm is not None else None)
 
 
 def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
@@ -174,8 +252,16 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
     t_st = time.perf_counter()
     with torch.cuda.stream(copy_s) if copy_s is not None else nullcontext():
         levels = _pack_levels(groups, s0, s1, keep) if (s1 > s0 and groups) else {}
-        for c in cols:
-            hc, mm = _stage_column(c, s0, s1, levels, statistics, keep)
+        staged = [_column_values(c, s0, s1, levels) for c in cols]
+        # dictionary pages: build + pack of every offered column that has values, then ONE read-back
+        t_dc = time.perf_counter()
+        dicts = {ci: KPD.encode(vals.contiguous(), _page_start(vals, valid, m, s1 - s0))
+                 for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)) if c.offered and vals.numel()}
+        states = dict(zip(dicts, KPD.read_back_states(list(dicts.values()))))
+        if dicts:
+            LAST_TIMING["dict_s"] += time.perf_counter() - t_dc
+        for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
+            hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep)
             host.append(hc)
             if statistics:
                 stats.append(mm)
@@ -273,13 +359,15 @@ def _row_ranges(i, n, k, row_group, touched):
             yield j, s0, min(b, s0 + row_group)
 
 
-def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads):
+def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads,
+                offered=frozenset()):
     """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
     with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
     ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
+    ``offered``: the columns whose chunks are dictionary-encoded where that makes them smaller.
     -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
     LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
-                       levels_s=0.0)
+                       levels_s=0.0, dict_s=0.0)
     t_all = time.perf_counter()
     copy_s = None
     touched = set()
@@ -290,7 +378,7 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
                 n = len(part)
                 if shuffle is not None and n > 1:
                     part = part.take_rows(device_permutation(n, part))
-                cols, groups = _prepare(part, n, dtypes)
+                cols, groups = _prepare(part, n, dtypes, offered)
                 on_gpu = any(c.data.is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
