@@ -111,7 +111,7 @@ struct OrderSortedJob {
   uint64_t flat_slots;
 };
 int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t s);
-// LDS head image of an ordered int32 vocabulary for the cache-mode encode (nvt_encode.hip)
+// LDS head image of an ordered int32 vocabulary for the cache-mode encode (nvt_encode_build.hip)
 int encode_head_build(const int32_t *vocab_keys, uint64_t n, int64_t first_label, void *image,
                       hipStream_t s);
 int encode_head_build_many(const int32_t *const *vocab_keys, const uint64_t *n, const int64_t *first_label,
@@ -135,7 +135,7 @@ struct OrderTail {
 };
 int vocab_order_tail_batch(const OrderTail *t, int nt, hipStream_t s);
 
-// nvt_encode.hip
+// nvt_encode_build.hip
 int encode_clear_any(int key_bytes, void *table, uint64_t capacity, int64_t *sentinel_label,
                      hipStream_t s);
 // insert vocab[0 .. n) with labels first_label + i into an already cleared / partly filled table

@@ -1,6 +1,6 @@
 // Monotone key -> slot map of the range path, shared by the counting kernels
 // (nvt_range_count.hip), the vocabulary ordering (nvt_vocab_order.hip) and the encode kernel
-// (nvt_encode.hip): the per-bucket LDS tables of the counting pass are dumped as they are and
+// (nvt_encode_pipe.hpp): the per-bucket LDS tables of the counting pass are dumped as they are and
 // BECOME the encode table ("range table"), so all three must address it the same way.
 #pragma once
 #include "nvt_common.hpp"

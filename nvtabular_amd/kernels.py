@@ -5,8 +5,9 @@ every O(rows) computation below is a hand-written gfx950 kernel reached through
 ``libnvt_hip.so``.  Nothing in this module has a CPU code path.
 
 This file is the facade of the host driver: the subjects with a module of their own
-(``kernels_count.py``: Categorify's counting driver and its path policy; ``kernels_groupby.py``,
-``kernels_lookup.py``, ``kernels_exchange.py``) are re-exported at the bottom, and the switches
+(``kernels_count.py``: Categorify's counting driver and its path policy; ``kernels_encode.py``: its
+encode tables and their kind policy; ``kernels_groupby.py``, ``kernels_lookup.py``,
+``kernels_exchange.py``) are re-exported at the bottom, and the switches
 that tests, bench.py or a tool assign live here -- those modules read them as ``K.<NAME>`` when
 they are called.
 """
@@ -300,7 +301,6 @@ PATH_TINY_MAX = 64                  # path 6: path 0 with hot keys replicated pe
 # most distinct keys the range path (path 9) is started on; beyond: the sort path
 PATH_RANGE_MAX_DISTINCT = int(os.environ.get("NVT_RANGE_MAX", 6_500_000))
 RANGE_PIECES = 64   # nvt_range.hpp kRpPieces: pieces of the piecewise range map (range_splitters)
-USE_FLAT_TABLE = os.environ.get("NVT_FLAT_TABLE", "1") != "0"
 _check_streams = {}   # device index -> side stream of the read-backs that must not wait for work queued later
 # Columns of one nvt_dense_count_many call that are given different workspaces run on different
 # internal streams (include/nvt_hip.h); COUNT_STREAMS workspaces are kept per device.
@@ -536,365 +536,9 @@ def vocab_sort(keys: torch.Tensor, counts: torch.Tensor, max_count: int = 0):
 
 
 # --------------------------------------------------------------------------
-# Categorify.transform: encode tables
+# Categorify.transform (kernels_encode.py): what bench.py and A / B runs set on the facade
 # --------------------------------------------------------------------------
-ENCODE_RESIDENT_I32, ENCODE_RESIDENT_I64 = 8192, 6144  # include/nvt_hip.h
-_ENC_BYTES = {}   # (key_bytes, capacity) -> nvt_encode_table_bytes
 ASYNC_FINALIZE = os.environ.get("NVT_ASYNC_FINALIZE", "1") != "0"
-_SORT_BYTES = {}  # (key_bytes, n) -> nvt_vocab_sort_tmp_bytes
-
-
-ENCODE_HEAD_IMAGE = os.environ.get("NVT_ENCODE_HEAD_IMAGE", "1") != "0"
-
-
-class EncodeTable:
-    """key -> label probe table built from an ordered vocabulary."""
-
-    FLAT_AUX_WORDS, FLAT_AUX_MAXDISP = 8192 + 16, 8192 + 8   # include/nvt_hip.h NVT_FLAT_AUX_*
-    FLAT_MAX_DISPLACEMENT = 4096   # longer probe runs than this: the keys cluster, use a hashed table
-
-    def __init__(self, vocab_keys: torch.Tensor, first_label: int, unique: bool = False,
-                 defer_build: bool = False, range_table=None, flat: bool = False):
-        """range_table = (table, aux, bits): the table was dumped by the range path of the
-        counting stage and is addressed by the monotone map stored in ``aux``; it is completed
-        (positions -> labels) by nvt_vocab_finalize_many -- no table is allocated or built here."""
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.suffix = _key_suffix(vocab_keys)
-        self.key_dtype = vocab_keys.dtype
-        self.key_bytes = 4 if self.suffix == "i32" else 8
-        self.n_vocab = int(vocab_keys.numel())
-        self.first_label = int(first_label)
-        self.unique = bool(unique)
-        self.capacity = next_pow2(max(64, (4 if self.n_vocab <= (1 << 20) else 2) * self.n_vocab + 1))
-        dev = vocab_keys.device
-        vk = vocab_keys.contiguous()
-        self._vk = vk
-        # kept: the head of the (frequency-ordered, duplicate-free) vocabulary is staged in LDS
-        self.vocab_keys = vk if unique else None
-        # a duplicate-free vocabulary that fits the LDS table in full (include/nvt_hip.h:
-        # NVT_ENCODE_RESIDENT_*) is encoded from LDS alone: no global table, no build kernel
-        resident = ENCODE_RESIDENT_I32 if self.key_bytes == 4 else ENCODE_RESIDENT_I64
-        self.table = self.sentinel_label = None
-        self.range_aux, self.range_bits = None, 0
-        self.flat_slots = 0
-        self.sort_tmp = None
-        self._counts = None    # the counts tensor while an internal stream still orders it
-        self._src = None       # key-sorted source list of the one-pass ordering, same lifetime
-        self.ready = None      # Event recorded behind the sort / build on an internal stream
-        self.pending = False   # True until the current stream has been made to wait for it
-        self._release = False  # True between fill_encode_desc and release_ordering (encode_many)
-        # the LDS head of the cache-mode encode, built ONCE per vocabulary by
-        # nvt_vocab_finalize_many (include/nvt_hip.h nvt_vocab_col.head_image): only tables whose
-        # vocabulary is ordered there (defer_build) get one
-        self.head_image = None
-        if unique and 0 < self.n_vocab <= resident:
-            return
-        if ENCODE_HEAD_IMAGE and defer_build and unique and self.key_bytes == 4:
-            self.head_image = torch.empty(_lib.ENCODE_HEAD_BYTES, dtype=torch.uint8, device=dev)
-        if range_table is not None:
-            assert defer_build and unique and self.key_bytes == 4
-            self.table, self.range_aux, self.range_bits = range_table
-            self.capacity = 0
-            self.sentinel_label = torch.empty(1, dtype=torch.int64, device=dev)
-            return
-        if flat and USE_FLAT_TABLE and defer_build and unique and self.key_bytes == 4:
-            # flat range table laid out from the key-sorted source by nvt_vocab_finalize_many
-            # (prefix maximum, no random inserts): 2^k >= 2 n slots + n + 64 tail slots
-            # home slots at load FLAT_INDEX_LOAD (no power of two: 36 M keys took 2^27 slots = 1 GiB
-            # to clear and fill, now 576 MB)
-            self.flat_slots = max(64, int(self.n_vocab / FLAT_INDEX_LOAD) + 1)
-            self.capacity = self.flat_slots + self.n_vocab + 64
-            self.table = torch.empty(self.capacity * 8, dtype=torch.uint8, device=dev)
-            self.range_aux = torch.empty(self.FLAT_AUX_WORDS, dtype=torch.int32, device=dev)
-            self.sentinel_label = torch.empty(1, dtype=torch.int64, device=dev)
-            return
-        key = (self.key_bytes, self.capacity)
-        nbytes = _ENC_BYTES.get(key)
-        if nbytes is None:
-            out = C.c_uint64()
-            check(self.lib.nvt_encode_table_bytes(self.key_bytes, self.capacity, C.byref(out)))
-            nbytes = _ENC_BYTES[key] = out.value
-        self.table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.sentinel_label = torch.empty(1, dtype=torch.int64, device=dev)
-        if defer_build:  # built by nvt_vocab_finalize_many, after the vocabulary is ordered
-            return
-        check(
-            getattr(self.lib, f"nvt_encode_build_{self.suffix}")(
-                vk.data_ptr() if self.n_vocab else None, self.n_vocab, self.first_label,
-                self.table.data_ptr(), self.capacity, self.sentinel_label.data_ptr(),
-                1 if unique else 0, stream_ptr(),
-            ),
-            "nvt_encode_build",
-        )
-
-    def fill_vocab_desc(self, d: "_lib.VocabCol", counts: torch.Tensor, max_count: int, src=None):
-        """One nvt_vocab_col: order (self vocab keys, counts) in place, then build the table.
-        ``src`` = (keys, counts, cls_hist, n_big) of a KEY-SORTED list (range path): the
-        vocabulary is then written out of place into (self vocab keys, counts) by one stable
-        counting pass that also fills the table."""
-        n = self.n_vocab
-        if src is not None:
-            return self._fill_vocab_desc_sorted(d, counts, max_count, src)
-        d.src_keys = d.src_counts = d.cls_hist = d.range_aux = None
-        d.n_big = 0
-        d.range_nb_log2 = 0
-        d.flat_slots = 0
-        # the counts are ordered in place on the same internal stream as the keys: they must
-        # outlive the hand-off event exactly like keys / table / sort_tmp (a rank that writes
-        # no artifacts used to drop its only reference right after the launch)
-        self._counts = counts
-        d.keys = self._vk.data_ptr()
-        d.counts = counts.data_ptr()
-        d.n = n
-        d.max_count = int(max_count)
-        d.key_bytes = self.key_bytes
-        d.unique_keys = 1 if self.unique else 0
-        small = self.key_bytes == 4 and 2 <= n <= 16384 and 0 < int(max_count) < (1 << 32)
-        if n > 1 and not small:
-            key = (self.key_bytes, n)
-            nbytes = _SORT_BYTES.get(key)
-            if nbytes is None:
-                out = C.c_uint64()
-                check(self.lib.nvt_vocab_sort_tmp_bytes(self.key_bytes, n, C.byref(out)))
-                nbytes = _SORT_BYTES[key] = out.value
-            self.sort_tmp = torch.empty(nbytes + 16, dtype=torch.uint8, device=self._vk.device)
-            d.sort_tmp = self.sort_tmp.data_ptr()
-        else:
-            d.sort_tmp = None
-        d.first_label = self.first_label
-        d.table = ptr(self.table)
-        d.capacity = self.capacity
-        d.sentinel_label = ptr(self.sentinel_label)
-        d.head_image = ptr(self.head_image)
-        if n > 1 and not small and ASYNC_FINALIZE:
-            # ordered on an internal stream: hand-off by event instead of a stream join, so the
-            # caller's stream keeps working (fill + normalize, encodes of the small vocabularies)
-            # underneath this vocabulary's radix passes and table build
-            if self.ready is None:
-                self.ready = Event()
-            d.ready_event = self.ready.handle
-            self.pending = True
-        else:
-            d.ready_event = None
-
-    def _fill_vocab_desc_sorted(self, d, counts, max_count, src):
-        src_keys, src_counts, cls_hist, n_big = src[:4]
-        # (a fifth element: int32 positions of the source entries in the vocabulary order -- a
-        # multi-GPU fit whose owners labelled their shards; no ordering pass is run then)
-        labels = src[4] if len(src) > 4 else None
-        if labels is not None:
-            assert labels.dtype == torch.int32 and labels.numel() == src_keys.numel()
-            labels, n_big = labels.contiguous(), 0
-            stat_add("labelled_vocabularies")
-        n = self.n_vocab
-        assert self.key_bytes == 4 and src_keys.numel() == n and counts.numel() == n
-        self._counts = counts
-        self._src = (src_keys, src_counts, cls_hist, labels)  # read on an internal stream until `ready`
-        d.keys = self._vk.data_ptr()
-        d.counts = counts.data_ptr()
-        d.n = n
-        d.max_count = int(max_count)
-        d.key_bytes = 4
-        d.unique_keys = 1
-        d.src_keys = src_keys.data_ptr()
-        d.src_counts = src_counts.data_ptr()
-        d.cls_hist = ptr(cls_hist)
-        d.src_labels = ptr(labels)
-        d.n_big = int(n_big)
-        d.range_aux = ptr(self.range_aux)
-        d.range_nb_log2 = int(self.range_bits)
-        d.flat_slots = int(self.flat_slots)
-        key = ("order", n, int(n_big))
-        nbytes = _SORT_BYTES.get(key)
-        if nbytes is None:
-            out = C.c_uint64()
-            check(self.lib.nvt_vocab_order_tmp_bytes(n, int(n_big), C.byref(out)))
-            nbytes = _SORT_BYTES[key] = out.value
-        self.sort_tmp = torch.empty(nbytes + 16, dtype=torch.uint8, device=self._vk.device)
-        d.sort_tmp = self.sort_tmp.data_ptr()
-        d.first_label = self.first_label
-        d.head_image = ptr(self.head_image)
-        d.table = ptr(self.table)
-        d.capacity = self.capacity
-        d.sentinel_label = ptr(self.sentinel_label)
-        if ASYNC_FINALIZE:
-            if self.ready is None:
-                self.ready = Event()
-            d.ready_event = self.ready.handle
-            self.pending = True
-        else:
-            d.ready_event = None
-
-    def flat_ok(self) -> bool:
-        """Flat range tables only: True when no entry sits further than FLAT_MAX_DISPLACEMENT slots
-        from its home slot.  Synchronises (the finalisation of this vocabulary has to be done)."""
-        self.wait_ready()
-        return int(self.range_aux[self.FLAT_AUX_MAXDISP].item()) & 0xFFFFFFFF <= self.FLAT_MAX_DISPLACEMENT
-
-    def wait_ready(self):
-        """Order the CURRENT stream behind this vocabulary's sort / table build (no host
-        synchronisation).  Every consumer of the vocabulary or the table calls this first."""
-        if self.pending:
-            self.ready.wait()
-            self.pending = False
-            self.sort_tmp = None  # scratch of the finished sort: safe to recycle from here on
-            self._counts = None
-            self._src = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "pending", False):
-                self.wait_ready()  # the buffers are about to be recycled on this stream
-        except Exception:
-            pass
-
-    def fill_encode_desc(self, d: "_lib.EncodeCol", keys, valid, null_label, oov_label,
-                         num_buckets, out):
-        d.keys = keys.data_ptr()
-        d.valid = ptr(valid)
-        d.n = keys.numel()
-        d.table = ptr(self.table)
-        d.capacity = self.capacity
-        d.sentinel_label = ptr(self.sentinel_label)
-        d.null_label = int(null_label)
-        d.oov_label = int(oov_label)
-        d.num_buckets = int(num_buckets or 0)
-        d.key_bytes = self.key_bytes
-        d.out_bytes = out.element_size()
-        d.out = out.data_ptr()
-        d.vocab_keys = ptr(self.vocab_keys) if self.n_vocab else None
-        d.n_vocab = self.n_vocab if self.vocab_keys is not None else 0
-        d.first_label = self.first_label
-        d.range_aux = ptr(self.range_aux)
-        d.head_image = ptr(self.head_image)
-        if self.pending:
-            # nvt_encode_many waits on the launch stream.  The ordering's buffers are let go by
-            # release_ordering(), AFTER that call is enqueued: dropped here, a block as large as a
-            # label column (the n + 1 entry list of the sort path) went straight to the `out` of
-            # the next column, whose encode waits for its OWN vocabulary only and wrote its labels
-            # over the counts this vocabulary's ordering pass was still reading
-            d.wait_event = self.ready.handle
-            self.pending = False
-            self._release = True
-        else:
-            d.wait_event = None
-
-    def release_ordering(self):
-        """Behind nvt_encode_many (which joined its streams into the launch stream, each behind
-        the ready events it was given): the scratch of the finished ordering may be recycled."""
-        if self._release:
-            self._release = False
-            self.sort_tmp = None
-            self._counts = None
-            self._src = None
-
-    def encode(
-        self,
-        keys: torch.Tensor,
-        valid: Optional[torch.Tensor],
-        null_label: int,
-        oov_label: int,
-        num_buckets: int = 0,
-        out_dtype: torch.dtype = torch.int64,
-    ) -> torch.Tensor:
-        if self.range_aux is not None:  # range tables go through the descriptor entry point
-            return encode_many([(self, keys, valid, null_label, oov_label, num_buckets)], out_dtype)[0]
-        self.wait_ready()
-        if keys.dtype != self.key_dtype:
-            keys = keys.to(self.key_dtype)
-        keys = aligned(keys)
-        if out_dtype not in (torch.int32, torch.int64):
-            raise TypeError("Categorify output dtype must be int32 or int64")
-        out = torch.empty(keys.numel(), dtype=out_dtype, device=keys.device)
-        with _timed(f"encode_{self.suffix}", keys.numel() * (self.key_bytes + out.element_size())):
-            check(
-                getattr(self.lib, f"nvt_encode_{self.suffix}")(
-                    keys.data_ptr(), ptr(valid), keys.numel(), ptr(self.table),
-                    self.capacity, ptr(self.sentinel_label), int(null_label),
-                    int(oov_label), int(num_buckets or 0), out.data_ptr(), out.element_size(),
-                    ptr(self.vocab_keys) if self.n_vocab else None,
-                    self.n_vocab if self.vocab_keys is not None else 0, self.first_label,
-                    stream_ptr(),
-                ),
-                "nvt_encode",
-            )
-        return out
-
-
-def flat_tables_ok(tabs) -> List[bool]:
-    """EncodeTable.flat_ok for several flat range tables with ONE read-back, taken on a side
-    stream that waits for nothing but the tables' own finalisation events: work already queued on
-    the current stream (the encodes that use these very tables) is neither waited for by the host
-    nor held up on the device.  The tables must have been finalised with a ready event."""
-    dev = tabs[0].range_aux.device
-    side = _check_streams.get(dev.index)
-    if side is None:
-        side = _check_streams[dev.index] = torch.cuda.Stream(device=dev)
-    for t in tabs:
-        if t.ready is not None:
-            t.ready.wait(stream=side.cuda_stream)
-        else:
-            side.wait_stream(torch.cuda.current_stream(dev))  # finalised on the caller's stream
-    with torch.cuda.stream(side):
-        words = torch.stack([t.range_aux[EncodeTable.FLAT_AUX_MAXDISP] for t in tabs]).to(torch.int64)
-        vals = read_back(words)
-    return [(int(d) & 0xFFFFFFFF) <= EncodeTable.FLAT_MAX_DISPLACEMENT for d in vals]
-
-
-def encode_many(items, out_dtype: torch.dtype = torch.int64):
-    """items: [(EncodeTable, keys, valid, null_label, oov_label, num_buckets)] -> [labels];
-    every column of a Categorify.transform enqueued by ONE C call (nvt_encode_many)."""
-    if out_dtype not in (torch.int32, torch.int64):
-        raise TypeError("Categorify output dtype must be int32 or int64")
-    # vocabularies still being ordered on an internal stream go last, largest first (the order
-    # nvt_vocab_finalize_many works through them): everything that is ready runs underneath
-    order = sorted(range(len(items)),
-                   key=lambda i: (1, -items[i][0].n_vocab) if items[i][0].pending else (0, 0))
-    descs = (_lib.EncodeCol * max(1, len(items)))()
-    outs, keep = [None] * len(items), []
-    for d, i in zip(descs, order):
-        tab, keys, valid, null_label, oov_label, nb = items[i]
-        if keys.dtype != tab.key_dtype:
-            keys = keys.to(tab.key_dtype)
-        keys = aligned(keys)
-        out = torch.empty(keys.numel(), dtype=out_dtype, device=keys.device)
-        tab.fill_encode_desc(d, keys, valid, null_label, oov_label, nb, out)
-        outs[i] = out
-        keep.append(keys)
-    try:
-        if items:
-            check(_lib.load().nvt_encode_many(descs, len(items), stream_ptr()), "nvt_encode_many")
-    finally:
-        for it in items:
-            it[0].release_ordering()
-    return outs
-
-
-def hash_bucket(
-    keys: torch.Tensor,
-    num_buckets: int,
-    xor_in: Optional[torch.Tensor] = None,
-    want_hash: bool = False,
-    want_bucket: bool = True,
-    valid: Optional[torch.Tensor] = None,
-):
-    """(bucket int32 or None, hash64 or None).  hash64 is carried as int64 bits.  Rows whose
-    ``valid`` bit is clear hash as key 0 (the slot under a null holds arbitrary bytes)."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    keys = aligned(keys)
-    n = keys.numel()
-    out = torch.empty(n, dtype=torch.int32, device=keys.device) if want_bucket else None
-    xo = torch.empty(n, dtype=torch.int64, device=keys.device) if want_hash else None
-    check(
-        getattr(lib, f"nvt_hash_bucket_{_key_suffix(keys)}")(
-            keys.data_ptr(), ptr(valid), n, int(num_buckets), ptr(out), ptr(xor_in), ptr(xo),
-            stream_ptr()
-        ),
-        "nvt_hash_bucket",
-    )
-    return out, xo
 
 
 # --------------------------------------------------------------------------
@@ -1340,6 +984,10 @@ from .kernels_lookup import (  # noqa: E402,F401
 )
 from .kernels_exchange import (  # noqa: E402,F401
     ExchangeBatch, exchange_unpack, merge_counts_sorted,
+)
+from .kernels_encode import (  # noqa: E402,F401
+    ENCODE_RESIDENT_I32, ENCODE_RESIDENT_I64, EncodeTable, encode_kind, encode_launch_shape, flat_tables_ok,
+    encode_many, hash_bucket,
 )
 from .kernels_count import (  # noqa: E402,F401
     MIN_COUNT_CAPACITY, CountTable, count_into_new_table,

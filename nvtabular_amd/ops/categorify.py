@@ -551,7 +551,7 @@ class Categorify(StatOperator):
         self._flat_unchecked = [g.name for g, _, _, tab, _ in built if tab.flat_slots]
         for g, keys, counts, tab, start in built:
             if not tab.pending:
-                tab.sort_tmp = None  # scratch of work already ordered on this stream
+                tab._drop_ordering()  # scratch of work already ordered on this stream
             self._encoders[g.name] = _SingleEncoder(tab, start)
             n = int(counts.numel())
             final = dict(

@@ -1,6 +1,6 @@
 """Plain numpy references of Categorify's encode step and of the hash-bucket step, for the
-kernel-level tests of csrc/nvt_encode.hip (test_gpu_encode_kernels.py).  test_encode_reference.py
-pins them to the pandas oracle on the CPU.  Nothing here shares code with the device side: the
+kernel-level tests of csrc/nvt_encode.hip, nvt_encode_build.hip and nvt_hash_bucket.hip
+(test_gpu_encode_kernels.py).  test_encode_reference.py pins them to the pandas oracle on the CPU.  Nothing here shares code with the device side: the
 lookup is ``np.unique`` + ``searchsorted``, the hash is the oracle's murmur3 finaliser (itself
 pinned to the documented constants in test_oracle_golden.py).
 """

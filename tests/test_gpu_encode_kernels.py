@@ -1,11 +1,14 @@
-"""Kernel-level matrix for Categorify's encode step (nvtabular_amd/csrc/nvt_encode.hip):
+"""Kernel-level matrix for Categorify's encode step (nvtabular_amd/csrc/nvt_encode.hip with its
+kernel headers nvt_encode_head.hpp / nvt_encode_pipe.hpp, nvt_encode_build.hip, nvt_hash_bucket.hip):
 ``K.EncodeTable``, ``K.encode_many`` and ``K.hash_bucket`` called directly on torch tensors, every
 label compared with the numpy references of encode_reference.py (which test_encode_reference.py
 pins to the pandas oracle on the CPU).  Nothing is approximate here: every comparison is exact.
 
 One helper per way of obtaining a table, so that every launch shape of ``encode_launch`` is reached
-on purpose, and every helper asserts the kind of table it got (a silent fallback would turn a
-test into a second copy of the generic-kernel test):
+on purpose, and every helper asserts the kind of table it got -- ``tab.kind`` (kernels_encode.py:
+``encode_kind``) and the attributes that kind stands for (a silent fallback would turn a test into
+a second copy of the generic-kernel test).  The launch shapes are named by
+``K.encode_launch_shape``:
 
     hashed       EncodeTable(vk, first)                       encode_kernel<K, OUT>
     resident     EncodeTable(vk, first, unique=True), small   encode_small_kernel<2048 / 4096> (int32 keys,
@@ -58,6 +61,9 @@ MEDIUM_SIZES = [8185, 8191, 8193, 8199, 12288, 12288 + 4 * 1024 + 7, 100_003]
 KINDS = ["hashed", "hashed64", "resident", "resident64", "cache_eager", "i64_linear", "cache_image", "flat",
          "dumped"]
 KEY_DTYPE = {"hashed64": "int64", "resident64": "int64", "i64_linear": "int64"}
+TABLE_KIND = {"hashed": "generic", "hashed64": "generic", "resident": "resident", "resident64": "resident",
+              "cache_eager": "cache", "cache_image": "cache", "i64_linear": "linear64", "flat": "flat",
+              "dumped": "dumped"}     # EncodeTable.kind of each of KINDS
 
 
 @pytest.fixture(scope="module")
@@ -142,18 +148,11 @@ class Tab:
 
     def shape(self, out_dtype):
         """The launch shape encode_launch picks for this table (for messages and assertions)."""
+        from nvtabular_amd import kernels as K
+
         t = self.tab
-        if t.vocab_keys is None:
-            return "encode_kernel"
-        if t.n_vocab <= RES[self.dtype]:
-            if self.dtype == "int32" and out_dtype == "int64" and t.n_vocab <= 2048:
-                return "encode_small_kernel<2048>" if t.n_vocab <= 1024 else "encode_small_kernel<4096>"
-            return "encode_hot_kernel<GLOBAL=false>"
-        if self.dtype == "int64":
-            return "encode_hot_kernel<int64,GLOBAL=true>"
-        if t.range_aux is not None:
-            return "encode_pipe_kernel<2>" if t.capacity > 0 else "encode_pipe_kernel<1>"
-        return "cache mode, head image" if t.head_image is not None else "cache mode, head per launch"
+        return K.encode_launch_shape(t.kind, t.key_bytes, np.dtype(out_dtype).itemsize, t.n_vocab,
+                                     t.head_image is not None)
 
     def describe(self, out_dtype):
         return f"{self.kind} [{self.shape(out_dtype)}] {self.dtype} keys n_vocab={self.vk.size} first={self.first}"
@@ -178,6 +177,7 @@ def build(K, kind, n_vocab, first=3, sentinel="head", dist=None, seed=0, verify=
         vk = keys if sentinel == "absent" else place_sentinel(keys, sentinel, lo)
         unique = not kind.startswith("hashed")
         tab = K.EncodeTable(dev(vk), first, unique=unique)
+        assert tab.kind == TABLE_KIND[kind]
         if not unique:
             assert tab.table is not None and tab.vocab_keys is None and tab.range_aux is None
             assert tab.capacity == K.next_pow2(max(64, (4 if n_vocab <= (1 << 20) else 2) * n_vocab + 1))
@@ -223,6 +223,8 @@ def build(K, kind, n_vocab, first=3, sentinel="head", dist=None, seed=0, verify=
         _finalize(K, tab, oc, info["max_count"], src=(dk, dc, info["cls_hist"], info["n_big"], None))
         assert tab.range_bits == info["range_bits"] and tab.capacity == 0 and tab.flat_slots == 0
         assert tab.range_aux is not None and tab.table is info["range_table"] and tab.head_image is not None
+
+    assert tab.kind == TABLE_KIND[kind]
 
     def check_vocab():
         tab.wait_ready()

@@ -80,6 +80,72 @@ def test_path_selection_thresholds():
     assert sorted(K.PATH_ORDER) == [0, 1, 2, 3, 6, 7] and set(K._path_max()) >= set(K.PATH_ORDER)
 
 
+def test_encode_kind_and_launch_shape_tables():
+    """kernels_encode.encode_kind / encode_launch_shape: the kind of table a vocabulary gets and the
+    kernel it is encoded with, as literal tables (csrc/nvt_encode.hip: enc_shape_of decides the
+    second one again, under the same names)."""
+    from nvtabular_amd import kernels as K
+
+    # (key_bytes, n_vocab, unique, defer_build, has_range_table, flat) -> kind
+    kinds = [
+        ((4, 5000, True, False, False, False), "resident"),
+        ((4, 100_000, True, True, True, False), "dumped"),
+        ((4, 100_000, True, True, False, True), "flat"),
+        ((4, 100_000, True, False, False, False), "cache"),
+        ((4, 100_000, True, True, False, False), "cache"),
+        ((8, 100_000, True, False, False, False), "linear64"),
+        ((4, 100_000, False, False, False, False), "generic"),
+        # the resident boundary
+        ((4, 1, True, False, False, False), "resident"), ((4, 8192, True, False, False, False), "resident"),
+        ((4, 8193, True, False, False, False), "cache"),
+        ((8, 6144, True, False, False, False), "resident"), ((8, 6145, True, False, False, False), "linear64"),
+        ((8, 8192, True, True, False, False), "linear64"),
+        # no keys: a hashed table with nothing in it, whatever else was asked for
+        ((4, 0, True, False, False, False), "generic"), ((8, 0, True, True, False, False), "generic"),
+        ((4, 0, False, False, False, False), "generic"),
+        # duplicate keys: never staged in LDS, however few
+        ((4, 10, False, False, False, False), "generic"), ((8, 6144, False, False, False, False), "generic"),
+        ((4, 100_000, False, True, False, True), "generic"),
+        # a range table or flat offered to a vocabulary that fits LDS: still resident
+        ((4, 8192, True, True, True, False), "resident"), ((4, 4097, True, True, False, True), "resident"),
+        ((4, 8193, True, True, True, False), "dumped"), ((4, 8193, True, True, False, True), "flat"),
+        # flat needs defer_build and int32 keys
+        ((4, 100_000, True, False, False, True), "cache"), ((8, 100_000, True, True, False, True), "linear64"),
+    ]
+    for args, kind in kinds:
+        assert K.encode_kind(*args) == kind, (args, kind)
+    for bad in ((4, 100_000, True, False, True, False), (4, 100_000, False, True, True, False),
+                (8, 100_000, True, True, True, False)):
+        try:
+            K.encode_kind(*bad)
+        except AssertionError:
+            continue
+        raise AssertionError(f"a range table was accepted for {bad}")
+
+    small, wide = "encode_small_kernel<2048>", "encode_small_kernel<4096>"
+    hot = "encode_hot_kernel<GLOBAL=false>"
+    # (kind, key_bytes, out_bytes, n_vocab, has_head_image) -> launch shape
+    shapes = [
+        (("generic", 4, 8, 100_000, False), "encode_kernel"), (("generic", 8, 4, 0, False), "encode_kernel"),
+        (("resident", 4, 8, 1, False), small), (("resident", 4, 8, 1024, False), small),
+        (("resident", 4, 8, 1025, False), wide), (("resident", 4, 8, 2048, False), wide),
+        (("resident", 4, 8, 2049, False), hot), (("resident", 4, 8, 8192, False), hot),
+        (("resident", 4, 4, 1024, False), hot), (("resident", 4, 4, 1025, False), hot),
+        (("resident", 4, 4, 2048, False), hot), (("resident", 4, 4, 2049, False), hot),
+        (("resident", 8, 8, 1024, False), hot), (("resident", 8, 4, 2048, False), hot),
+        (("resident", 8, 8, 6144, False), hot),
+        (("linear64", 8, 8, 6145, False), "encode_hot_kernel<int64,GLOBAL=true>"),
+        (("linear64", 8, 4, 100_000, False), "encode_hot_kernel<int64,GLOBAL=true>"),
+        (("cache", 4, 8, 8193, True), "cache mode, head image"),
+        (("cache", 4, 4, 8193, False), "cache mode, head per launch"),
+        (("flat", 4, 8, 100_000, True), "encode_pipe_kernel<2>"), (("flat", 4, 4, 100_000, False), "encode_pipe_kernel<2>"),
+        (("dumped", 4, 8, 100_000, True), "encode_pipe_kernel<1>"),
+        (("dumped", 4, 4, 100_000, False), "encode_pipe_kernel<1>"),
+    ]
+    for args, shape in shapes:
+        assert K.encode_launch_shape(*args) == shape, (args, shape)
+
+
 def test_count_escalation_replays_the_recorded_grid():
     """kernels_count.escalate + _launch_path_of against tests/golden/count_escalation_v1.json: what
     DenseCountJob.resolve did with every overflow word before the policy became a pure function
