@@ -1562,6 +1562,38 @@ int nvt_take_list_offsets(const int64_t *offsets, uint64_t n_src, const int64_t 
                           int64_t *out_offsets, void *ws, uint64_t ws_bytes, void *stream);
 int nvt_take_list_many(const nvt_take_col *cols, int ncols, const int64_t *offsets, const int64_t *index,
                        const int64_t *out_offsets, uint64_t m, uint64_t total, void *stream);
+/* The same three gathers over SEVERAL sources: a chunk of partitions that is shuffled as a whole.
+ * index[j] is a row of the concatenation of nsrc sources (1 <= nsrc <= NVT_TAKE_MAX_SOURCES);
+ * src_begin[0 .. nsrc] (device int64, non-decreasing, src_begin[0] = 0) holds the first row of every
+ * source and src_begin[nsrc] the number of rows: a row outside [0, src_begin[nsrc]) is out of range
+ * and never dereferenced.  src_begin[s] == src_begin[s + 1] is an empty source, whose pointers may
+ * be NULL.  n_total is the host's copy of src_begin[nsrc]; it only guards the identity index.
+ * The source tables live in DEVICE memory, so the number of sources is not bounded by the kernel
+ * arguments:
+ *   nvt_batch_take_multi: cols[c].src points at nsrc records nvt_take_src on the device, one per
+ *     source (sources of one column may differ in bitmap and dtype; a source without a bitmap is
+ *     all valid); cols[c].src_valid and cols[c].src_dtype are ignored.  The caller keeps every
+ *     (source dtype, dst_dtype) pair inside the casts of nvt_batch_take_many; they are not visible
+ *     to the host here.  Layout, staging, null policy and dst_valid exactly as nvt_batch_take_many.
+ *   nvt_take_list_offsets_multi: offsets = device array of nsrc pointers to the sources' offsets
+ *     (src rows + 1 entries each, offsets[s][0] may be non-zero).  ws as nvt_take_list_offsets.
+ *   nvt_take_list_multi: the leaves; cols[c].src points at nsrc records nvt_take_src that describe
+ *     the LEAVES of every source (leaf 0 = the leaf at offsets[s][0]).
+ * A lane finds its source by a binary search in src_begin, staged in LDS up to 1024 sources. */
+#define NVT_TAKE_MAX_SOURCES 4096
+typedef struct nvt_take_src {
+  const void *src;
+  const uint8_t *src_valid; /* bitmap or NULL (all valid)                       */
+  int64_t src_dtype;        /* NVT_F32 .. NVT_I16                               */
+} nvt_take_src;
+int nvt_batch_take_multi(const int64_t *index, uint64_t m, const int64_t *src_begin, int nsrc, uint64_t n_total,
+                         const nvt_take_col *cols, int ncols, void *stream);
+int nvt_take_list_offsets_multi(const int64_t *const *offsets, const int64_t *src_begin, int nsrc, uint64_t n_total,
+                                const int64_t *index, uint64_t m, int64_t *out_offsets, void *ws, uint64_t ws_bytes,
+                                void *stream);
+int nvt_take_list_multi(const nvt_take_col *cols, int ncols, const int64_t *const *offsets, const int64_t *src_begin,
+                        int nsrc, const int64_t *index, const int64_t *out_offsets, uint64_t m, uint64_t total,
+                        void *stream);
 
 /* ---- delimited text (CSV / TSV) parsed on the device (nvtabular_amd/csv_text.py) ----
  * `text` is one byte range of a file that ends in '\n': nbytes < 2^31 bytes, 16-byte aligned and

@@ -443,6 +443,14 @@ SIGNATURES.update({
     "nvt_take_list_offsets": [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
     "nvt_take_list_many": [C.POINTER(TakeCol), _i32, _vp, _vp, _vp, _u64, _u64, _vp],
 })
+# the multi-source forms: TakeCol.src points at the column's row of the device source table, records
+# of three int64 words {src, src_valid, src_dtype} (nvt_take_src), one per source
+TAKE_MAX_SOURCES, TAKE_SRC_WORDS = 4096, 3
+SIGNATURES.update({
+    "nvt_batch_take_multi": [_vp, _u64, _vp, _i32, _u64, C.POINTER(TakeCol), _i32, _vp],
+    "nvt_take_list_offsets_multi": [_vp, _vp, _i32, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
+    "nvt_take_list_multi": [C.POINTER(TakeCol), _i32, _vp, _vp, _i32, _vp, _vp, _u64, _u64, _vp],
+})
 
 class CsvCol(C.Structure):
     """nvt_csv_col: one numeric column parsed by nvt_csv_parse_many."""

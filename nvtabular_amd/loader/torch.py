@@ -1,7 +1,7 @@
 """``TorchAsyncItr``: the batches of a Dataset as device tensors, on the batch-gather kernels.
 
 One chunk (``parts_per_chunk`` partitions) at a time is gathered -- shuffled, cast and laid out -- by
-``kernels_loader.take_frame`` into buffers allocated for that chunk, and the batches handed out are
+``kernels_loader.take_frames`` into buffers allocated for that chunk, and the batches handed out are
 views of those buffers.  Nothing is copied per batch."""
 from __future__ import annotations
 
@@ -17,6 +17,30 @@ from .. import kernels_loader as KD
 from ..device import DeviceColumn, DeviceFrame, as_device_frame
 from ..schema import Tags
 from .backend import _augment_schema
+
+
+def partition_order(parts: List[int], seed: int) -> List[int]:
+    """The epoch's order of the partitions ``parts``: ``torch.randperm`` of a host generator."""
+    host_gen = torch.Generator()
+    host_gen.manual_seed(int(seed))
+    return [parts[i] for i in torch.randperm(len(parts), generator=host_gen).tolist()]
+
+
+def epoch_row_order(lengths: List[int], parts: List[int], seed: int, parts_per_chunk: int, device) -> torch.Tensor:
+    """The order contract of ``shuffle=True`` as code: the rows of an epoch over an in-memory dataset,
+    as ``(partition, row in partition)`` pairs, int64 ``[rows, 2]`` on ``device``.  ``lengths[p]``:
+    rows of partition p; ``parts``: this rank's partitions.  The loader does not run this -- it
+    gathers with the same draws -- the tests hold the two against each other."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    live = [p for p in partition_order(list(parts), seed) if lengths[p] > 0]
+    out = [torch.empty((0, 2), dtype=torch.int64, device=device)]
+    for k in range(0, len(live), parts_per_chunk):
+        chunk = live[k:k + parts_per_chunk]
+        rows = torch.cat([torch.stack([torch.full((lengths[p],), p, dtype=torch.int64, device=device),
+                                       torch.arange(lengths[p], device=device)], dim=1) for p in chunk])
+        out.append(rows[torch.randperm(len(rows), device=device, generator=gen)])     # the chunk's one draw
+    return torch.cat(out)
 
 
 class TorchAsyncItr(torch.utils.data.IterableDataset):
@@ -39,10 +63,16 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
     A null row gives 0 in an integer tensor and NaN in a float tensor.  String columns raise
     ``TypeError``: Categorify them first.
 
-    ``shuffle=True`` permutes the order of the partitions and the rows of every partition of a chunk
-    (``torch.randperm`` on the device), seeded from ``seed_fn()`` when given.  Rows are not mixed
-    across the partitions of one chunk, and a streamed source (parquet files, a transformed
-    dataset) keeps its partition order: ``Dataset.to_iter`` is a forward iterator.
+    ``shuffle=True`` permutes the order of the partitions and then the rows of every CHUNK as a
+    whole: the ``parts_per_chunk`` partitions of a chunk are shuffled together, so more partitions
+    per chunk give better mixed batches.  The order is a contract (``epoch_row_order`` states it as
+    code): the partition order is ``torch.randperm`` of a host generator seeded with ``seed_fn()``
+    (a random seed when None); a device generator gets the same seed and every chunk, in chunk
+    order, makes ONE draw ``torch.randperm(rows of the chunk's partitions)`` that numbers those rows
+    in the order the chunk holds its partitions (empty partitions are skipped before chunks are
+    formed).  The spill rows of the previous chunk stay in front as they are.  A streamed source
+    (parquet files, a transformed dataset) keeps its partition order: ``Dataset.to_iter`` is a
+    forward iterator.
 
     Despite the name nothing here is asynchronous to the caller: every launch goes on the current
     stream, the loader starts no thread and no second stream, and the only overlap is the prefetch of
@@ -167,10 +197,12 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
                 raise TypeError(f"label column '{n}' is a list column")
 
     def _gather(self, frames, spill, gen):
-        """The chunk's buffers: the spill rows, then every partition's rows (permuted)."""
+        """The chunk's buffers: the spill rows as they are, then the rows of all partitions of the
+        chunk under ONE permutation."""
         dev = frames[0][self._columns[0]].data.device
         srows = spill["rows"] if spill else 0
-        M = srows + sum(len(f) for f in frames)
+        m = sum(len(f) for f in frames)
+        M = srows + m
         bufs: Dict[str, torch.Tensor] = {}
         mats = []
         if self.stacked:
@@ -190,66 +222,55 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
         if spill:
             for k, t in spill["bufs"].items():
                 bufs[k][:srows].copy_(t)
-        # host bookkeeping of the lists: leaves before every batch boundary of the chunk
-        B = self.batch_size
-        cuts = list(range(0, M, B)) + [M]
-        pieces = {n: ([spill["lists"][n]] if spill and srows else []) for n in self._lists}
-        leafpos = {n: {} for n in self._lists}
-        leaves = {n: (int(spill["lists"][n][0].numel()) if spill and srows else 0) for n in self._lists}
-        for n in self._lists:
-            if spill and srows:
-                leafpos[n][0] = 0
-        row = srows
-        for f in frames:
-            m = len(f)
-            index = torch.randperm(m, device=dev, generator=gen) if self.shuffle else None
-            plan = []
-            if self.stacked:
-                for key, names, _ in mats:
-                    plan += [KD.Take(n, bufs[key], column=c, row=row) for c, n in enumerate(names)]
-            else:
-                for n in self._scalar_cats + self._scalar_conts:
-                    col = f[n]
-                    if col.valid is None and col.fill is None and col.data.dtype == bufs[n].dtype:
-                        # a plain copy in the column's own dtype: torch's gather, which measured
-                        # faster than the batched kernel for this layout (profiles/loader_notes.md)
-                        if index is None:
-                            bufs[n][row:row + m].copy_(col.data)
-                        else:
-                            torch.index_select(col.data, 0, index, out=bufs[n][row:row + m])
-                    else:
-                        plan.append(KD.Take(n, bufs[n], row=row))
-            if self.label_names:
-                y = bufs["__y__"]
-                plan += [KD.Take(n, y, column=None if y.dim() == 1 else c, row=row)
-                         for c, n in enumerate(self.label_names)]
-            KD.take_frame(f, index, plan, m)
-            if self._lists and m:
-                local = [c - row for c in cuts if row <= c <= row + m]
-                want = torch.tensor(local, dtype=torch.int64, device=dev)
-                got, bounds = KD.take_lists(f, self._lists, index, m, want_offsets=want)
-                for n in self._lists:
-                    values, offsets, _ = got[n]
-                    for r, b in zip(local, bounds[n]):
-                        leafpos[n][row + r] = leaves[n] + int(b)
-                    pieces[n].append((values, offsets))
-                    leaves[n] += int(values.numel())
-            row += m
+        # the chunk's one draw: a row number in the partitions laid one behind the other
+        index = torch.randperm(m, device=dev, generator=gen) if self.shuffle else None
+        plan = []
+        if self.stacked:
+            for key, names, _ in mats:
+                plan += [KD.Take(n, bufs[key], column=c, row=srows) for c, n in enumerate(names)]
+        else:
+            for n in self._scalar_cats + self._scalar_conts:
+                plain = all(f[n].valid is None and f[n].fill is None and f[n].data.dtype == bufs[n].dtype
+                            for f in frames)
+                if plain and (index is None or len(frames) == 1):
+                    self._plain(n, frames, index, bufs[n][srows:])
+                else:
+                    plan.append(KD.Take(n, bufs[n], row=srows))
+        if self.label_names:
+            y = bufs["__y__"]
+            plan += [KD.Take(n, y, column=None if y.dim() == 1 else c, row=srows)
+                     for c, n in enumerate(self.label_names)]
+        KD.take_frames(frames, index, plan, m)
         lists = {}
-        for n in self._lists:
-            ps = pieces[n]
-            if len(ps) == 1:
-                values, offsets = ps[0]
-            else:
-                values = torch.cat([p[0] for p in ps])
-                offs, base = [ps[0][1]], int(ps[0][0].numel())
-                for v, o in ps[1:]:
-                    offs.append(o[1:] + base)
-                    base += int(v.numel())
-                offsets = torch.cat(offs)
-            leafpos[n][M] = leaves[n]
-            lists[n] = (values, offsets, leafpos[n])
+        if self._lists:
+            # the spill's lists are one more source in front, taken in order: the chunk's lists come
+            # out whole, with ONE read-back (the leaf total and the offsets at the batch boundaries)
+            sources, lindex = frames, index
+            if srows:
+                sources = [DeviceFrame({n: DeviceColumn(v, None, o) for n, (v, o) in spill["lists"].items()})] + frames
+                if index is not None:
+                    lindex = torch.cat([torch.arange(srows, device=dev), index + srows])
+            cuts = list(range(0, M, self.batch_size)) + [M]
+            want = torch.tensor(cuts, dtype=torch.int64, device=dev)
+            got, bounds = KD.take_lists_multi(sources, self._lists, lindex, M, want_offsets=want)
+            for n in self._lists:
+                values, offsets, _ = got[n]
+                lists[n] = (values, offsets, {c: int(b) for c, b in zip(cuts, bounds[n])})
         return M, bufs, lists
+
+    @staticmethod
+    def _plain(name, frames, index, out):
+        """Dict mode, a column without bitmap, fill or cast, in order or from ONE partition: a plain
+        copy in the column's own dtype.  Shuffled across several partitions it goes with the other
+        columns through the multi-source kernel (profiles/loader_notes.md has both measurements)."""
+        if index is None:
+            row = 0
+            for f in frames:
+                out[row:row + len(f)].copy_(f[name].data)
+                row += len(f)
+        else:
+            # torch's gather, which measured faster than the batched kernel for this layout
+            torch.index_select(frames[0][name].data, 0, index, out=out)
 
     def _list_batch(self, name, values, offsets, leafpos, a, b, out):
         lo, hi = leafpos[a], leafpos[b]
@@ -287,9 +308,7 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
         gen = None
         if self.shuffle:
             seed = int(self.seed_fn()) if self.seed_fn is not None else int.from_bytes(os.urandom(7), "little")
-            host_gen = torch.Generator()
-            host_gen.manual_seed(seed)
-            order = [order[i] for i in torch.randperm(len(order), generator=host_gen).tolist()]
+            order = partition_order(order, seed)
         parts = self._partitions(order)
         B = self.batch_size
         spill = None
@@ -326,9 +345,12 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
             spill = None
             if not last and full < M:
                 spill = {"rows": M - full, "bufs": {k: t[full:] for k, t in bufs.items()}, "lists": {}}
+                shared = {}     # columns that share their offsets keep sharing them in the spill
                 for n, (values, offsets, leafpos) in lists.items():
                     lo = leafpos[full]
-                    spill["lists"][n] = (values[lo:], offsets[full:] - lo)
+                    if offsets.data_ptr() not in shared:
+                        shared[offsets.data_ptr()] = offsets[full:] - lo
+                    spill["lists"][n] = (values[lo:], shared[offsets.data_ptr()])
             if last:
                 return
 
