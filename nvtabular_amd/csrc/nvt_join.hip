@@ -79,8 +79,10 @@ __device__ __forceinline__ uint64_t canon(const JKey &k, uint64_t row, bool &nul
   return null ? 0 : (uint64_t)v;
 }
 
+// The null bits are mixed before the first word meets them: XOR-ed in raw, bit k of `nulls` and
+// bit k of w[0] + constant cancel, and the ordinary keys (0, null) and (2, 0) share a tag.
 __device__ __forceinline__ uint64_t tuple_tag(const uint64_t *w, unsigned nulls, int nkeys) {
-  uint64_t h = 0x243F6A8885A308D3ull ^ nulls;
+  uint64_t h = fmix64(0x243F6A8885A308D3ull ^ nulls);
 #pragma unroll
   for (int j = 0; j < kMaxKeys; ++j)
     if (j < nkeys) h = fmix64(h ^ (w[j] + 0x9E3779B97F4A7C15ull * (uint64_t)(j + 1)));
