@@ -1353,6 +1353,35 @@ int nvt_pq_dict_pack(const void *values, int dtype, uint64_t n, uint64_t max_ent
                      const int64_t *page_start, uint64_t npages, uint64_t *state, uint8_t *out,
                      uint64_t out_cap, void *ws, uint64_t ws_bytes, void *stream);
 
+/* ---- parquet out: string columns (PLAIN BYTE_ARRAY pages) ----
+ * A string column is int64 surrogates and a host dict {surrogate -> string}.  The dict travels to
+ * the device once as an ENTRY TABLE: keys[n_entries] ascending, and the entries in key order as Arrow
+ * string buffers -- offsets int64[n_entries + 1], chars 4-byte aligned and readable up to the 4-byte
+ * boundary behind the last byte (what nvt_str_hash reads).  n_entries < 2^31.
+ * nvt_pq_str_entry_ids: out_ids[j] = the position of surrogates[j] in keys (binary search) for the m
+ *   NON-NULL values of a chunk; a surrogate that is no key gives id 0 and adds 1 to *bad (uint64 on
+ *   the device, zeroed by the caller).
+ * nvt_pq_byte_array_plan: the value at position j takes 4 + len(entry ids[j]) bytes (an id outside
+ *   the table counts as the empty entry).  pos[m + 1] receives the 64-bit exclusive scan of those
+ *   sizes, pos[m] the total; page_at[p] = pos[page_start[p]] for p in [0, pages] (page_start
+ *   int64[pages + 1] on the device, in value positions, clamped to [0, m]): a page without values
+ *   has page_at[p] == page_at[p + 1].  ws: nvt_pq_byte_array_ws_bytes(m) bytes, 8-byte aligned.
+ * nvt_pq_byte_array_fill: every value's length as 4 bytes little endian, then its bytes, at
+ *   out + pos[j] -- parquet's PLAIN encoding of BYTE_ARRAY.  out 4-byte aligned; the chars are read
+ *   with aligned 4-byte loads, and no word is loaded that holds no byte of the entry.  A value that
+ *   would end past out_bytes, or whose pos[j + 1] - pos[j] is not 4 + its length, is not written;
+ *   nothing is ever written outside [out, out + out_bytes).
+ * m = 0: nothing is done (no output is touched).  Stream-ordered, no allocation, no synchronisation. */
+int nvt_pq_str_entry_ids(const int64_t *keys, uint64_t n_entries, const int64_t *surrogates, uint64_t m,
+                         int32_t *out_ids, uint64_t *bad, void *stream);
+int nvt_pq_byte_array_ws_bytes(uint64_t m, uint64_t *bytes);
+int nvt_pq_byte_array_plan(const int32_t *ids, uint64_t m, const int64_t *offsets, uint64_t n_entries,
+                           const int64_t *page_start, uint64_t pages, uint64_t *pos, uint64_t *page_at, void *ws,
+                           uint64_t ws_bytes, void *stream);
+int nvt_pq_byte_array_fill(const int32_t *ids, uint64_t m, const int64_t *offsets, const uint8_t *chars,
+                           uint64_t n_entries, const uint64_t *pos, uint8_t *out, uint64_t out_bytes,
+                           void *stream);
+
 /* ---- exact column medians: ops.FillMedian (MSD radix select) ----
  * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a
  * negative value and the sign bit of the others, integers flip the sign bit.  The two middle

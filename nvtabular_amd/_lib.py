@@ -369,6 +369,13 @@ SIGNATURES.update({
     "nvt_pq_dict_build": [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
     "nvt_pq_dict_pack": [_vp, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp],
 })
+# parquet out: string columns (kernels_parquet_str_out.py)
+SIGNATURES.update({
+    "nvt_pq_str_entry_ids": [_vp, _u64, _vp, _u64, _vp, _vp, _vp],
+    "nvt_pq_byte_array_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_pq_byte_array_plan": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp],
+    "nvt_pq_byte_array_fill": [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp],
+})
 
 class SelectCol(C.Structure):
     """nvt_select_col: one chunk of one column read by nvt_select_hist_many."""

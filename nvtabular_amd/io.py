@@ -18,6 +18,7 @@ import pandas as pd
 
 from .device import DeviceFrame, as_device_frame
 from .parquet_plain import READER_CHUNKS, PlainParquetFile, StagedPartition, read_row_groups_staged
+from .kernels_parquet_str_out import StringTables
 from .parquet_write import LAST_TIMING, device_permutation, dictionary_columns, plain_eligible, write_plain  # noqa: F401
 from .schema import Schema
 
@@ -337,10 +338,13 @@ class Dataset:
           ``False`` keeps the row order.
         * ``dtypes``: {column: dtype} casts applied on the way out (an entry that names a list
           column sends the frame to pyarrow, whose cast does not convert lists).
-        * ``compression``: ``None`` (default) lets fixed-width numeric frames -- flat int32 / int64 /
-          float32 / float64 and datetime columns, and list columns with such number leaves (written
-          as the standard three-level list, levels packed on the device) -- take the hand-written
-          PLAIN writer (uncompressed pages, no dictionary, no column statistics: files are larger
+        * ``compression``: ``None`` (default) lets frames of flat int32 / int64 / float32 / float64 and
+          datetime columns, list columns with such number leaves (written as the standard
+          three-level list, levels packed on the device) and flat string columns on the device
+          (BYTE_ARRAY / UTF8 pages filled on the device from the surrogates and the column's dict;
+          lists of strings, string columns on the host, with a ``dtypes`` entry, with a dict value
+          that is not a ``str`` or with an entry longer than 2^30 - 4 bytes send the frame to
+          pyarrow) take the hand-written PLAIN writer (uncompressed pages, no dictionary, no column statistics: files are larger
           than pyarrow's snappy + dictionary output and carry no min / max for predicate
           pushdown -- the price of writing at tens of GB/s); any codec name (``"snappy"``,
           ``"zstd"``, ``"none"`` ...) selects pyarrow's writer with that codec, statistics and
@@ -348,10 +352,12 @@ class Dataset:
           pyarrow the default.
         * ``statistics=True``: the PLAIN writer also records min / max of every column chunk
           (computed on the device next to the copy out); the null count of every chunk is always
-          written.  pyarrow's writer always writes statistics.
+          written.  String columns get no min / max.  pyarrow's writer always writes statistics.
         * ``use_dictionary`` (pyarrow's name and value shapes): ``None`` / ``False`` (default) write
           exactly the PLAIN pages described above.  ``True`` offers every flat int32 / int64 column
-          (after a ``dtypes`` cast), every datetime column and every list column of int32 / int64
+          (after a ``dtypes`` cast), every datetime column, every flat string column (its
+          dictionary page holds the chunk's distinct strings; the rule below is then in bytes) and
+          every list column of int32 / int64
           leaves to the PLAIN writer's dictionary encoding, which runs on the device (columns of a
           frame on the host are not offered); float columns stay PLAIN silently (repeated floats
           are not dictionary-encoded).  A list of column names offers only those; a
@@ -360,8 +366,8 @@ class Dataset:
           and ``RLE_DICTIONARY`` data pages whose indices are bit-packed on the device, but only when
           that makes the chunk smaller and it has at most 2^20 distinct values -- otherwise that
           chunk stays PLAIN, so the option never makes a file larger ("Dictionary pages
-          in the PLAIN parquet writer").  When the frame goes to pyarrow's writer anyway (strings, a
-          codec, ``Shuffle.PER_WORKER`` with ``out_files_per_proc``, ``NVT_PLAIN_PARQUET=0``), a
+          in the PLAIN parquet writer").  When the frame goes to pyarrow's writer anyway (lists of
+          strings, a codec, ``Shuffle.PER_WORKER`` with ``out_files_per_proc``, ``NVT_PLAIN_PARQUET=0``), a
           value other than ``None`` is handed to pyarrow as its own ``use_dictionary``.
         * writes ``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and
           ``_metadata.json`` (file stats + cats / conts / labels) next to the data files.
@@ -384,13 +390,18 @@ class Dataset:
         parts = iter(self.to_iter(shard=(rank, world) if world > 1 else None))
         first = next(parts, None)
         parts = itertools.chain([first], parts) if first is not None else iter(())
-        if first is not None and PLAIN_PARQUET and compression is None and plain_eligible(first, dtypes) and \
-                not (shuffle == Shuffle.PER_WORKER and k):
-            # fixed-width numeric columns: PLAIN pages written straight from pinned column
-            # buffers (parquet_write.py) -- no dictionary pass, no compression, no statistics
+        tables = StringTables()   # the entry tables of string columns, for this call
+        if first is not None and PLAIN_PARQUET and compression is None and \
+                not (shuffle == Shuffle.PER_WORKER and k) and plain_eligible(first, dtypes, tables):
+            # fixed-width numeric columns, lists of them and flat string columns on the device: PLAIN
+            # pages written straight from pinned column buffers (parquet_write.py; a string column's
+            # BYTE_ARRAY pages are filled on the device from its surrogates and its dict's entries) --
+            # no compression, no statistics, dictionary pages only on request.  Lists of strings,
+            # string columns on the host, with a dtypes= entry or with a dict value that is no str,
+            # bools and narrow leaves go to pyarrow below
             offered = dictionary_columns(first, dtypes, use_dictionary)   # (raises before any file exists)
             names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
-                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered)
+                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered, tables)
             collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
             schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
         else:

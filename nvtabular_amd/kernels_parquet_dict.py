@@ -90,17 +90,26 @@ def encode(values: torch.Tensor, page_start: torch.Tensor, max_entries: int = DI
                       (ws, values, page_start))
 
 
-def read_back_states(dicts: Sequence[DeviceDict]) -> List[tuple]:
+def read_back_states(dicts: Sequence[DeviceDict], extra: Sequence[torch.Tensor] = None):
     """[(d, overflow, page_start as a numpy array)] of the enqueued chunks: ONE read-back for all of
-    them (the page starts come along: a flat column's are popcounts only the device has)."""
-    if not dicts:
-        return []
+    them (the page starts come along: a flat column's are popcounts only the device has).
+    ``extra``: further int64 tensors on the device that ride along in the same read-back (the page
+    tables of string columns); the result is then (the list above, [their numpy arrays])."""
+    if not dicts and not extra:
+        return [] if extra is None else ([], [])
     K.stat_add("pqdict_readback")
-    w = K.read_back(torch.cat([t for dd in dicts for t in (dd.state, dd.page_start)])).view(np.int64)
+    w = K.read_back(torch.cat([t for dd in dicts for t in (dd.state, dd.page_start)] +
+                              [t.reshape(-1) for t in (extra or ())])).view(np.int64)
     out, at = [], 0
     for dd in dicts:
         ps = w[at + STATE_WORDS: at + STATE_WORDS + dd.page_start.numel()]
         out.append((int(w[at]), int(w[at + 1]), np.array(ps, dtype=np.int64)))
         at += STATE_WORDS + dd.page_start.numel()
         dd._keep = None   # (the kernels are done: the workspace goes back to the allocator)
-    return out
+    if extra is None:
+        return out
+    more = []
+    for t in extra:
+        more.append(np.array(w[at: at + t.numel()], dtype=np.int64))
+        at += t.numel()
+    return out, more

@@ -30,15 +30,25 @@ with both level streams ONE bit-packed run each (bit width 1 and 2), packed on t
 leaves is max(L, 1) slots and every page starts at a row ("List columns in the PLAIN
 parquet writer").  The reading half below takes such lists too, from any writer ("List
 columns in the parquet reader"); other nested files are read with pyarrow.
-Anything else (strings, lists of strings or of bool / 8 / 16-bit leaves, booleans, casts of list
-columns) stays with pyarrow's writer.
+A flat string column (int64 surrogates and a {surrogate -> str} dict) is a BYTE_ARRAY column annotated
+UTF8 / STRING whose page is
+
+    thrift PageHeader | definition levels | per non-null value: u32 length, UTF-8 bytes
+
+The value sections of a chunk's pages are filled on the device (kernels_parquet_str_out,
+csrc/nvt_parquet_str_out.hip) and handed over as ``ByteArrayPages``; the rows per page follow the
+longest entry (``string_page_rows``) so that no page passes 2^30 bytes; string chunks carry a null
+count and no min / max ("String columns in the PLAIN parquet writer").
+Anything else (lists of strings or of bool / 8 / 16-bit leaves, booleans, string columns on the host or
+with bytes / mixed objects in their dict, casts of list or string columns) stays with pyarrow's writer.
 With ``to_parquet(use_dictionary=...)`` an int32 / int64 column chunk (datetime counts and list leaves
 too) may instead be a dictionary page -- its distinct non-null values, ascending -- followed by data
 pages of the same cut whose values are ``W | ONE bit-packed run of indices`` (encoding
 RLE_DICTIONARY), handed over as ``DictPages``: dictionary and indices are made on the device
 (kernels_parquet_dict, csrc/nvt_parquet_dict.hip), and ``dict_pays`` keeps a chunk PLAIN unless
-the dictionary makes it smaller ("Dictionary pages in the PLAIN parquet writer").  Not
-done: float, string and bool dictionaries, RLE runs inside the index stream, DELTA encodings.
+the dictionary makes it smaller ("Dictionary pages in the PLAIN parquet writer").  A string
+chunk's dictionary page is the PLAIN BYTE_ARRAY encoding of its distinct entries.  Not
+done: float and bool dictionaries, RLE runs inside the index stream, DELTA encodings.
 The reading half also takes flat STRING columns (any writer's dictionary / PLAIN pages): their
 dictionary entries and index runs are staged as the file holds them and expanded, hashed and
 gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "String columns in
@@ -59,6 +69,24 @@ from .parquet_thrift import _CT_BINARY, _CT_I32, _CT_STRUCT, _Struct, _TReader, 
 _PQ_TYPE = {np.dtype("int32"): 1, np.dtype("int64"): 2, np.dtype("float32"): 4, np.dtype("float64"): 5}   # physical types
 PAGE_VALUES = 1 << 20          # values per data page (8 MiB of int64)
 ROW_GROUP_ROWS = 1 << 23       # rows per row group
+STRING_DTYPE = np.dtype("O")   # what a flat string column (BYTE_ARRAY, UTF8 / STRING) is in ``dtypes``
+MAX_PAGE_BYTES = 1 << 30       # a string page's body (a thrift page size is an i32)
+MAX_ENTRY_BYTES = MAX_PAGE_BYTES - 4   # the longest string the PLAIN writer takes
+
+
+def _ptype(dt) -> int:
+    """Physical type of a column of the writer."""
+    return 6 if dt == STRING_DTYPE else _PQ_TYPE[dt]
+
+
+def string_page_rows(longest: int) -> int:
+    """Rows per data page of a string column whose longest entry has ``longest`` bytes:
+    min(PAGE_VALUES, max(1, 2^30 // (longest + 4))), so that no page body passes 2^30 bytes -- rounded
+    down to a multiple of 8 when it is 8 or more, so that every page starts at a byte of the validity
+    bitmap and its definition levels are a slice of it (fewer than 8 rows per page: entries of 128 MiB
+    and more; ``_flat_pages`` then re-packs the bits of a page)."""
+    rows = min(PAGE_VALUES, max(1, MAX_PAGE_BYTES // (int(longest) + 4)))
+    return rows if rows < 8 else rows & ~7
 
 
 # datetime unit -> (TimeUnit union field of LogicalType TIMESTAMP, converted type or None)
@@ -106,6 +134,28 @@ def _packed_levels(slots: int, width: int) -> bytes:
     groups = (slots + 7) // 8
     head = _varint((groups << 1) | 1)
     return struct.pack("<I", len(head) + groups * width) + head
+
+
+def _flat_pages(valid, n: int, page_rows: int):
+    """(rows, bitmap bytes or None, non-null values) of the data pages a flat chunk of n rows is cut
+    into, ``page_rows`` rows each (n = 0: one page without rows)."""
+    vb = memoryview(np.ascontiguousarray(valid)).cast("B") if valid is not None else None
+    done_rows = 0
+    while True:
+        rows = min(page_rows, n - done_rows)
+        if vb is not None:
+            page_valid = vb[done_rows // 8: (done_rows + rows + 7) // 8]
+            bits = np.unpackbits(np.frombuffer(page_valid, dtype=np.uint8), bitorder="little")
+            if done_rows % 8:   # (a page that starts inside a byte of the bitmap: its bits are re-packed)
+                bits = bits[done_rows % 8:]
+                page_valid = memoryview(np.packbits(bits[:rows], bitorder="little")).cast("B")
+            nv = int(bits[:rows].sum()) if rows else 0
+        else:
+            page_valid, nv = None, rows
+        yield rows, page_valid, nv
+        done_rows += rows
+        if done_rows >= n:
+            return
 
 
 class ListLevels:
@@ -167,31 +217,39 @@ class DictPages:
     first, pad bits 0 -- at ``dict_page_offsets(nv, W)[0][p]``) and ``nv[p]``, the non-null values of
     data page p (the pages are cut where a PLAIN chunk's are).  The device packs them
     (kernels_parquet_dict; tests/pq_dict_reference.py restates the layout).  Like the values,
-    ``dictionary`` and ``packed`` may still be in flight when the row group is laid out."""
+    ``dictionary`` and ``packed`` may still be in flight when the row group is laid out.
+    A string column's chunk: ``entries`` = d and ``dictionary`` the uint8 bytes of the dictionary page,
+    the PLAIN BYTE_ARRAY encoding of the d entries; ``page_rows``: the rows per data page of the chunk."""
 
-    __slots__ = ("dictionary", "packed", "W", "nv", "at")
+    __slots__ = ("dictionary", "packed", "W", "nv", "at", "entries", "page_rows")
 
-    def __init__(self, dictionary, packed, W, nv):
+    def __init__(self, dictionary, packed, W, nv, entries=None, page_rows=None):
         self.dictionary, self.packed, self.W = dictionary, packed, int(W)
         self.nv = [int(x) for x in nv]
-        d = int(np.asarray(dictionary).size)
+        self.entries = int(entries) if entries is not None else None
+        self.page_rows = int(page_rows) if page_rows is not None else None   # (None: PAGE_VALUES)
+        d = int(np.asarray(dictionary).size) if entries is None else self.entries
         if d < 1 or self.W != dict_index_width(d):
             raise ValueError(f"DictPages: index width {self.W} for a dictionary of {d} entries")
+        if entries is not None and not 4 * d <= len(dictionary) <= MAX_PAGE_BYTES:
+            raise ValueError(f"DictPages: a dictionary page of {len(dictionary)} bytes for {d} strings")
         self.at, total = dict_page_offsets(self.nv, self.W)
         if len(packed) < total:
             raise ValueError(f"DictPages: {len(packed)} packed bytes, the pages take {total}")
 
     @property
     def dtype(self):
-        return np.asarray(self.dictionary).dtype
+        return STRING_DTYPE if self.entries is not None else np.asarray(self.dictionary).dtype
 
     def prologue(self, dt, at):
         """([(offset, bytes-like)] of the dictionary page laid out from ``at``, the offset behind it)."""
         dic = np.asarray(self.dictionary)
-        if dic.dtype != dt or dic.ndim != 1 or not dic.flags.c_contiguous:
-            raise TypeError(f"PlainParquetWriter: dictionary is {dic.dtype}, the file's column is {dt}")
-        head = _dict_page_header(dic.size, dic.size * dt.itemsize)
-        return [(at, head), (at + len(head), memoryview(dic).cast("B"))], at + len(head) + dic.size * dt.itemsize
+        if self.dtype != dt or dic.ndim != 1 or not dic.flags.c_contiguous or \
+                (self.entries is not None and dic.dtype != np.uint8):
+            raise TypeError(f"PlainParquetWriter: dictionary is {self.dtype}, the file's column is {dt}")
+        d, nbytes = (dic.size, dic.size * dt.itemsize) if self.entries is None else (self.entries, dic.size)
+        head = _dict_page_header(d, nbytes)
+        return [(at, head), (at + len(head), memoryview(dic).cast("B"))], at + len(head) + nbytes
 
     def indices(self, p, nv):
         """[bytes-like] of data page p's value section: the width byte, then the run."""
@@ -205,8 +263,49 @@ class DictPages:
                 memoryview(self.packed).cast("B")[self.at[p]: self.at[p] + groups * self.W]]
 
 
+class ByteArrayPages:
+    """One PLAIN column chunk of a flat string column, as ``write_row_group`` takes it in the place of
+    the values: ``body`` (bytes-like, uint8) holds the value sections of all data pages of the chunk
+    -- per non-null value its length as a little-endian u32, then its UTF-8 bytes -- page p's at
+    ``body[page_at[p]: page_at[p + 1]]``; ``nv[p]`` is the number of non-null values of page p and
+    ``page_rows`` the rows every page but the last holds (``string_page_rows`` of the column's
+    longest entry).  The device fills the body (kernels_parquet_str_out; tests/pq_str_out_reference.py
+    restates the layout); it may still be in flight when the row group is laid out, the tables not."""
+
+    __slots__ = ("body", "page_at", "nv", "page_rows")
+
+    def __init__(self, body, page_at, nv, page_rows=None):
+        self.body, self.page_rows = body, int(page_rows if page_rows is not None else PAGE_VALUES)
+        self.page_at = [int(x) for x in page_at]
+        self.nv = [int(x) for x in nv]
+        if self.page_rows < 1 or len(self.page_at) != len(self.nv) + 1 or len(self.nv) < 1:
+            raise ValueError(f"ByteArrayPages: {len(self.page_at)} page starts for {len(self.nv)} pages "
+                             f"of {self.page_rows} rows")
+        if self.page_at[0] < 0 or self.page_at[-1] > len(body):
+            raise ValueError(f"ByteArrayPages: pages at {self.page_at[0]} .. {self.page_at[-1]} of a body of "
+                             f"{len(body)} bytes")
+        for p, k in enumerate(self.nv):
+            size = self.page_at[p + 1] - self.page_at[p]
+            if k < 0 or size < 4 * k or (k == 0 and size) or size > MAX_PAGE_BYTES:
+                raise ValueError(f"ByteArrayPages: page {p} holds {k} values in {size} bytes")
+
+    @property
+    def dtype(self):
+        return STRING_DTYPE
+
+    def page(self, p, nv):
+        """The value section of data page p (bytes-like)."""
+        if not 0 <= p < len(self.nv) or self.nv[p] != nv:
+            raise ValueError(f"PlainParquetWriter: page {p} has {nv} non-null values, its ByteArrayPages say "
+                             f"{self.nv[p] if 0 <= p < len(self.nv) else 'nothing'}")
+        if self.page_at[p + 1] == self.page_at[p]:
+            return memoryview(b"")
+        return memoryview(self.body).cast("B")[self.page_at[p]: self.page_at[p + 1]]
+
+
 class PlainParquetWriter:
     """One parquet file of int32 / int64 / float32 / float64 columns, flat or "list of" such leaves,
+    and flat string columns (``STRING_DTYPE``: BYTE_ARRAY annotated UTF8 / STRING),
     every column OPTIONAL (like pyarrow writes nullable Arrow columns), PLAIN encoding, no
     compression.  A list column is the standard three-level list (optional group ``name`` (LIST) >
     repeated group ``list`` > optional ``element``); there are no null lists.
@@ -223,7 +322,7 @@ class PlainParquetWriter:
         self.names = list(names)
         self.dtypes = [np.dtype(d) for d in dtypes]
         for d in self.dtypes:
-            if d not in _PQ_TYPE:
+            if d not in _PQ_TYPE and d != STRING_DTYPE:
                 raise TypeError(f"PlainParquetWriter: unsupported dtype {d}")
         self.logical = [np.dtype(x) if x is not None else None for x in (logical or [None] * len(self.names))]
         for d, x in zip(self.dtypes, self.logical):
@@ -234,6 +333,8 @@ class PlainParquetWriter:
             raise ValueError("PlainParquetWriter: names and lists differ in length")
         if any(l and x is not None for l, x in zip(self.lists, self.logical)):
             raise TypeError("PlainParquetWriter: list columns of datetime leaves are not written")
+        if any(l and d == STRING_DTYPE for l, d in zip(self.lists, self.dtypes)):
+            raise TypeError("PlainParquetWriter: list columns of strings are not written")
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
         os.pwrite(self.fd, b"PAR1", 0)
         self.pos = 4
@@ -247,26 +348,22 @@ class PlainParquetWriter:
         offset of its first data page."""
         if isinstance(values, DictPages):
             return self._plan_dict_column(values, valid, n, dt, start)
-        values = np.asarray(values)
-        if values.dtype != dt or not values.flags.c_contiguous:
+        bp = values if isinstance(values, ByteArrayPages) else None
+        if (bp is not None) != (dt == STRING_DTYPE):
+            raise TypeError(f"PlainParquetWriter: column buffer is {getattr(values, 'dtype', type(values))}, "
+                            f"the file's column is {'string' if dt == STRING_DTYPE else dt}")
+        values = np.asarray(values) if bp is None else None
+        if bp is None and (values.dtype != dt or not values.flags.c_contiguous):
             # never cast here: the buffer may still be the target of an asynchronous device-to-host
             # copy (`ready`), and a silent cast would hide a schema change between row groups
             raise TypeError(f"PlainParquetWriter: column buffer is {values.dtype} "
                             f"(contiguous={values.flags.c_contiguous}), the file's column is {dt}")
-        vbytes = memoryview(values).cast("B") if values.size else memoryview(b"")
-        vb = memoryview(np.ascontiguousarray(valid)).cast("B") if valid is not None else None
+        vbytes = memoryview(values).cast("B") if (bp is None and values.size) else memoryview(b"")
         segs, at = [], start
-        done_rows, done_vals = 0, 0
-        while True:
-            rows = min(PAGE_VALUES, n - done_rows)
-            if vb is not None:
-                page_valid = vb[done_rows // 8: (done_rows + rows + 7) // 8]
-                nv = int(np.unpackbits(np.frombuffer(page_valid, dtype=np.uint8),
-                                       bitorder="little")[:rows].sum()) if rows else 0
-            else:
-                page_valid, nv = None, rows
+        done_vals = 0
+        for p, (rows, page_valid, nv) in enumerate(_flat_pages(valid, n, PAGE_VALUES if bp is None else bp.page_rows)):
             prefix, bitmap = _def_levels(rows, page_valid)
-            payload = vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize]
+            payload = vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize] if bp is None else bp.page(p, nv)
             body = len(prefix) + (len(bitmap) if bitmap is not None else 0) + len(payload)
             head = _page_header(rows, body) + prefix
             segs.append((at, head))
@@ -277,29 +374,20 @@ class PlainParquetWriter:
             if len(payload):
                 segs.append((at, payload))
                 at += len(payload)
-            done_rows += rows
             done_vals += nv
-            if done_rows >= n:
-                break
-        if done_vals != values.size:
+        if bp is not None and p + 1 != len(bp.nv):
+            raise ValueError(f"PlainParquetWriter: {p + 1} data pages, the ByteArrayPages hold {len(bp.nv)}")
+        if bp is None and done_vals != values.size:
             raise ValueError("PlainParquetWriter: the values do not match the validity bitmap "
                              f"({values.size} values, {done_vals} valid rows)")
         return segs, at - start, start
 
     def _plan_dict_column(self, dp, valid, n, dt, start):
         """A flat chunk of dictionary pages: dictionary page | data pages (header | def levels | W | run)."""
-        vb = memoryview(np.ascontiguousarray(valid)).cast("B") if valid is not None else None
         segs, at = dp.prologue(dt, start)
         first = at
-        done_rows, p = 0, 0
-        while True:
-            rows = min(PAGE_VALUES, n - done_rows)
-            if vb is not None:
-                page_valid = vb[done_rows // 8: (done_rows + rows + 7) // 8]
-                nv = int(np.unpackbits(np.frombuffer(page_valid, dtype=np.uint8),
-                                       bitorder="little")[:rows].sum()) if rows else 0
-            else:
-                page_valid, nv = None, rows
+        p = 0
+        for rows, page_valid, nv in _flat_pages(valid, n, dp.page_rows or PAGE_VALUES):
             prefix, bitmap = _def_levels(rows, page_valid)
             bufs = [bitmap] + dp.indices(p, nv)
             body = len(prefix) + sum(len(b) for b in bufs if b is not None)
@@ -307,10 +395,7 @@ class PlainParquetWriter:
                 if buf is not None and len(buf):
                     segs.append((at, buf))
                     at += len(buf)
-            done_rows += rows
             p += 1
-            if done_rows >= n:
-                break
         if p != len(dp.nv):
             raise ValueError(f"PlainParquetWriter: {p} data pages, the DictPages hold {len(dp.nv)}")
         return segs, at - start, first
@@ -378,8 +463,9 @@ class PlainParquetWriter:
         """columns[j] = (values, valid): `values` a 1-D numpy array of the column's dtype holding
         the NON-NULL values in row order, `valid` None or the Arrow validity bitmap (uint8, LSB
         first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
-        non-null LEAVES of the n rows in order and their ``ListLevels``.  A dictionary-encoded chunk
-        (of either kind): a ``DictPages`` in the place of ``values``.  Argument errors raise
+        non-null LEAVES of the n rows in order and their ``ListLevels``.  A string column: a
+        ``ByteArrayPages`` in the place of ``values``.  A dictionary-encoded chunk
+        (of any kind): a ``DictPages`` in the place of ``values``.  Argument errors raise
         before anything of the row group is written.  wait=False (with a pool): returns the
         futures of the column writes instead of waiting for them -- the layout is fixed, so later
         row groups (of this or of other files) can be written meanwhile; the caller keeps the
@@ -389,8 +475,8 @@ class PlainParquetWriter:
         from their popcounts).
         stats[j]: None, or a 2-element numpy array of the column's dtype that holds {min, max} of
         the non-null values by the time close() runs (it may still be in flight now): written as
-        the chunk's min / max statistics (NaN / empty chunks: omitted).  The null count of every
-        chunk is always written."""
+        the chunk's min / max statistics (NaN / empty chunks: omitted; string columns take None:
+        they get no min / max).  The null count of every chunk is always written."""
         chunks, plans = [], []
         total = 0
         if len(columns) != len(self.names):
@@ -410,7 +496,7 @@ class PlainParquetWriter:
             plans.append(segs)
             pos += size
             is_dict = isinstance(values, DictPages)
-            nvalid = sum(values.nv) if is_dict else int(np.asarray(values).size)
+            nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else int(np.asarray(values).size)
             chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
                                minmax=stats[j] if (stats is not None and nvalid > 0) else None,
                                is_list=self.lists[j], first_data=first if is_dict else None))
@@ -454,7 +540,7 @@ class PlainParquetWriter:
         # a dictionary chunk: encodings PLAIN, RLE, RLE_DICTIONARY; data_page_offset (9) is its first
         # data page, dictionary_page_offset (11) the chunk's start; the sizes include the dictionary
         first = c.get("first_data")
-        meta = (_Struct().i32(1, _PQ_TYPE[dt])
+        meta = (_Struct().i32(1, _ptype(dt))
                 .list(2, _CT_I32, [_zigzag(0), _zigzag(3)] + ([_zigzag(8)] if first is not None else []))
                 .list(3, _CT_BINARY, [_varint(len(x.encode())) + x.encode() for x in path])
                 .i32(4, 0).i64(5, c["n"]).i64(6, c["size"]).i64(7, c["size"])
@@ -477,7 +563,10 @@ class PlainParquetWriter:
                 schema.append(_Struct().i32(3, 2).binary(4, "list").i32(5, 1).done())
                 schema.append(_Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, "element").done())
                 continue
-            el = _Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, name)
+            el = _Struct().i32(1, _ptype(dt)).i32(3, 1).binary(4, name)
+            if dt == STRING_DTYPE:
+                # BYTE_ARRAY, converted type UTF8 (0), LogicalType STRING (union field 1, an empty struct)
+                el.i32(6, 0).struct(10, _Struct().struct(1, _Struct().done()).done())
             if logical is not None:
                 field, conv = _TS_UNIT[timestamp_unit(logical)]
                 if conv is not None:

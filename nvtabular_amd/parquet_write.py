@@ -15,7 +15,13 @@ go through kernels_parquet_dict (dictionary build + index pack, enqueued for all
 ONE read-back per row group brings their state records {d, overflow} and page starts, the chunk
 rule (``parquet_plain.dict_pays``) is applied on the host, and each chunk then copies out what it
 really needs: dictionary + packed indices, or the plain values ("Dictionary pages in
-the PLAIN parquet writer")."""
+the PLAIN parquet writer").
+String columns: the column's {surrogate -> str} dict goes to the device once per to_parquet call as an
+entry table (kernels_parquet_str_out.StringTables); per row group the non-null surrogates become entry
+ids and a byte plan, the page table and the count of unknown surrogates ride in the read-back of the
+dictionary states, then the BYTE_ARRAY body is filled on the device and copied out like the values of
+a number column.  An offered string column costs one more read-back per row group (shared by all of
+them): the size of its dictionary page ("String columns in the PLAIN parquet writer")."""
 from __future__ import annotations
 
 import os
@@ -31,13 +37,16 @@ import torch
 from . import kernels as K
 from . import kernels_parquet_dict as KPD
 from . import kernels_parquet_list as KPL
+from . import kernels_parquet_str_out as KSO
 from . import parquet_plain as PP
 from .device import pack_bitmap_device
-from .parquet_plain import DictPages, ListLevels, PlainParquetWriter
+from .parquet_plain import ByteArrayPages, DictPages, ListLevels, PlainParquetWriter
 
 # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
 # levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables;
-# dict_s (a part of stage_s): enqueueing dictionary build + pack and waiting for the state records
+# dict_s (a part of stage_s): enqueueing dictionary build + pack and waiting for the state records;
+# strings_s (a part of stage_s): entry ids, byte plans and fills of string columns, and the read-back
+# of their dictionary page sizes
 LAST_TIMING = {}
 _TORCH_OF = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
 
@@ -51,6 +60,7 @@ class _Column(NamedTuple):
     offsets: Optional[torch.Tensor] = None   # of a list column
     bitmap: Optional[torch.Tensor] = None    # leaf bitmap of a list column (what `mask` unpacks)
     offered: bool = False                    # its chunks are dictionary-encoded where that pays
+    table: Any = None                        # EntryTable of a string column (``data``: its surrogates)
 
 
 class _HostColumn(NamedTuple):
@@ -70,16 +80,33 @@ class _RowGroup(NamedTuple):
     stats: Optional[list]   # per column: {min, max} as a 2-element array (in flight) or None
 
 
-def plain_eligible(frame, dtypes) -> bool:
+def _string_table(name, col, dtypes, tables):
+    """The EntryTable of a flat string column the PLAIN writer takes, else None: surrogates on the
+    device, no ``dtypes`` entry, every value of the dict a ``str`` of at most 2^30 - 4 bytes."""
+    if col.offsets is not None or not col.data.is_cuda or col.data.dtype != torch.int64 or \
+            col.logical is not None or (dtypes and name in dtypes):
+        return None
+    return tables.get(col.strings)
+
+
+def plain_eligible(frame, dtypes, tables=None) -> bool:
     """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
-    casts), a datetime column in ms / us / ns, or a list column on the device whose leaves are
+    casts), a datetime column in ms / us / ns, a flat string column on the device whose dict holds
+    only ``str`` values, or a list column on the device whose leaves are
     int32 / int64 / float32 / float64 numbers: the hand-written PLAIN writer takes the partition;
-    anything else (datetime64[s] too: parquet has no seconds unit; string, bool and 8 / 16-bit
-    leaves; a cast of a list column) goes to pyarrow."""
+    anything else (datetime64[s] too: parquet has no seconds unit; lists of strings, string columns
+    on the host, with a ``dtypes`` entry or with bytes / mixed objects in their dict, bool and
+    8 / 16-bit leaves; a cast of a list column) goes to pyarrow.  ``tables``: the StringTables of the
+    to_parquet call (the entry table built for this verdict is the one the write uses)."""
     if len(frame.columns) == 0:
         return False
+    tables = tables if tables is not None else KSO.StringTables()
     for name, col in frame.items():
-        if col.strings is not None or col.data.dtype not in _TORCH_OF.values():
+        if col.strings is not None:
+            if _string_table(name, col, dtypes, tables) is None:
+                return False
+            continue
+        if col.data.dtype not in _TORCH_OF.values():
             return False
         if col.offsets is not None and (not col.data.is_cuda or col.logical is not None or
                                         (dtypes and name in dtypes)):
@@ -93,7 +120,10 @@ def plain_eligible(frame, dtypes) -> bool:
 
 def _dict_eligible(col, dtypes, name) -> bool:
     """A column of a plain-eligible frame whose chunks can be dictionary-encoded: int32 / int64 (after
-    the requested cast; datetime counts are int64), flat or as list leaves, on the device."""
+    the requested cast; datetime counts are int64), flat or as list leaves, or a string column, on
+    the device."""
+    if col.strings is not None:
+        return bool(col.data.is_cuda)
     dt = np.dtype(dtypes[name]) if (dtypes and name in dtypes) else None
     is_int = (dt in (np.dtype("int32"), np.dtype("int64"))) if dt is not None else \
         col.data.dtype in (torch.int32, torch.int64)
@@ -118,8 +148,8 @@ def dictionary_columns(frame, dtypes, use_dictionary):
         if name not in cols:
             raise ValueError(f"to_parquet: use_dictionary names '{name}', which is no column of {cols}")
         if name not in eligible:
-            raise ValueError(f"to_parquet: use_dictionary names '{name}': only int32 / int64 and datetime columns "
-                             f"and lists of int32 / int64 on the device are dictionary-encoded (these: {eligible})")
+            raise ValueError(f"to_parquet: use_dictionary names '{name}': only int32 / int64, datetime and string "
+                             f"columns and lists of int32 / int64 on the device are dictionary-encoded (these: {eligible})")
     return frozenset(names)
 
 
@@ -135,13 +165,23 @@ def _to_host(t):
     return h
 
 
-def _prepare(part, n, dtypes, offered=frozenset()):
+def _prepare(part, n, dtypes, offered=frozenset(), tables=None):
     """-> ([_Column] of a partition of n rows, [[list columns that share one offsets tensor]]: they share
     plan, page table and repetition stream).  ``offered``: names of the columns whose chunks may be
-    dictionary-encoded."""
+    dictionary-encoded.  ``tables``: the StringTables of the call."""
     cols, groups = [], {}
+    tables = tables if tables is not None else KSO.StringTables()
     for name, col in part.items():
         col = col.materialize()
+        if col.strings is not None:
+            table = _string_table(name, col, dtypes, tables)
+            if table is None:   # (the first partition decided for the PLAIN writer; never cast silently)
+                raise ValueError(f"to_parquet: partition schema differs: string column '{name}' of this partition "
+                                 "is not one the PLAIN writer takes (host data, a list, or a dict value that is "
+                                 "no str)")
+            mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
+            cols.append(_Column(name, col.data, mask, None, offered=name in offered, table=table))
+            continue
         if col.offsets is not None:
             leaves = col.data.contiguous()
             mask = K.unpack_bitmap(col.valid, leaves.numel()) if col.valid is not None else None
@@ -208,20 +248,22 @@ def _column_values(c: _Column, s0, s1, levels):
     return vals, valid, m
 
 
-def _page_start(vals, valid, m, rows):
+def _page_start(vals, valid, m, rows, page_rows=None):
     """int64[pages + 1] on the device: the positions in ``vals`` (the non-null values) at which the data
     pages of the chunk start -- a list column: from the non-null counts of its page table; a flat column:
-    from the per-page popcounts of the row mask, or by arithmetic when there is no mask."""
+    from the per-page popcounts of the row mask, or by arithmetic when there is no mask.  ``page_rows``:
+    the rows per page of a flat column (None: PAGE_VALUES; a string column's follow its longest entry)."""
     dev = vals.device
     if isinstance(valid, ListLevels):
         ps = np.concatenate([[0], np.cumsum(valid.nonnull)]).astype(np.int64)
         return torch.from_numpy(ps).to(dev)
-    npages = max(1, -(-rows // PP.PAGE_VALUES))
+    page_rows = PP.PAGE_VALUES if page_rows is None else page_rows
+    npages = max(1, -(-rows // page_rows))
     if m is None:
-        return torch.clamp(torch.arange(npages + 1, device=dev, dtype=torch.int64) * PP.PAGE_VALUES, max=rows)
-    padded = torch.zeros(npages * PP.PAGE_VALUES, dtype=torch.bool, device=dev)
+        return torch.clamp(torch.arange(npages + 1, device=dev, dtype=torch.int64) * page_rows, max=rows)
+    padded = torch.zeros(npages * page_rows, dtype=torch.bool, device=dev)
     padded[:rows] = m
-    counts = padded.view(npages, PP.PAGE_VALUES).sum(dim=1, dtype=torch.int64)
+    counts = padded.view(npages, page_rows).sum(dim=1, dtype=torch.int64)
     return torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
 
 
@@ -245,6 +287,82 @@ def _stage_column(c: _Column, vals, valid, encoded, statistics, keep):
     return _HostColumn(c.name, hv, hb, c.logical), (mm.numpy() if mm is not None else None)
 
 
+class _StrChunk:
+    """One string column's chunk of a row group between its plan and its fill."""
+
+    def __init__(self, col, surrogates, valid, ids, page_start, pos, page_at, bad):
+        self.col, self.surrogates, self.valid, self.ids = col, surrogates, valid, ids
+        self.page_start, self.pos, self.page_at, self.bad = page_start, pos, page_at, bad
+
+    def device_words(self):
+        return [self.page_at, self.page_start, self.bad]
+
+    def take_words(self, arrays):
+        """The front of ``arrays`` (what the read-back made of ``device_words``) becomes the host's
+        page table; an unknown surrogate raises."""
+        page_at, page_start, bad = arrays[:3]
+        del arrays[:3]
+        if int(bad[0]):
+            raise ValueError(f"to_parquet: column '{self.col.name}': {int(bad[0])} values whose surrogate is no key "
+                             "of the column's dictionary of strings")
+        self.page_at_host, self.nv = page_at, np.diff(page_start)
+
+
+def _plan_strings(cols, staged, rows):
+    """{column index: _StrChunk} of the string columns of a row group of ``rows`` rows: entry ids and
+    byte plan enqueued, nothing read back."""
+    strs = {}
+    for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
+        if c.table is None:
+            continue
+        keys, offsets, _ = c.table.on(vals.device)
+        vals = vals.contiguous()
+        bad = torch.zeros(1, dtype=torch.int64, device=vals.device)
+        page_start = _page_start(vals, valid, m, rows, c.table.page_rows)
+        ids = KSO.entry_ids(keys, vals, bad)
+        pos, page_at = KSO.plan(ids, offsets, page_start)
+        strs[ci] = _StrChunk(c, vals, valid, ids, page_start, pos, page_at, bad)
+    return strs
+
+
+def _stage_strings(strs, dicts, states, keep):
+    """{column index: _HostColumn} of the string chunks after the read-back: the bodies are filled on
+    the device and are on their way to pinned memory.  The chunk rule in bytes: an offered chunk takes
+    the dictionary iff it has at most 2^20 distinct entries and dictionary page + indices are SMALLER
+    than its PLAIN body; the dictionary pages' sizes are ONE more read-back for all of them."""
+    cand = {}
+    for ci, sc in strs.items():
+        d, overflow = states[ci][:2] if ci in dicts else (0, 1)
+        if not overflow and 1 <= d <= PP.DICT_MAX_ENTRIES:
+            cand[ci] = KSO.plan(dicts[ci].dictionary[:d], sc.col.table.on(sc.ids.device)[1])[0]
+    sizes = {}
+    if cand:
+        K.stat_add("pq_str_dict_readback")
+        sizes = dict(zip(cand, K.read_back(torch.cat([p[-1:] for p in cand.values()])).tolist()))
+    hosts = {}
+    for ci, sc in strs.items():
+        _, offsets, chars = sc.col.table.on(sc.ids.device)
+        total, hv = int(sc.page_at_host[-1]), None
+        if ci in cand:
+            d, W = states[ci][0], PP.dict_index_width(states[ci][0])
+            if sizes[ci] <= PP.MAX_PAGE_BYTES and sizes[ci] + PP.dict_index_bytes(sc.nv, W) < total:
+                dd = dicts[ci]
+                body = KSO.fill(dd.dictionary[:d], offsets, chars, cand[ci], sizes[ci])
+                hd, hp = _to_host(body), _to_host(dd.packed[:PP.dict_page_offsets(sc.nv, W)[1]])
+                hv = DictPages(hd.numpy(), hp.numpy(), W, sc.nv, entries=d, page_rows=sc.col.table.page_rows)
+                keep.append((dd, cand[ci], body, hd, hp))
+        if hv is None:
+            body = KSO.fill(sc.ids, offsets, chars, sc.pos, total) if total else None
+            hbody = _to_host(body) if total else None
+            hv = ByteArrayPages(hbody.numpy() if total else np.zeros(0, dtype=np.uint8), sc.page_at_host, sc.nv,
+                                sc.col.table.page_rows)
+            keep.append((body, hbody))
+        hb = _to_host(sc.valid).numpy() if sc.valid is not None else None
+        keep.append((sc, hv, hb))
+        hosts[ci] = _HostColumn(sc.col.name, hv, hb, None)
+    return hosts
+
+
 def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
     """Enqueue everything that brings rows [s0, s1) to the host, on ``copy_s`` (None: the frame is
     on the host already), and record one event behind it."""
@@ -253,15 +371,37 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
     with torch.cuda.stream(copy_s) if copy_s is not None else nullcontext():
         levels = _pack_levels(groups, s0, s1, keep) if (s1 > s0 and groups) else {}
         staged = [_column_values(c, s0, s1, levels) for c in cols]
+        # string columns: entry ids and the byte plan of every one of them (no read-back of their own)
+        t_ss = time.perf_counter()
+        strs = _plan_strings(cols, staged, s1 - s0)
+        LAST_TIMING["strings_s"] += time.perf_counter() - t_ss
         # dictionary pages: build + pack of every offered column that has values, then ONE read-back
+        # (the page tables of the string columns and their unknown surrogates ride along)
         t_dc = time.perf_counter()
-        dicts = {ci: KPD.encode(vals.contiguous(), _page_start(vals, valid, m, s1 - s0))
+        dicts = {ci: KPD.encode(strs[ci].ids, strs[ci].page_start) if ci in strs else
+                 KPD.encode(vals.contiguous(), _page_start(vals, valid, m, s1 - s0))
                  for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)) if c.offered and vals.numel()}
-        states = dict(zip(dicts, KPD.read_back_states(list(dicts.values()))))
+        if strs:
+            got, more = KPD.read_back_states(list(dicts.values()), [t for sc in strs.values() for t in sc.device_words()])
+            for sc in strs.values():
+                sc.take_words(more)
+        else:
+            got = KPD.read_back_states(list(dicts.values()))
+        states = dict(zip(dicts, got))
         if dicts:
             LAST_TIMING["dict_s"] += time.perf_counter() - t_dc
+        elif strs:   # (the read-back waited for entry ids and plans alone)
+            LAST_TIMING["strings_s"] += time.perf_counter() - t_dc
+        t_ss = time.perf_counter()
+        hosts = _stage_strings(strs, dicts, states, keep)
+        if strs:
+            LAST_TIMING["strings_s"] += time.perf_counter() - t_ss
         for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
-            hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep)
+            if ci in hosts:
+                hc, mm = hosts[ci], None   # (no min / max for string chunks)
+            else:
+                hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics,
+                                       keep)
             host.append(hc)
             if statistics:
                 stats.append(mm)
@@ -360,15 +500,17 @@ def _row_ranges(i, n, k, row_group, touched):
 
 
 def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads,
-                offered=frozenset()):
+                offered=frozenset(), tables=None):
     """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
     with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
     ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
     ``offered``: the columns whose chunks are dictionary-encoded where that makes them smaller.
+    ``tables``: the StringTables ``plain_eligible`` judged the first partition with (None: a fresh one).
     -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
     LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
-                       levels_s=0.0, dict_s=0.0)
+                       levels_s=0.0, dict_s=0.0, strings_s=0.0)
     t_all = time.perf_counter()
+    tables = tables if tables is not None else KSO.StringTables()
     copy_s = None
     touched = set()
     with ThreadPoolExecutor(max_workers=threads) as pool:
@@ -378,7 +520,7 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
                 n = len(part)
                 if shuffle is not None and n > 1:
                     part = part.take_rows(device_permutation(n, part))
-                cols, groups = _prepare(part, n, dtypes, offered)
+                cols, groups = _prepare(part, n, dtypes, offered, tables)
                 on_gpu = any(c.data.is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
