@@ -85,7 +85,12 @@ __device__ __forceinline__ void cls_scatter_body(
   for (int r = 0; r < kS2Rows; ++r) {
     const uint64_t i = s2_elem(tile, w, r, l);
     c[r] = ~0ull;
-    if (i < n) c[r] = comp_make(keys[i], cnts[i]);
+    if (i < n) {
+      // the packed word keeps 32 count bits: a count beyond them (class 255 whatever its low word
+      // says) is packed as the largest one, and written out from the source list further down
+      const int64_t cn = cnts[i];
+      c[r] = comp_make(keys[i], cn > 0xFFFFFFFFll ? 0xFFFFFFFFll : cn);
+    }
   }
   const uint64_t tile_base = (uint64_t)tile * kS2Tile;
 #pragma unroll
@@ -160,6 +165,7 @@ __device__ __forceinline__ void cls_scatter_body(
       // labelled after its own sort: -1 here)
       if (label_of != nullptr) label_of[i] = d != 0 ? (int32_t)(first_label + goff[d] + sidx) : -1;
       if (big_src != nullptr && d == 0) big_src[goff[0] + sidx] = (int32_t)i;
+      if (d == 0) out_cnts[goff[0] + sidx] = cnts[i];  // class 255: the count itself, all 64 bits
     }
   }
   __syncthreads();
@@ -174,7 +180,7 @@ __device__ __forceinline__ void cls_scatter_body(
       const unsigned dst = goff[d] + idx;
       const int32_t key = comp_key(v);
       out_keys[dst] = key;
-      out_cnts[dst] = comp_cnt(v);
+      if (d != 0) out_cnts[dst] = comp_cnt(v);
       if (key == INT32_MIN && d != 0 && sentinel_label != nullptr) {
         *sentinel_label = first_label + (int64_t)dst;
       } else if (table != nullptr && d != 0) {  // class 255 gets its labels after its own sort

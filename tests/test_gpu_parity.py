@@ -506,7 +506,9 @@ def test_dense_count_paths_vs_numpy(dtype, card, n, weighted):
 @pytest.mark.parametrize("dtype", ["int32", "int64"])
 @pytest.mark.parametrize("n", [2, 3, 100, 4097, 8192, 8193, 50_000, 300_000])
 def test_vocab_sort_vs_numpy(dtype, n):
-    """(count desc, key asc) on both code paths: LDS bitonic (n <= 8192) and LSD radix."""
+    """(count desc, key asc): the LDS bitonic network (n <= 8192) and, beyond it, the generic LSD radix
+    sort with the histogram read-back (max_count 0, counts of 2^40).  The route int32 vocabularies
+    take with a count bound, vocab_sort_onesweep, is reached by test_gpu_order_kernels.py."""
     from nvtabular_amd import kernels as K
 
     rng = np.random.default_rng(n)

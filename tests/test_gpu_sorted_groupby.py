@@ -504,6 +504,92 @@ def test_exchange_batch_kernels_vs_torch():
         assert torch.equal(cnts[dst_off[s]:dst_off[s] + b - a], w >> 32)
 
 
+def test_exchange_ordered_kernels_vs_numpy():
+    """nvt_exchange_ranges_sorted / _pack_ordered / _unpack2 (the device work of the ordered exchange,
+    which keeps every list in key order) against numpy, with G = 8 virtual owners: every (owner,
+    column) cell of the send buffer is the contiguous slice of its column IN KEY ORDER -- compared as
+    it lies, not sorted -- and the unpack moves keys, counts and an int32 payload."""
+    from nvtabular_amd import kernels as K
+
+    rng = np.random.default_rng(14)
+    dev = "cuda"
+    G = 8
+    sizes = [200_000, 0, 3, 77_777, 1, 4096, 4097, 50_000, 10, 123_456]
+    lists, los, widths = [], [], []
+    boundary = clamped = 0
+    for j, m in enumerate(sizes):
+        if j == 0:     # both ends of int32 but one: a span of 2^32 - 1 keys
+            k = np.unique(np.concatenate([rng.integers(-2**31, 2**31 - 2, m + 100), [-2**31, 2**31 - 2]]))
+        elif j % 2 == 0:
+            k = np.unique(rng.integers(-2**31, 2**31 - 2, m + 100))
+        else:
+            k = np.unique(rng.integers(-1000 * j, -1000 * j + 3 * m + 5, 2 * m))
+        k = np.sort(rng.permutation(k)[:m]) if j else np.concatenate([k[:1], np.sort(rng.permutation(k[1:-1])[:m - 2]), k[-1:]])
+        assert k.size == m
+        lo, hi = (int(k[0]), int(k[-1])) if m else (0, 0)
+        if m > 1 and (hi - lo + 1) % G == 0:
+            k[-1] += 1
+            hi += 1
+        # even columns: ceil(span / G) keys per owner; odd columns: a narrower width, so that the keys at
+        # the far end would belong to an owner >= G and are clamped to G - 1
+        span = hi - lo + 1
+        width = max(1, -(-span // G) if j % 2 == 0 else span // (G + 3))
+        if m >= 1000:  # keys on both sides of every owner boundary
+            edge = lo + width * np.arange(1, G, dtype=np.int64)
+            edge = np.concatenate([edge, edge - 1])
+            edge = edge[(edge > lo) & (edge < hi)]
+            inner = np.setdiff1d(k[1:-1], edge)
+            k = np.sort(np.concatenate([k[:1], k[-1:], edge, rng.permutation(inner)[:m - 2 - edge.size]]))
+            assert k.size == m and np.unique(k).size == m and k[0] == lo and k[-1] == hi
+            assert (hi - lo + 1) % G != 0
+        o = (k.astype(np.int64) - lo) // width
+        boundary += int((((k.astype(np.int64) - lo) % width == 0) & (o > 0) & (o < G)).sum())
+        clamped += int((o >= G).sum())
+        c = rng.integers(1, 10_000, m).astype(np.int64)
+        lists.append((k.astype(np.int32), c, np.minimum(o, G - 1)))
+        los.append(lo)
+        widths.append(width)
+    assert boundary >= 7 * 5 and clamped > 100
+    ncol = len(lists)
+    xb = K.ExchangeBatch([(torch.from_numpy(k).to(dev), torch.from_numpy(c).to(dev)) for k, c, _ in lists])
+    big = np.iinfo(np.int64).max
+    got = xb.ranges_sorted().cpu().numpy()
+    for j, (k, c, _) in enumerate(lists):
+        assert got[j].tolist() == ([-int(k[0]), int(k[-1]), 0] if k.size else [-big, -big, 0]), j
+    exp_mat = np.stack([np.bincount(o, minlength=G) for _, _, o in lists], axis=1).astype(np.int64)   # [G, ncol]
+    mat = xb.hist(los, widths, G)
+    np.testing.assert_array_equal(mat.cpu().numpy(), exp_mat)
+    first_row = np.cumsum(exp_mat, axis=0) - exp_mat                 # rows of the column in front of the slice
+    flat = exp_mat.reshape(-1)
+    starts = (np.cumsum(flat) - flat).reshape(G, ncol)               # cells in (owner, column) order
+    rows = xb.pack_ordered(los, widths, G, torch.from_numpy(starts).to(dev), torch.from_numpy(first_row).to(dev))
+    rows = rows.cpu().numpy()
+    assert rows.size == sum(sizes) == int(flat.sum())
+    for g in range(G):
+        for j, (k, c, o) in enumerate(lists):
+            a, m = int(first_row[g, j]), int(exp_mat[g, j])
+            assert (o[a:a + m] == g).all() and (g == 0 or a == 0 or o[a - 1] < g)   # the slice IS owner g's
+            exp = (c[a:a + m] << 32) | (k[a:a + m].astype(np.int64) & 0xFFFFFFFF)
+            np.testing.assert_array_equal(rows[starts[g, j]:starts[g, j] + m], exp, err_msg=f"owner {g}, column {j}")
+    # unpack with a payload: an empty segment, destinations that are not 16-byte aligned
+    n = rows.size
+    words = torch.from_numpy(rows).to(dev)
+    extra = rng.integers(-2**31, 2**31 - 1, n).astype(np.int32)
+    seg_off = [0, 5, 5, 1000, n]
+    dst_off = [3 + (n - 1000) + 2, 1, 3 + (n - 1000) + 2 + 5 + 1, 3]
+    out_n = dst_off[2] + 995 + 4
+    assert all(d % 4 for d in dst_off) and all(d % 2 for d in dst_off)      # int32 and int64 outputs
+    keys, cnts, lab = K.exchange_unpack(words, seg_off, dst_off, out_n, extra=torch.from_numpy(extra).to(dev))
+    assert keys.dtype == torch.int32 and cnts.dtype == torch.int64 and lab.dtype == torch.int32
+    keys, cnts, lab = keys.cpu().numpy(), cnts.cpu().numpy(), lab.cpu().numpy()
+    for s in range(4):
+        a, b, d = seg_off[s], seg_off[s + 1], dst_off[s]
+        w = rows[a:b]
+        np.testing.assert_array_equal(keys[d:d + b - a], (w & 0xFFFFFFFF).astype(np.uint32).view(np.int32), err_msg=f"segment {s}")
+        np.testing.assert_array_equal(cnts[d:d + b - a], w >> 32, err_msg=f"segment {s}")
+        np.testing.assert_array_equal(lab[d:d + b - a], extra[a:b], err_msg=f"segment {s}")
+
+
 @pytest.mark.parametrize("keyed", [True, False])
 def test_clustered_keys_fall_back_to_a_hashed_index(tmp_path, monkeypatch, keyed):
     """Dense ids plus one far outlier: the sort path still aggregates, but the flat index would have
