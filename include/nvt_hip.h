@@ -641,7 +641,8 @@ int nvt_te_image(const int64_t *tot_count, const double *tot_sum, const int64_t 
  *   dir[b] = uint32[4] {first, k0, k1, k2}, b = 0 .. dir_slots : first = index of the first key
  *            that maps to a bucket >= b under the monotone range map over [keys32[0],
  *            keys32[nkeys - 1]] (dir[dir_slots].first = nkeys); k0..k2 = the bucket's first three
- *            keys (a shorter bucket repeats its last key, an empty one holds the list's next key);
+ *            keys (a shorter bucket repeats its last key, an empty one holds the list's next key,
+ *            or the last key when there is none behind it);
  * a row whose key is k0 / k1 / k2 has its group from that read, a key above k2 walks keys32 from
  * first + 3 (bisection inside the bucket when the keys cluster).  No parameter block, no failure
  * mode to read back.

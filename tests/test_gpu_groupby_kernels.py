@@ -44,9 +44,11 @@ every partial sum is a multiple of 2^-4 below 2^33 (37 bits) and every partial s
 multiple of 2^-8 below 2^43 (51 bits): any order of summation gives the same float64.
 ``assert_exact`` checks that on the generated data.
 
-Left out, by name: the nvt_sgb_* sort path and merge_sorted_comps, the flat index, the exchange
-kernels, te_apply* and gather (test_gpu_sorted_groupby.py and the operator tests), the retry and
-demotion logic of ops/_groupby.py, string keys, multi-rank merges.
+Left out, by name: the nvt_sgb_* sort path and merge_sorted_comps, the exchange kernels
+(test_gpu_sorted_groupby.py and the operator tests), the flat index, the key directory and the
+record reads (test_gpu_lookup_kernels.py against lookup_reference.py), te_apply* and gather
+(test_gpu_cont_kernels.py), the retry and demotion logic of ops/_groupby.py, string keys,
+multi-rank merges.
 """
 import math
 import zlib

@@ -3,13 +3,18 @@ nvt_keydir_lookup_image / nvt_image_build): the transform side of JoinGroupby
 (join_groupby.py:198-217) and TargetEncoding (target_encoding.py:341-371) on the sort path's groups
 with one random line of HBM per row.  Equal to numpy's searchsorted on the key list, bit for bit
 to the flat-table lookup and the per-operator image kernels, and end to end to the same workflow
-with both switched off."""
+with both switched off.  The independent reference of the key -> group step and of the record
+reads (every layout, bucket size and key-offset edge) lives in test_gpu_lookup_kernels.py with
+lookup_reference.py, whose ``check_keydir`` holds the directory against its definition here too;
+the kernel-versus-kernel comparison of the one-pass build below remains as a consistency check."""
 import ctypes as C
 
 import numpy as np
 import pandas as pd
 import pytest
 import torch
+
+import lookup_reference as R
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +33,7 @@ def _lookup(ids, rows, valid=None, key_offset=0, null_group=-1, load=1.0, dtype=
     d = torch.empty(4 * (B + 1), dtype=torch.int32, device=dev)
     K.check(lib.nvt_keydir_build(keys32.data_ptr(), n, B, d.data_ptr(), K.stream_ptr()), "nvt_keydir_build")
     # directory == the definition: `first` monotone from 0 to n, then the bucket's first keys
-    dh = d.cpu().numpy().reshape(B + 1, 4)
-    first = dh[:, 0].astype(np.int64) & 0xFFFFFFFF
-    assert first[0] == 0 and first[-1] == n and np.all(np.diff(first) >= 0)
-    cnt = np.diff(np.append(first, n))
-    has = cnt > 0
-    np.testing.assert_array_equal(dh[has, 1], ids[first[has]])
-    two = cnt > 1
-    np.testing.assert_array_equal(dh[two, 2], ids[first[two] + 1])
-    np.testing.assert_array_equal(dh[has & ~two, 2], dh[has & ~two, 1])
+    R.check_keydir(d.cpu().numpy(), ids, B)
     recs = n + (1 if null_group >= 0 else 0)
     image = torch.arange(recs, dtype=torch.int64, device=dev)          # record g = the int64 g
     key = torch.from_numpy(rows.astype(dtype)).to(dev)

@@ -2,8 +2,11 @@
 nvt_te_image): ONE probe and ONE packed per-group record per row for every operator fitted on a
 key column -- JoinGroupby.transform (join_groupby.py:198-217) and TargetEncoding.transform
 (target_encoding.py:341-371) on the same key.  Bit-for-bit equal to the per-operator kernels
-(nvt_flat_lookup_gather / nvt_flat_lookup_te), which stay the reference implementation of the
-engine, and to the oracle end to end."""
+(nvt_flat_lookup_gather / nvt_flat_lookup_te) -- a consistency check between kernels that share
+their arithmetic -- and to the oracle end to end.  The independent reference of the probe and of
+the record reads lives in test_gpu_lookup_kernels.py (numpy: lookup_reference.py), which also
+holds the references of the values the builders write (jg_stats, te_values, build_image; pinned
+on the CPU in test_lookup_reference.py)."""
 import ctypes as C
 
 import numpy as np
