@@ -1383,6 +1383,73 @@ int nvt_pq_byte_array_fill(const int32_t *ids, uint64_t m, const int64_t *offset
                            uint64_t n_entries, const uint64_t *pos, uint8_t *out, uint64_t out_bytes,
                            void *stream);
 
+/* ---- parquet out: snappy pages, Dataset.to_parquet(device_compression="snappy") ----
+ * The values regions of the column chunks of a row group become snappy ELEMENT streams (literals and
+ * copies with 2-byte offsets; the varint in front of a page body is the host's).  A region is cut at
+ * its page starts and then into fragments of at most NVT_SNAPPY_FRAG bytes; a fragment is parsed on
+ * its own (no copy reaches in front of it), so the streams of a page's fragments, one behind the
+ * other, are the page's elements.  All columns of a row group go through three calls that take the
+ * same descriptors and the same batch; each launches once per NVT_SNAPPY_MAX_COLS descriptors.
+ * Descriptor: src (nbytes readable bytes, any alignment; only words that hold a byte of src are
+ *   loaded), page_start[npages + 1] on the device in units of `unit` bytes (a value is clamped to
+ *   [0, nbytes], a descending pair is an empty page), elem (4 or 8: the parse also looks one element
+ *   back), frag_base / max_frags (the column's records in the batch: frag_base of column 0 is 0,
+ *   every next one follows; max_frags >= ceil(nbytes / FRAG) + npages), dense (dense_cap bytes,
+ *   4-byte aligned) and out[npages + NVT_SNAPPY_OUT_WORDS] (8-byte aligned): out[p] = compressed
+ *   bytes of page p, then {total, error, fragments, 0}.  error: NVT_SNAPPY_ERR_PLAN (the page table
+ *   needs more than max_frags records) or NVT_SNAPPY_ERR_SLOT (a fragment's stream did not fit
+ *   slot_cap; it reports 0 bytes): the column's output means nothing then.
+ * Batch: frag_table (total_frags records of NVT_SNAPPY_FRAG_WORDS uint64 {source byte offset,
+ *   bytes, page, column}; bytes = 0: unused), frag_size / frag_pos (total_frags + 1 uint64: the
+ *   bytes of every fragment's stream and their exclusive scan over the batch), slots (total_frags
+ *   * slot_cap bytes, 4-byte aligned; fragment e writes slots + e * slot_cap and never more than
+ *   slot_cap bytes; NVT_SNAPPY_SLOT_BYTES holds any stream: DESIGN.md), ws (nvt_snappy_ws_bytes).
+ * nvt_snappy_plan_many fills the table and clears every out; nvt_snappy_compress_many parses (one
+ *   wave per fragment; the same input gives the same bytes); nvt_snappy_gather_many scans the sizes
+ *   and moves the streams of column c, page after page, to dense: page p's elements start at the
+ *   sum of out[q < p].  A column whose total passes dense_cap is not moved (its sizes stand).
+ * Argument errors (null pointers, ncols <= 0, an element size other than 4 / 8, ranges that do not
+ * tile [0, total_frags)) return NVT_EINVAL before anything is launched.  Stream-ordered, no
+ * allocation, no synchronisation. */
+#define NVT_SNAPPY_FRAG 32768u
+#define NVT_SNAPPY_SLOT_BYTES (NVT_SNAPPY_FRAG + NVT_SNAPPY_FRAG / 32 + 16)
+#define NVT_SNAPPY_MAX_COLS 16
+#define NVT_SNAPPY_FRAG_WORDS 4
+#define NVT_SNAPPY_OUT_WORDS 4
+#define NVT_SNAPPY_OUT_TOTAL 0
+#define NVT_SNAPPY_OUT_ERROR 1
+#define NVT_SNAPPY_OUT_FRAGS 2
+#define NVT_SNAPPY_ERR_PLAN 1
+#define NVT_SNAPPY_ERR_SLOT 2
+typedef struct nvt_snappy_col {
+  const uint8_t *src;
+  const int64_t *page_start;
+  uint64_t npages;
+  uint64_t nbytes;
+  uint32_t unit;
+  uint32_t elem;
+  uint64_t frag_base;
+  uint64_t max_frags;
+  uint8_t *dense;
+  uint64_t dense_cap;
+  uint64_t *out;
+} nvt_snappy_col;
+typedef struct nvt_snappy_batch {
+  uint64_t *frag_table;
+  uint64_t *frag_size;
+  uint64_t *frag_pos;
+  uint8_t *slots;
+  uint64_t total_frags;
+  uint64_t slot_cap;
+  void *ws;
+  uint64_t ws_bytes;
+} nvt_snappy_batch;
+int nvt_snappy_slot_bytes(uint64_t *bytes);
+int nvt_snappy_ws_bytes(uint64_t total_frags, uint64_t *bytes);
+int nvt_snappy_plan_many(const nvt_snappy_col *cols, int ncols, const nvt_snappy_batch *batch, void *stream);
+int nvt_snappy_compress_many(const nvt_snappy_col *cols, int ncols, const nvt_snappy_batch *batch, void *stream);
+int nvt_snappy_gather_many(const nvt_snappy_col *cols, int ncols, const nvt_snappy_batch *batch, void *stream);
+
 /* ---- exact column medians: ops.FillMedian (MSD radix select) ----
  * A value maps to an order-preserving unsigned key of its own width: floats flip all bits of a
  * negative value and the sign bit of the others, integers flip the sign bit.  The two middle

@@ -377,6 +377,33 @@ SIGNATURES.update({
     "nvt_pq_byte_array_fill": [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp],
 })
 
+class SnappyCol(C.Structure):
+    """nvt_snappy_col: the values region of one column chunk compressed by nvt_snappy_*_many."""
+    _fields_ = [("src", _vp), ("page_start", _vp), ("npages", _u64), ("nbytes", _u64), ("unit", _u32),
+                ("elem", _u32), ("frag_base", _u64), ("max_frags", _u64), ("dense", _vp), ("dense_cap", _u64),
+                ("out", _vp)]
+
+
+class SnappyBatch(C.Structure):
+    """nvt_snappy_batch: the fragment arrays, slots and scan workspace the descriptors of a call share."""
+    _fields_ = [("frag_table", _vp), ("frag_size", _vp), ("frag_pos", _vp), ("slots", _vp),
+                ("total_frags", _u64), ("slot_cap", _u64), ("ws", _vp), ("ws_bytes", _u64)]
+
+
+# include/nvt_hip.h NVT_SNAPPY_*
+SNAPPY_FRAG, SNAPPY_MAX_COLS, SNAPPY_FRAG_WORDS, SNAPPY_OUT_WORDS = 32768, 16, 4, 4
+SNAPPY_SLOT_BYTES = SNAPPY_FRAG + SNAPPY_FRAG // 32 + 16
+SNAPPY_OUT_TOTAL, SNAPPY_OUT_ERROR, SNAPPY_OUT_FRAGS = 0, 1, 2
+SNAPPY_ERR_PLAN, SNAPPY_ERR_SLOT = 1, 2
+SIGNATURES.update({
+    "nvt_snappy_slot_bytes": [C.POINTER(_u64)],
+    "nvt_snappy_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_snappy_plan_many": [C.POINTER(SnappyCol), _i32, C.POINTER(SnappyBatch), _vp],
+    "nvt_snappy_compress_many": [C.POINTER(SnappyCol), _i32, C.POINTER(SnappyBatch), _vp],
+    "nvt_snappy_gather_many": [C.POINTER(SnappyCol), _i32, C.POINTER(SnappyBatch), _vp],
+})
+
+
 class SelectCol(C.Structure):
     """nvt_select_col: one chunk of one column read by nvt_select_hist_many."""
     _fields_ = [("x", _vp), ("valid", _vp), ("n", _u64), ("dtype", C.c_int32), ("has_fill", C.c_int32),

@@ -324,7 +324,8 @@ class Dataset:
 
     def to_parquet(self, output_path, shuffle=None, out_files_per_proc=None, dtypes=None,
                    cats=None, conts=None, labels=None, preserve_files=False, suffix=".parquet",
-                   num_threads=0, compression=None, statistics=False, use_dictionary=None, **_):
+                   num_threads=0, compression=None, statistics=False, use_dictionary=None,
+                   device_compression=None, **_):
         """Write the (transformed) dataset as parquet (merlin.io.Dataset.to_parquet; contract in
         tests/unit/workflow/test_workflow.py:171-187,363-396,444-500 and
         bench/datasets/tools/nvt_etl.py:154-171 of the reference).
@@ -369,6 +370,19 @@ class Dataset:
           in the PLAIN parquet writer").  When the frame goes to pyarrow's writer anyway (lists of
           strings, a codec, ``Shuffle.PER_WORKER`` with ``out_files_per_proc``, ``NVT_PLAIN_PARQUET=0``), a
           value other than ``None`` is handed to pyarrow as its own ``use_dictionary``.
+        * ``device_compression``: ``None`` (default) writes exactly the files described above.
+          ``"snappy"`` (case-insensitive) keeps the frame with the PLAIN writer and compresses its
+          pages on the device: the pages are cut where they are cut today, a page body becomes a
+          snappy raw stream (the level bytes inside one literal, the values region parsed on the
+          device, one wave per 32 KiB fragment), and a column chunk is written SNAPPY only when that
+          makes it smaller, page headers included -- otherwise it is written as today, so the option
+          never makes a file larger (an incompressible float column costs one pass and nothing on
+          disk).  The rule is applied after ``use_dictionary``'s, to the form the chunk takes: a
+          dictionary chunk compresses its dictionary page.  Any other value, or a ``compression``
+          next to it, raises ``ValueError`` before any file exists; ``compression="snappy"`` alone
+          still selects pyarrow's writer.  When the frame goes to pyarrow's writer anyway, the value
+          is handed to pyarrow as its ``compression`` ("Snappy pages in the PLAIN parquet
+          writer").
         * writes ``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and
           ``_metadata.json`` (file stats + cats / conts / labels) next to the data files.
         """
@@ -379,6 +393,13 @@ class Dataset:
         from . import dist
 
         shuffle = Shuffle.coerce(shuffle)
+        if device_compression is not None:   # (argument errors come before anything is created)
+            if not isinstance(device_compression, str) or device_compression.lower() != "snappy":
+                raise ValueError(f"to_parquet: device_compression takes None or 'snappy', not {device_compression!r}")
+            if compression is not None:
+                raise ValueError("to_parquet: compression= selects pyarrow's writer and device_compression= the PLAIN "
+                                 f"writer's codec: pass one of them, not both ({compression!r}, {device_compression!r})")
+            device_compression = "snappy"
         os.makedirs(str(output_path), exist_ok=True)
         output_path = str(output_path)
         rank, world = dist.rank(), dist.world_size()
@@ -391,7 +412,10 @@ class Dataset:
         first = next(parts, None)
         parts = itertools.chain([first], parts) if first is not None else iter(())
         tables = StringTables()   # the entry tables of string columns, for this call
-        if first is not None and PLAIN_PARQUET and compression is None and \
+        # (a frame on the host has nothing to compress its pages with: pyarrow gets the codec)
+        on_host = device_compression is not None and first is not None and \
+            not all(col.data.is_cuda for _, col in first.items())
+        if first is not None and PLAIN_PARQUET and compression is None and not on_host and \
                 not (shuffle == Shuffle.PER_WORKER and k) and plain_eligible(first, dtypes, tables):
             # fixed-width numeric columns, lists of them and flat string columns on the device: PLAIN
             # pages written straight from pinned column buffers (parquet_write.py; a string column's
@@ -401,11 +425,13 @@ class Dataset:
             # bools and narrow leaves go to pyarrow below
             offered = dictionary_columns(first, dtypes, use_dictionary)   # (raises before any file exists)
             names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
-                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered, tables)
+                                             PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered, tables,
+                                             snappy=device_compression is not None)
             collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
             schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
         else:
-            pq_kw = {} if compression is None else {"compression": compression}
+            codec = compression if compression is not None else device_compression
+            pq_kw = {} if codec is None else {"compression": codec}
             if use_dictionary is not None:
                 pq_kw["use_dictionary"] = use_dictionary
             names, rows, order, schema, collector = _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw)

@@ -49,6 +49,11 @@ RLE_DICTIONARY), handed over as ``DictPages``: dictionary and indices are made o
 the dictionary makes it smaller ("Dictionary pages in the PLAIN parquet writer").  A string
 chunk's dictionary page is the PLAIN BYTE_ARRAY encoding of its distinct entries.  Not
 done: float and bool dictionaries, RLE runs inside the index stream, DELTA encodings.
+With ``to_parquet(device_compression="snappy")`` a column chunk may be written SNAPPY (codec 1): the
+same pages, every body the snappy raw stream ``varint(U) | one literal holding the level bytes | the
+elements of the values region`` with the elements made on the device (kernels_snappy,
+csrc/nvt_snappy.hip), handed over as ``SnappyPages``; ``snappy_pays`` keeps a chunk as it is written
+today unless the codec makes it smaller ("Snappy pages in the PLAIN parquet writer").
 The reading half also takes flat STRING columns (any writer's dictionary / PLAIN pages): their
 dictionary entries and index runs are staged as the file holds them and expanded, hashed and
 gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "String columns in
@@ -107,14 +112,16 @@ def timestamp_unit(logical) -> Optional[str]:
     return unit if unit in _TS_UNIT else None
 
 
-def _page_header(num_values: int, page_bytes: int, encoding: int = 0) -> bytes:
+def _page_header(num_values: int, page_bytes: int, encoding: int = 0, compressed: Optional[int] = None) -> bytes:
+    """``compressed``: the bytes of the body as it is written (None: ``page_bytes``, no codec)."""
     dph = _Struct().i32(1, num_values).i32(2, encoding).i32(3, 3).i32(4, 3).done()  # PLAIN / RLE_DICTIONARY, RLE, RLE
-    return _Struct().i32(1, 0).i32(2, page_bytes).i32(3, page_bytes).struct(5, dph).done()
+    return (_Struct().i32(1, 0).i32(2, page_bytes).i32(3, page_bytes if compressed is None else compressed)
+            .struct(5, dph).done())
 
 
-def _dict_page_header(d: int, page_bytes: int) -> bytes:
+def _dict_page_header(d: int, page_bytes: int, compressed: Optional[int] = None) -> bytes:
     """PageHeader of a DICTIONARY_PAGE (type 2) of d PLAIN values."""
-    return (_Struct().i32(1, 2).i32(2, page_bytes).i32(3, page_bytes)
+    return (_Struct().i32(1, 2).i32(2, page_bytes).i32(3, page_bytes if compressed is None else compressed)
             .struct(7, _Struct().i32(1, d).i32(2, 0).done()).done())
 
 
@@ -303,6 +310,110 @@ class ByteArrayPages:
         return memoryview(self.body).cast("B")[self.page_at[p]: self.page_at[p + 1]]
 
 
+def _snappy_literal_tag(n: int) -> bytes:
+    """The tag of a snappy literal element of n >= 1 bytes: ``(n - 1) << 2`` up to 60 bytes, else
+    ``(59 + k) << 2`` and n - 1 in k little-endian bytes."""
+    if n <= 60:
+        return bytes([(n - 1) << 2])
+    k = ((n - 1).bit_length() + 7) // 8
+    return bytes([(59 + k) << 2]) + (n - 1).to_bytes(k, "little")
+
+
+def flat_level_bytes(rows: int, nulls: bool) -> int:
+    """Bytes of the definition levels of a flat page of ``rows`` rows (``_def_levels``)."""
+    if not nulls:
+        return 4 + len(_varint(rows << 1)) + 1
+    groups = (rows + 7) // 8
+    return 4 + len(_varint((groups << 1) | 1)) + groups
+
+
+def list_level_bytes(slots: int) -> int:
+    """Bytes of the repetition and definition levels of a list page of ``slots`` slots."""
+    return len(_packed_levels(slots, 1)) + len(_packed_levels(slots, 2)) + 3 * ((slots + 7) // 8)
+
+
+def snappy_chunk_bytes(pages, dictionary=None):
+    """(bytes of the chunk written SNAPPY, bytes of the same chunk as it is written today), page
+    headers included.  ``pages``: per data page (num_values, literal, raw, elements, encoding) -- the
+    bytes of its body that travel inside the literal element (levels, and the indices of a dictionary
+    page), the bytes of its values region, the bytes of the region's element stream and 0 (PLAIN) or 8
+    (RLE_DICTIONARY).  ``dictionary``: None, or (entries, raw, elements) of the dictionary page."""
+    comp = plain = 0
+    if dictionary is not None:
+        d, raw, el = (int(x) for x in dictionary)
+        c = len(_varint(raw)) + el
+        comp += len(_dict_page_header(d, raw, c)) + c
+        plain += len(_dict_page_header(d, raw)) + raw
+    for num_values, literal, raw, el, encoding in pages:
+        U = int(literal) + int(raw)
+        c = len(_varint(U)) + (len(_snappy_literal_tag(literal)) + literal if literal else 0) + int(el)
+        comp += len(_page_header(num_values, U, encoding, c)) + c
+        plain += len(_page_header(num_values, U, encoding)) + U
+    return comp, plain
+
+
+def snappy_pays(compressed: int, plain: int) -> bool:
+    """The chunk rule of ``device_compression``: a chunk is written SNAPPY iff that form, page headers
+    included, is SMALLER than the chunk as it is written today (``snappy_chunk_bytes``).  Applied
+    after ``dict_pays``, to whichever form the chunk takes; an incompressible chunk stays as it is."""
+    return int(compressed) < int(plain)
+
+
+class SnappyPages:
+    """One SNAPPY column chunk, as ``write_row_group`` takes it in the place of the values.  The
+    pages are the pages of the uncompressed chunk; a page body is the snappy raw stream
+
+        varint(U) | ONE literal element { the level bytes as they are written today } | elements
+
+    where the elements are those of the page's values region, made on the device (kernels_snappy;
+    tests/snappy_reference.py restates the format).  ``dense`` (bytes-like, uint8) holds the element
+    streams of all pages one behind the other, ``sizes[p]`` the bytes of page p's stream and
+    ``raw[p]`` the bytes of its values region (a number column: non-null values x item size).
+    ``dtype``: the column's (``STRING_DTYPE``: the regions are PLAIN BYTE_ARRAY bodies, and
+    ``page_rows`` the rows per page as in ``ByteArrayPages``).
+    A dictionary chunk: ``indices`` = (W, packed, nv, entries) as in ``DictPages`` (``entries``: the
+    dictionary's), ``dense`` / ``sizes[0]`` / ``raw[0]`` the elements of the dictionary page alone;
+    the width byte and the index run of a data page travel inside its literal.
+    Like the values, ``dense`` and ``packed`` may still be in flight when the row group is laid out."""
+
+    __slots__ = ("dtype", "dense", "sizes", "raw", "at", "page_rows", "W", "packed", "nv", "idx_at", "entries")
+
+    def __init__(self, dtype, dense, sizes, raw, page_rows=None, indices=None):
+        self.dtype = STRING_DTYPE if dtype == STRING_DTYPE else np.dtype(dtype)
+        self.dense = dense
+        self.sizes, self.raw = [int(x) for x in sizes], [int(x) for x in raw]
+        self.page_rows = int(page_rows) if page_rows is not None else None
+        if len(self.sizes) != len(self.raw) or len(self.sizes) < 1:
+            raise ValueError(f"SnappyPages: {len(self.sizes)} stream sizes for {len(self.raw)} regions")
+        if any(c < 0 or u < 0 or (u == 0) != (c == 0) or u > MAX_PAGE_BYTES for c, u in zip(self.sizes, self.raw)):
+            raise ValueError("SnappyPages: a page's stream and its region must both be empty or both hold bytes")
+        self.at = [0]
+        for c in self.sizes:
+            self.at.append(self.at[-1] + c)
+        if len(dense) < self.at[-1]:
+            raise ValueError(f"SnappyPages: {len(dense)} dense bytes, the pages take {self.at[-1]}")
+        self.W = self.packed = self.nv = self.idx_at = self.entries = None
+        if indices is not None:
+            W, packed, nv, entries = indices
+            self.W, self.packed, self.nv, self.entries = int(W), packed, [int(x) for x in nv], int(entries)
+            if len(self.sizes) != 1 or self.entries < 1 or self.W != dict_index_width(self.entries):
+                raise ValueError(f"SnappyPages: index width {self.W} for a dictionary of {self.entries} entries")
+            self.idx_at, total = dict_page_offsets(self.nv, self.W)
+            if len(packed) < total:
+                raise ValueError(f"SnappyPages: {len(packed)} packed bytes, the pages take {total}")
+
+    def indices(self, p, nv):
+        """[bytes-like] of data page p's value section of a dictionary chunk: the width byte, then the run."""
+        if not 0 <= p < len(self.nv) or self.nv[p] != nv:
+            raise ValueError(f"PlainParquetWriter: page {p} has {nv} non-null values, its SnappyPages say "
+                             f"{self.nv[p] if 0 <= p < len(self.nv) else 'nothing'}")
+        if nv == 0:
+            return [bytes([self.W])]
+        groups = (nv + 7) // 8
+        return [bytes([self.W]) + _varint((groups << 1) | 1),
+                memoryview(self.packed).cast("B")[self.idx_at[p]: self.idx_at[p] + groups * self.W]]
+
+
 class PlainParquetWriter:
     """One parquet file of int32 / int64 / float32 / float64 columns, flat or "list of" such leaves,
     and flat string columns (``STRING_DTYPE``: BYTE_ARRAY annotated UTF8 / STRING),
@@ -409,8 +520,6 @@ class PlainParquetWriter:
             raise TypeError(f"PlainParquetWriter: leaf buffer is {values.dtype} "
                             f"(contiguous={values.flags.c_contiguous}), the file's column is list of {dt}")
         vbytes = memoryview(values).cast("B") if values.size else memoryview(b"")
-        rep = memoryview(levels.rep).cast("B") if len(levels.rep) else memoryview(b"")
-        dfn = memoryview(levels.dfn).cast("B") if len(levels.dfn) else memoryview(b"")
         npages = len(levels.slots)
         if not (len(levels.nonnull) == len(levels.rep_at) == len(levels.def_at) == npages):
             raise ValueError("PlainParquetWriter: the page table's columns differ in length")
@@ -420,21 +529,11 @@ class PlainParquetWriter:
             if len(dp.nv) != npages:
                 raise ValueError(f"PlainParquetWriter: {npages} data pages, the DictPages hold {len(dp.nv)}")
         first = at
-        for p in range(npages):
-            slots, nv = levels.slots[p], levels.nonnull[p]
-            groups = (slots + 7) // 8
-            r0, d0 = levels.rep_at[p], levels.def_at[p]
-            if slots <= 0 or not 0 <= nv <= slots:
-                raise ValueError(f"PlainParquetWriter: page {p} has {slots} slots and {nv} non-null leaves")
-            if r0 < 0 or d0 < 0 or r0 + groups > len(rep) or d0 + 2 * groups > len(dfn):
-                raise ValueError(f"PlainParquetWriter: the level bytes do not match the page table (page {p}: "
-                                 f"{slots} slots at {r0} of {len(rep)} rep bytes, at {d0} of {len(dfn)} def bytes)")
+        for p, (slots, lev, nv) in enumerate(self._list_page_levels(levels)):
             payload = [vbytes[done_vals * dt.itemsize: (done_vals + nv) * dt.itemsize]] if dp is None else \
                 dp.indices(p, nv)
-            rhead, dhead = _packed_levels(slots, 1), _packed_levels(slots, 2)
-            body = len(rhead) + groups + len(dhead) + 2 * groups + sum(len(b) for b in payload)
-            for buf in [_page_header(slots, body, 0 if dp is None else 8) + rhead, rep[r0: r0 + groups], dhead,
-                        dfn[d0: d0 + 2 * groups]] + payload:
+            body = sum(len(b) for b in lev) + sum(len(b) for b in payload)
+            for buf in [_page_header(slots, body, 0 if dp is None else 8) + lev[0]] + lev[1:] + payload:
                 if len(buf):
                     segs.append((at, buf))
                     at += len(buf)
@@ -449,6 +548,79 @@ class PlainParquetWriter:
             raise ValueError("PlainParquetWriter: the values do not match the page table "
                              f"({values.size} values, {done_vals} non-null leaves)")
         return segs, at - start, first
+
+    @staticmethod
+    def _list_page_levels(levels):
+        """(slots, [level buffers], non-null leaves) of every page of a list chunk, as
+        ``_plan_list_column`` lays them out."""
+        rep = memoryview(levels.rep).cast("B") if len(levels.rep) else memoryview(b"")
+        dfn = memoryview(levels.dfn).cast("B") if len(levels.dfn) else memoryview(b"")
+        npages = len(levels.slots)
+        if not (len(levels.nonnull) == len(levels.rep_at) == len(levels.def_at) == npages):
+            raise ValueError("PlainParquetWriter: the page table's columns differ in length")
+        for p in range(npages):
+            slots, nv = levels.slots[p], levels.nonnull[p]
+            groups = (slots + 7) // 8
+            r0, d0 = levels.rep_at[p], levels.def_at[p]
+            if slots <= 0 or not 0 <= nv <= slots:
+                raise ValueError(f"PlainParquetWriter: page {p} has {slots} slots and {nv} non-null leaves")
+            if r0 < 0 or d0 < 0 or r0 + groups > len(rep) or d0 + 2 * groups > len(dfn):
+                raise ValueError(f"PlainParquetWriter: the level bytes do not match the page table (page {p}: "
+                                 f"{slots} slots at {r0} of {len(rep)} rep bytes, at {d0} of {len(dfn)} def bytes)")
+            yield slots, [_packed_levels(slots, 1), rep[r0: r0 + groups], _packed_levels(slots, 2),
+                          dfn[d0: d0 + 2 * groups]], nv
+
+    def _plan_snappy_column(self, sp, valid, n, dt, start, is_list):
+        """A SNAPPY chunk, flat or list: the pages of the uncompressed chunk, every body the raw stream
+        varint(U) | literal { levels (dictionary chunk: and W | run) } | the region's elements.
+        -> (segments, bytes written, offset of the first data page of a dictionary chunk or None, the
+        bytes the chunk takes uncompressed, its non-null values)."""
+        if sp.dtype != dt:
+            raise TypeError(f"PlainParquetWriter: SnappyPages of {sp.dtype}, the file's column is "
+                            f"{'string' if dt == STRING_DTYPE else dt}")
+        dense = memoryview(sp.dense).cast("B") if len(sp.dense) else memoryview(b"")
+        segs, at, raw_size, first = [], start, 0, None
+        if sp.W is not None:
+            U, c = sp.raw[0], sp.sizes[0]
+            pre = _varint(U)
+            for buf in (_dict_page_header(sp.entries, U, len(pre) + c) + pre, dense[:c]):
+                segs.append((at, buf))
+                at += len(buf)
+            raw_size += len(_dict_page_header(sp.entries, U)) + U
+            first = at
+        if is_list:
+            pages = self._list_page_levels(valid)
+        else:
+            pages = ((rows, list(_def_levels(rows, page_valid)), nv)
+                     for rows, page_valid, nv in _flat_pages(valid, n, sp.page_rows or PAGE_VALUES))
+        p = nvalid = 0
+        for num_values, literal, nv in pages:
+            if sp.W is None:
+                if p >= len(sp.sizes):
+                    raise ValueError(f"PlainParquetWriter: more than the {len(sp.sizes)} data pages the SnappyPages hold")
+                region, elements = sp.raw[p], dense[sp.at[p]: sp.at[p + 1]]
+                if (region != nv * dt.itemsize) if dt != STRING_DTYPE else (region < 4 * nv or (nv == 0 and region)):
+                    raise ValueError(f"PlainParquetWriter: page {p} has {nv} non-null values, its SnappyPages "
+                                     f"hold a region of {region} bytes")
+            else:
+                literal = literal + sp.indices(p, nv)
+                region, elements = 0, memoryview(b"")
+            literal = [b for b in literal if b is not None and len(b)]
+            L = sum(len(b) for b in literal)
+            U = L + region
+            pre = _varint(U) + (_snappy_literal_tag(L) if L else b"")
+            head = _page_header(num_values, U, 0 if sp.W is None else 8, len(pre) + L + len(elements)) + pre
+            for buf in [head] + literal + [elements]:
+                if len(buf):
+                    segs.append((at, buf))
+                    at += len(buf)
+            raw_size += len(_page_header(num_values, U, 0 if sp.W is None else 8)) + U
+            nvalid += nv
+            p += 1
+        if p != (len(sp.nv) if sp.W is not None else len(sp.sizes)):
+            raise ValueError(f"PlainParquetWriter: {p} data pages, the SnappyPages hold "
+                             f"{len(sp.nv) if sp.W is not None else len(sp.sizes)}")
+        return segs, at - start, first, raw_size, nvalid
 
     def _run(self, segs, ready=None):
         if ready is not None:
@@ -465,7 +637,8 @@ class PlainParquetWriter:
         first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
         non-null LEAVES of the n rows in order and their ``ListLevels``.  A string column: a
         ``ByteArrayPages`` in the place of ``values``.  A dictionary-encoded chunk
-        (of any kind): a ``DictPages`` in the place of ``values``.  Argument errors raise
+        (of any kind): a ``DictPages`` in the place of ``values``.  A SNAPPY chunk (of any kind, also
+        a dictionary chunk): a ``SnappyPages`` in the place of ``values``.  Argument errors raise
         before anything of the row group is written.  wait=False (with a pool): returns the
         futures of the column writes instead of waiting for them -- the layout is fixed, so later
         row groups (of this or of other files) can be written meanwhile; the caller keeps the
@@ -487,7 +660,11 @@ class PlainParquetWriter:
             if self.lists[j] != isinstance(valid, ListLevels):
                 raise TypeError(f"PlainParquetWriter: column '{name}' is a {'list' if self.lists[j] else 'flat'} "
                                 f"column of the file, this row group passes it as the other kind")
-            if self.lists[j]:
+            raw_size = None
+            if isinstance(values, SnappyPages):
+                segs, size, first, raw_size, nvalid = self._plan_snappy_column(values, valid, n, dt, start, self.lists[j])
+                nv = sum(valid.slots) if self.lists[j] else n
+            elif self.lists[j]:
                 segs, size, first = self._plan_list_column(values, valid, dt, start)
                 nv = sum(valid.slots)   # (num_values of a list chunk counts slots, not leaves or rows)
             else:
@@ -495,12 +672,14 @@ class PlainParquetWriter:
                 nv = n
             plans.append(segs)
             pos += size
-            is_dict = isinstance(values, DictPages)
-            nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else int(np.asarray(values).size)
+            is_dict = isinstance(values, DictPages) or (raw_size is not None and values.W is not None)
+            if raw_size is None:
+                nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else int(np.asarray(values).size)
             chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
                                minmax=stats[j] if (stats is not None and nvalid > 0) else None,
-                               is_list=self.lists[j], first_data=first if is_dict else None))
-            total += size
+                               is_list=self.lists[j], first_data=first if is_dict else None,
+                               raw_size=size if raw_size is None else raw_size, codec=0 if raw_size is None else 1))
+            total += chunks[-1]["raw_size"]   # (a row group's total_byte_size counts uncompressed bytes)
         self.pos = pos
         futures = []
         if self.pool is not None:
@@ -543,7 +722,7 @@ class PlainParquetWriter:
         meta = (_Struct().i32(1, _ptype(dt))
                 .list(2, _CT_I32, [_zigzag(0), _zigzag(3)] + ([_zigzag(8)] if first is not None else []))
                 .list(3, _CT_BINARY, [_varint(len(x.encode())) + x.encode() for x in path])
-                .i32(4, 0).i64(5, c["n"]).i64(6, c["size"]).i64(7, c["size"])
+                .i32(4, c.get("codec", 0)).i64(5, c["n"]).i64(6, c.get("raw_size", c["size"])).i64(7, c["size"])
                 .i64(9, c["start"] if first is None else first))
         if first is not None:
             meta.i64(11, c["start"])

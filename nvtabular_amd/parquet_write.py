@@ -21,7 +21,13 @@ entry table (kernels_parquet_str_out.StringTables); per row group the non-null s
 ids and a byte plan, the page table and the count of unknown surrogates ride in the read-back of the
 dictionary states, then the BYTE_ARRAY body is filled on the device and copied out like the values of
 a number column.  An offered string column costs one more read-back per row group (shared by all of
-them): the size of its dictionary page ("String columns in the PLAIN parquet writer")."""
+them): the size of its dictionary page ("String columns in the PLAIN parquet writer").
+Snappy pages (``device_compression="snappy"``): behind the dictionary decision and the string fills the
+values regions of ALL chunks of the row group -- the non-null values, a string chunk's BYTE_ARRAY body,
+a dictionary chunk's dictionary page -- go through kernels_snappy (plan, compress, gather: three
+batched calls), ONE read-back brings the compressed bytes of every page, ``parquet_plain.snappy_pays``
+decides per chunk, and a chunk copies out its dense compressed bytes or, where snappy does not make
+it smaller, what it copies out today ("Snappy pages in the PLAIN parquet writer")."""
 from __future__ import annotations
 
 import os
@@ -38,11 +44,14 @@ from . import kernels as K
 from . import kernels_parquet_dict as KPD
 from . import kernels_parquet_list as KPL
 from . import kernels_parquet_str_out as KSO
+from . import kernels_snappy as KS
 from . import parquet_plain as PP
 from .device import pack_bitmap_device
-from .parquet_plain import ByteArrayPages, DictPages, ListLevels, PlainParquetWriter
+from .parquet_plain import ByteArrayPages, DictPages, ListLevels, PlainParquetWriter, SnappyPages
 
 # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
+# snappy_s (a part of stage_s): plan, compress and gather of a row group's chunks, the read-back of
+# their page sizes and the enqueueing of the copies behind it;
 # levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables;
 # dict_s (a part of stage_s): enqueueing dictionary build + pack and waiting for the state records;
 # strings_s (a part of stage_s): entry ids, byte plans and fills of string columns, and the read-back
@@ -325,11 +334,12 @@ def _plan_strings(cols, staged, rows):
     return strs
 
 
-def _stage_strings(strs, dicts, states, keep):
-    """{column index: _HostColumn} of the string chunks after the read-back: the bodies are filled on
-    the device and are on their way to pinned memory.  The chunk rule in bytes: an offered chunk takes
-    the dictionary iff it has at most 2^20 distinct entries and dictionary page + indices are SMALLER
-    than its PLAIN body; the dictionary pages' sizes are ONE more read-back for all of them."""
+def _fill_strings(strs, dicts, states, keep):
+    """{column index: form} of the string chunks after the read-back, their bodies filled on the
+    device: ("dict", dictionary page body, d, W, the DeviceDict) or ("plain", body or None, bytes).
+    The chunk rule in bytes: an offered chunk takes the dictionary iff it has at most 2^20 distinct
+    entries and dictionary page + indices are SMALLER than its PLAIN body; the dictionary pages'
+    sizes are ONE more read-back for all of them."""
     cand = {}
     for ci, sc in strs.items():
         d, overflow = states[ci][:2] if ci in dicts else (0, 1)
@@ -339,33 +349,163 @@ def _stage_strings(strs, dicts, states, keep):
     if cand:
         K.stat_add("pq_str_dict_readback")
         sizes = dict(zip(cand, K.read_back(torch.cat([p[-1:] for p in cand.values()])).tolist()))
-    hosts = {}
+    forms = {}
     for ci, sc in strs.items():
         _, offsets, chars = sc.col.table.on(sc.ids.device)
-        total, hv = int(sc.page_at_host[-1]), None
+        total = int(sc.page_at_host[-1])
         if ci in cand:
             d, W = states[ci][0], PP.dict_index_width(states[ci][0])
             if sizes[ci] <= PP.MAX_PAGE_BYTES and sizes[ci] + PP.dict_index_bytes(sc.nv, W) < total:
-                dd = dicts[ci]
-                body = KSO.fill(dd.dictionary[:d], offsets, chars, cand[ci], sizes[ci])
-                hd, hp = _to_host(body), _to_host(dd.packed[:PP.dict_page_offsets(sc.nv, W)[1]])
-                hv = DictPages(hd.numpy(), hp.numpy(), W, sc.nv, entries=d, page_rows=sc.col.table.page_rows)
-                keep.append((dd, cand[ci], body, hd, hp))
-        if hv is None:
-            body = KSO.fill(sc.ids, offsets, chars, sc.pos, total) if total else None
-            hbody = _to_host(body) if total else None
-            hv = ByteArrayPages(hbody.numpy() if total else np.zeros(0, dtype=np.uint8), sc.page_at_host, sc.nv,
-                                sc.col.table.page_rows)
-            keep.append((body, hbody))
-        hb = _to_host(sc.valid).numpy() if sc.valid is not None else None
-        keep.append((sc, hv, hb))
-        hosts[ci] = _HostColumn(sc.col.name, hv, hb, None)
-    return hosts
+                body = KSO.fill(dicts[ci].dictionary[:d], offsets, chars, cand[ci], sizes[ci])
+                keep.append((dicts[ci], cand[ci], body))
+                forms[ci] = ("dict", body, d, W, dicts[ci])
+                continue
+        body = KSO.fill(sc.ids, offsets, chars, sc.pos, total) if total else None
+        keep.append(body)
+        forms[ci] = ("plain", body, total)
+    return forms
 
 
-def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
+def _snappy_geometry(rows, page_rows, nulls, levels):
+    """[(num_values, level bytes)] of the data pages of a chunk: a list chunk's from its ListLevels,
+    a flat chunk's ``rows`` rows cut every ``page_rows``."""
+    if levels is not None:
+        return [(s, PP.list_level_bytes(s)) for s in levels.slots]
+    cuts = list(range(0, rows, page_rows)) + [rows] if rows else [0, 0]
+    return [(b - a, PP.flat_level_bytes(b - a, nulls)) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep):
+    """``device_compression="snappy"``: every chunk of the row group in the form it takes (after
+    ``dict_pays``) -> ([_HostColumn], [min / max or None]).  Plan, compress and gather are enqueued for
+    the values regions of ALL chunks at once (a dictionary chunk: its dictionary page), ONE read-back
+    brings their per-page compressed sizes (and the page starts only the device has),
+    ``parquet_plain.snappy_pays`` decides per chunk on the host, and every chunk then copies out
+    only what it needs: the dense compressed bytes, or the raw values as today."""
+    forms = _fill_strings(strs, dicts, states, keep)
+    dev = next((v.device for v, _, _ in staged if v.is_cuda), None)
+    whole = torch.arange(2, dtype=torch.int64, device=dev) if dev is not None else None   # one page: [0, 1] units
+    regions, plans, extra = [], {}, []
+    for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
+        nulls = (strs[ci].valid if ci in strs else valid) is not None
+        levels = valid if isinstance(valid, ListLevels) else None
+        if ci in strs:
+            sc, form = strs[ci], forms[ci]
+            geo = _snappy_geometry(rows, sc.col.table.page_rows, nulls, None)
+            if form[0] == "dict":
+                plan = dict(kind="dict", geo=geo, nv=sc.nv, d=form[2], W=form[3], dd=form[4], raw=int(form[1].numel()),
+                            region=KS.Region(form[1], whole, int(form[1].numel()), 4))
+            elif form[2]:
+                plan = dict(kind="plain", geo=geo, raw=np.diff(sc.page_at_host), region=KS.Region(form[1], sc.page_at, 1, 4))
+            else:
+                continue
+        elif not vals.numel() or not vals.is_cuda:
+            continue
+        else:
+            size = vals.element_size()
+            geo = _snappy_geometry(rows, PP.PAGE_VALUES, nulls, levels)
+            d, overflow, ps = states[ci] if ci in dicts else (0, 1, None)
+            if ci in dicts and not overflow and PP.dict_pays(d, np.diff(ps), size):
+                plan = dict(kind="dict", geo=geo, nv=np.diff(ps), d=d, W=PP.dict_index_width(d), dd=dicts[ci], raw=d * size,
+                            region=KS.Region(dicts[ci].dictionary[:d], whole, d * size, size))
+            else:
+                src = vals.contiguous()
+                dps = dicts[ci].page_start if ci in dicts else _page_start(src, valid, m, rows)
+                plan = dict(kind="plain", geo=geo, raw=None if ps is None else np.diff(ps) * size,
+                            region=KS.Region(src, dps, size, size))
+                if ps is None:
+                    plan["extra"] = len(extra)
+                    extra.append(dps)
+        plan["at"] = len(regions)
+        regions.append(plan["region"])
+        plans[ci] = plan
+    got, more = [], []
+    if regions:
+        ds = KS.compress(regions)
+        got, more = KS.read_back(ds, extra=extra)
+        keep.append(ds.dense)
+    host, stats = [], []
+    for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
+        plan = plans.get(ci)
+        hv = None
+        if plan is not None:
+            ps, geo = got[plan["at"]], plan["geo"]
+            if ps.error:
+                raise RuntimeError(f"to_parquet: column '{c.name}': the snappy kernels report error {ps.error} "
+                                   "(a fragment outgrew its slot, or the page table its fragment records)")
+            if plan["kind"] == "dict":
+                idx = [PP.dict_index_bytes([k], plan["W"]) for k in plan["nv"]]
+                sizes = PP.snappy_chunk_bytes([(nvl, lv + i, 0, 0, 8) for (nvl, lv), i in zip(geo, idx)],
+                                              (plan["d"], plan["raw"], ps.total))
+            else:
+                raw = plan["raw"] if plan["raw"] is not None else np.diff(more[plan["extra"]]) * vals.element_size()
+                if len(raw) != len(geo) or len(ps.sizes) != len(geo):
+                    raise RuntimeError(f"to_parquet: column '{c.name}': {len(geo)} data pages, {len(raw)} regions")
+                sizes = PP.snappy_chunk_bytes([(nvl, lv, int(u), int(s), 0)
+                                               for (nvl, lv), u, s in zip(geo, raw, ps.sizes)])
+            if PP.snappy_pays(*sizes):
+                hd = _to_host(ds.dense[plan["at"]][:ps.total])
+                dt = PP.STRING_DTYPE if ci in strs else np.dtype(str(vals.dtype).replace("torch.", ""))
+                page_rows = strs[ci].col.table.page_rows if ci in strs else None
+                if plan["kind"] == "dict":
+                    dd = plan["dd"]
+                    hp = _to_host(dd.packed[:PP.dict_page_offsets(plan["nv"], plan["W"])[1]])
+                    hv = SnappyPages(dt, hd.numpy(), [ps.total], [plan["raw"]], page_rows,
+                                     (plan["W"], hp.numpy(), plan["nv"], plan["d"]))
+                    keep.append((dd, hp))
+                else:
+                    hv = SnappyPages(dt, hd.numpy(), ps.sizes, raw, page_rows)
+                keep.append(hd)
+        if ci in strs:
+            sc = strs[ci]
+            if hv is None:
+                hc = _host_string(sc, forms[ci], keep)
+            else:
+                hb = _to_host(sc.valid).numpy() if sc.valid is not None else None
+                keep.append((sc, hv, hb))
+                hc = _HostColumn(sc.col.name, hv, hb, None)
+            mm = None   # (no min / max for string chunks)
+        elif hv is None:
+            hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep)
+        else:
+            hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
+            mm = _min_max(vals) if statistics else None
+            keep.append((vals, valid, mm, hv))
+            hc, mm = _HostColumn(c.name, hv, hb, c.logical), (mm.numpy() if mm is not None else None)
+        host.append(hc)
+        stats.append(mm)
+    return host, stats
+
+
+def _host_string(sc, form, keep):
+    """One string chunk on its way to pinned memory, as it is written without a codec -> _HostColumn."""
+    if form[0] == "dict":
+        _, body, d, W, dd = form
+        hd, hp = _to_host(body), _to_host(dd.packed[:PP.dict_page_offsets(sc.nv, W)[1]])
+        hv = DictPages(hd.numpy(), hp.numpy(), W, sc.nv, entries=d, page_rows=sc.col.table.page_rows)
+        keep.append((hd, hp))
+    else:
+        _, body, total = form
+        hbody = _to_host(body) if total else None
+        hv = ByteArrayPages(hbody.numpy() if total else np.zeros(0, dtype=np.uint8), sc.page_at_host, sc.nv,
+                            sc.col.table.page_rows)
+        keep.append(hbody)
+    hb = _to_host(sc.valid).numpy() if sc.valid is not None else None
+    keep.append((sc, hv, hb))
+    return _HostColumn(sc.col.name, hv, hb, None)
+
+
+def _stage_strings(strs, dicts, states, keep):
+    """{column index: _HostColumn} of the string chunks after the read-back: the bodies are filled on
+    the device (``_fill_strings``) and are on their way to pinned memory."""
+    forms = _fill_strings(strs, dicts, states, keep)
+    return {ci: _host_string(sc, forms[ci], keep) for ci, sc in strs.items()}
+
+
+def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) -> _RowGroup:
     """Enqueue everything that brings rows [s0, s1) to the host, on ``copy_s`` (None: the frame is
-    on the host already), and record one event behind it."""
+    on the host already), and record one event behind it.  ``snappy``: the chunks' pages are
+    compressed on the device where that makes them smaller (``_stage_snappy``)."""
     host, keep, stats = [], [], ([] if statistics else None)
     t_st = time.perf_counter()
     with torch.cuda.stream(copy_s) if copy_s is not None else nullcontext():
@@ -393,8 +533,14 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics) -> _RowGroup:
         elif strs:   # (the read-back waited for entry ids and plans alone)
             LAST_TIMING["strings_s"] += time.perf_counter() - t_dc
         t_ss = time.perf_counter()
-        hosts = _stage_strings(strs, dicts, states, keep)
-        if strs:
+        if snappy:
+            # snappy pages: plan + compress + gather of every chunk in the form it takes, ONE read-back
+            host, mms = _stage_snappy(cols, staged, strs, dicts, states, s1 - s0, statistics, keep)
+            stats = mms if statistics else None
+            LAST_TIMING["snappy_s"] += time.perf_counter() - t_ss
+            staged = []   # (every column is staged)
+        hosts = _stage_strings(strs, dicts, states, keep) if not snappy else {}
+        if strs and not snappy:
             LAST_TIMING["strings_s"] += time.perf_counter() - t_ss
         for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
             if ci in hosts:
@@ -500,15 +646,17 @@ def _row_ranges(i, n, k, row_group, touched):
 
 
 def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads,
-                offered=frozenset(), tables=None):
+                offered=frozenset(), tables=None, snappy=False):
     """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
     with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
     ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
     ``offered``: the columns whose chunks are dictionary-encoded where that makes them smaller.
     ``tables``: the StringTables ``plain_eligible`` judged the first partition with (None: a fresh one).
+    ``snappy``: ``device_compression="snappy"`` -- chunks on the device are written SNAPPY where that
+    makes them smaller.
     -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
     LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
-                       levels_s=0.0, dict_s=0.0, strings_s=0.0)
+                       levels_s=0.0, dict_s=0.0, strings_s=0.0, snappy_s=0.0)
     t_all = time.perf_counter()
     tables = tables if tables is not None else KSO.StringTables()
     copy_s = None
@@ -527,7 +675,8 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
                 if on_gpu:
                     copy_s.wait_stream(torch.cuda.current_stream())
                 for j, s0, s1 in _row_ranges(i, n, k, row_group, touched):
-                    files.flush(_stage_row_group(j, cols, groups, s0, s1, copy_s if on_gpu else None, statistics))
+                    files.flush(_stage_row_group(j, cols, groups, s0, s1, copy_s if on_gpu else None, statistics,
+                                                 snappy and on_gpu))
             files.close()
         except BaseException:
             files.abort()
