@@ -875,6 +875,12 @@ typedef struct nvt_count_col {
                                key-ordered output list}.  nvt_vocab_finalize_many turns the positions
                                into labels (nvt_vocab_col.range_table), nvt_encode_many probes it
                                (nvt_encode_col.range_aux).                                        */
+  uint32_t *out_slots;      /* optional, read only together with range_table: uint32[out_capacity].
+                               out_slots[i] = the slot of range_table that holds entry i of the
+                               output list (0xFFFFFFFF for the smallest int32, which owns none).
+                               Passed on as nvt_vocab_col.src_slots, it lets the ordering write the
+                               labels straight into the table instead of streaming over all of it.
+                               Unspecified after an overflow (state[NVT_ST_OVERFLOW] != 0).        */
 } nvt_count_col;
 /* bytes of the range table of a column counted with 2^nb_log2 buckets */
 int nvt_range_table_bytes(int nb_log2, uint64_t *bytes);
@@ -891,7 +897,10 @@ typedef struct nvt_vocab_col {
   uint64_t n;
   int64_t max_count;        /* upper bound on counts (<= 0: unknown)             */
   int32_t key_bytes, unique_keys;
-  void *sort_tmp;           /* nvt_vocab_sort_tmp_bytes(); per column            */
+  void *sort_tmp;           /* nvt_vocab_sort_tmp_bytes(); per column.  Optional for int32 keys with
+                             * 2 <= n <= 16384 and 0 < max_count < 2^32 (8 n bytes are used when it
+                             * is there: above 2048 entries the list is then sorted by many
+                             * workgroups instead of one)                                  */
   int64_t first_label;
   void *table;              /* encode table to build, or NULL                    */
   uint64_t capacity;
@@ -934,6 +943,12 @@ typedef struct nvt_vocab_col {
    * out as the launch's workgroups hold them -- built once here, on the stream that orders the
    * vocabulary, instead of by every workgroup of every encode launch (nvt_encode_col.head_image). */
   void *head_image;
+  /* optional, with a dumped range table (flat_slots == 0) and no src_labels: uint32[n], the slot of
+   * `table` that holds each source entry (nvt_count_col.out_slots of the same counting pass;
+   * 0xFFFFFFFF: none).  The ordering pass then stores every label into its slot and the streaming
+   * pass over the whole table is not run.  NULL (a list that was merged or otherwise no longer
+   * matches the dump entry for entry): the streaming pass. */
+  const uint32_t *src_slots;
 } nvt_vocab_col;
 #define NVT_ENCODE_HEAD_BYTES (12288 * 12 + 64)
 #define NVT_FLAT_AUX_WORDS (NVT_RANGE_AUX_LO + 16)

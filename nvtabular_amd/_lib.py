@@ -173,7 +173,7 @@ class CountCol(C.Structure):
     _fields_ = [("keys", _vp), ("valid", _vp), ("weights", _vp), ("n", _u64),
                 ("key_bytes", C.c_int32), ("path", C.c_int32), ("ws", _vp), ("out_keys", _vp),
                 ("out_counts", _vp), ("out_capacity", _u64), ("state", _vp), ("hot_image", _vp),
-                ("range_table", _vp)]
+                ("range_table", _vp), ("out_slots", _vp)]
 
 
 class VocabCol(C.Structure):
@@ -183,7 +183,7 @@ class VocabCol(C.Structure):
                 ("sentinel_label", _vp), ("ready_event", _vp), ("src_keys", _vp),
                 ("src_counts", _vp), ("cls_hist", _vp), ("n_big", _u64), ("range_aux", _vp),
                 ("range_nb_log2", C.c_int32), ("flat_slots", C.c_uint64), ("src_labels", _vp),
-                ("head_image", _vp)]
+                ("head_image", _vp), ("src_slots", _vp)]
 
 
 class MergeCol(C.Structure):

@@ -117,7 +117,7 @@ static int count_column(const CountPath &p, const nvt_count_col &c, hipStream_t 
                             (int32_t *)c.out_keys, c.out_counts, c.out_capacity, c.state, s);
     return range_count_i32((const int32_t *)c.keys, c.valid, c.n, p.nb_log2, c.ws, c.hot_image,
                            (int32_t *)c.out_keys, c.out_counts, c.out_capacity, c.range_table,
-                           c.state, s, p.pieces);
+                           c.out_slots, c.state, s, p.pieces);
   }
   NVT_PROF(prof_name(p), c.n * c.key_bytes, s);
   if (clear_state) NVT_CHECK_HIP(hipMemsetAsync(c.state, 0, NVT_STATE_WORDS * 8, s));

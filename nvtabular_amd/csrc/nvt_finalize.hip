@@ -6,8 +6,9 @@
 // ~60 us of host time each) was longer than the kernels of the 13 small Criteo vocabularies,
 // and on a slow host it left the GPU idle for half of every step.  Here the host enqueues
 // everything back to back:
-//   * all small vocabularies (int32 keys, <= 16384 entries) are sorted by ONE launch, one
-//     workgroup per vocabulary (LDS bitonic network over packed words);
+//   * all small vocabularies (int32 keys, <= 16384 entries) are sorted by one launch pair: a
+//     workgroup per 2048-word chunk (LDS bitonic network over packed words), then the chunks of a
+//     longer list merged by rank through its sort_tmp;
 //   * the large ones go largest-first round-robin onto three internal streams forked from /
 //     joined into the caller's stream, so their short tail kernels overlap;
 //   * every table build follows its sort on the same stream.
@@ -109,8 +110,8 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
       need_join = true;
     return NVT_OK;
   };
-  // the small vocabularies first, on the caller's stream: their one-workgroup-per-vocabulary
-  // kernel needs a whole CU's LDS and would otherwise wait until the radix passes drain
+  // the small vocabularies first, on the caller's stream: short kernels that would otherwise
+  // wait until the radix passes drain
   if (!small.empty()) {
     std::vector<SmallSortDesc> d(small.size());
     for (size_t j = 0; j < small.size(); ++j) {
@@ -118,6 +119,7 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
       d[j].keys = (int32_t *)c.keys;
       d[j].counts = c.counts;
       d[j].n = (unsigned)c.n;
+      d[j].tmp = c.sort_tmp;
     }
     int rc = vocab_sort_small_batch(d.data(), (int)d.size(), main_s);
     if (rc) return rc;
@@ -147,7 +149,7 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
       NVT_CHECK_ARG(c.sort_tmp, "null sort_tmp");
       jobs.push_back({(const int32_t *)c.src_keys, c.src_counts, c.n, c.cls_hist, c.n_big, c.max_count,
                       (int32_t *)c.keys, c.counts, c.sort_tmp, c.first_label, c.table, c.capacity,
-                      c.sentinel_label, c.range_aux, c.range_nb_log2, c.flat_slots});
+                      c.sentinel_label, c.range_aux, c.range_nb_log2, c.flat_slots, c.src_slots});
       job_cols.push_back(i);
       batched[i] = 1;
     }
@@ -193,11 +195,11 @@ static int finalize_impl(const nvt_vocab_col *cols, int ncols, hipStream_t main_
                                        c.n_big, c.max_count, (int32_t *)c.keys, c.counts,
                                        c.sort_tmp, c.first_label, c.table, c.capacity,
                                        c.sentinel_label, c.range_aux, c.range_nb_log2, s,
-                                       &deferred, c.flat_slots);
+                                       &deferred, c.flat_slots, c.src_slots);
       if (rc) return rc;
       if (deferred) {
         tails.push_back({(int32_t *)c.keys, c.counts, c.n_big, c.first_label, c.table, c.capacity,
-                         c.sentinel_label, c.range_aux});
+                         c.sentinel_label, c.range_aux, c.sort_tmp, c.n});
         tail_cols.push_back(big[j]);
         continue;  // its ready event is recorded behind the batched tail
       }

@@ -24,8 +24,10 @@ struct SmallSortDesc {
   int32_t *keys;
   int64_t *counts;
   unsigned n;
+  void *tmp;  // 8 n bytes of scratch, or nullptr (n > 2048 is then sorted by one workgroup)
 };
-// int32 keys, 2 <= n <= 16384, 0 < max_count < 2^32: sorted by the one-launch batched kernel
+// int32 keys, 2 <= n <= 16384, 0 < max_count < 2^32: sorted by the batched small sort (chunks of
+// 2048 in LDS, one workgroup each; longer lists are then merged by rank through their scratch)
 bool vocab_sort_small_eligible(int key_bytes, uint64_t n, int64_t max_count);
 int vocab_sort_small_batch(const SmallSortDesc *cols, int ncols, hipStream_t s);
 
@@ -72,7 +74,7 @@ int part_count(const nvt_count_col &c, int kind, bool hot, hipStream_t s);
 uint64_t range_count_ws_bytes(uint64_t n, int nb_log2);
 int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int nb_log2, void *ws,
                     int32_t *aux, int32_t *out_keys, int64_t *out_cnt, uint64_t out_cap,
-                    void *range_table, uint64_t *state, hipStream_t s, bool pieces);
+                    void *range_table, uint32_t *out_slots, uint64_t *state, hipStream_t s, bool pieces);
 
 // nvt_sort_count.hip: path NVT_PATH_SORT of nvt_dense_count_* (radix sort + run lengths; hist =
 // the column's uint32[256] class histogram block)
@@ -89,7 +91,8 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
                             int32_t *out_keys, int64_t *out_cnts, void *tmp, int64_t first_label,
                             void *table, uint64_t capacity, int64_t *sentinel_label,
                             const int32_t *range_aux, int range_nb_log2, hipStream_t s,
-                            bool *tail_deferred, uint64_t flat_slots = 0);
+                            bool *tail_deferred, uint64_t flat_slots = 0,
+                            const uint32_t *src_slots = nullptr);
 // the same for several vocabularies that own a range table (dumped or flat): one launch per
 // stage for ALL of them, class-255 tails included
 struct OrderSortedJob {
@@ -109,6 +112,7 @@ struct OrderSortedJob {
   const int32_t *range_aux;
   int range_nb_log2;
   uint64_t flat_slots;
+  const uint32_t *src_slots;  // dumped table: the slot of every source entry, or nullptr (patch pass)
 };
 int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t s);
 // LDS head image of an ordered int32 vocabulary for the cache-mode encode (nvt_encode_build.hip)
@@ -132,6 +136,8 @@ struct OrderTail {
   uint64_t capacity;
   int64_t *sentinel_label;
   const int32_t *range_aux;
+  void *tmp;   // the vocabulary's ordering workspace (its sort scratch serves the small sort)
+  uint64_t n;  // entries of the whole vocabulary: what the workspace was laid out for
 };
 int vocab_order_tail_batch(const OrderTail *t, int nt, hipStream_t s);
 

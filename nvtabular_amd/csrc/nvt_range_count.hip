@@ -418,7 +418,7 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
     const int32_t *__restrict__ aux, const unsigned *__restrict__ hot_tot, int nb_log2,
     unsigned long long *status, unsigned *ticket, int32_t *__restrict__ out_keys,
     int64_t *__restrict__ out_cnt, uint64_t out_cap, unsigned *cls_hist,
-    unsigned long long *__restrict__ range_table, uint64_t *state) {
+    unsigned long long *__restrict__ range_table, uint32_t *__restrict__ out_slots, uint64_t *state) {
   constexpr int NSL = kRpSlots + kRpTail;
   constexpr int NW = kRpBS / kWave;
   __shared__ int32_t lkeys[NSL];
@@ -728,6 +728,7 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
   if (extra && threadIdx.x == 0) {
     out_keys[base] = kEmpty;
     out_cnt[base] = (int64_t)sent_rows;
+    if (out_slots != nullptr) out_slots[base] = 0xFFFFFFFFu;  // (the sentinel key owns no slot)
     const unsigned cls = sent_rows < 255 ? (unsigned)sent_rows : 255u;
     atomicAdd(&hist[cls], 1u);
     unsigned long long *gm = reinterpret_cast<unsigned long long *>(&state[NVT_ST_MAXCOUNT]);
@@ -817,6 +818,8 @@ __global__ __launch_bounds__(kRpBS) void rp_count_kernel(
       const unsigned c = lcnt[i];
       out_keys[pos] = k;
       out_cnt[pos] = (int64_t)c;
+      // where the dump below puts this entry: the ordering writes its label straight there
+      if (out_slots != nullptr) out_slots[pos] = b * (unsigned)NSL + (unsigned)i;
       atomicAdd(&hist[c < 255u ? c : 255u], 1u);
       mx = c > mx ? c : mx;
       dump = ((unsigned long long)(uint32_t)pos << 32) | (uint32_t)k;
@@ -893,7 +896,8 @@ uint64_t range_count_ws_bytes(uint64_t n, int nb_log2) {
 // by hot_sample_kernel ahead of this call) and the class histogram (cleared here)
 int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int nb_log2, void *wsp,
                     int32_t *aux, int32_t *out_keys, int64_t *out_cnt, uint64_t out_cap,
-                    void *range_table, uint64_t *state, hipStream_t s, bool pieces) {
+                    void *range_table, uint32_t *out_slots, uint64_t *state, hipStream_t s, bool pieces) {
+  if (range_table == nullptr) out_slots = nullptr;  // (slots of a table that is not dumped)
   NVT_CHECK_ARG(nb_log2 >= 6 && nb_log2 <= kRpMaxNbLog2, "range path: 64 .. 1024 buckets");
   NVT_CHECK_ARG(aux != nullptr, "range path: the column needs its aux block (hot_image)");
   NVT_PROF("dense_count_r9", n * 4, s);
@@ -923,12 +927,12 @@ int range_count_i32(const int32_t *keys, const uint8_t *valid, uint64_t n, int n
     rp_count_kernel<true><<<NB, kRpBS, 0, s>>>(w.regions, w.fills, cap, aux, w.hot_tot, nb_log2, w.status,
                                                w.ticket, out_keys, out_cnt, out_cap,
                                                (unsigned *)(aux + NVT_RANGE_AUX_HIST),
-                                               (unsigned long long *)range_table, state);
+                                               (unsigned long long *)range_table, out_slots, state);
   else
     rp_count_kernel<false><<<NB, kRpBS, 0, s>>>(w.regions, w.fills, cap, aux, w.hot_tot, nb_log2, w.status,
                                                 w.ticket, out_keys, out_cnt, out_cap,
                                                 (unsigned *)(aux + NVT_RANGE_AUX_HIST),
-                                                (unsigned long long *)range_table, state);
+                                                (unsigned long long *)range_table, out_slots, state);
   NVT_CHECK_LAUNCH();
   return NVT_OK;
 }

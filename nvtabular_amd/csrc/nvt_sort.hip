@@ -751,18 +751,35 @@ int sort_packed_keys(const void *keys, int key_dtype, int64_t key_bias, const ui
   return sort_words_impl(nullptr, keys, key_dtype, key_bias, fold, rb, n, rb, 64, tmp, result, stream);
 }
 
-// ---- all small vocabularies of a fit in ONE launch: workgroup b sorts vocabulary b --------
-// packed words in LDS (128 KiB for up to 16384 entries), bitonic network, ascending.
+// ---- all small vocabularies of a fit: the whole device sorts them ----------------------------
+// packed words, ascending.  Every list is cut into chunks of kSmallChunk words; launch A sorts
+// each chunk in LDS (16 KiB: many workgroups per CU), which finishes a list of one chunk.  The
+// sorted chunks of a longer list go to its scratch as packed words, and launch B ranks every
+// element among all chunks of its list -- its index in its own chunk + a binary search in each
+// other chunk, equal words ordered by chunk -- and writes it out unpacked at that rank.  No
+// workgroup waits for another.  (One 1024-thread workgroup per list over 128 KiB of LDS kept 13
+// of 256 CUs busy for ~120 us; a caller without scratch still gets that kernel.)
 constexpr int kSmallPackedMax = 16384;
+constexpr int kSmallChunk = 2048, kSmallRankBS = 256;
+constexpr int kSmallMaxChunks = kSmallPackedMax / kSmallChunk;
 struct SmallCol {
   int32_t *keys;
   int64_t *counts;
+  uint64_t *tmp;  // kSmallChunk < n: n packed words (the sorted chunks between the two launches)
   unsigned n;
 };
 constexpr int kSmallBatch = 64;
 struct SmallBatch {
   SmallCol c[kSmallBatch];
+  unsigned chunk_start[kSmallBatch + 1];  // launch A: first workgroup of every list
+  unsigned rank_start[kSmallBatch + 1];   // launch B: the same (lists of one chunk take none)
+  int ncols;
 };
+__device__ __forceinline__ int small_col_of(const unsigned *start, int n, unsigned b) {
+  int c = 0;
+  while (c + 1 < n && b >= start[c + 1]) ++c;
+  return c;
+}
 __global__ __launch_bounds__(kSmallBS) void sort_small_packed_many_kernel(SmallBatch b) {
   __shared__ uint64_t sv[kSmallPackedMax];
   const SmallCol col = b.c[blockIdx.x];
@@ -792,6 +809,106 @@ __global__ __launch_bounds__(kSmallBS) void sort_small_packed_many_kernel(SmallB
     col.keys[i] = comp_key(v);
     col.counts[i] = comp_cnt(v);
   }
+}
+
+// launch A: workgroup = one chunk of one list; a thread per compare-exchange of a stage (the device
+// is idle beside these few workgroups: what counts is the length of the 66 stages, not occupancy)
+__global__ __launch_bounds__(kSmallBS) void sort_small_chunk_kernel(SmallBatch b) {
+  __shared__ uint64_t sv[kSmallChunk];
+  const int ci = small_col_of(b.chunk_start, b.ncols, blockIdx.x);
+  const SmallCol col = b.c[ci];
+  const unsigned first = (blockIdx.x - b.chunk_start[ci]) * kSmallChunk;
+  const unsigned n = col.n - first < (unsigned)kSmallChunk ? col.n - first : (unsigned)kSmallChunk;
+  unsigned m = 2;
+  while (m < n) m <<= 1;
+  for (unsigned i = threadIdx.x; i < m; i += kSmallBS)
+    sv[i] = i < n ? comp_make(col.keys[first + i], col.counts[first + i]) : ~0ull;  // padding sorts last
+  __syncthreads();
+  // A stage of stride <= 64 pairs words inside blocks of 128, and thread t works in block t / 64:
+  // every wave stays in its own 128 words, so such stages only wait for the wave's own LDS traffic.
+  // A wider stage reads what other waves wrote: workgroup barriers around it.  (56 of the 66 stages
+  // of a full chunk are narrow; a barrier of 16 waves per stage was most of this kernel's time.)
+  for (unsigned size = 2; size <= m; size <<= 1) {
+    for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+      const bool wide = stride > (unsigned)kWave;
+      if (wide) __syncthreads();
+      for (unsigned t = threadIdx.x; t < m / 2; t += kSmallBS) {
+        const unsigned lo = 2 * t - (t & (stride - 1));
+        const unsigned hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const uint64_t a = sv[lo], c = sv[hi];
+        if (up ? (c < a) : (a < c)) {
+          sv[lo] = c;
+          sv[hi] = a;
+        }
+      }
+      if (wide) {
+        __syncthreads();
+      } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    }
+  }
+  __syncthreads();
+  if (col.n > (unsigned)kSmallChunk) {
+    for (unsigned i = threadIdx.x; i < n; i += kSmallBS) col.tmp[first + i] = sv[i];
+    return;
+  }
+  for (unsigned i = threadIdx.x; i < n; i += kSmallBS) {
+    const uint64_t v = sv[i];
+    col.keys[i] = comp_key(v);
+    col.counts[i] = comp_cnt(v);
+  }
+}
+
+// launch B: thread = one element of a list of several chunks.  The searches in the other chunks
+// do not depend on one another: they advance in step, one load each per round.
+__global__ __launch_bounds__(kSmallRankBS) void sort_small_rank_kernel(SmallBatch b) {
+  const int ci = small_col_of(b.rank_start, b.ncols, blockIdx.x);
+  const SmallCol col = b.c[ci];
+  const unsigned e = (blockIdx.x - b.rank_start[ci]) * kSmallRankBS + threadIdx.x;
+  if (e >= col.n) return;
+  const uint64_t *__restrict__ src = col.tmp;
+  const uint64_t v = src[e];
+  const unsigned own = e / kSmallChunk;
+  const unsigned nchunks = (col.n + kSmallChunk - 1) / kSmallChunk;
+  unsigned lo[kSmallMaxChunks], hi[kSmallMaxChunks];
+#pragma unroll
+  for (int q = 0; q < kSmallMaxChunks; ++q) {
+    const unsigned at = (unsigned)q * kSmallChunk;
+    lo[q] = 0;
+    hi[q] = 0;
+    if ((unsigned)q < nchunks && (unsigned)q != own)
+      hi[q] = col.n - at < (unsigned)kSmallChunk ? col.n - at : (unsigned)kSmallChunk;
+  }
+  // entries of chunk q in front of v: words below it, and equal words of the chunks before its own.
+  // All loads of a round are issued before any is looked at (a search that is over reads its own
+  // element again): 12 load latencies per thread, not 12 per chunk.
+  for (int step = 0; step < 12; ++step) {  // 2^12 > kSmallChunk + 1 outcomes
+    unsigned mid[kSmallMaxChunks];
+    uint64_t a[kSmallMaxChunks];
+#pragma unroll
+    for (int q = 0; q < kSmallMaxChunks; ++q) {
+      mid[q] = (lo[q] + hi[q]) >> 1;
+      a[q] = src[lo[q] < hi[q] ? (unsigned)q * kSmallChunk + mid[q] : e];
+    }
+#pragma unroll
+    for (int q = 0; q < kSmallMaxChunks; ++q) {
+      if (lo[q] < hi[q]) {
+        if (a[q] < v || (a[q] == v && (unsigned)q < own))
+          lo[q] = mid[q] + 1;
+        else
+          hi[q] = mid[q];
+      }
+    }
+  }
+  unsigned rank = e - own * kSmallChunk;
+#pragma unroll
+  for (int q = 0; q < kSmallMaxChunks; ++q) rank += lo[q];
+  col.keys[rank] = comp_key(v);
+  col.counts[rank] = comp_cnt(v);
 }
 
 // tmp layout of the packed path: compA[n] | compB[n] | tile_hist | chunk_tot
@@ -948,16 +1065,36 @@ bool vocab_sort_small_eligible(int key_bytes, uint64_t n, int64_t max_count) {
 int vocab_sort_small_batch(const SmallSortDesc *cols, int ncols, hipStream_t s) {
   for (int c0 = 0; c0 < ncols; c0 += kSmallBatch) {
     const int nc = ncols - c0 < kSmallBatch ? ncols - c0 : kSmallBatch;
-    SmallBatch b;
+    SmallBatch b, whole;  // whole: lists of several chunks without scratch, one workgroup each
     memset(&b, 0, sizeof(b));
+    memset(&whole, 0, sizeof(whole));
+    int nb = 0, nw = 0;
     for (int i = 0; i < nc; ++i) {
-      b.c[i].keys = cols[c0 + i].keys;
-      b.c[i].counts = cols[c0 + i].counts;
-      b.c[i].n = cols[c0 + i].n;
+      const SmallSortDesc &d = cols[c0 + i];
+      if (d.n > (unsigned)kSmallChunk && d.tmp == nullptr) {
+        whole.c[nw++] = {d.keys, d.counts, nullptr, d.n};
+        continue;
+      }
+      b.c[nb] = {d.keys, d.counts, reinterpret_cast<uint64_t *>(d.tmp), d.n};
+      const unsigned chunks = (d.n + kSmallChunk - 1) / kSmallChunk;
+      b.chunk_start[nb + 1] = b.chunk_start[nb] + chunks;
+      b.rank_start[nb + 1] = b.rank_start[nb] + (chunks > 1 ? (d.n + kSmallRankBS - 1) / kSmallRankBS : 0u);
+      ++nb;
     }
+    b.ncols = nb;
     NVT_PROF("vocab_sort_small", 0, s);
-    sort_small_packed_many_kernel<<<nc, kSmallBS, 0, s>>>(b);
-    NVT_CHECK_LAUNCH();
+    if (b.chunk_start[nb]) {
+      sort_small_chunk_kernel<<<b.chunk_start[nb], kSmallBS, 0, s>>>(b);
+      NVT_CHECK_LAUNCH();
+    }
+    if (b.rank_start[nb]) {
+      sort_small_rank_kernel<<<b.rank_start[nb], kSmallRankBS, 0, s>>>(b);
+      NVT_CHECK_LAUNCH();
+    }
+    if (nw) {
+      sort_small_packed_many_kernel<<<nw, kSmallBS, 0, s>>>(whole);
+      NVT_CHECK_LAUNCH();
+    }
   }
   return NVT_OK;
 }

@@ -18,8 +18,10 @@
 //    key-sorted list, the entries of class 255 in front and still unlabelled (-1).
 //  * the encode table of the vocabulary, one of three kinds:
 //      hashed -- the scatter inserts every entry of the classes below 255 itself;
-//      dumped -- the counting pass left {key, position} slots in key order: range_patch* replace
-//                the positions by label_of[position];
+//      dumped -- the counting pass left {key, position} slots in key order.  Where it also recorded
+//                the slot of every entry (src_slots), the scatter stores each label into that slot
+//                and label_of[] is not written; otherwise (C-ABI callers without slots) range_patch*
+//                stream over the table and replace the positions by label_of[position];
 //      flat   -- laid out from the sorted keys by a prefix maximum (flat_params* + flat_build*,
 //                also the groupby index of nvt_flat_index_build; read by nvt_flat_lookup.hip).
 //  * the class-255 tail: sorted by nvt_sort.hip (one batched small sort for all vocabularies of a
@@ -48,7 +50,11 @@ __device__ __forceinline__ void cls_scatter_body(
     const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n,
     const unsigned *__restrict__ cls_hist, unsigned *status, unsigned *ticket, int32_t *out_keys,
     int64_t *out_cnts, unsigned long long *table, uint64_t mask, int64_t first_label,
-    int64_t *sentinel_label, int32_t *label_of, int32_t *big_src = nullptr) {
+    int64_t *sentinel_label, int32_t *label_of, int32_t *big_src = nullptr,
+    const uint32_t *__restrict__ src_slots = nullptr, unsigned long long *slot_table = nullptr,
+    uint64_t nslots = 0) {
+  // src_slots set (a dumped range table whose counting pass recorded the slot of every entry): the
+  // label goes straight into the high word of slot_table[src_slots[i]], label_of[] is not written
   // big_src set (a SHARD of a list that several ranks own, nvt_vocab_label_shard): only the
   // entries of class 255 are written out (compacted in key order at the front of out_*, with
   // their positions in the shard), every other entry only gets its label
@@ -163,7 +169,14 @@ __device__ __forceinline__ void cls_scatter_body(
       stage[sidx] = c[r];
       // range table: label of the entry at position i of the key-ordered list (class 255 is
       // labelled after its own sort: -1 here)
-      if (label_of != nullptr) label_of[i] = d != 0 ? (int32_t)(first_label + goff[d] + sidx) : -1;
+      const int32_t lab = d != 0 ? (int32_t)(first_label + goff[d] + sidx) : -1;
+      if (src_slots != nullptr) {
+        // (the smallest int32 owns no slot: 0xFFFFFFFF, past the end of every table)
+        const uint32_t sl = src_slots[i];
+        if (sl < nslots) reinterpret_cast<uint32_t *>(slot_table + sl)[1] = (uint32_t)lab;
+      } else if (label_of != nullptr) {
+        label_of[i] = lab;
+      }
       if (big_src != nullptr && d == 0) big_src[goff[0] + sidx] = (int32_t)i;
       if (d == 0) out_cnts[goff[0] + sidx] = cnts[i];  // class 255: the count itself, all 64 bits
     }
@@ -199,9 +212,10 @@ __global__ __launch_bounds__(kS2BS) void cls_scatter_kernel(
     const int32_t *__restrict__ keys, const int64_t *__restrict__ cnts, uint64_t n,
     const unsigned *__restrict__ cls_hist, unsigned *status, unsigned *ticket, int32_t *out_keys,
     int64_t *out_cnts, unsigned long long *table, uint64_t mask, int64_t first_label,
-    int64_t *sentinel_label, int32_t *label_of) {
+    int64_t *sentinel_label, int32_t *label_of, const uint32_t *__restrict__ src_slots,
+    unsigned long long *slot_table, uint64_t nslots) {
   cls_scatter_body(keys, cnts, n, cls_hist, status, ticket, out_keys, out_cnts, table, mask,
-                   first_label, sentinel_label, label_of);
+                   first_label, sentinel_label, label_of, nullptr, src_slots, slot_table, nslots);
 }
 
 // ---- the same ordering for SEVERAL vocabularies per launch --------------------------------
@@ -219,6 +233,7 @@ struct OrdJob {
   int32_t *out_keys;
   int64_t *out_cnts;
   int32_t *label_of;
+  const uint32_t *src_slots;  // dumped table: labels go through these, no patch pass
   unsigned long long *table;
   int64_t *sentinel_label;
   int32_t *aux;
@@ -253,7 +268,8 @@ __global__ __launch_bounds__(kS2BS) void cls_scatter_many_kernel(OrdBatch b) {
   const int ji = ord_job_of(b.tile_start, b.njobs, blockIdx.x);
   const OrdJob &j = b.j[ji];
   cls_scatter_body(j.keys, j.cnts, j.n, j.cls_hist, j.status, j.ticket, j.out_keys, j.out_cnts,
-                   nullptr, 0, (int64_t)j.first_label, j.sentinel_label, j.label_of);
+                   nullptr, 0, (int64_t)j.first_label, j.sentinel_label, j.label_of, nullptr,
+                   j.src_slots, j.table, j.nslots);
 }
 
 // Range table (dumped by the counting pass: slot = {key, position in the key-ordered list}):
@@ -316,7 +332,7 @@ __global__ __launch_bounds__(kBlock) void range_fix_prefix_kernel(
 
 __global__ __launch_bounds__(kBlock) void range_patch_many_kernel(OrdBatch b) {
   const OrdJob &j = b.j[blockIdx.y];
-  if (j.flat_slots || j.nslots == 0) return;
+  if (j.flat_slots || j.nslots == 0 || j.src_slots != nullptr) return;
   range_patch_body(j.table, j.nslots, j.label_of);
 }
 
@@ -637,7 +653,7 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
                             int32_t *out_keys, int64_t *out_cnts, void *tmp, int64_t first_label,
                             void *table, uint64_t capacity, int64_t *sentinel_label,
                             const int32_t *range_aux, int range_nb_log2, hipStream_t s,
-                            bool *tail_deferred, uint64_t flat_slots) {
+                            bool *tail_deferred, uint64_t flat_slots, const uint32_t *src_slots) {
   *tail_deferred = false;
   if (n == 0) return NVT_OK;
   NVT_CHECK_ARG(n < (1ull << 30), "at most 2^30-1 vocabulary entries");
@@ -649,6 +665,9 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
   // out from the sorted keys by a prefix maximum, see flat_build_kernel.
   const bool flat = table != nullptr && range_aux != nullptr && flat_slots > 0;
   const bool ranged = table != nullptr && range_aux != nullptr;
+  // dumped table + the slots the counting pass recorded: the scatter labels the slots itself
+  const bool slotted = ranged && !flat && src_slots != nullptr;
+  const uint64_t nslots = ((uint64_t)1 << range_nb_log2) * kRpRegion + kRpGuard;
   if (flat) {
     NVT_CHECK_ARG(flat_slots >= 64 && flat_slots < (1ull << 32), "flat table: 64 .. 2^32-1 slots");
     NVT_CHECK_ARG(capacity >= flat_slots + n + 64, "flat table: slots + n + 64");
@@ -666,7 +685,8 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
     cls_scatter_kernel<<<(unsigned)w.ntiles, kS2BS, 0, s>>>(
         src_keys, src_cnts, n, cls_hist, w.status, w.ticket, out_keys, out_cnts,
         ranged ? nullptr : (unsigned long long *)table, capacity - 1, first_label, sentinel_label,
-        ranged ? w.label_of : nullptr);
+        ranged ? w.label_of : nullptr, slotted ? src_slots : nullptr,
+        slotted ? (unsigned long long *)table : nullptr, slotted ? nslots : 0);
     NVT_CHECK_LAUNCH();
     if (flat) {
       int32_t *aux = const_cast<int32_t *>(range_aux);
@@ -676,8 +696,7 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
       flat_build_kernel<<<(unsigned)w.ntiles, kS2BS, 0, s>>>(
           src_keys, w.label_of, n, aux, w.fb_status, w.fb_ticket, (unsigned long long *)table, capacity);
       NVT_CHECK_LAUNCH();
-    } else if (ranged) {
-      const uint64_t nslots = ((uint64_t)1 << range_nb_log2) * kRpRegion + kRpGuard;
+    } else if (ranged && !slotted) {
       range_patch_kernel<<<stream_grid(nslots / 2, kBlock, 8), kBlock, 0, s>>>(
           (unsigned long long *)table, nslots, w.label_of);
       NVT_CHECK_LAUNCH();
@@ -710,7 +729,7 @@ int vocab_order_from_sorted(const int32_t *src_keys, const int64_t *src_cnts, ui
 
 // vocab_order_from_sorted for several vocabularies that own a range table (dumped or flat): every
 // stage one launch (ord_prep / cls_scatter_many / flat_params_many + flat_build_many /
-// range_patch_many), then the class-255 tails (one batched small sort + one label launch; a tail
+// range_patch_many, the last only when a dumped table came without slots), then the class-255 tails (one batched small sort + one label launch; a tail
 // too long for the small sort is sorted on its own).
 int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t s) {
   for (int j0 = 0; j0 < njobs; j0 += kOrdBatch) {
@@ -719,7 +738,7 @@ int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t 
     memset(&b, 0, sizeof(b));
     std::vector<OrderTail> tails;
     OrderWs ws[kOrdBatch];
-    bool any_flat = false, any_ranged = false;
+    bool any_flat = false, any_patch = false;  // any_patch: a dumped table without slots
     for (int i = 0; i < nj; ++i) {
       const OrderSortedJob &q = jobs[j0 + i];
       NVT_CHECK_ARG(q.n > 0 && q.n < (1ull << 30), "1 .. 2^30-1 vocabulary entries");
@@ -735,6 +754,7 @@ int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t 
       o.out_keys = q.out_keys;
       o.out_cnts = q.out_cnts;
       o.label_of = w.label_of;
+      o.src_slots = q.flat_slots ? nullptr : q.src_slots;
       o.table = reinterpret_cast<unsigned long long *>(q.table);
       o.sentinel_label = q.sentinel_label;
       o.aux = const_cast<int32_t *>(q.range_aux);
@@ -750,8 +770,8 @@ int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t 
         NVT_CHECK_ARG(q.flat_slots >= 64 && q.flat_slots < (1ull << 32), "flat table: 64 .. 2^32-1 slots");
         NVT_CHECK_ARG(q.capacity >= q.flat_slots + q.n + 64, "flat table: slots + n + 64");
         any_flat = true;
-      } else {
-        any_ranged = true;
+      } else if (q.src_slots == nullptr) {
+        any_patch = true;
       }
       b.tile_start[i + 1] = b.tile_start[i] + (unsigned)w.ntiles;
       b.flat_start[i + 1] = b.flat_start[i] + (q.flat_slots ? (unsigned)w.ntiles : 0u);
@@ -769,7 +789,7 @@ int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t 
         flat_build_many_kernel<<<b.flat_start[nj], kS2BS, 0, s>>>(b);
         NVT_CHECK_LAUNCH();
       }
-      if (any_ranged) {
+      if (any_patch) {
         range_patch_many_kernel<<<dim3(1024, nj), kBlock, 0, s>>>(b);
         NVT_CHECK_LAUNCH();
       }
@@ -779,7 +799,7 @@ int vocab_order_sorted_batch(const OrderSortedJob *jobs, int njobs, hipStream_t 
       if (q.n_big == 0) continue;
       if (vocab_sort_small_eligible(4, q.n_big, q.max_count)) {
         tails.push_back({q.out_keys, q.out_cnts, q.n_big, q.first_label, q.table, q.capacity,
-                         q.sentinel_label, q.range_aux});
+                         q.sentinel_label, q.range_aux, q.tmp, q.n});
         continue;
       }
       // a class 255 beyond the one-workgroup sort (merged multi-partition vocabularies), or of
@@ -812,6 +832,7 @@ int vocab_order_tail_batch(const OrderTail *t, int nt, hipStream_t s) {
     d[i].keys = t[i].keys;
     d[i].counts = t[i].counts;
     d[i].n = (unsigned)t[i].n_big;
+    d[i].tmp = t[i].tmp ? order_ws(t[i].tmp, t[i].n, t[i].n_big).sort_tmp : nullptr;
   }
   int rc = vocab_sort_small_batch(d.data(), nt, s);
   if (rc) return rc;

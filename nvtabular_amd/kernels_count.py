@@ -353,6 +353,7 @@ class DenseCountJob:
         _lib.require_gpu()
         self.want_table = True    # range path: also dump the count tables as the encode table
         self.range_table = None
+        self.range_slots = None   # uint32 per entry of the output list: its slot in range_table
         self.allow_range = allow_range
         self.range_failed = False
         self.range_fail_bits = 0
@@ -413,7 +414,8 @@ class DenseCountJob:
         desc.out_capacity = out_cap
         desc.state = self.state.data_ptr()
         desc.hot_image = None
-        desc.range_table = None
+        desc.range_table = desc.out_slots = None
+        self.range_slots = None
         if path == PATH_SORT:
             # uint32[256] block that receives the histogram of min(count, 255)
             self.hot_image = torch.empty(256, dtype=torch.int32, device=self.dev)
@@ -435,6 +437,9 @@ class DenseCountJob:
                 self.range_table = torch.empty(rt_bytes, dtype=torch.uint8, device=self.dev)
                 self.table_bits = bits
                 desc.range_table = self.range_table.data_ptr()
+                # where the dump puts every entry of the list: the ordering labels the table through it
+                self.range_slots = torch.empty(out_cap + 1, dtype=torch.int32, device=self.dev)
+                desc.out_slots = self.range_slots.data_ptr()
         elif lpath & PATH_HOT:
             # the column's own hot-key table image: sampled for all columns by one launch
             self.hot_image = torch.empty(HOT_IMAGE_WORDS, dtype=torch.int32, device=self.dev)
@@ -478,6 +483,7 @@ class DenseCountJob:
         if self.path == PATH_RANGE:
             info.update(cls_hist=self.hot_image[RANGE_AUX_HIST:RANGE_AUX_HIST + 256],
                         range_aux=self.hot_image, range_table=self.range_table,
+                        range_slots=self.range_slots[:m] if self.range_slots is not None else None,
                         range_bits=self.table_bits if self.range_table is not None else 0,
                         range_bits_floor=self.min_range_bits)
         return info

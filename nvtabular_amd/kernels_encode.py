@@ -75,6 +75,9 @@ def _lib_bytes(name: str, *args) -> int:
     return _BYTES[key]
 
 
+SMALL_SORT_CHUNK = 2048   # csrc/nvt_sort.hip kSmallChunk: lists up to here need no sort scratch
+
+
 class EncodeTable:
     """key -> label probe table built from an ordered vocabulary."""
 
@@ -83,9 +86,11 @@ class EncodeTable:
 
     def __init__(self, vocab_keys: torch.Tensor, first_label: int, unique: bool = False,
                  defer_build: bool = False, range_table=None, flat: bool = False):
-        """range_table = (table, aux, bits): the table was dumped by the range path of the
+        """range_table = (table, aux, bits[, slots]): the table was dumped by the range path of the
         counting stage and is addressed by the monotone map stored in ``aux``; it is completed
-        (positions -> labels) by nvt_vocab_finalize_many -- no table is allocated or built here."""
+        (positions -> labels) by nvt_vocab_finalize_many -- no table is allocated or built here.
+        ``slots`` (int32 per entry of the key-sorted list that the same counting pass emitted, or
+        None): the table slot of every entry, through which the ordering writes the labels."""
         _lib.require_gpu()
         self.suffix = K._key_suffix(vocab_keys)
         self.key_dtype = vocab_keys.dtype
@@ -105,12 +110,13 @@ class EncodeTable:
         self.ready = None      # Event recorded behind the sort / build on an internal stream
         self.pending = False   # True until the current stream has been made to wait for it
         self._release = False  # True between fill_encode_desc and release_ordering (encode_many)
-        self.table = self.range_aux = None
+        self.table = self.range_aux = self.range_slots = None
         self.range_bits = self.flat_slots = 0
         self.capacity = K.next_pow2(max(64, (4 if n <= (1 << 20) else 2) * n + 1))   # hashed tables
         hashed = kind in ("generic", "cache", "linear64")
         if kind == "dumped":
-            self.table, self.range_aux, self.range_bits = range_table
+            self.table, self.range_aux, self.range_bits = range_table[:3]
+            self.range_slots = range_table[3] if len(range_table) > 3 else None
             self.capacity = 0
         elif kind == "flat":
             # flat range table laid out from the key-sorted source by nvt_vocab_finalize_many
@@ -148,7 +154,7 @@ class EncodeTable:
         counting pass that also fills the table."""
         n = self.n_vocab
         src_keys = src_counts = cls_hist = labels = None
-        n_big = 0
+        n_big = small_scratch = 0
         if src is not None:
             src_keys, src_counts, cls_hist, n_big = src[:4]
             # (a fifth element: int32 positions of the source entries in the vocabulary order -- a
@@ -164,6 +170,10 @@ class EncodeTable:
         else:
             small = self.key_bytes == 4 and 2 <= n <= 16384 and 0 < int(max_count) < (1 << 32)
             scratch = _lib_bytes("nvt_vocab_sort_tmp_bytes", self.key_bytes, n) if n > 1 and not small else None
+            if small and n > SMALL_SORT_CHUNK:
+                # the batched small sort merges the sorted chunks of a longer list through 8 n bytes;
+                # it runs on the caller's stream, so no hand-off event goes with this scratch
+                small_scratch = 8 * n
         # the counts are ordered in place on the same internal stream as the keys: they must
         # outlive the hand-off event exactly like keys / table / sort_tmp (a rank that writes
         # no artifacts used to drop its only reference right after the launch)
@@ -176,13 +186,19 @@ class EncodeTable:
         d.unique_keys = 1 if self.unique else 0
         d.src_keys, d.src_counts = K.ptr(src_keys), K.ptr(src_counts)
         d.cls_hist, d.src_labels = K.ptr(cls_hist), K.ptr(labels)
+        d.src_slots = None
+        if self.range_slots is not None and src is not None and labels is None:
+            assert self.range_slots.dtype == torch.int32 and self.range_slots.numel() == n
+            d.src_slots = self.range_slots.data_ptr()
         d.n_big = int(n_big)
         d.range_aux = K.ptr(self.range_aux)
         d.range_nb_log2 = int(self.range_bits)
         d.flat_slots = int(self.flat_slots)
         if scratch is not None:
             self.sort_tmp = torch.empty(scratch + 16, dtype=torch.uint8, device=self._vk.device)
-        d.sort_tmp = K.ptr(self.sort_tmp) if scratch is not None else None
+        elif small_scratch:
+            self.sort_tmp = torch.empty(small_scratch + 16, dtype=torch.uint8, device=self._vk.device)
+        d.sort_tmp = K.ptr(self.sort_tmp) if scratch is not None or small_scratch else None
         d.first_label = self.first_label
         d.table = K.ptr(self.table)
         d.capacity = self.capacity
@@ -211,6 +227,7 @@ class EncodeTable:
         self.sort_tmp = None
         self._counts = None
         self._src = None
+        self.range_slots = None
 
     def wait_ready(self):
         """Order the CURRENT stream behind this vocabulary's sort / table build (no host

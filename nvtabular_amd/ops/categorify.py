@@ -534,7 +534,8 @@ class Categorify(StatOperator):
                 src = (keys, counts, info["cls_hist"], info["n_big"], info.get("label_of"))
                 keys, counts = torch.empty_like(keys), torch.empty_like(counts)
                 if info.get("range_table") is not None:
-                    rtab = (info["range_table"], info["range_aux"], info["range_bits"])
+                    rtab = (info["range_table"], info["range_aux"], info["range_bits"],
+                            info.get("range_slots"))
             # a key-sorted source without a dumped table (sort path, multi-GPU merge): the table
             # is laid out from the sorted keys in one pass (flat range table)
             # (a vocabulary whose keys cluster in their range -- found out by an earlier fit's
