@@ -248,6 +248,28 @@ def test_format_variants(tmp_path, variant):
     assert_equals_pandas(parts, pandas_frame(text, dtypes, sep=sep), dtypes)
 
 
+def test_crlf_last_column_float32_on_the_host_slow_path(tmp_path):
+    # quoted 25-digit values in the last column of a CRLF file: the device parser declines them, the
+    # host parses the text that is left without the '\r' and the quotes, and float32 rounds that double
+    rng = np.random.default_rng(12)
+    digits = ["".join(map(str, rng.integers(0, 10, 25))) for _ in range(150)]
+    cells = ['"%s.%s"' % (d[:i % 24 + 1], d[i % 24 + 1:]) for i, d in enumerate(digits)]
+    cells[3], cells[70], cells[149] = "", '"-1234567890123456789012345"', "0.1000000000000000055511151"
+    text = "a,y\r\n" + "".join(f"{i},{c}\r\n" for i, c in enumerate(cells))
+    dtypes = {"a": "int64", "y": "float32"}
+    p = write(tmp_path, "slow.csv", text)
+    from nvtabular_amd import kernels as K
+
+    before = K.STATS.get("csv_slow_fields", 0)
+    parts = frames(nvt.Dataset(p, dtypes=dtypes))
+    assert K.STATS.get("csv_slow_fields", 0) - before == 149
+    assert_equals_pandas(parts, pandas_frame(text, dtypes), dtypes)
+    vals, mask, _ = column_arrays(parts, "y")
+    want = np.array([float(c.strip('"')) if c else np.nan for c in cells], dtype=np.float64).astype(np.float32)
+    np.testing.assert_array_equal(vals[mask].view(np.uint32), want[mask].view(np.uint32))
+    assert mask.sum() == 149 and not mask[3]
+
+
 def test_headerless_with_names(tmp_path):
     text, dtypes = mixed_text(200, seed=6, header=False)
     p = write(tmp_path, "h.csv", text)
