@@ -539,7 +539,10 @@ int nvt_merge_payload(const int32_t *src_a, const int32_t *src_b, uint64_t n, in
  *                         device uint64[G][ncol]
  *   nvt_exchange_unpack   n gathered words in nseg segments [seg_off[s], seg_off[s + 1]) ->
  *                         keys_out / counts_out at dst_off[s] + (position in the segment)
- * lo / width: HOST arrays; seg_off / dst_off: device arrays.  No host synchronisation. */
+ * lo / width: HOST arrays; seg_off / dst_off: device arrays.  No host synchronisation.
+ * A column whose counts sum to 0 is reported by nvt_exchange_ranges like a column without entries.
+ * A count of 2^31 or more does not fit the word: its low 32 bits travel and nvt_exchange_unpack
+ * returns them sign-extended, so callers keep every count below 2^31. */
 typedef struct nvt_xcol {
   const int32_t *keys;
   const int64_t *counts;
