@@ -1630,6 +1630,30 @@ int nvt_partition_plan(const uint32_t *pid, uint64_t n, uint32_t P, int64_t *per
 int nvt_partition_gather_many(const nvt_partition_col *cols, int ncols, const nvt_partition_seg *segs, int nsegs,
                               uint64_t m, void *stream);
 
+/* ---- dense labels of a low-cardinality key: Dataset.to_parquet(partition_on=...) ----
+ * nvt_key_labels: `tags`, `nulls` and `words` are what nvt_join_hash produced for the same n rows
+ *   (`words` [nkeys][n] is read only for nkeys >= 2).  Two rows have the same key when their tags
+ *   are equal; with nkeys == 1 a row with nulls[i] != 0 belongs to the null key whatever its tag
+ *   (with more components the tag fingerprints the null bits).  Every 64-bit tag is a legal key.
+ *     label[i]      rank of row i's key among the distinct keys ordered by their first row
+ *                   (row 0's key is label 0); the labels feed nvt_partition_plan
+ *     first_row[l]  that first row, for l < D; entries from D on are not written
+ *     state[0]      D, the number of distinct keys
+ *     state[1]      0 ok | 1 more than NVT_LABEL_MAX distinct keys (label and first_row are then
+ *                   unspecified; nothing is written outside the outputs) | 2 with nkeys >= 2, two
+ *                   rows with equal tags whose words or null bits differ (a fingerprint collision)
+ *   No result depends on timing: first rows come from atomicMin and the ranks are taken over first
+ *   rows, so two runs on the same input are bit-identical.  n < 2^32; n = 0 is a no-op (nothing is
+ *   written); the call is stream-ordered; the workspace of nvt_key_labels_ws_bytes(n) bytes is
+ *   16-byte aligned.  Workgroups walk tiles of nvt_key_labels_tile_rows() = NVT_LABEL_TILE rows. */
+#define NVT_LABEL_MAX 4096            /* = NVT_PARTITION_MAX */
+#define NVT_LABEL_TILE 2048
+int nvt_key_labels_tile_rows(void);
+int nvt_key_labels_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_key_labels(const uint64_t *tags, const uint8_t *nulls, const uint64_t *words, int nkeys, uint64_t n,
+                   uint32_t *label, uint32_t *first_row, uint64_t *state, void *ws, uint64_t ws_bytes,
+                   void *stream);
+
 /* ---- device dataloader: batch gather of a chunk (nvtabular.loader.torch.TorchAsyncItr) ----
  * nvt_batch_take_many: dst[j * dst_stride] = cast(src[index[j]]) for the m output rows of every
  *   descriptor, ONE launch per NVT_TAKE_MAX_COLS descriptors (the entry loops).  index: m int64 on

@@ -463,6 +463,14 @@ SIGNATURES.update({
     "nvt_partition_gather_many": [C.POINTER(PartitionCol), _i32, _vp, _i32, _u64, _vp],
 })
 
+# include/nvt_hip.h NVT_LABEL_MAX
+LABEL_MAX = 4096
+SIGNATURES.update({
+    "nvt_key_labels_tile_rows": [],
+    "nvt_key_labels_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_key_labels": [_vp, _vp, _vp, _i32, _u64, _vp, _vp, _vp, _vp, _u64, _vp],
+})
+
 class TakeCol(C.Structure):
     """nvt_take_col: one column gathered by nvt_batch_take_many / nvt_take_list_many."""
     _fields_ = [("src", _vp), ("src_valid", _vp), ("dst", _vp), ("dst_valid", _vp), ("dst_stride", _i64),

@@ -508,6 +508,10 @@ def as_device_frame(df, device=None):
 
     if isinstance(df, StagedPartition):
         return df.to_device(device), False   # (the hand-written parquet reader)
+    from .hive import HivePart
+
+    if isinstance(df, HivePart):
+        return df.to_device(device), False   # (a partition of a hive dataset: its key columns attached)
     try:
         import pyarrow as pa
 

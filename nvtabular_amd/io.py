@@ -56,7 +56,14 @@ class Dataset:
         csv; anything else is read as parquet).  ``sep``, ``names``, ``header``, ``dtypes``,
         ``part_size``, ``quotechar`` and ``parse_dates`` belong to the csv engine (csv_text.py):
         delimited text is cut into byte ranges of about ``part_size`` and parsed on the device; the
-        columns named in ``parse_dates`` (ISO-8601 text) become datetime64[ns]."""
+        columns named in ``parse_dates`` (ISO-8601 text) become datetime64[ns].
+
+        A parquet directory without ``*.parquet`` files at its top level but with ``name=value``
+        subdirectories is read as a hive-partitioned dataset (hive.py): the leaf directories' files
+        are the pieces, in sorted walk order, and the key columns follow the files' columns in path
+        order.  Their values come from the paths (``__HIVE_DEFAULT_PARTITION__`` is a null); their
+        dtypes from ``_metadata.json`` (``partition_on``, as ``to_parquet`` records it), else int64
+        when every non-null segment of a key is ``-?[0-9]+`` and string otherwise."""
         self.cpu = bool(cpu)  # accepted for API compatibility; compute always runs on the GPU
         self.engine = engine
         self._schema = schema
@@ -109,10 +116,18 @@ class Dataset:
         if isinstance(paths, (str, os.PathLike)):
             paths = [str(paths)]
         files: List[str] = []
+        hive = None   # the layout of a hive-partitioned directory (hive.HiveLayout)
         for p in paths:
             p = str(p)
             if os.path.isdir(p):
-                files += sorted(glob.glob(os.path.join(p, "*.parquet")))
+                found = sorted(glob.glob(os.path.join(p, "*.parquet")))
+                if not found and len(paths) == 1:
+                    # no parquet file at the top level: key=value directories are walked
+                    from .hive import layout_of
+
+                    hive = layout_of(p)
+                    found = hive.files if hive is not None else []
+                files += found
             elif any(ch in p for ch in "*?["):
                 files += sorted(glob.glob(p))
             else:
@@ -120,16 +135,29 @@ class Dataset:
         if not files:
             raise FileNotFoundError(f"no parquet files under {paths}")
         self._files = files
+        self._hive = hive
         pieces = []
         for f in files:
             md = pq.ParquetFile(f)
+            if hive is not None:
+                from .hive import check_clash
+
+                check_clash(hive.keys, md.schema_arrow.names, f)
             ng = md.num_row_groups
             for g0 in range(0, ng, row_groups_per_part):
                 pieces.append((f, list(range(g0, min(ng, g0 + row_groups_per_part)))))
         self._pieces = pieces
         self._n = len(pieces)
         if self._schema is None:
-            self._schema = Schema.from_frame(pq.ParquetFile(files[0]).schema_arrow)
+            import numpy as np
+            import pyarrow as pa
+
+            file_schema = pq.ParquetFile(files[0]).schema_arrow
+            if hive is not None:   # the key columns behind the files' columns, in path order
+                for name, dt in zip(hive.keys, hive.dtypes):
+                    file_schema = file_schema.append(pa.field(name, pa.string() if dt == "string" else
+                                                              pa.from_numpy_dtype(np.dtype(dt))))
+            self._schema = Schema.from_frame(file_schema)
 
         # files the hand-written reader takes (flat numeric columns, three-level lists of such
         # leaves and flat string columns; PLAIN or dictionary-encoded values, uncompressed or snappy:
@@ -151,6 +179,22 @@ class Dataset:
             return plain_files[f]
 
         def read(piece, columns):
+            if hive is None:
+                return read_file(piece, columns)
+            # the key columns are not passed to the file readers: the path spells them, and they are
+            # attached where the partition becomes a DeviceFrame (hive.HivePart.to_device)
+            from .hive import HivePart
+
+            f, groups = piece
+            want = hive.keys if columns is None else [c for c in columns if c in hive.keys]
+            file_cols = None if columns is None else [c for c in columns if c not in hive.keys]
+            if file_cols is not None and not file_cols:   # only key columns: the footer has the row count
+                md = pq.ParquetFile(f).metadata
+                return HivePart(None, sum(md.row_group(g).num_rows for g in groups), hive, hive.values[f], want)
+            inner = read_file(piece, file_cols)
+            return HivePart(inner, inner.num_rows, hive, hive.values[f], want)
+
+        def read_file(piece, columns):
             f, groups = piece
             pf = plain_file(f)
             if pf is not None:
@@ -325,7 +369,7 @@ class Dataset:
     def to_parquet(self, output_path, shuffle=None, out_files_per_proc=None, dtypes=None,
                    cats=None, conts=None, labels=None, preserve_files=False, suffix=".parquet",
                    num_threads=0, compression=None, statistics=False, use_dictionary=None,
-                   device_compression=None, **_):
+                   device_compression=None, partition_on=None, max_partitions=1024, **_):
         """Write the (transformed) dataset as parquet (merlin.io.Dataset.to_parquet; contract in
         tests/unit/workflow/test_workflow.py:171-187,363-396,444-500 and
         bench/datasets/tools/nvt_etl.py:154-171 of the reference).
@@ -383,6 +427,25 @@ class Dataset:
           still selects pyarrow's writer.  When the frame goes to pyarrow's writer anyway, the value
           is handed to pyarrow as its ``compression`` ("Snappy pages in the PLAIN parquet
           writer").
+        * ``partition_on``: ``None`` (default) writes exactly the files described above.  A column name
+          or a list of 1 to 4 names writes a hive-partitioned dataset, laid out as
+          ``pyarrow.parquet.write_to_dataset`` does: every input partition is split by the key tuple
+          on the device (kernels_labels: a dense label per row, then one stable permutation), and the
+          rows of a tuple are appended, in input order, as row groups of
+          ``<k1>=<v1>/<k2>=<v2>/part_<rank><suffix>``; the key columns are not in the files.  A
+          segment value is ``urllib.parse.quote(str(value), safe="")``, the empty string gives
+          ``k=``, a null ``__HIVE_DEFAULT_PARTITION__``.  Keys are flat integer or flat string columns
+          (nullable or not); a float, bool, datetime or list key raises ``TypeError`` (cast first); a
+          name that is no column, a repeated name, keys that leave no data column,
+          ``out_files_per_proc`` or ``Shuffle.PER_WORKER`` next to it raise ``ValueError`` -- all
+          before anything is created.  ``Shuffle.PER_PARTITION`` shuffles first, then splits.  Every
+          other option keeps its meaning, applied to the frame without its key columns.  At most
+          4096 distinct tuples per input partition.  ``_metadata.json`` records the keys and their
+          dtypes (``"partition_on"``), which ``Dataset(path)`` restores.
+        * ``max_partitions`` (pyarrow's keyword and default): more directories than this over the
+          whole call raise ``ValueError`` (the part files written so far are removed); one
+          descriptor is held per directory, so a value that does not fit under the process's limit
+          of open files is refused before anything is written.
         * writes ``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and
           ``_metadata.json`` (file stats + cats / conts / labels) next to the data files.
         """
@@ -400,6 +463,7 @@ class Dataset:
                 raise ValueError("to_parquet: compression= selects pyarrow's writer and device_compression= the PLAIN "
                                  f"writer's codec: pass one of them, not both ({compression!r}, {device_compression!r})")
             device_compression = "snappy"
+        keys = self._partition_keys(partition_on, out_files_per_proc, shuffle, max_partitions)
         os.makedirs(str(output_path), exist_ok=True)
         output_path = str(output_path)
         rank, world = dist.rank(), dist.world_size()
@@ -411,6 +475,17 @@ class Dataset:
         parts = iter(self.to_iter(shard=(rank, world) if world > 1 else None))
         first = next(parts, None)
         parts = itertools.chain([first], parts) if first is not None else iter(())
+        splitter = None
+        if keys:
+            from . import _lib
+            from .hive import HiveSplitter, check_key_columns
+
+            _lib.require_gpu()
+            splitter = HiveSplitter(output_path, keys, rank, suffix, max_partitions)
+            fname = splitter.fname
+            if first is not None:
+                check_key_columns(first, keys)   # (TypeError before any file or directory is created)
+                first = first.drop(keys)         # the writers' eligibility rules see the data columns
         tables = StringTables()   # the entry tables of string columns, for this call
         # (a frame on the host has nothing to compress its pages with: pyarrow gets the codec)
         on_host = device_compression is not None and first is not None and \
@@ -426,7 +501,7 @@ class Dataset:
             offered = dictionary_columns(first, dtypes, use_dictionary)   # (raises before any file exists)
             names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
                                              PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered, tables,
-                                             snappy=device_compression is not None)
+                                             snappy=device_compression is not None, splitter=splitter)
             collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
             schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
         else:
@@ -434,18 +509,60 @@ class Dataset:
             pq_kw = {} if codec is None else {"compression": codec}
             if use_dictionary is not None:
                 pq_kw["use_dictionary"] = use_dictionary
-            names, rows, order, schema, collector = _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw)
+            names, rows, order, schema, collector = _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw,
+                                                                   splitter)
         for md, j in zip(collector, order):
             md.set_file_path(names[j])
+        recorded = None
+        if splitter is not None:
+            recorded = [{"col_name": c, "dtype": dt} for c, dt in zip(keys, splitter.dtypes or [])]
         _write_summary(output_path, [(names[j], rows.get(j, 0)) for j in order], schema, collector,
-                       cats, conts, labels)
+                       cats, conts, labels, recorded)
         return None
 
+    def _partition_keys(self, partition_on, out_files_per_proc, shuffle, max_partitions):
+        """``to_parquet(partition_on=...)`` -> the key names ([]: not partitioned).  Everything that
+        can be refused from the arguments and the schema is refused here, before anything exists."""
+        if partition_on is None:
+            return []
+        keys = [partition_on] if isinstance(partition_on, str) else list(partition_on)
+        from . import _lib
+        from .hive import check_descriptors
 
-def _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw):
+        if not 1 <= len(keys) <= _lib.JOIN_MAX_KEYS:
+            raise ValueError(f"to_parquet: partition_on takes 1 to {_lib.JOIN_MAX_KEYS} column names, got {len(keys)}")
+        if len(set(keys)) != len(keys):
+            raise ValueError(f"to_parquet: partition_on repeats a column: {keys}")
+        if out_files_per_proc:
+            raise ValueError("to_parquet: partition_on writes one part file per directory and process; "
+                             "out_files_per_proc cannot be combined with it")
+        if shuffle == Shuffle.PER_WORKER:
+            raise ValueError("to_parquet: Shuffle.PER_WORKER cannot be combined with partition_on "
+                             "(Shuffle.PER_PARTITION can: it shuffles, then splits)")
+        if int(max_partitions) < 1:
+            raise ValueError(f"to_parquet: max_partitions must be at least 1, got {max_partitions}")
+        schema = self.schema
+        missing = [c for c in keys if c not in schema]
+        if missing:
+            raise ValueError(f"to_parquet: partition_on names {missing}, which are no columns of {schema.column_names}")
+        if len(schema) <= len(keys):
+            raise ValueError(f"to_parquet: partition_on={keys} leaves no data column to write")
+        for c in keys:
+            cs = schema[c]
+            kind = getattr(cs.dtype, "kind", "O")
+            if cs.is_list or kind in "fbMm":
+                raise TypeError(f"to_parquet: partition_on column {c!r} is {'a list of ' if cs.is_list else ''}"
+                                f"{cs.dtype}; keys are flat integer or string columns: cast it first")
+        check_descriptors(int(max_partitions))
+        return keys
+
+
+def _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw, splitter=None):
     """Dataset.to_parquet with pyarrow's writer (strings, bools, a codec, Shuffle.PER_WORKER with
     ``k`` files ...): partition i goes to file i, or with ``k`` is cut into k pieces for files
-    0 .. k-1.  -> (names {file index: name}, rows {file index: rows}, file indices in order, the
+    0 .. k-1; with ``splitter`` (``partition_on``) the partition is split by key tuple on the device
+    and every tuple's rows go to the file of its directory.
+    -> (names {file index: name}, rows {file index: rows}, file indices in order, the
     files' Arrow schema, their FileMetaData in that order)."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
@@ -485,23 +602,51 @@ def _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw):
         inflight.acquire()
         pending.append(lanes[j % NLANES].submit(write, j, table))
 
-    for i, part in enumerate(parts):
-        n = len(part)
-        if shuffle is not None and n > 1:
-            part = part.take_rows(device_permutation(n, part))
-        table = part.to_arrow()  # pinned async copies, no pandas round trip
-        for c, t in (dtypes or {}).items():
-            if c in table.column_names:
-                ci = table.column_names.index(c)  # NOT `i`: that is the partition index
-                table = table.set_column(ci, c, table.column(c).cast(pa.from_numpy_dtype(np.dtype(t))))
-        if k is None:
-            emit(i, table)
-            continue
-        bounds = [(n * j) // k for j in range(k + 1)]
-        for j in range(k):
-            if bounds[j + 1] > bounds[j] or j not in touched:
-                touched.add(j)
-                emit(j, table.slice(bounds[j], bounds[j + 1] - bounds[j]))
+    def abort():
+        """A failed partitioned write: no footer-less part files are left behind."""
+        for f in pending:
+            try:
+                f.result()
+            except Exception:
+                pass
+        for j, w in writers.items():
+            try:
+                w.close()
+                os.remove(os.path.join(output_path, names[j]))
+            except Exception:
+                pass
+
+    try:
+        for i, part in enumerate(parts):
+            n = len(part)
+            if shuffle is not None and n > 1:
+                part = part.take_rows(device_permutation(n, part))
+            pieces = None
+            if splitter is not None:
+                part, pieces = splitter.split(part)
+                if not pieces:
+                    continue
+            table = part.to_arrow()  # pinned async copies, no pandas round trip
+            for c, t in (dtypes or {}).items():
+                if c in table.column_names:
+                    ci = table.column_names.index(c)  # NOT `i`: that is the partition index
+                    table = table.set_column(ci, c, table.column(c).cast(pa.from_numpy_dtype(np.dtype(t))))
+            if pieces is not None:
+                for j, s0, s1 in pieces:
+                    emit(j, table.slice(s0, s1 - s0))
+                continue
+            if k is None:
+                emit(i, table)
+                continue
+            bounds = [(n * j) // k for j in range(k + 1)]
+            for j in range(k):
+                if bounds[j + 1] > bounds[j] or j not in touched:
+                    touched.add(j)
+                    emit(j, table.slice(bounds[j], bounds[j + 1] - bounds[j]))
+    except BaseException:
+        if splitter is not None:
+            abort()
+        raise
     for f in pending:
         f.result()  # re-raises a writer's exception here
     for ex in lanes:
@@ -520,10 +665,12 @@ def _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw):
     return names, rows_in, order, schema, collector
 
 
-def _write_summary(output_path, files, schema, collector, cats, conts, labels):
+def _write_summary(output_path, files, schema, collector, cats, conts, labels, partition_on=None):
     """``_metadata`` (parquet summary of all row groups), ``_file_list.txt`` and ``_metadata.json``
     next to the data files.  ``files``: this rank's [(name, rows)]; ``collector``: their
-    FileMetaData with the file paths set.  Under torch.distributed rank 0 writes for every rank."""
+    FileMetaData with the file paths set.  Under torch.distributed rank 0 writes for every rank.
+    ``partition_on``: the [{col_name, dtype}] of a hive-partitioned write (file names are then paths
+    relative to ``output_path``; the keys are no columns of ``schema``, so ``pick`` drops them)."""
     import json
 
     import pyarrow.parquet as pq
@@ -554,6 +701,8 @@ def _write_summary(output_path, files, schema, collector, cats, conts, labels):
     pick = lambda lst: [{"col_name": c, "index": cols.index(c)} for c in (lst or []) if c in cols]
     meta = {"file_stats": [{"file_name": name, "num_rows": int(nr)} for name, nr in files],
             "cats": pick(cats), "conts": pick(conts), "labels": pick(labels)}
+    if partition_on is not None:
+        meta["partition_on"] = partition_on
     with open(os.path.join(output_path, "_metadata.json"), "w") as f:
         json.dump(meta, f)
 

@@ -645,8 +645,16 @@ def _row_ranges(i, n, k, row_group, touched):
             yield j, s0, min(b, s0 + row_group)
 
 
+def _piece_ranges(pieces, row_group):
+    """The row groups of the pieces [(file index, first row, row behind the last)] of a split partition
+    (``hive.HiveSplitter.split``): every piece has rows and is cut every ``row_group`` rows."""
+    for j, a, b in pieces:
+        for s0 in range(a, b, row_group):
+            yield j, s0, min(b, s0 + row_group)
+
+
 def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads,
-                offered=frozenset(), tables=None, snappy=False):
+                offered=frozenset(), tables=None, snappy=False, splitter=None):
     """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
     with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
     ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
@@ -654,6 +662,9 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
     ``tables``: the StringTables ``plain_eligible`` judged the first partition with (None: a fresh one).
     ``snappy``: ``device_compression="snappy"`` -- chunks on the device are written SNAPPY where that
     makes them smaller.
+    ``splitter`` (``partition_on``; then ``k`` is None and ``fname`` the splitter's): every partition is
+    permuted once so that the rows of a key tuple are contiguous, its key columns are dropped, and
+    the tuple's row range goes to the file of its directory.
     -> (names {file index: name}, rows {file index: rows}, file indices in order)."""
     LAST_TIMING.update(wait_copy_s=0.0, write_s=0.0, stage_s=0.0, total_s=0.0, input_s=0.0, close_s=0.0,
                        levels_s=0.0, dict_s=0.0, strings_s=0.0, snappy_s=0.0)
@@ -668,13 +679,19 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
                 n = len(part)
                 if shuffle is not None and n > 1:
                     part = part.take_rows(device_permutation(n, part))
+                pieces = None
+                if splitter is not None:
+                    part, pieces = splitter.split(part)
+                    if not pieces:
+                        continue
                 cols, groups = _prepare(part, n, dtypes, offered, tables)
                 on_gpu = any(c.data.is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
                 if on_gpu:
                     copy_s.wait_stream(torch.cuda.current_stream())
-                for j, s0, s1 in _row_ranges(i, n, k, row_group, touched):
+                for j, s0, s1 in (_row_ranges(i, n, k, row_group, touched) if pieces is None else
+                                  _piece_ranges(pieces, row_group)):
                     files.flush(_stage_row_group(j, cols, groups, s0, s1, copy_s if on_gpu else None, statistics,
                                                  snappy and on_gpu))
             files.close()
