@@ -58,7 +58,7 @@ extern "C" {
 #define NVT_I32 2
 #define NVT_I64 3
 #define NVT_U8 4
-/* narrow integers: outputs of nvt_cast_many only, every other entry point refuses them */
+/* narrow integers: outputs of nvt_cast_many and sources of nvt_pq_widen_i32_many only */
 #define NVT_I8 5
 #define NVT_I16 6
 
@@ -814,6 +814,52 @@ int nvt_pq_expand_runs(const uint32_t *runs, uint64_t nruns, const uint32_t *clo
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes);
 int nvt_expand_valid(const void *packed, int type_size, const uint8_t *bitmap, uint64_t n, void *out,
                      void *ws, void *stream);
+
+/* ---- parquet, flat int8 / int16 / bool columns ("Narrow and bool columns in the parquet
+ * path"; the reference's label idiom (col > 3).astype("int8"), ops/reduce_dtype_size.py) ----
+ * In the file an int8 / int16 column is an INT32 column (annotated INTEGER{8 | 16, signed}) of
+ * sign-extended values and a BOOLEAN page holds its non-null values one per bit, LSB first.
+ *
+ * nvt_pq_decode_bool_chunk (HOST function, no GPU, thread-safe): one column chunk of a flat BOOLEAN
+ * column -- DataPage v1 / v2, codec 0 / 1, definition levels as nvt_pq_decode_chunk_codec, values
+ * PLAIN (bit-packed) or RLE (u32 length | RLE / bit-packed hybrid at bit width 1).  Writes the rows'
+ * validity bits at valid_bit_offset like its neighbours and the non-null values ONE BYTE EACH (0 / 1)
+ * into values_out (values_cap bytes).  scratch: the largest page uncompressed; may be null for codec
+ * 0.  NVT_EINVAL: any length that does not fit what remains of its page or chunk, a run that claims
+ * more values than its page still owes, row counts that do not add up; nothing outside
+ * [chunk, chunk + chunk_bytes) is read.  NVT_EUNSUPPORTED: other codecs / encodings / page kinds.
+ *
+ * nvt_expand_narrow (device): out[i] = bit i of bitmap ? (dst type) packed[valid rows in front of i]
+ * : 0 for n < 2^32 rows; src_size -> dst_size is 4 -> 1, 4 -> 2 (int32 staging values to int8 /
+ * int16: a value outside the target range keeps its low bits) or 1 -> 1 (bool bytes).  bitmap NULL:
+ * the pure narrowing copy out[i] = (dst type) packed[i] (ws may be NULL).  bitmap 8-byte aligned,
+ * ceil(n / 64) * 8 bytes readable; ws: nvt_expand_valid_ws_bytes(n).
+ *
+ * nvt_pq_widen_i32_many (device): dst[i] = (int32) src[i] for every descriptor, one launch per 32
+ * of them.  src (NVT_I8 / NVT_I16) is aligned to its element size only, dst to 4 bytes; nothing
+ * outside [src, src + n) is read; n == 0 launches nothing.
+ *
+ * nvt_pq_bool_pack (device): the non-null values `vals` of a chunk (one byte each, != 0 is true) cut
+ * into pages at page_start[npages + 1] (device, int64, value positions): page p's values become bits,
+ * LSB first, from out + byte_at[p] (device, int64[npages + 1]; byte_at[p + 1] - byte_at[p] >=
+ * ceil(values of p / 8)); exactly ceil(values / 8) bytes per page are written, the tail bits of the
+ * last one 0.  npages == 0 launches nothing.  No read-back; works on `stream` only. */
+typedef struct nvt_pq_widen_col {
+  const void *src;
+  int32_t *dst;
+  uint64_t n;
+  int32_t src_dtype; /* NVT_I8 / NVT_I16 */
+  int32_t reserved;
+} nvt_pq_widen_col;
+int nvt_pq_decode_bool_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
+                             uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                             uint8_t *values_out, uint64_t values_cap, uint8_t *scratch, uint64_t scratch_bytes,
+                             uint64_t *rows_out, uint64_t *values_count);
+int nvt_expand_narrow(const void *packed, int src_size, int dst_size, const uint8_t *bitmap, uint64_t n, void *out,
+                      void *ws, void *stream);
+int nvt_pq_widen_i32_many(const nvt_pq_widen_col *cols, int ncols, void *stream);
+int nvt_pq_bool_pack(const uint8_t *vals, const int64_t *page_start, const int64_t *byte_at, uint64_t npages,
+                     uint8_t *out, void *stream);
 
 /* ---- batched entry points: ONE call per operator per partition -----------------------
  * The reference hands a whole dataframe to the backend per operator call

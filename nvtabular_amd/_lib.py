@@ -442,6 +442,21 @@ SIGNATURES.update({
     "nvt_cast_many": [C.POINTER(CastCol), _i32, _vp],
 })
 
+class PqWidenCol(C.Structure):
+    """nvt_pq_widen_col: one int8 / int16 source sign-extended to int32 by nvt_pq_widen_i32_many."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("n", _u64), ("src_dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+# parquet, flat int8 / int16 / bool columns (include/nvt_hip.h)
+SIGNATURES.update({
+    "nvt_pq_decode_bool_chunk": [_vp, _u64, _i32, _i32, _u64, _vp, _u64, _vp, _u64, _vp, _u64,
+                                 C.POINTER(_u64), C.POINTER(_u64)],
+    "nvt_expand_narrow": [_vp, _i32, _i32, _vp, _u64, _vp, _vp, _vp],
+    "nvt_pq_widen_i32_many": [C.POINTER(PqWidenCol), _i32, _vp],
+    "nvt_pq_bool_pack": [_vp, _vp, _vp, _u64, _vp, _vp],
+})
+
+
 class PartitionSeg(C.Structure):
     """nvt_partition_seg: one segment of an output partition (a DEVICE array of these is passed)."""
     _fields_ = [("idx", _vp), ("start", _u64)]

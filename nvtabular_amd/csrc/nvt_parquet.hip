@@ -1180,6 +1180,190 @@ int nvt_pq_decode_str_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int code
   return NVT_OK;
 }
 
+// ---- bool columns: one bit per non-null value in the file, one byte each in the staging buffer
+// ("Narrow and bool columns in the parquet path") ----------------------------------------
+namespace {
+
+// bits [0, count) of src (LSB first) -> one byte each
+inline void bits_to_bytes(const uint8_t *src, uint64_t count, uint8_t *out) {
+  for (uint64_t i = 0; i < count; ++i) out[i] = (uint8_t)((src[i >> 3] >> (i & 7)) & 1);
+}
+
+// `count` values of an RLE page (the hybrid at bit width 1 in [p, end)) -> one byte each.  A run is
+// taken only if the page still owes its values: a repeat run longer than that, or a bit-packed run
+// with a whole group more, is an error, like a run whose bytes leave the page.
+bool decode_bool_rle(const uint8_t *p, const uint8_t *end, uint64_t count, uint8_t *out) {
+  TReader r{p, end};
+  uint64_t done = 0;
+  while (done < count) {
+    const uint64_t head = r.varint();
+    if (!r.ok) return false;
+    const uint64_t avail = (uint64_t)(r.end - r.p);
+    if (head & 1) {
+      const uint64_t groups = head >> 1;
+      if (groups == 0 || groups > (count - done + 7) / 8) return false;   // (compared in groups: no product)
+      uint64_t take = groups * 8;
+      if (take > count - done) take = count - done;
+      if (avail < (take + 7) / 8) return false;   // (a writer may cut the last group's padding, not its values)
+      bits_to_bytes(r.p, take, out + done);
+      r.skip_bytes(groups < avail ? groups : avail);
+      done += take;
+    } else {
+      const uint64_t n = head >> 1;
+      if (n == 0 || n > count - done || avail < 1) return false;
+      const uint8_t v = *r.p++;
+      if (v > 1) return false;
+      memset(out + done, v, n);
+      done += n;
+    }
+  }
+  return true;
+}
+
+}  // namespace
+
+int nvt_pq_decode_bool_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
+                             uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                             uint8_t *values_out, uint64_t values_cap, uint8_t *scratch, uint64_t scratch_bytes,
+                             uint64_t *rows_out, uint64_t *values_count) {
+  NVT_CHECK_ARG(chunk && values_out && rows_out && values_count, "null pointer");
+  NVT_CHECK_ARG(max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
+  NVT_CHECK_ARG(max_def_level == 0 || valid_out, "null validity buffer");
+  if (codec != 0 && codec != 1) {
+    set_error("nvt_pq_decode_bool_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
+    return NVT_EUNSUPPORTED;
+  }
+  // page body -> `want` uncompressed bytes: the body itself, or the scratch buffer
+  auto inflate = [&](const uint8_t *src, uint64_t nsrc, uint64_t want, bool compressed, const uint8_t **out) -> int {
+    if (!compressed) {
+      if (nsrc != want) {
+        set_error("nvt_pq_decode_bool_chunk: an uncompressed page of %llu bytes that says %llu",
+                  (unsigned long long)nsrc, (unsigned long long)want);
+        return NVT_EINVAL;
+      }
+      *out = src;
+      return NVT_OK;
+    }
+    if (scratch == nullptr || scratch_bytes < want) {
+      set_error("nvt_pq_decode_bool_chunk: scratch too small for a page of %llu bytes", (unsigned long long)want);
+      return NVT_EINVAL;
+    }
+    if (snappy_uncompress(src, nsrc, scratch, want) != (int64_t)want) {
+      set_error("nvt_pq_decode_bool_chunk: malformed snappy block");
+      return NVT_EINVAL;
+    }
+    *out = scratch;
+    return NVT_OK;
+  };
+  const uint8_t *p = chunk, *end = chunk + chunk_bytes;
+  uint64_t rows = 0, vals = 0;
+  while (p < end && rows < expect_rows) {
+    TReader r{p, end};
+    PageHead h;
+    if (!read_page_header(r, h)) {
+      set_error("nvt_pq_decode_bool_chunk: malformed page header at byte %llu", (unsigned long long)(p - chunk));
+      return NVT_EINVAL;
+    }
+    const uint8_t *body = r.p;
+    if (h.compressed < 0 || h.uncompressed < 0 || (uint64_t)(end - body) < (uint64_t)h.compressed) {
+      set_error("nvt_pq_decode_bool_chunk: page of %lld bytes runs past the chunk", (long long)h.compressed);
+      return NVT_EINVAL;
+    }
+    if (h.type == 1) {  // index page: nothing for us
+      p = body + h.compressed;
+      continue;
+    }
+    if (h.type != 0 && h.type != 3) {   // (a dictionary page too: parquet has no bool dictionaries)
+      set_error("nvt_pq_decode_bool_chunk: page type %d", h.type);
+      return NVT_EUNSUPPORTED;
+    }
+    if (h.encoding != 0 && h.encoding != 3) {   // PLAIN (bit-packed) / RLE
+      set_error("nvt_pq_decode_bool_chunk: value encoding %d (PLAIN and RLE are decoded here)", h.encoding);
+      return NVT_EUNSUPPORTED;
+    }
+    const uint64_t prow = (uint64_t)h.num_values;
+    if (h.num_values < 0 || prow > expect_rows - rows) {
+      set_error("nvt_pq_decode_bool_chunk: more rows than the row group holds");
+      return NVT_EINVAL;
+    }
+    const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
+    uint64_t pvalid = prow;
+    if (h.type == 0) {   // v1: levels and values are compressed together
+      const uint8_t *u = nullptr;
+      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
+      if (rc) return rc;
+      q = u;
+      pend = u + h.uncompressed;
+      if (max_def_level == 1) {
+        if (h.def_encoding != 3) {  // RLE (the hybrid)
+          set_error("nvt_pq_decode_bool_chunk: definition level encoding %d", h.def_encoding);
+          return NVT_EUNSUPPORTED;
+        }
+        uint32_t lb = 0;
+        if (pend - q >= 4) memcpy(&lb, q, 4);
+        if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb ||
+            !decode_levels(q + 4, lb, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
+          set_error("nvt_pq_decode_bool_chunk: malformed definition levels");
+          return NVT_EINVAL;
+        }
+        q += 4 + (uint64_t)lb;
+      }
+    } else {  // v2: definition levels uncompressed in front, no length prefix
+      if (h.rep_bytes != 0) {
+        set_error("nvt_pq_decode_bool_chunk: repetition levels (nested column)");
+        return NVT_EUNSUPPORTED;
+      }
+      if (h.def_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
+          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes) {
+        set_error("nvt_pq_decode_bool_chunk: definition levels run past the page");
+        return NVT_EINVAL;
+      }
+      if (max_def_level == 1 &&
+          !decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
+        set_error("nvt_pq_decode_bool_chunk: malformed definition levels");
+        return NVT_EINVAL;
+      }
+      const uint8_t *u = nullptr;
+      const uint64_t lbytes = (uint64_t)h.def_bytes;
+      int rc = inflate(body + lbytes, (uint64_t)h.compressed - lbytes, (uint64_t)h.uncompressed - lbytes,
+                       codec != 0 && h.v2_compressed, &u);
+      if (rc) return rc;
+      q = u;
+      pend = u + ((uint64_t)h.uncompressed - lbytes);
+    }
+    if (pvalid > prow || vals > values_cap || pvalid > values_cap - vals) {
+      set_error("nvt_pq_decode_bool_chunk: values buffer too small");
+      return NVT_EINVAL;
+    }
+    if (h.encoding == 0) {
+      if ((uint64_t)(pend - q) < (pvalid + 7) / 8) {
+        set_error("nvt_pq_decode_bool_chunk: page holds fewer values than its levels say");
+        return NVT_EINVAL;
+      }
+      bits_to_bytes(q, pvalid, values_out + vals);
+    } else if (pvalid) {
+      // RLE: u32 length | runs of the hybrid at bit width 1
+      uint32_t lb = 0;
+      if (pend - q >= 4) memcpy(&lb, q, 4);
+      if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb || !decode_bool_rle(q + 4, q + 4 + lb, pvalid, values_out + vals)) {
+        set_error("nvt_pq_decode_bool_chunk: malformed RLE values");
+        return NVT_EINVAL;
+      }
+    }
+    vals += pvalid;
+    rows += prow;
+    p = body + h.compressed;
+  }
+  if (rows != expect_rows) {
+    set_error("nvt_pq_decode_bool_chunk: %llu rows in the pages, %llu expected", (unsigned long long)rows,
+              (unsigned long long)expect_rows);
+    return NVT_EINVAL;
+  }
+  *rows_out = rows;
+  *values_count = vals;
+  return NVT_OK;
+}
+
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes) {
   NVT_CHECK_ARG(bytes, "null out");
   const uint64_t ntiles = (n + kExpWaveRows - 1) / kExpWaveRows;

@@ -39,8 +39,16 @@ The value sections of a chunk's pages are filled on the device (kernels_parquet_
 csrc/nvt_parquet_str_out.hip) and handed over as ``ByteArrayPages``; the rows per page follow the
 longest entry (``string_page_rows``) so that no page passes 2^30 bytes; string chunks carry a null
 count and no min / max ("String columns in the PLAIN parquet writer").
-Anything else (lists of strings or of bool / 8 / 16-bit leaves, booleans, string columns on the host or
-with bytes / mixed objects in their dict, casts of list or string columns) stays with pyarrow's writer.
+A flat int8 / int16 column is an INT32 column of sign-extended values annotated INTEGER{8 | 16, signed}
+(converted type INT_8 / INT_16): the writer takes its values as int32.  A flat bool column is a BOOLEAN
+column whose page is
+
+    thrift PageHeader | definition levels | ceil(nv / 8) bytes: the nv non-null values one per bit, LSB first
+
+packed on the device (kernels_parquet_narrow, csrc/nvt_parquet_narrow.hip) and handed over as
+``BoolPages`` ("Narrow and bool columns in the parquet path"); the reading half takes both.
+Anything else (lists of strings or of bool / 8 / 16-bit leaves, unsigned integers, string columns on the
+host or with bytes / mixed objects in their dict, casts of list or string columns) stays with pyarrow's writer.
 With ``to_parquet(use_dictionary=...)`` an int32 / int64 column chunk (datetime counts and list leaves
 too) may instead be a dictionary page -- its distinct non-null values, ascending -- followed by data
 pages of the same cut whose values are ``W | ONE bit-packed run of indices`` (encoding
@@ -79,9 +87,20 @@ MAX_PAGE_BYTES = 1 << 30       # a string page's body (a thrift page size is an 
 MAX_ENTRY_BYTES = MAX_PAGE_BYTES - 4   # the longest string the PLAIN writer takes
 
 
+BOOL_DTYPE = np.dtype(bool)     # a flat bool column: physical BOOLEAN, ``BoolPages`` in the place of the values
+# a flat int8 / int16 column: physical INT32 (the writer takes its values sign-extended to int32),
+# annotated LogicalType INTEGER{bitWidth, signed} and the converted type INT_8 / INT_16
+_NARROW = {np.dtype("int8"): (8, 15), np.dtype("int16"): (16, 16)}
+
+
 def _ptype(dt) -> int:
     """Physical type of a column of the writer."""
-    return 6 if dt == STRING_DTYPE else _PQ_TYPE[dt]
+    return 6 if dt == STRING_DTYPE else 0 if dt == BOOL_DTYPE else _PQ_TYPE[dt]
+
+
+def physical_dtype(dt):
+    """The dtype of the buffers the writer takes for a column of ``dt``: int32 for int8 / int16."""
+    return np.dtype("int32") if dt in _NARROW else dt
 
 
 def string_page_rows(longest: int) -> int:
@@ -310,6 +329,34 @@ class ByteArrayPages:
         return memoryview(self.body).cast("B")[self.page_at[p]: self.page_at[p + 1]]
 
 
+class BoolPages:
+    """One column chunk of a flat bool column, as ``write_row_group`` takes it in the place of the
+    values: ``packed`` (bytes-like, uint8) holds the value sections of all data pages of the chunk
+    one behind the other -- a page's ``nv`` non-null values one per bit, LSB first, in ceil(nv / 8)
+    bytes, the unused high bits of the last byte 0, every page starting at a byte -- and ``nvalues``
+    their number.  The pages are cut by rows like any flat column's, so their sizes follow from the
+    validity bitmap.  The device packs the bits (kernels_parquet_narrow.bool_pack); ``packed`` may
+    still be in flight when the row group is laid out."""
+
+    __slots__ = ("packed", "nvalues")
+
+    def __init__(self, packed, nvalues):
+        self.packed, self.nvalues = packed, int(nvalues)
+        if self.nvalues < 0 or len(packed) < (self.nvalues + 7) // 8:
+            raise ValueError(f"BoolPages: {len(packed)} packed bytes for {self.nvalues} values")
+
+    @property
+    def dtype(self):
+        return BOOL_DTYPE
+
+    def page(self, at, nv):
+        """The value section of a data page of nv values whose bytes start at ``at`` (bytes-like)."""
+        size = (nv + 7) // 8
+        if at + size > len(self.packed):
+            raise ValueError(f"PlainParquetWriter: a page of {nv} values at byte {at} of {len(self.packed)} packed bytes")
+        return memoryview(self.packed).cast("B")[at: at + size] if size else memoryview(b"")
+
+
 def _snappy_literal_tag(n: int) -> bytes:
     """The tag of a snappy literal element of n >= 1 bytes: ``(n - 1) << 2`` up to 60 bytes, else
     ``(59 + k) << 2`` and n - 1 in k little-endian bytes."""
@@ -416,6 +463,7 @@ class SnappyPages:
 
 class PlainParquetWriter:
     """One parquet file of int32 / int64 / float32 / float64 columns, flat or "list of" such leaves,
+    flat int8 / int16 columns (their values passed as int32) and bool columns (``BoolPages``),
     and flat string columns (``STRING_DTYPE``: BYTE_ARRAY annotated UTF8 / STRING),
     every column OPTIONAL (like pyarrow writes nullable Arrow columns), PLAIN encoding, no
     compression.  A list column is the standard three-level list (optional group ``name`` (LIST) >
@@ -433,8 +481,9 @@ class PlainParquetWriter:
         self.names = list(names)
         self.dtypes = [np.dtype(d) for d in dtypes]
         for d in self.dtypes:
-            if d not in _PQ_TYPE and d != STRING_DTYPE:
+            if d not in _PQ_TYPE and d != STRING_DTYPE and d != BOOL_DTYPE and d not in _NARROW:
                 raise TypeError(f"PlainParquetWriter: unsupported dtype {d}")
+        self.physical = [physical_dtype(d) for d in self.dtypes]   # what the columns' buffers hold
         self.logical = [np.dtype(x) if x is not None else None for x in (logical or [None] * len(self.names))]
         for d, x in zip(self.dtypes, self.logical):
             if x is not None and (timestamp_unit(x) is None or d != np.dtype("int64")):
@@ -446,6 +495,8 @@ class PlainParquetWriter:
             raise TypeError("PlainParquetWriter: list columns of datetime leaves are not written")
         if any(l and d == STRING_DTYPE for l, d in zip(self.lists, self.dtypes)):
             raise TypeError("PlainParquetWriter: list columns of strings are not written")
+        if any(l and (d == BOOL_DTYPE or d in _NARROW) for l, d in zip(self.lists, self.dtypes)):
+            raise TypeError("PlainParquetWriter: list columns of bool / int8 / int16 leaves are not written")
         self.fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
         os.pwrite(self.fd, b"PAR1", 0)
         self.pos = 4
@@ -459,6 +510,8 @@ class PlainParquetWriter:
         offset of its first data page."""
         if isinstance(values, DictPages):
             return self._plan_dict_column(values, valid, n, dt, start)
+        if isinstance(values, BoolPages) or dt == BOOL_DTYPE:
+            return self._plan_bool_column(values, valid, n, dt, start)
         bp = values if isinstance(values, ByteArrayPages) else None
         if (bp is not None) != (dt == STRING_DTYPE):
             raise TypeError(f"PlainParquetWriter: column buffer is {getattr(values, 'dtype', type(values))}, "
@@ -491,6 +544,27 @@ class PlainParquetWriter:
         if bp is None and done_vals != values.size:
             raise ValueError("PlainParquetWriter: the values do not match the validity bitmap "
                              f"({values.size} values, {done_vals} valid rows)")
+        return segs, at - start, start
+
+    def _plan_bool_column(self, bp, valid, n, dt, start):
+        """A flat bool chunk: page = header | def levels | ceil(nv / 8) bytes of bits."""
+        if not isinstance(bp, BoolPages) or dt != BOOL_DTYPE:
+            raise TypeError(f"PlainParquetWriter: column buffer is {getattr(bp, 'dtype', type(bp))}, "
+                            f"the file's column is {dt}")
+        segs, at, byte_at, done_vals = [], start, 0, 0
+        for rows, page_valid, nv in _flat_pages(valid, n, PAGE_VALUES):
+            prefix, bitmap = _def_levels(rows, page_valid)
+            payload = bp.page(byte_at, nv)
+            body = len(prefix) + (len(bitmap) if bitmap is not None else 0) + len(payload)
+            for buf in (_page_header(rows, body) + prefix, bitmap, payload):
+                if buf is not None and len(buf):
+                    segs.append((at, buf))
+                    at += len(buf)
+            byte_at += len(payload)
+            done_vals += nv
+        if done_vals != bp.nvalues:
+            raise ValueError("PlainParquetWriter: the values do not match the validity bitmap "
+                             f"({bp.nvalues} values, {done_vals} valid rows)")
         return segs, at - start, start
 
     def _plan_dict_column(self, dp, valid, n, dt, start):
@@ -636,7 +710,8 @@ class PlainParquetWriter:
         the NON-NULL values in row order, `valid` None or the Arrow validity bitmap (uint8, LSB
         first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
         non-null LEAVES of the n rows in order and their ``ListLevels``.  A string column: a
-        ``ByteArrayPages`` in the place of ``values``.  A dictionary-encoded chunk
+        ``ByteArrayPages`` in the place of ``values``, a bool column: a ``BoolPages``; an int8 / int16
+        column: its values sign-extended to int32.  A dictionary-encoded chunk
         (of any kind): a ``DictPages`` in the place of ``values``.  A SNAPPY chunk (of any kind, also
         a dictionary chunk): a ``SnappyPages`` in the place of ``values``.  Argument errors raise
         before anything of the row group is written.  wait=False (with a pool): returns the
@@ -655,7 +730,7 @@ class PlainParquetWriter:
         if len(columns) != len(self.names):
             raise ValueError(f"PlainParquetWriter: {len(columns)} columns for a file of {len(self.names)}")
         pos = self.pos
-        for j, ((values, valid), name, dt) in enumerate(zip(columns, self.names, self.dtypes)):
+        for j, ((values, valid), name, dt) in enumerate(zip(columns, self.names, self.physical)):
             start = pos
             if self.lists[j] != isinstance(valid, ListLevels):
                 raise TypeError(f"PlainParquetWriter: column '{name}' is a {'list' if self.lists[j] else 'flat'} "
@@ -674,7 +749,8 @@ class PlainParquetWriter:
             pos += size
             is_dict = isinstance(values, DictPages) or (raw_size is not None and values.W is not None)
             if raw_size is None:
-                nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else int(np.asarray(values).size)
+                nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else \
+                    values.nvalues if isinstance(values, BoolPages) else int(np.asarray(values).size)
             chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
                                minmax=stats[j] if (stats is not None and nvalid > 0) else None,
                                is_list=self.lists[j], first_data=first if is_dict else None,
@@ -742,10 +818,14 @@ class PlainParquetWriter:
                 schema.append(_Struct().i32(3, 2).binary(4, "list").i32(5, 1).done())
                 schema.append(_Struct().i32(1, _PQ_TYPE[dt]).i32(3, 1).binary(4, "element").done())
                 continue
-            el = _Struct().i32(1, _ptype(dt)).i32(3, 1).binary(4, name)
+            el = _Struct().i32(1, _ptype(physical_dtype(dt))).i32(3, 1).binary(4, name)
             if dt == STRING_DTYPE:
                 # BYTE_ARRAY, converted type UTF8 (0), LogicalType STRING (union field 1, an empty struct)
                 el.i32(6, 0).struct(10, _Struct().struct(1, _Struct().done()).done())
+            if dt in _NARROW:
+                # INT32, converted type INT_8 / INT_16, LogicalType INTEGER (union field 10) {bitWidth, isSigned}
+                bits, conv = _NARROW[dt]
+                el.i32(6, conv).struct(10, _Struct().struct(10, _Struct().byte(1, bits).bool(2, True).done()).done())
             if logical is not None:
                 field, conv = _TS_UNIT[timestamp_unit(logical)]
                 if conv is not None:
@@ -789,10 +869,11 @@ class PlainParquetWriter:
 _PQ_NP = {1: np.dtype("int32"), 2: np.dtype("int64"), 4: np.dtype("float32"), 5: np.dtype("float64")}
 
 
-def _judge_leaf(e):
+def _judge_leaf(e, narrow=False):
     """(dtype, unit, reason or None) of a primitive SchemaElement (1 physical type, 3 repetition
     {0 required, 1 optional, 2 repeated}, 4 name, 6 converted type, 10 LogicalType): the rule for
-    flat columns and for list leaves.  ``unit``: "ms" / "us" / "ns" of an INT64 TIMESTAMP."""
+    flat columns (``narrow``: bool / int8 / int16 too) and for list leaves.  ``unit``: "ms" / "us" /
+    "ns" of an INT64 TIMESTAMP."""
     ptype, conv, logical = e.get(1), e.get(6), e.get(10)
     dt, who = _PQ_NP.get(ptype), f"column {e.get(4)!r}"
     # an INT64 TIMESTAMP (LogicalType union field 8 {1: isAdjustedToUTC, 2: unit}, or the
@@ -815,6 +896,18 @@ def _judge_leaf(e):
     # and INT_64 (18) on INT64 keep dtype AND bits -- the same rule as for the LogicalType INTEGER;
     # everything else is left to the pyarrow reader
     integer = logical.get(10) if isinstance(logical, dict) else None
+    if narrow:
+        # a FLAT column may also be a BOOLEAN without an annotation (bool) or an INT32 annotated
+        # INTEGER{8 | 16, signed} and / or with the legacy converted type INT_8 / INT_16 alone
+        # (int8 / int16: the values are staged as int32 and narrowed on the device)
+        if ptype == 0 and conv is None and logical is None and e.get(3, 0) != 2:
+            return BOOL_DTYPE, None, None
+        for ndt, (bits, nconv) in _NARROW.items():
+            by_logical = (integer is not None and len(logical) == 1 and integer.get(1, 0) == bits and
+                          integer.get(2, False) is True)
+            if ptype == 1 and e.get(3, 0) != 2 and conv in ((None, nconv) if by_logical else (nconv,)) and \
+                    (by_logical or logical is None):
+                return ndt, None, None
     if logical is not None and not (integer is not None and integer.get(2, True) and len(logical) == 1 and
                                     integer.get(1, 0) == (32 if ptype == 1 else 64)):
         return dt, unit, f"{who}: logical type {logical}"
@@ -849,7 +942,7 @@ def _judge_column(schema, at):
         col.update(kind="string", outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1)
         return col, (f"column {name!r}: a repeated string" if e.get(3, 0) == 2 else None)
     if not e.get(5):
-        dt, unit, why = _judge_leaf(e)
+        dt, unit, why = _judge_leaf(e, narrow=True)
         col.update(outer_optional=e.get(3, 0) == 1, max_def=0 if e.get(3, 0) == 0 else 1, leaf_dtype=dt, unit=unit)
         return col, why
     col["kind"] = "list"
@@ -908,7 +1001,8 @@ class PlainParquetFile:
     """Footer of one parquet file and the verdict on whether the hand-written reader takes it.
     ``decodable``: every top-level column is a flat column (physical type INT32 / INT64 / FLOAT /
     DOUBLE without a converted / logical type that changes the meaning of the bits: dates, decimals,
-    unsigned), a flat string column (BYTE_ARRAY annotated UTF8 / STRING, ``kind`` "string": DESIGN.md,
+    unsigned; BOOLEAN, and INT32 annotated INTEGER{8 | 16, signed} or INT_8 / INT_16: bool / int8 /
+    int16), a flat string column (BYTE_ARRAY annotated UTF8 / STRING, ``kind`` "string": DESIGN.md,
     "String columns in the parquet reader") or the standard three-level list of such number leaves (a group annotated LIST, optional or
     required, holding one repeated group, holding one primitive leaf, optional or required; the two
     inner names are not looked at), and every column chunk follows its column, with codec
@@ -1119,6 +1213,8 @@ class StagedPartition:
         return next(iter(self.columns.values())).rows if self.columns else 0
 
     def to_device(self, device=None):
+        import torch
+
         from . import kernels as K
         from . import kernels_parquet_list as KPL
         from .device import DeviceColumn, DeviceFrame, default_device
@@ -1150,6 +1246,15 @@ class StagedPartition:
                 offsets, bitmap = unpacked[key]
                 data = packed if bitmap is None else K.expand_valid(packed, bitmap, sc.leaves)
                 out[name] = DeviceColumn(data, bitmap, offsets)
+            elif sc.dtype == BOOL_DTYPE or sc.dtype in _NARROW:
+                # staged as int32 values / one byte per bool: expanded and narrowed in one pass
+                from . import kernels_parquet_narrow as KPN
+
+                bitmap = None
+                if sc.valid is not None:
+                    bitmap = sc.valid[: ((sc.rows + 63) // 64) * 8].to(device, non_blocking=True)
+                out[name] = DeviceColumn(KPN.expand_narrow(packed, getattr(torch, sc.dtype.name), bitmap, sc.rows),
+                                         bitmap)
             elif sc.valid is None:
                 out[name] = DeviceColumn(packed, logical=sc.logical)
             else:
@@ -1288,19 +1393,30 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if pf.columns[j]["kind"] == "string":
             return str_task(n, j)
         dt = pf.dtypes[j]
-        vals = torch.empty(total, dtype=getattr(torch, dt.name), pin_memory=pinned)
+        # an int8 / int16 column is staged as the INT32 values the file holds, a bool column one byte
+        # per non-null value: the device narrows them (StagedPartition.to_device)
+        st = np.dtype("uint8") if dt == BOOL_DTYPE else physical_dtype(dt)
+        vals = torch.empty(total, dtype=getattr(torch, st.name), pin_memory=pinned)
         valid = None
         if pf.max_def[j]:
             valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         row_at = val_at = 0
         for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
             r, v = C.c_uint64(), C.c_uint64()
-            rc = lib.nvt_pq_decode_chunk_codec(cbuf, cc["size"], cc.get("codec", 0), dt.itemsize, pf.max_def[j],
-                                               rows, valid.data_ptr() if valid is not None else None, row_at,
-                                               vals.data_ptr() + val_at * dt.itemsize,
-                                               (total - val_at) * dt.itemsize, sbuf, sbytes,
-                                               C.byref(r), C.byref(v))
-            decoded("nvt_pq_decode_chunk_codec", rc, n, g)
+            if dt == BOOL_DTYPE:
+                fn = "nvt_pq_decode_bool_chunk"
+                rc = lib.nvt_pq_decode_bool_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
+                                                  valid.data_ptr() if valid is not None else None, row_at,
+                                                  vals.data_ptr() + val_at, total - val_at, sbuf, sbytes,
+                                                  C.byref(r), C.byref(v))
+            else:
+                fn = "nvt_pq_decode_chunk_codec"
+                rc = lib.nvt_pq_decode_chunk_codec(cbuf, cc["size"], cc.get("codec", 0), st.itemsize, pf.max_def[j],
+                                                   rows, valid.data_ptr() if valid is not None else None, row_at,
+                                                   vals.data_ptr() + val_at * st.itemsize,
+                                                   (total - val_at) * st.itemsize, sbuf, sbytes,
+                                                   C.byref(r), C.byref(v))
+            decoded(fn, rc, n, g)
             row_at += rows
             val_at += int(v.value)
         logical = np.dtype(f"datetime64[{pf.units[j]}]") if pf.units[j] is not None else None

@@ -42,6 +42,11 @@ class _Struct:
             self.b += _zigzag(fid)
         self.last = fid
 
+    def byte(self, fid, v):
+        self._head(fid, 3)
+        self.b.append(int(v) & 0xFF)
+        return self
+
     def i32(self, fid, v):
         self._head(fid, _CT_I32)
         self.b += _zigzag(int(v))

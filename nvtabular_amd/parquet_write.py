@@ -43,11 +43,12 @@ import torch
 from . import kernels as K
 from . import kernels_parquet_dict as KPD
 from . import kernels_parquet_list as KPL
+from . import kernels_parquet_narrow as KPN
 from . import kernels_parquet_str_out as KSO
 from . import kernels_snappy as KS
 from . import parquet_plain as PP
 from .device import pack_bitmap_device
-from .parquet_plain import ByteArrayPages, DictPages, ListLevels, PlainParquetWriter, SnappyPages
+from .parquet_plain import BoolPages, ByteArrayPages, DictPages, ListLevels, PlainParquetWriter, SnappyPages
 
 # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
 # snappy_s (a part of stage_s): plan, compress and gather of a row group's chunks, the read-back of
@@ -58,6 +59,8 @@ from .parquet_plain import ByteArrayPages, DictPages, ListLevels, PlainParquetWr
 # of their dictionary page sizes
 LAST_TIMING = {}
 _TORCH_OF = {"int32": torch.int32, "int64": torch.int64, "float32": torch.float32, "float64": torch.float64}
+# flat device columns of these dtypes go out as INT32 annotated INTEGER{8 | 16} / as BOOLEAN
+_NARROW_OF = {torch.int8: np.dtype("int8"), torch.int16: np.dtype("int16"), torch.bool: np.dtype(bool)}
 
 
 class _Column(NamedTuple):
@@ -78,6 +81,7 @@ class _HostColumn(NamedTuple):
     values: Any          # the non-null values / leaves (pinned; may still be in flight), or a DictPages
     valid: Any           # None, the rows' validity bitmap (uint8 array) or a list column's ListLevels
     logical: Any
+    dtype: Any = None    # the file's dtype where the values' is not it (int8 / int16: the values are int32)
 
 
 class _RowGroup(NamedTuple):
@@ -99,13 +103,14 @@ def _string_table(name, col, dtypes, tables):
 
 
 def plain_eligible(frame, dtypes, tables=None) -> bool:
-    """Every column a flat int32 / int64 / float32 / float64 device column (after the requested
-    casts), a datetime column in ms / us / ns, a flat string column on the device whose dict holds
+    """Every column a flat int32 / int64 / float32 / float64 column (after the requested
+    casts), a flat int8 / int16 / bool column on the device without a ``dtypes`` entry, a datetime column in ms / us / ns, a flat string column on the device whose dict holds
     only ``str`` values, or a list column on the device whose leaves are
     int32 / int64 / float32 / float64 numbers: the hand-written PLAIN writer takes the partition;
     anything else (datetime64[s] too: parquet has no seconds unit; lists of strings, string columns
-    on the host, with a ``dtypes`` entry or with bytes / mixed objects in their dict, bool and
-    8 / 16-bit leaves; a cast of a list column) goes to pyarrow.  ``tables``: the StringTables of the
+    on the host, with a ``dtypes`` entry or with bytes / mixed objects in their dict, lists of bool and
+    8 / 16-bit leaves, uint8, narrow columns on the host; a cast of a list column or to a narrow type)
+    goes to pyarrow.  ``tables``: the StringTables of the
     to_parquet call (the entry table built for this verdict is the one the write uses)."""
     if len(frame.columns) == 0:
         return False
@@ -113,6 +118,13 @@ def plain_eligible(frame, dtypes, tables=None) -> bool:
     for name, col in frame.items():
         if col.strings is not None:
             if _string_table(name, col, dtypes, tables) is None:
+                return False
+            continue
+        if col.data.dtype in _NARROW_OF:
+            # int8 / int16 / bool: flat, on the device, as they are (a dtypes= cast stays with pyarrow,
+            # whose safe cast raises on overflow)
+            if col.offsets is not None or not col.data.is_cuda or col.logical is not None or \
+                    (dtypes and name in dtypes):
                 return False
             continue
         if col.data.dtype not in _TORCH_OF.values():
@@ -135,7 +147,7 @@ def _dict_eligible(col, dtypes, name) -> bool:
         return bool(col.data.is_cuda)
     dt = np.dtype(dtypes[name]) if (dtypes and name in dtypes) else None
     is_int = (dt in (np.dtype("int32"), np.dtype("int64"))) if dt is not None else \
-        col.data.dtype in (torch.int32, torch.int64)
+        col.data.dtype in (torch.int32, torch.int64, torch.int8, torch.int16)
     return bool(is_int and col.strings is None and col.data.is_cuda)
 
 
@@ -203,7 +215,7 @@ def _prepare(part, n, dtypes, offered=frozenset(), tables=None):
             data = data.to(_TORCH_OF[str(np.dtype(dtypes[name]))])
         mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
         cols.append(_Column(name, data, mask, col.logical, offered=name in offered and data.is_cuda and
-                            data.dtype in (torch.int32, torch.int64)))
+                            data.dtype in (torch.int32, torch.int64, torch.int8, torch.int16)))
     return cols, list(groups.values())
 
 
@@ -276,10 +288,40 @@ def _page_start(vals, valid, m, rows, page_rows=None):
     return torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
 
 
-def _stage_column(c: _Column, vals, valid, encoded, statistics, keep):
+def _file_dtype(c: _Column):
+    """int8 / int16 of a narrow column (its values travel as int32), else None."""
+    return _NARROW_OF.get(c.data.dtype) if c.data.dtype in (torch.int8, torch.int16) else None
+
+
+def _widen_narrow(cols, staged, rows, keep):
+    """The narrow columns of a row group behind the compaction: the non-null values of ALL int8 / int16
+    columns become int32 in one launch (from here on their chunks are int32 chunks: dictionary, snappy
+    and statistics see nothing else), the non-null values of every bool column the bytes of its BOOLEAN
+    pages.  -> (staged with the widened values, {column index: packed bytes on the device})."""
+    narrow = [ci for ci, c in enumerate(cols) if _file_dtype(c) is not None and staged[ci][0].is_cuda]
+    wide = KPN.widen_many([staged[ci][0].contiguous() for ci in narrow])
+    staged = list(staged)
+    for ci, w in zip(narrow, wide):
+        keep.append(staged[ci][0])
+        staged[ci] = (w,) + tuple(staged[ci][1:])
+    bools = {}
+    for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)):
+        if c.data.dtype == torch.bool and c.offsets is None and vals.is_cuda:
+            vals = vals.contiguous()
+            bools[ci] = KPN.bool_pack(vals, _page_start(vals, valid, m, rows))
+    return staged, bools
+
+
+def _stage_column(c: _Column, vals, valid, encoded, statistics, keep, packed=None):
     """One column of a row group on its way to the host -> (_HostColumn, min / max or None).
-    ``encoded``: None, or (DeviceDict, d, overflow, page starts) of an offered column after the read-back."""
+    ``encoded``: None, or (DeviceDict, d, overflow, page starts) of an offered column after the read-back.
+    ``packed``: the bytes of a bool chunk's pages on the device (``_widen_narrow``)."""
     hv = None
+    if packed is not None:   # (a bool chunk: a null count, no min / max)
+        hp = _to_host(packed)   # (ceil(nv / 8) + pages bytes: the bound; the host lays the pages out from the bitmap)
+        hb = _to_host(valid).numpy() if valid is not None else None
+        keep.append((vals, valid, packed, hp))
+        return _HostColumn(c.name, BoolPages(hp.numpy(), int(vals.numel())), hb, None), None
     if encoded is not None:
         dd, d, overflow, ps = encoded
         nv = np.diff(ps)
@@ -293,7 +335,7 @@ def _stage_column(c: _Column, vals, valid, encoded, statistics, keep):
     hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
     mm = _min_max(vals) if statistics else None
     keep.append((vals, valid, mm, hv))
-    return _HostColumn(c.name, hv, hb, c.logical), (mm.numpy() if mm is not None else None)
+    return _HostColumn(c.name, hv, hb, c.logical, _file_dtype(c)), (mm.numpy() if mm is not None else None)
 
 
 class _StrChunk:
@@ -375,7 +417,7 @@ def _snappy_geometry(rows, page_rows, nulls, levels):
     return [(b - a, PP.flat_level_bytes(b - a, nulls)) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
-def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep):
+def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep, bools):
     """``device_compression="snappy"``: every chunk of the row group in the form it takes (after
     ``dict_pays``) -> ([_HostColumn], [min / max or None]).  Plan, compress and gather are enqueued for
     the values regions of ALL chunks at once (a dictionary chunk: its dictionary page), ONE read-back
@@ -399,7 +441,7 @@ def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep):
                 plan = dict(kind="plain", geo=geo, raw=np.diff(sc.page_at_host), region=KS.Region(form[1], sc.page_at, 1, 4))
             else:
                 continue
-        elif not vals.numel() or not vals.is_cuda:
+        elif not vals.numel() or not vals.is_cuda or ci in bools:   # (bool chunks are written uncompressed)
             continue
         else:
             size = vals.element_size()
@@ -466,12 +508,13 @@ def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep):
                 hc = _HostColumn(sc.col.name, hv, hb, None)
             mm = None   # (no min / max for string chunks)
         elif hv is None:
-            hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep)
+            hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep,
+                                   bools.get(ci))
         else:
             hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
             mm = _min_max(vals) if statistics else None
             keep.append((vals, valid, mm, hv))
-            hc, mm = _HostColumn(c.name, hv, hb, c.logical), (mm.numpy() if mm is not None else None)
+            hc, mm = _HostColumn(c.name, hv, hb, c.logical, _file_dtype(c)), (mm.numpy() if mm is not None else None)
         host.append(hc)
         stats.append(mm)
     return host, stats
@@ -511,6 +554,7 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) 
     with torch.cuda.stream(copy_s) if copy_s is not None else nullcontext():
         levels = _pack_levels(groups, s0, s1, keep) if (s1 > s0 and groups) else {}
         staged = [_column_values(c, s0, s1, levels) for c in cols]
+        staged, bools = _widen_narrow(cols, staged, s1 - s0, keep)
         # string columns: entry ids and the byte plan of every one of them (no read-back of their own)
         t_ss = time.perf_counter()
         strs = _plan_strings(cols, staged, s1 - s0)
@@ -535,7 +579,7 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) 
         t_ss = time.perf_counter()
         if snappy:
             # snappy pages: plan + compress + gather of every chunk in the form it takes, ONE read-back
-            host, mms = _stage_snappy(cols, staged, strs, dicts, states, s1 - s0, statistics, keep)
+            host, mms = _stage_snappy(cols, staged, strs, dicts, states, s1 - s0, statistics, keep, bools)
             stats = mms if statistics else None
             LAST_TIMING["snappy_s"] += time.perf_counter() - t_ss
             staged = []   # (every column is staged)
@@ -547,7 +591,7 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) 
                 hc, mm = hosts[ci], None   # (no min / max for string chunks)
             else:
                 hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics,
-                                       keep)
+                                       keep, bools.get(ci))
             host.append(hc)
             if statistics:
                 stats.append(mm)
@@ -578,7 +622,7 @@ class _PartFiles:
         ready = rg.event.synchronize if rg.event is not None else None
         t1 = time.perf_counter()
         LAST_TIMING["wait_copy_s"] += t1 - t0
-        schema = ([c.name for c in rg.columns], [c.values.dtype for c in rg.columns],
+        schema = ([c.name for c in rg.columns], [c.dtype if c.dtype is not None else c.values.dtype for c in rg.columns],
                   [c.logical for c in rg.columns], [isinstance(c.valid, ListLevels) for c in rg.columns])
         w = self.writers.get(rg.file)
         if w is None:
