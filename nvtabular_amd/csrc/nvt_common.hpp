@@ -47,6 +47,8 @@ inline unsigned stream_grid(uint64_t work_items, unsigned per_block, unsigned bl
 
 // workspace layouts: every block starts on a 16-byte boundary
 inline uint64_t pad16(uint64_t x) { return (x + 15) & ~15ull; }
+// ... or, in the groupby family, on a 256-byte boundary
+inline uint64_t pad256(uint64_t x) { return (x + 255) & ~255ull; }
 
 // ---- hashing ---------------------------------------------------------------
 // Public hash: murmur3 fmix64 of the sign-extended key.

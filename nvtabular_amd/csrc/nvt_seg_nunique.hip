@@ -150,8 +150,6 @@ __global__ __launch_bounds__(kBlock) void nu_count_kernel(const uint64_t *__rest
   if (c_g != kNone && lane == 0 && c_cnt) atomicAdd(&out[c_g], (unsigned long long)c_cnt);
 }
 
-static uint64_t nu_pad(uint64_t x) { return (x + 255) & ~255ull; }
-
 // key bits of a dtype's image, 0 = unknown dtype
 static int nu_key_bits(int dtype) {
   switch (dtype) {
@@ -171,7 +169,7 @@ extern "C" {
 int nvt_seg_nunique_ws_bytes(uint64_t n, uint64_t *bytes) {
   NVT_CHECK_ARG(bytes, "null out");
   // key[n] u64 | gid[n] u32 | sort words[n] u64 | radix sort scratch
-  *bytes = 2 * nu_pad(n * 8) + nu_pad(n * 4) + sort_words_tmp_bytes(n) + 512;
+  *bytes = 2 * pad256(n * 8) + pad256(n * 4) + sort_words_tmp_bytes(n) + 512;
   return NVT_OK;
 }
 
@@ -194,11 +192,11 @@ int nvt_seg_nunique(const uint64_t *words, uint64_t n, uint64_t ngroups, const v
   NVT_PROF("groupby_nunique", 0, s);
   char *p = reinterpret_cast<char *>(ws);
   uint64_t *key = reinterpret_cast<uint64_t *>(p);
-  p += nu_pad(n * 8);
+  p += pad256(n * 8);
   uint64_t *sort_words = reinterpret_cast<uint64_t *>(p);
-  p += nu_pad(n * 8);
+  p += pad256(n * 8);
   uint32_t *gid = reinterpret_cast<uint32_t *>(p);
-  p += nu_pad(n * 4);
+  p += pad256(n * 4);
   void *sort_tmp = p;
   int gid_bits = 1;
   while ((1ull << gid_bits) <= ngroups) ++gid_bits;  // ids 0..ngroups (ngroups = null marker)

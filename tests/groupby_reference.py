@@ -1,7 +1,8 @@
 """Plain numpy references of what csrc/nvt_groupby.hip computes for ``K.GroupbyTable`` (the hash-table
-groupby of 1..3 int64 key columns: update, merge, compact, index_build, lookup), ``K.order_rows``
-(sort-key images + stable radix refinement) and ``K.seg_aggregate`` (segmented reduction over rows
-ordered by group), for the kernel-level tests of test_gpu_groupby_kernels.py.
+groupby of 1..3 int64 key columns: update, merge, compact, index_build, lookup), csrc/nvt_order_rows.hip
+for ``K.order_rows`` (sort-key images + stable radix refinement) and csrc/nvt_segreduce.hip for
+``K.seg_aggregate`` (segmented reduction over rows ordered by group), for the kernel-level tests of
+test_gpu_groupby_kernels.py.
 test_groupby_reference.py pins them to pandas on the CPU.  Nothing here shares code with the
 device side: grouping is ``np.lexsort`` + ``ufunc.reduceat`` in float64, orders are value ranks
 from ``np.unique`` fed to a stable ``np.argsort`` (never a bit image of the value).

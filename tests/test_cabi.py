@@ -259,6 +259,52 @@ def test_count_workspace_sizes_are_unchanged(key_bytes, path, weighted):
         assert nbytes.value == want, (n, nbytes.value, want)
 
 
+_GB_WS_N = (1, 4095, 4096, 4097, 32768, 1 << 20, (1 << 26) - 1)
+# read from the library of the commit before the split of nvt_groupby.hip into four units
+_GB_WS_BYTES = {
+    "nvt_gb_update_ws_bytes": (8406064, 8504080, 8504096, 8512560, 9249568, 35660576, 1753228048),
+    "nvt_order_rows_ws_bytes": (8406064, 8504080, 8504096, 8512560, 9249568, 35660576, 1753228048),
+    "nvt_sgb_sort_ws_bytes": (8406272, 8504320, 8504320, 8512768, 9249792, 35660800, 1753228288),
+    "nvt_sgb_regroup_ws_bytes": (512, 512, 512, 512, 512, 2560, 131584),
+    "nvt_count_merge_sorted_ws_bytes": (8407040, 8553728, 8553728, 8562688, 9643264, 48246016, 2558665984),
+}
+# (nkeys, nvals, flags) -> bytes at capacity 64 and 1 << 20; flags 3 = NVT_GB_SUMSQ | NVT_GB_MINMAX
+_GB_TABLE_BYTES = {
+    (1, 0, 0): (2560, 33554944),
+    (1, 1, 0): (3072, 41943552),
+    (3, 8, 3): (19968, 318767616),
+    (2, 0, 3): (3072, 41943552),
+}
+
+
+def test_groupby_workspace_sizes_are_unchanged():
+    """The workspaces and the table block of the groupby family, byte for byte what the unsplit
+    nvt_groupby.hip asked for; the shapes and the short block a table refuses."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    lib = _lib.load()
+    assert (_lib.NVT_GB_SUMSQ | _lib.NVT_GB_MINMAX) == 3
+    nbytes = C.c_uint64()
+    for name, wants in sorted(_GB_WS_BYTES.items()):
+        for n, want in zip(_GB_WS_N, wants):
+            assert getattr(lib, name)(n, C.byref(nbytes)) == 0, (name, n, lib.nvt_last_error())
+            assert nbytes.value == want, (name, n, nbytes.value, want)
+    for (nkeys, nvals, flags), wants in sorted(_GB_TABLE_BYTES.items()):
+        for capacity, want in zip((64, 1 << 20), wants):
+            assert lib.nvt_gb_table_bytes(nkeys, nvals, flags, capacity, C.byref(nbytes)) == 0
+            assert nbytes.value == want, (nkeys, nvals, flags, capacity, nbytes.value, want)
+    for nkeys, nvals in ((0, 0), (4, 0), (1, 9)):
+        assert lib.nvt_gb_table_bytes(nkeys, nvals, 0, 64, C.byref(nbytes)) == _lib.NVT_EINVAL, (nkeys, nvals)
+    # a block one byte short (host memory: the refusal comes before anything touches it)
+    want = _GB_TABLE_BYTES[1, 1, 0][0]
+    raw = (C.c_uint8 * want)()
+    handle = C.c_void_p()
+    assert lib.nvt_gb_create_in(1, 1, 0, 64, C.addressof(raw), want - 1, C.byref(handle)) == _lib.NVT_EINVAL
+    assert b"too small" in lib.nvt_last_error() and not handle.value
+
+
 def test_count_workspace_refuses_the_paths_the_launch_refuses():
     import ctypes as C
 

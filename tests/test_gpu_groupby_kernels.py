@@ -1,6 +1,7 @@
-"""Kernel-level matrix for csrc/nvt_groupby.hip: ``K.GroupbyTable`` (the hash-table groupby of
-JoinGroupby / TargetEncoding / Groupby), ``K.order_rows`` and ``K.seg_aggregate`` (the Groupby
-operator) called directly on torch tensors and compared with the numpy references of
+"""Kernel-level matrix for csrc/nvt_groupby.hip, nvt_order_rows.hip and nvt_segreduce.hip:
+``K.GroupbyTable`` (the hash-table groupby of JoinGroupby / TargetEncoding / Groupby),
+``K.order_rows`` and ``K.seg_aggregate`` (the Groupby operator) called directly on torch tensors
+and compared with the numpy references of
 groupby_reference.py, which test_groupby_reference.py pins to pandas on the CPU.  Every comparison
 is exact, except the two general-value cases at the end of the table and the segmented-reduce
 sections: those use the summation bound (m - 1) * 2^-53 * sum(|v|) and nothing else.
@@ -15,6 +16,8 @@ Helper -> kernels reached:
                         path it means and the helper asserts it from n against SWITCH = 1 << 15.
                         nvt_gb_compact: gb_compact_kernel.  nvt_gb_lookup on the compacted table:
                         gb_lookup_kernel (find_slot without insert, head.index)
+    own block           nvt_gb_create (one block for the arrays) and the table-owned scratch of
+                        nvt_gb_update, grown on demand: test_table_with_its_own_block_and_scratch
     merged(...)         nvt_gb_merge: gb_merge_kernel
     index + lookup      nvt_gb_index_build: gb_clear_kernel + gb_index_build_kernel; gb_lookup_kernel
     dev_order(...)      nvt_sort_key_u64: sort_key_kernel<float | double | int32 | int64 | uint8>
@@ -24,7 +27,7 @@ Helper -> kernels reached:
     dev_seg(...)        nvt_seg_aggregate: gb_segreduce_kernel<false, SQ, MM> with a per-column
                         value count (GbView::vcount) and no table behind it
 
-Sizes, from the constants of the .hip file.  nvt_gb_update switches paths at n == 1 << 15: 32 767
+Sizes, from the constants of the .hip files.  nvt_gb_update switches paths at n == 1 << 15: 32 767
 is the last per-row size, 32 768 the first sorted one.  gb_segreduce_kernel: the launch is
 stream_grid(n, kBlock * 4 = 1024, 8), at most 256 CUs * 8 = 2048 workgroups of 4 waves, and each
 wave walks roundup64(ceil(n / nwaves)) words in rows of kWave = 64, U = 4 rows (256 words) per
@@ -367,6 +370,65 @@ def test_updates_of_both_paths_accumulate_in_one_table(K, order):
     one = R.table_groups(*parts[1][:4], sumsq=True, minmax=True)
     _, got = compacted(K, t, f"{order} after clear", rows=parts[1][0][0].size, groups=one["n"])
     R.assert_same_groups(got, one, f"{order} after clear")
+
+
+def test_table_with_its_own_block_and_scratch(K):
+    """nvt_gb_create and no nvt_gb_set_workspace: the table allocates its arrays as one block and
+    the sort path's scratch itself (K.GroupbyTable never does: nvt_gb_create_in and a torch
+    workspace).  nkeys 2, nvals 1, sumsq and min / max, capacity 65 536; keys from about 3000
+    tuples.  Updates of 32 768 rows (the smallest sort-path n: the scratch is allocated, a quarter
+    over what this n needs), of 100 003 rows and of 150 001 rows, then compact and destroy.  The
+    100 003 rows fit into the first buffer (11.0 MB needed, 11.6 MB there); the 150 001 need
+    12.3 MB, so that update frees the buffer and grows a new one.  The sizes are asserted below
+    from nvt_gb_update_ws_bytes, which is what nvt_gb_update needs (the unsplit unit needed 256
+    bytes less of each)."""
+    import ctypes as C
+
+    from nvtabular_amd import _lib
+
+    sizes = [SWITCH, 100_003, 150_001]
+    lib = _lib.load()
+    ws = C.c_uint64()
+    need = []
+    for m in sizes:
+        assert lib.nvt_gb_update_ws_bytes(m, C.byref(ws)) == 0
+        need.append(ws.value)
+    grown = need[0] + need[0] // 4
+    assert need[1] + 4096 < grown < need[2] - 4096, (need, grown)
+    n = sum(sizes)
+    rng = np.random.default_rng(seed_of("own block"))
+    ids = rng.integers(I64.min, I64.max, 1000, dtype=np.int64)
+    keys = [ids[(rng.random(n) ** 3 * 1000).astype(np.int64)], rng.integers(-1, 2, n)]
+    kvalid = [rng.random(n) >= 0.1, None]
+    vals, vvalid = value_columns(rng, n, 1, keys)
+    exp = R.table_groups(keys, kvalid, vals, vvalid, sumsq=True, minmax=True)
+    assert_exact(vals, int(exp["size"].max()))
+    assert 2000 < exp["n"] < 6000, exp["n"]
+    # a GroupbyTable around the handle of nvt_gb_create: state(), compact() and lookup() as usual
+    t = K.GroupbyTable.__new__(K.GroupbyTable)
+    t.lib, t.nkeys, t.nvals, t.capacity, t._mem, t._ws = lib, 2, 1, 65536, None, None
+    t.flags = _lib.NVT_GB_SUMSQ | _lib.NVT_GB_MINMAX
+    t.device = torch.device("cuda", torch.cuda.current_device())
+    t.handle = C.c_void_p()
+    _lib.check(lib.nvt_gb_create(2, 1, t.flags, t.capacity, C.byref(t.handle)), "nvt_gb_create")
+    t.clear()
+    lo = 0
+    for m in sizes:
+        s = slice(lo, lo + m)
+        k = [dev(c[s]) for c in keys]
+        kv, v = bitmap(kvalid[0][s]), dev(vals[0][s])
+        _lib.check(lib.nvt_gb_update(t.handle, _lib.ptr_array([c.data_ptr() for c in k]),
+                                     _lib.ptr_array([kv.data_ptr(), None]), _lib.ptr_array([v.data_ptr()]),
+                                     (C.c_int * 1)(K.dtype_code(v.dtype)), _lib.ptr_array([None]), m,
+                                     K.stream_ptr()), "nvt_gb_update")
+        torch.cuda.current_stream().synchronize()     # the columns of this part go away
+        lo += m
+    comp, got = compacted(K, t, "own block", rows=n, groups=exp["n"])
+    R.assert_same_groups(got, exp, "own block")
+    rows_find_their_group(K, t, comp, keys, kvalid, "own block")
+    torch.cuda.current_stream().synchronize()
+    lib.nvt_gb_destroy(t.handle)
+    t.handle = None
 
 
 def merged(K, comps, nkeys, nvals, sumsq, minmax, capacity, what, drop=()):
