@@ -1157,8 +1157,52 @@ int nvt_str_gather(const int64_t *strs, uint64_t m, const void *offsets, int off
  * nvt_compact_list_offsets: the m + 1 new offsets (from 0) of a list column whose leaves were
  *   compacted with leaf_plan (n_leaves = 0: every list is empty and leaf_plan may be NULL).
  * Every entry is stream-ordered and does not synchronise; n = 0 is a no-op.  Nothing is read back:
- * the caller sizes the outputs from *out_m. */
+ * the caller sizes the outputs from *out_m.
+ *
+ * nvt_compact_keep_terms (Dataset(filters=...)) is a keep-mask producer like the two of step 1, in
+ * ONE launch and without global atomics: it writes the plan's mask words (bits past n zero) and the
+ * tile counts from a predicate in disjunctive normal form.  `terms` are 1 to NVT_FILTER_MAX_TERMS
+ * comparisons sorted by `conj` (non-decreasing, from 0); a row is kept iff in some conjunction
+ * every term holds.  A term names one of the 1 to NVT_FILTER_MAX_COLS columns (`col`), whose
+ * dtype is NVT_F32 .. NVT_I16 (a bool column is NVT_U8): a float column is widened to double and
+ * compared with value.f, an integer column to int64 and compared with value.i (string surrogates
+ * and datetime counts are int64 columns).  NVT_FILTER_IN / NVT_FILTER_NOT_IN bisect the run
+ * sets[set_off, set_off + set_len) of 8-byte words (int64, or double bit patterns for a float
+ * column), ascending and distinct, -0.0 stored as 0.0; set_len = 0 is legal (`in` keeps nothing).
+ * A null (bitmap bit 0) fails every term but NVT_FILTER_NOT_IN, which it passes; a NaN fails
+ * every comparison but NVT_FILTER_NE and is in no set; -0.0 == 0.0.  Adjacent terms on one column
+ * share the load of its value.  Refused with NVT_EINVAL before the launch: null descriptors, ncols /
+ * nterms out of range, a dtype, op or col out of range, an x that is null or not aligned to its
+ * dtype, terms not sorted by conj, a set run past set_words, n >= 2^32 - 2048, a null, misaligned
+ * or short workspace. */
 #define NVT_COMPACT_MAX_COLS 64
+#define NVT_FILTER_MAX_COLS 16
+#define NVT_FILTER_MAX_TERMS 64
+#define NVT_FILTER_EQ 0
+#define NVT_FILTER_NE 1
+#define NVT_FILTER_LT 2
+#define NVT_FILTER_LE 3
+#define NVT_FILTER_GT 4
+#define NVT_FILTER_GE 5
+#define NVT_FILTER_IN 6
+#define NVT_FILTER_NOT_IN 7
+typedef struct nvt_filter_col {
+  const void *x;            /* n values, aligned to their width                 */
+  const uint8_t *valid;     /* bitmap or NULL                                   */
+  int32_t dtype;            /* NVT_F32 .. NVT_I16                               */
+  int32_t reserved;
+} nvt_filter_col;
+typedef struct nvt_filter_term {
+  int32_t col;              /* index into the column descriptors                */
+  int32_t op;               /* NVT_FILTER_EQ .. NVT_FILTER_NOT_IN               */
+  int32_t conj;             /* the conjunction this term belongs to             */
+  int32_t set_len;          /* IN / NOT_IN: words of the run                    */
+  uint64_t set_off;         /* IN / NOT_IN: first word of the run in `sets`     */
+  union {
+    int64_t i;              /* the constant of an integer column                */
+    double f;               /* the constant of a float column                   */
+  } value;
+} nvt_filter_term;
 typedef struct nvt_dropna_col {
   const void *x;            /* values (read for NVT_F32 / NVT_F64 only)         */
   const uint8_t *valid;     /* bitmap or NULL                                   */
@@ -1179,6 +1223,9 @@ int nvt_compact_ws_bytes(uint64_t n, uint64_t *bytes);
 int nvt_compact_keep_mask(const uint8_t *mask, uint64_t n, void *ws, uint64_t ws_bytes, void *stream);
 int nvt_compact_keep_dropna(const nvt_dropna_col *cols, int ncols, uint64_t n, void *ws, uint64_t ws_bytes,
                             void *stream);
+int nvt_compact_keep_terms(const nvt_filter_col *cols, int ncols, const nvt_filter_term *terms, int nterms,
+                           const void *sets, uint64_t set_words, uint64_t n, void *ws, uint64_t ws_bytes,
+                           void *stream);
 int nvt_compact_list_keep(const int64_t *offsets, uint64_t n, const void *row_plan, uint64_t n_leaves,
                           void *leaf_ws, uint64_t leaf_ws_bytes, void *stream);
 int nvt_compact_plan(uint64_t n, void *ws, uint64_t ws_bytes, uint64_t *out_m, void *stream);

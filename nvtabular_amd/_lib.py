@@ -272,8 +272,28 @@ class CompactCol(C.Structure):
                 ("n", _u64), ("width", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FilterCol(C.Structure):
+    """nvt_filter_col: one column read by nvt_compact_keep_terms."""
+    _fields_ = [("x", _vp), ("valid", _vp), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FilterValue(C.Union):
+    _fields_ = [("i", C.c_int64), ("f", C.c_double)]
+
+
+class FilterTerm(C.Structure):
+    """nvt_filter_term: one comparison of nvt_compact_keep_terms."""
+    _fields_ = [("col", C.c_int32), ("op", C.c_int32), ("conj", C.c_int32), ("set_len", C.c_int32),
+                ("set_off", _u64), ("value", FilterValue)]
+
+
 COMPACT_MAX_COLS = 64   # include/nvt_hip.h NVT_COMPACT_MAX_COLS
+FILTER_MAX_COLS, FILTER_MAX_TERMS = 16, 64   # NVT_FILTER_MAX_COLS, NVT_FILTER_MAX_TERMS
+# NVT_FILTER_EQ .. NVT_FILTER_NOT_IN
+FILTER_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "in": 6, "not in": 7}
 SIGNATURES.update({
+    "nvt_compact_keep_terms": [C.POINTER(FilterCol), _i32, C.POINTER(FilterTerm), _i32, _vp, _u64, _u64, _vp, _u64,
+                               _vp],
     "nvt_compact_ws_bytes": [_u64, C.POINTER(_u64)],
     "nvt_compact_keep_mask": [_vp, _u64, _vp, _u64, _vp],
     "nvt_compact_keep_dropna": [C.POINTER(DropnaCol), _i32, _u64, _vp, _u64, _vp],

@@ -6,7 +6,8 @@
 //   base   uint32[ntiles + 1]    kept rows per tile; after nvt_compact_plan the exclusive scan of
 //                                them: tile t's kept rows go to [base[t], base[t + 1]), base[ntiles] = m
 //   chunk  uint64[...]           the scan's chunk totals (nvt_scan.hpp)
-// The producers (a bool mask, the null test of Dropna, the leaf expansion of a list column) write
+// The producers (a bool mask, the null test of Dropna, the terms of a Dataset filter, the leaf
+// expansion of a list column) write
 // the words and the per-tile counts in one pass; the scan has no inter-workgroup waits and the data
 // path no global atomics except the two boundary words of a tile's validity run, which are merged
 // with atomicOr into a bitmap zeroed first (OR does not depend on the order: the bits come out the
@@ -127,6 +128,95 @@ __global__ __launch_bounds__(kBlock) void keep_dropna_kernel(NaBatch b, uint64_t
       if (c.dtype == NVT_F64 && is_nan(((const double *)c.x)[row])) return false;
     }
     return true;
+  });
+}
+
+// Dataset(filters=): a row is kept iff in some conjunction every term holds.  The descriptors are
+// kernel arguments (scalar loads: the term loop is uniform); the row's value lives in two scalars,
+// reloaded only when a term names another column than the term before it, so terms on one column
+// share a load.  A conjunction no lane of the wave still satisfies skips its remaining terms.
+struct FCol {
+  const void *x;
+  const uint8_t *valid;
+  int dtype;
+};
+struct FTerm {
+  int col, op, conj, set_len;
+  uint64_t set_off;
+  union {
+    int64_t i;
+    double f;
+  } value;
+};
+struct FBatch {
+  FCol c[NVT_FILTER_MAX_COLS];
+  FTerm t[NVT_FILTER_MAX_TERMS];
+  const uint64_t *sets;
+  int nterms;
+};
+
+template <typename T>
+__device__ __forceinline__ bool term_holds(const FTerm &t, const uint64_t *__restrict__ sets, T v, T c) {
+  switch (t.op) {
+    case NVT_FILTER_EQ: return v == c;
+    case NVT_FILTER_NE: return v != c;
+    case NVT_FILTER_LT: return v < c;
+    case NVT_FILTER_LE: return v <= c;
+    case NVT_FILTER_GT: return v > c;
+    case NVT_FILTER_GE: return v >= c;
+    default: {  // NVT_FILTER_IN / NVT_FILTER_NOT_IN: the lower bound of v in the term's sorted run
+      const T *s = reinterpret_cast<const T *>(sets + t.set_off);
+      int lo = 0, len = t.set_len;
+      while (len > 0) {
+        const int half = len >> 1;
+        if (s[lo + half] < v) {
+          lo += half + 1;
+          len -= half + 1;
+        } else {
+          len = half;
+        }
+      }
+      const bool in = lo < t.set_len && s[lo] == v;  // (a NaN is below nothing and equals nothing)
+      return in == (t.op == NVT_FILTER_IN);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void keep_terms_kernel(FBatch b, uint64_t n, Plan p) {
+  produce_tiles(n, p, false, [&](uint64_t row) {
+    bool any = false, acc = false;
+    int conj = -1, loaded = -1;
+    int64_t vi = 0;
+    double vf = 0.0;
+    bool ok = false, flt = false;
+    for (int k = 0; k < b.nterms; ++k) {
+      const FTerm &t = b.t[k];
+      if (t.conj != conj) {
+        any |= acc;
+        acc = true;
+        conj = t.conj;
+      }
+      if (__ballot(acc) == 0) continue;  // (uniform over the lanes that are rows)
+      if (t.col != loaded) {
+        const FCol &c = b.c[t.col];
+        loaded = t.col;
+        ok = bit_valid(c.valid, row);
+        flt = c.dtype == NVT_F32 || c.dtype == NVT_F64;
+        switch (c.dtype) {
+          case NVT_F32: vf = (double)((const float *)c.x)[row]; break;
+          case NVT_F64: vf = ((const double *)c.x)[row]; break;
+          case NVT_I32: vi = ((const int32_t *)c.x)[row]; break;
+          case NVT_I64: vi = ((const int64_t *)c.x)[row]; break;
+          case NVT_U8: vi = ((const uint8_t *)c.x)[row]; break;
+          case NVT_I8: vi = ((const int8_t *)c.x)[row]; break;
+          default: vi = ((const int16_t *)c.x)[row]; break;  // NVT_I16
+        }
+      }
+      bool holds = t.op == NVT_FILTER_NOT_IN;  // a null fails every term but `not in`
+      if (ok) holds = flt ? term_holds<double>(t, b.sets, vf, t.value.f) : term_holds<int64_t>(t, b.sets, vi, t.value.i);
+      acc = acc && holds;
+    }
+    return any || acc;
   });
 }
 
@@ -386,6 +476,60 @@ int nvt_compact_keep_dropna(const nvt_dropna_col *cols, int ncols, uint64_t n, v
     keep_dropna_kernel<<<tile_grid(p.ntiles), kBlock, 0, s>>>(b, n, p, i0 > 0);
     NVT_CHECK_LAUNCH();
   }
+  return NVT_OK;
+}
+
+int nvt_compact_keep_terms(const nvt_filter_col *cols, int ncols, const nvt_filter_term *terms, int nterms,
+                           const void *sets, uint64_t set_words, uint64_t n, void *ws, uint64_t ws_bytes,
+                           void *stream) {
+  NVT_CHECK_ARG(cols && terms, "null descriptors");
+  NVT_CHECK_ARG(ncols >= 1 && ncols <= NVT_FILTER_MAX_COLS, "ncols must be 1 to NVT_FILTER_MAX_COLS");
+  NVT_CHECK_ARG(nterms >= 1 && nterms <= NVT_FILTER_MAX_TERMS, "nterms must be 1 to NVT_FILTER_MAX_TERMS");
+  NVT_CHECK_ARG(sets || set_words == 0, "null sets");
+  NVT_CHECK_ARG((reinterpret_cast<uintptr_t>(sets) & 7) == 0, "sets must be 8-byte aligned");
+  static const int kWidth[] = {4, 8, 4, 8, 1, 1, 2};  // NVT_F32 .. NVT_I16
+  uint64_t bytes = 0;
+  for (int j = 0; j < ncols; ++j) {
+    const nvt_filter_col &c = cols[j];
+    NVT_CHECK_ARG(c.dtype >= NVT_F32 && c.dtype <= NVT_I16, "unsupported dtype");
+    NVT_CHECK_ARG(c.x || n == 0, "null x");
+    NVT_CHECK_ARG((reinterpret_cast<uintptr_t>(c.x) & (kWidth[c.dtype] - 1)) == 0, "x must be aligned to its dtype");
+    bytes += n * kWidth[c.dtype] + (c.valid ? n / 8 : 0);
+  }
+  for (int k = 0; k < nterms; ++k) {
+    const nvt_filter_term &t = terms[k];
+    NVT_CHECK_ARG(t.col >= 0 && t.col < ncols, "a term's col is no descriptor");
+    NVT_CHECK_ARG(t.op >= NVT_FILTER_EQ && t.op <= NVT_FILTER_NOT_IN, "unknown op");
+    NVT_CHECK_ARG(t.conj >= 0 && (k == 0 || t.conj >= terms[k - 1].conj), "terms must be sorted by conj");
+    if (t.op == NVT_FILTER_IN || t.op == NVT_FILTER_NOT_IN) {
+      NVT_CHECK_ARG(t.set_len >= 0, "set_len must not be negative");
+      NVT_CHECK_ARG(t.set_off <= set_words && (uint64_t)t.set_len <= set_words - t.set_off,
+                    "set_off + set_len lies past set_words");
+    }
+  }
+  if (n == 0) return NVT_OK;
+  const int rc = check_ws(ws, ws_bytes, n);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const Plan p = plan_of(ws, n);
+  FBatch b;
+  memset(&b, 0, sizeof(b));
+  for (int j = 0; j < ncols; ++j) b.c[j] = FCol{cols[j].x, cols[j].valid, cols[j].dtype};
+  for (int k = 0; k < nterms; ++k) {
+    const nvt_filter_term &t = terms[k];
+    FTerm &d = b.t[k];
+    d.col = t.col;
+    d.op = t.op;
+    d.conj = t.conj;
+    d.set_len = t.set_len;
+    d.set_off = t.set_off;
+    d.value.i = t.value.i;
+  }
+  b.sets = reinterpret_cast<const uint64_t *>(sets);
+  b.nterms = nterms;
+  NVT_PROF("compact_keep_terms", bytes + p.ntiles * (kTile / 8 + 4), s);
+  keep_terms_kernel<<<tile_grid(p.ntiles), kBlock, 0, s>>>(b, n, p);
+  NVT_CHECK_LAUNCH();
   return NVT_OK;
 }
 

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import glob
 import os
+import threading
 from typing import Iterable, List, Optional
 
 import pandas as pd
@@ -20,9 +21,10 @@ from .device import DeviceFrame, as_device_frame
 from .parquet_plain import READER_CHUNKS, PlainParquetFile, StagedPartition, read_row_groups_staged
 from .kernels_parquet_str_out import StringTables
 from .parquet_write import LAST_TIMING, device_permutation, dictionary_columns, plain_eligible, write_plain  # noqa: F401
-from .schema import Schema
+from .schema import ColumnSchema, Schema
 
 
+_STATS_LOCK = threading.Lock()   # Dataset.filter_stats is updated from the prefetch thread
 DECODE_AHEAD = int(os.environ.get("NVT_DECODE_AHEAD", "3"))  # parquet partitions decoded concurrently ahead of the consumer
 
 
@@ -51,7 +53,7 @@ class Dataset:
     def __init__(self, path_or_source, engine=None, cpu=None, part_size=None,
                  part_mem_fraction=None, npartitions=None, names=None, schema=None,
                  row_groups_per_part=1, sep=",", header="infer", dtypes=None, quotechar='"', parse_dates=None,
-                 **kwargs):
+                 filters=None, **kwargs):
         """``engine``: "parquet", "csv" or None (a first file ending in .csv / .tsv / .txt selects
         csv; anything else is read as parquet).  ``sep``, ``names``, ``header``, ``dtypes``,
         ``part_size``, ``quotechar`` and ``parse_dates`` belong to the csv engine (csv_text.py):
@@ -63,13 +65,46 @@ class Dataset:
         are the pieces, in sorted walk order, and the key columns follow the files' columns in path
         order.  Their values come from the paths (``__HIVE_DEFAULT_PARTITION__`` is a null); their
         dtypes from ``_metadata.json`` (``partition_on``, as ``to_parquet`` records it), else int64
-        when every non-null segment of a key is ``-?[0-9]+`` and string otherwise."""
+        when every non-null segment of a key is ``-?[0-9]+`` and string otherwise.
+
+        ``filters``: ``None`` (default) reads every row.  A list of ``(column, op, value)`` tuples (one
+        conjunction) or a list of such lists (an OR of conjunctions) reads the rows that pass, with the
+        semantics of ``pyarrow.parquet.read_table(filters=...)`` (filters.py): ``op`` is ``==``, ``=``,
+        ``!=``, ``<``, ``<=``, ``>``, ``>=``, ``in`` or ``not in``; a null fails every comparison and
+        ``in`` and passes ``not in``; NaN fails every comparison but ``!=``; ``-0.0 == 0.0``; ``in []``
+        keeps nothing.  Integers, bools and datetimes compare exactly in int64, floats in float64: a
+        float32 column is widened, the constant is not narrowed.  ``in`` on a float column compares
+        every member as ``==`` in float64; pyarrow narrows the members to the column's type instead, so
+        the two agree for members that type represents exactly.  Integer columns take integers (and
+        floats of integral value), float columns ints and floats, bool columns ``True`` / ``False``,
+        string columns ``str`` with ``==``, ``!=``, ``in``, ``not in`` only, datetime columns
+        ``pandas.Timestamp`` / ``datetime.datetime`` / ``numpy.datetime64`` that are a whole count of the
+        column's unit; hive key columns are ordinary columns.  Everything is checked here, before a
+        file is read: a malformed filter, an unknown operator or column, more than 16 distinct columns
+        or 64 terms raise ``ValueError``, a list column or a constant of another kind ``TypeError``; a
+        callable source takes no filter.  Hive files whose path fails every conjunction are dropped
+        before their footer is opened, row groups whose min / max / null-count statistics prove that no
+        row passes are dropped from ``_pieces`` (``filter_stats`` counts both), and every partition
+        that is read is filtered on the device by one ``nvt_compact_keep_terms`` launch plus the
+        compaction (kernels_compact.filter_frame).  A partition that loses every row stays, with 0
+        rows.  The schema does not change."""
         self.cpu = bool(cpu)  # accepted for API compatibility; compute always runs on the GPU
         self.engine = engine
         self._schema = schema
         self._parts_fn = None
+        self._filter = None   # filters.Filter: applied to every partition where it becomes a DeviceFrame
+        self.filter_stats = None
+        dnf = None
+        if filters is not None:
+            from .filters import normalize
+
+            dnf = normalize(filters)
+            self.filter_stats = {"files_pruned": 0, "row_groups_pruned": 0, "row_groups_kept": 0,
+                                 "rows_in": 0, "rows_out": 0}
         src = path_or_source
         if callable(src):  # lazy partition generator (transformed datasets)
+            if dnf is not None:
+                raise ValueError("filters= needs a source with a schema up front; a callable source has none")
             self._parts_fn = src
             self._n = npartitions
         elif isinstance(src, (pd.DataFrame, DeviceFrame)) or _is_arrow_table(src):
@@ -79,7 +114,11 @@ class Dataset:
         elif _csv_engine(src, engine):
             self._init_csv(src, sep, names, header, dtypes, part_size, quotechar, parse_dates)
         else:
-            self._init_parquet(src, row_groups_per_part, names)
+            self._init_parquet(src, row_groups_per_part, names, dnf)
+        if dnf is not None and self._filter is None:
+            from .filters import validate
+
+            self._filter = validate(dnf, self.schema)
 
     # ---- sources ---------------------------------------------------------------
     def _init_frames(self, frames):
@@ -110,8 +149,10 @@ class Dataset:
 
         self._parts_fn = gen
 
-    def _init_parquet(self, paths, row_groups_per_part, names):
+    def _init_parquet(self, paths, row_groups_per_part, names, dnf=None):
         import pyarrow.parquet as pq
+
+        from . import filters as F
 
         if isinstance(paths, (str, os.PathLike)):
             paths = [str(paths)]
@@ -134,8 +175,40 @@ class Dataset:
                 files.append(p)
         if not files:
             raise FileNotFoundError(f"no parquet files under {paths}")
-        self._files = files
         self._hive = hive
+        alive = {}    # file -> the conjunctions its hive path leaves standing (filters only)
+        if dnf is not None and hive is not None:
+            # the key terms decide on the path alone: a file no conjunction survives is dropped
+            # before its footer is opened (the key columns' dtypes come from the layout)
+            import numpy as np
+
+            key_schema = Schema([ColumnSchema(k, object if dt == "string" else np.dtype(dt))
+                                 for k, dt in zip(hive.keys, hive.dtypes)])
+            on_keys = F.validate(dnf, key_schema, partial=True)
+            kept = []
+            for f in files:
+                typed = {k: F.segment_value(t, dt) for k, dt, t in zip(hive.keys, hive.dtypes, hive.values[f])}
+                alive[f] = on_keys.alive_on_keys(typed)
+                if alive[f]:
+                    kept.append(f)
+                else:
+                    self.filter_stats["files_pruned"] += 1
+            first_file = kept[0] if kept else files[0]
+            files = kept
+        else:
+            first_file = files[0]
+        self._files = files
+        if self._schema is None:
+            import numpy as np
+            import pyarrow as pa
+
+            file_schema = pq.ParquetFile(first_file).schema_arrow
+            if hive is not None:   # the key columns behind the files' columns, in path order
+                for name, dt in zip(hive.keys, hive.dtypes):
+                    file_schema = file_schema.append(pa.field(name, pa.string() if dt == "string" else
+                                                              pa.from_numpy_dtype(np.dtype(dt))))
+            self._schema = Schema.from_frame(file_schema)
+        flt = self._filter = F.validate(dnf, self.schema) if dnf is not None else None
         pieces = []
         for f in files:
             md = pq.ParquetFile(f)
@@ -143,21 +216,22 @@ class Dataset:
                 from .hive import check_clash
 
                 check_clash(hive.keys, md.schema_arrow.names, f)
-            ng = md.num_row_groups
-            for g0 in range(0, ng, row_groups_per_part):
-                pieces.append((f, list(range(g0, min(ng, g0 + row_groups_per_part)))))
+            groups = list(range(md.num_row_groups))
+            if flt is not None:
+                # row groups whose statistics prove that no row passes are never read
+                meta, fields = md.metadata, md.schema_arrow
+                columns = F.flat_columns(meta)
+                pruned = {g for g in groups if flt.prunes_row_group(meta.row_group(g), columns, fields, alive.get(f))}
+                self.filter_stats["row_groups_pruned"] += len(pruned)
+                self.filter_stats["row_groups_kept"] += len(groups) - len(pruned)
+            else:
+                pruned = ()
+            for g0 in range(0, len(groups), row_groups_per_part):
+                part = [g for g in groups[g0: g0 + row_groups_per_part] if g not in pruned]
+                if part:   # (a piece that loses all of its row groups disappears)
+                    pieces.append((f, part))
         self._pieces = pieces
         self._n = len(pieces)
-        if self._schema is None:
-            import numpy as np
-            import pyarrow as pa
-
-            file_schema = pq.ParquetFile(files[0]).schema_arrow
-            if hive is not None:   # the key columns behind the files' columns, in path order
-                for name, dt in zip(hive.keys, hive.dtypes):
-                    file_schema = file_schema.append(pa.field(name, pa.string() if dt == "string" else
-                                                              pa.from_numpy_dtype(np.dtype(dt))))
-            self._schema = Schema.from_frame(file_schema)
 
         # files the hand-written reader takes (flat numeric columns, three-level lists of such
         # leaves and flat string columns; PLAIN or dictionary-encoded values, uncompressed or snappy:
@@ -286,14 +360,33 @@ class Dataset:
         cols = list(columns) if columns is not None else None
         if prefetch is None:
             prefetch = hasattr(self, "_pieces")
+        read, post = cols, None
+        if self._filter is not None:
+            # a filter column the caller leaves out is read, and dropped after the filter
+            if cols is not None:
+                read = cols + [c for c in self._filter.columns if c not in cols]
+            post = self._filter_frame
         if not prefetch:
-            for part in self._host_parts(cols, shard):
+            for part in self._host_parts(read, shard):
                 frame, _ = as_device_frame(part)
+                if post is not None:
+                    frame = post(frame)
                 if cols is not None:
                     frame = frame[[c for c in cols if c in frame]]
                 yield frame
             return
-        yield from _prefetch_frames(self._host_parts(cols, shard), cols)
+        yield from _prefetch_frames(self._host_parts(read, shard), cols, post=post)
+
+    def _filter_frame(self, frame):
+        """The rows of one partition that pass ``filters=`` (every consumer gets its partitions through
+        here); ``filter_stats`` counts the rows in and out."""
+        from .kernels_compact import filter_frame
+
+        out = filter_frame(frame, self._filter)
+        with _STATS_LOCK:
+            self.filter_stats["rows_in"] += len(frame)
+            self.filter_stats["rows_out"] += len(out)
+        return out
 
     def to_ddf(self, columns=None, **_):
         return _Collection(self if columns is None else self._select(columns))
@@ -748,7 +841,9 @@ class Shuffle:
         raise ValueError(f"unknown shuffle option {value!r}")
 
 
-def _prefetch_frames(host_parts, cols, depth: int = 2):
+def _prefetch_frames(host_parts, cols, depth: int = 2, post=None):
+    """``post`` (the dataset's filter) runs on the producer thread, on the side stream and in front of
+    the event: its read-back of the kept row count stalls the prefetch, not the consumer."""
     import queue
     import threading
 
@@ -777,6 +872,8 @@ def _prefetch_frames(host_parts, cols, depth: int = 2):
                     return
                 with torch.cuda.stream(side):
                     frame, _ = as_device_frame(part, dev)
+                    if post is not None:
+                        frame = post(frame)
                     if cols is not None:
                         frame = frame[[c for c in cols if c in frame]]
                     ev = torch.cuda.Event()

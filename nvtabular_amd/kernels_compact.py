@@ -1,7 +1,7 @@
 """Row compaction on the device: the host driver of ``nvt_compact_*`` (include/nvt_hip.h), behind
-``ops.Filter`` and ``ops.Dropna``.
+``ops.Filter``, ``ops.Dropna`` and ``Dataset(filters=...)``.
 
-A keep mask (from a bool tensor, or from the null test of Dropna) and its plan -- the exclusive
+A keep mask (from a bool tensor, from the null test of Dropna, or from the terms of a Dataset filter) and its plan -- the exclusive
 scan of the kept rows per 2048-row tile -- drive ONE ``nvt_compact_many`` launch that moves the
 kept rows of every column: values, validity bitmaps (bit-exact, bits past m zero), string
 surrogates, and the leaves of list columns, whose leaf keep mask is the row mask expanded over
@@ -20,7 +20,7 @@ from . import _lib
 from . import kernels as K
 from ._lib import check
 
-_WIDTHS = {torch.bool: 1, torch.uint8: 1, torch.int32: 4, torch.float32: 4, torch.int64: 8, torch.float64: 8}
+_WIDTHS = {torch.bool: 1, torch.uint8: 1, torch.int8: 1, torch.int32: 4, torch.float32: 4, torch.int64: 8, torch.float64: 8}
 
 
 def _plan_ws(n: int, device) -> torch.Tensor:
@@ -92,6 +92,69 @@ def dropna_frame(frame, subset: Optional[Iterable[str]] = None):
         K.stat_add("compact_keep")
         check(_lib.load().nvt_compact_keep_dropna(descs, len(tested), n, ws.data_ptr(), ws.numel(),
                                                   K.stream_ptr()), "nvt_compact_keep_dropna")
+        return _compact(frame, ws, n)
+
+
+_FILTER_CODE = {torch.float32: _lib.NVT_F32, torch.float64: _lib.NVT_F64, torch.int32: _lib.NVT_I32,
+                torch.int64: _lib.NVT_I64, torch.uint8: _lib.NVT_U8, torch.bool: _lib.NVT_U8,
+                torch.int8: _lib.NVT_I8, torch.int16: _lib.NVT_I16}
+
+
+def filter_frame(frame, flt):
+    """The rows of ``frame`` that pass ``flt`` (a ``filters.Filter``, or the ``filters.Lowered`` of
+    one), in order, renumbered from 0.  ONE ``nvt_compact_keep_terms`` launch reads the columns the
+    filter names at their own width (bool / int8 / int16 included: no temporary per term) and writes
+    the plan's mask; the compaction follows as in ``compact_frame``, with its one read-back.  A
+    column with a pending FillMissing constant is materialised first, in the result too."""
+    from .filters import Lowered
+
+    n = len(frame)
+    names = flt.columns
+    missing = [c for c in names if c not in frame]
+    if missing:
+        raise ValueError(f"filters: the frame has no columns {missing}")
+    cols, copied = [], False
+    for name in names:
+        col = frame[name]
+        if col.is_list:
+            raise TypeError(f"filters: column {name!r} is a list column")
+        if col.fill is not None:
+            if not copied:   # (the caller's frame keeps its pending constant)
+                frame, copied = frame.copy(), True
+            col = frame[name] = col.materialize()
+        if col.data.dtype not in _FILTER_CODE:
+            raise TypeError(f"filters: unsupported column dtype {col.data.dtype} of {name!r}")
+        cols.append(col)
+    low = flt if isinstance(flt, Lowered) else \
+        flt.lower({name: col.data.dtype in (torch.float32, torch.float64) for name, col in zip(names, cols)})
+    if n == 0:
+        return frame.copy()
+    _lib.require_gpu()
+    dev = cols[0].data.device
+    descs = (_lib.FilterCol * len(cols))()
+    keep_alive = []
+    for d, col in zip(descs, cols):
+        data = col.data.contiguous()
+        keep_alive.append(data)
+        d.x = data.data_ptr()
+        d.valid = K.ptr(col.valid)
+        d.dtype = _FILTER_CODE[data.dtype]
+    terms = (_lib.FilterTerm * len(low.terms))()
+    for d, (j, op, conj, set_len, set_off, value) in zip(terms, low.terms):
+        d.col, d.op, d.conj, d.set_len, d.set_off = j, op, conj, set_len, set_off
+        if low.floats[j]:
+            d.value.f = value
+        else:
+            d.value.i = value
+    with K.LAUNCH_LOCK:
+        sets = low._device_sets.get(dev)
+        if sets is None and low.sets.size:
+            sets = low._device_sets[dev] = torch.from_numpy(low.sets.view("int64").copy()).to(dev)
+        ws = _plan_ws(n, dev)
+        K.stat_add("compact_keep")
+        check(_lib.load().nvt_compact_keep_terms(descs, len(cols), terms, len(low.terms), K.ptr(sets),
+                                                 int(low.sets.size), n, ws.data_ptr(), ws.numel(), K.stream_ptr()),
+              "nvt_compact_keep_terms")
         return _compact(frame, ws, n)
 
 

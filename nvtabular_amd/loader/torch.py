@@ -144,7 +144,10 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
     def _num_rows(self) -> int:
         if self._rows is None:
             ds = self.dataset
-            if getattr(ds, "_frames", None) is not None:
+            if getattr(ds, "_filter", None) is not None:
+                # Dataset(filters=...): neither the frames' lengths nor the footers know the rows that pass
+                rows = sum(len(p) for p in self._partitions(None))
+            elif getattr(ds, "_frames", None) is not None:
                 rows = 0
                 for i in self._my_parts():
                     f = ds._frames[i]
@@ -176,6 +179,8 @@ class TorchAsyncItr(torch.utils.data.IterableDataset):
         if getattr(ds, "_frames", None) is not None:
             for i in (order if order is not None else self._my_parts()):
                 frame, _ = as_device_frame(ds._frames[i])
+                if getattr(ds, "_filter", None) is not None:
+                    frame = ds._filter_frame(frame)
                 yield frame[[c for c in cols if c in frame]]
             return
         shard = (self.global_rank, self.global_size) if self.global_size > 1 else None

@@ -143,7 +143,15 @@ class JoinExternal(Operator):
             return self._ext_frame
         import pyarrow as pa
 
-        parts = [_to_device(p, self._ext_cols) for p in self.df_ext._host_parts(self._ext_cols, None)]
+        flt = getattr(self.df_ext, "_filter", None)
+        if flt is None:
+            parts = [_to_device(p, self._ext_cols) for p in self.df_ext._host_parts(self._ext_cols, None)]
+        else:
+            # Dataset(filters=...): the filter's columns are read too, and the rows that pass are taken
+            # in THIS thread (to_iter's prefetch thread would wait for LAUNCH_LOCK, which is held here)
+            read = self._ext_cols + [c for c in flt.columns if c not in self._ext_cols]
+            parts = [self.df_ext._filter_frame(_to_device(p, read))[self._ext_cols]
+                     for p in self.df_ext._host_parts(read, None)]
         if len(parts) == 1 and not self.drop_duplicates_ext:
             frame = parts[0][self._ext_cols]
         elif not parts:
