@@ -861,6 +861,83 @@ int nvt_pq_widen_i32_many(const nvt_pq_widen_col *cols, int ncols, void *stream)
 int nvt_pq_bool_pack(const uint8_t *vals, const int64_t *page_start, const int64_t *byte_at, uint64_t npages,
                      uint8_t *out, void *stream);
 
+/* ---- parquet in: DELTA_BINARY_PACKED data pages of flat INT32 / INT64 columns (DESIGN.md,
+ * "DELTA_BINARY_PACKED in the parquet reader") ----
+ * The values region of such a page is
+ *   varint block_size | varint miniblocks_per_block | varint total_count | zigzag first_value |
+ *   blocks of { zigzag min_delta | one width byte per miniblock | the miniblocks, bit-packed LSB first }
+ * and value k >= 1 is first_value + sum_{j < k} (min_delta of j's block + unpacked delta j), wrapping in
+ * the column's width.  The host decodes none of it: per partition and column it fills a STAGE that
+ * travels to the device as it is --
+ *   bytes  the values regions of the delta pages, one behind the other, each cut behind its last needed
+ *          miniblock; 16 zero bytes lie behind the last (bytes_cap counts them).
+ *   pages  NVT_PQ_DELTA_RECORD_WORDS (5) words per page with values: {first_value, pos, count |
+ *          values_per_miniblock << 32, first_mb, at}: `pos` the position of the page's first value
+ *          among the column's packed (non-null) values of the partition, `first_mb` its first
+ *          miniblock record, `at` the byte of `bytes` where its values region starts.
+ *   mbs    2 words per needed miniblock, ceil((count - 1) / values_per_miniblock) per page:
+ *          {byte position in `bytes` | bit width << 56, min_delta of its block}.
+ * nbytes / npages / nmbs say how far the stage is filled; zero them for a new partition.
+ *
+ * nvt_pq_delta_stage_page (HOST, no GPU call): walks ONE values region (`region`, region_bytes; count =
+ * the page's non-null values; type_size 4 / 8) and appends it to the stage.  Everything the device
+ * relies on is checked here: block_size a multiple of 128 that its miniblock count divides into
+ * multiples of 32, total_count == count, every width <= 8 * type_size, every needed miniblock inside
+ * the region (NVT_EINVAL otherwise; NVT_EUNSUPPORTED: miniblocks of more than NVT_PQ_DELTA_TILE
+ * values).  NVT_PQ_DELTA_GROW: a staging buffer is too small -- need[3] = {bytes, pages, mbs} holds a
+ * capacity that suffices for that buffer (0 for the others); the stage is left as it was.
+ *
+ * nvt_pq_decode_chunk_delta (HOST, thread-safe; one thread per stage): nvt_pq_decode_chunk_codec for a
+ * chunk whose data pages may ALSO be DELTA_BINARY_PACKED (a dictionary or PLAIN page followed by delta
+ * pages: parquet-mr's fallback).  ptype: the column's physical type (1 INT32, 2 INT64; 4 FLOAT /
+ * 5 DOUBLE decode like nvt_pq_decode_chunk_codec and a delta page of theirs is NVT_EINVAL).  A delta
+ * page is staged, and its non-null values are a HOLE of that many values in values_out; values_offset
+ * = the position of values_out[0] among the column's packed values (the `pos` of the records).  The
+ * stage advances on NVT_OK only; after NVT_PQ_DELTA_GROW the caller enlarges and calls again.
+ *
+ * nvt_pq_delta_decode (device): fills the holes of EVERY delta page of a partition in three launches,
+ * whatever the number of columns and pages.  pages: npages records in DEVICE memory (8-byte aligned);
+ * tile_page: for each of the ntiles tiles its page (DEVICE, uint32); a tile is a run of
+ * floor(NVT_PQ_DELTA_TILE / values_per_miniblock) miniblocks of one page (the page's last: what is
+ * left), a page of `count` values has ceil((count - 1) / (that many * values_per_miniblock)) tiles,
+ * consecutive from `first_tile` on.  tile_sums: ntiles uint64 of workspace on the device.
+ *   pass 1   a workgroup per tile: unpack, add min_delta, wrapping sum of the tile -> tile_sums
+ *   scan     a wave per page: tile_sums becomes the value in front of every tile (first_value + the
+ *            sums of the tiles before it); writes the page's value 0
+ *   pass 2   a workgroup per tile: unpack again, inclusive scan, + the tile's carry, every value
+ *            stored once into its place of the hole.
+ * The records are trusted (nvt_pq_delta_stage_page made them): `bytes` 16-byte aligned with 16
+ * readable bytes behind the last miniblock, dst aligned to `width`.  No read-back; `stream` only. */
+#define NVT_PQ_DELTA_GROW 1
+#define NVT_PQ_DELTA_TILE 2048u
+#define NVT_PQ_DELTA_RECORD_WORDS 5
+typedef struct nvt_pq_delta_stage {
+  uint8_t *bytes;
+  uint64_t *pages;
+  uint64_t *mbs;
+  uint64_t bytes_cap, pages_cap, mbs_cap;
+  uint64_t nbytes, npages, nmbs;
+} nvt_pq_delta_stage;
+typedef struct nvt_pq_delta_page {
+  uint64_t bytes;      /* device address of the column's staged bytes */
+  uint64_t mbs;        /* device address of the page's first miniblock record */
+  uint64_t dst;        /* device address of the page's hole (value 0) */
+  int64_t first_value;
+  uint32_t count;      /* values of the page, >= 1 */
+  uint32_t vpm;        /* values per miniblock */
+  uint32_t width;      /* 4 or 8: bytes per value */
+  uint32_t first_tile;
+} nvt_pq_delta_page;
+int nvt_pq_delta_stage_page(const uint8_t *region, uint64_t region_bytes, int type_size, uint64_t count,
+                            uint64_t pos, nvt_pq_delta_stage *stage, uint64_t *need);
+int nvt_pq_decode_chunk_delta(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int ptype, int max_def_level,
+                              uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                              uint8_t *values_out, uint64_t values_cap_bytes, uint64_t values_offset,
+                              nvt_pq_delta_stage *stage, uint8_t *scratch, uint64_t scratch_bytes,
+                              uint64_t *rows_out, uint64_t *values_count, uint64_t *need);
+int nvt_pq_delta_decode(const nvt_pq_delta_page *pages, uint64_t npages, const uint32_t *tile_page, uint64_t ntiles,
+                        uint64_t *tile_sums, void *stream);
+
 /* ---- batched entry points: ONE call per operator per partition -----------------------
  * The reference hands a whole dataframe to the backend per operator call
  * (`df[cols].fillna(...)`, `for col in columns: _encode(...)` -- categorify.py:477-537,

@@ -477,6 +477,26 @@ SIGNATURES.update({
 })
 
 
+class PqDeltaStage(C.Structure):
+    """nvt_pq_delta_stage: the staged DELTA_BINARY_PACKED pages of one column of a partition and how
+    far the buffers are filled (nvt_pq_decode_chunk_delta)."""
+    _fields_ = [("bytes", _vp), ("pages", _vp), ("mbs", _vp), ("bytes_cap", _u64), ("pages_cap", _u64),
+                ("mbs_cap", _u64), ("nbytes", _u64), ("npages", _u64), ("nmbs", _u64)]
+
+
+# include/nvt_hip.h NVT_PQ_DELTA_* (RECORD_WORDS: the words of a staged page record); PAGE_WORDS: the
+# words of the device's nvt_pq_delta_page (48 bytes, pinned by static_asserts in nvt_parquet_delta.hip): {bytes, mbs, dst, first_value,
+# count | vpm << 32, width | first_tile << 32}
+PQ_DELTA_GROW, PQ_DELTA_TILE, PQ_DELTA_RECORD_WORDS, PQ_DELTA_PAGE_WORDS = 1, 2048, 5, 6
+SIGNATURES.update({
+    "nvt_pq_delta_stage_page": [_vp, _u64, _i32, _u64, _u64, C.POINTER(PqDeltaStage), C.POINTER(_u64)],
+    "nvt_pq_decode_chunk_delta": [_vp, _u64, _i32, _i32, _i32, _u64, _vp, _u64, _vp, _u64, _u64,
+                                  C.POINTER(PqDeltaStage), _vp, _u64, C.POINTER(_u64), C.POINTER(_u64),
+                                  C.POINTER(_u64)],
+    "nvt_pq_delta_decode": [_vp, _u64, _vp, _u64, _vp, _vp],
+})
+
+
 class PartitionSeg(C.Structure):
     """nvt_partition_seg: one segment of an output partition (a DEVICE array of these is passed)."""
     _fields_ = [("idx", _vp), ("start", _u64)]

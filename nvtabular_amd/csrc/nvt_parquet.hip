@@ -28,6 +28,11 @@
 //     the index streams a run table plus the bytes of their bit-packed runs; the device expands the
 //     runs to entry ids (nvt_pq_expand_runs, nvt_parquet_str.hip) and hashes every entry once.
 //
+//   DELTA_BINARY_PACKED pages of flat INT32 / INT64 columns: nvt_pq_decode_chunk_delta walks the same
+//     pages and the block headers of a delta page, checks them and stages the page's bytes with a
+//     record per page and per miniblock; the device unpacks and prefix-sums them into the hole the
+//     page leaves in the packed values (nvt_pq_delta_decode, nvt_parquet_delta.hip).
+//
 // Anything else in a chunk (other codecs / encodings, other nesting) is reported as
 // NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
 #include <hip/hip_runtime.h>
@@ -376,6 +381,103 @@ struct ListSink {
   uint64_t starts = 0, leaves = 0;
 };
 
+// ---- DELTA_BINARY_PACKED pages: staged, not decoded ("DELTA_BINARY_PACKED in the parquet
+// reader") ---------------------------------------------------------------------------------------
+// the fill state of a nvt_pq_delta_stage during one chunk: committed to the stage on NVT_OK only, so
+// a chunk that asked for larger buffers is decoded again from its first byte
+struct DeltaFill {
+  nvt_pq_delta_stage *st;
+  uint64_t nbytes, npages, nmbs;
+  uint64_t *need;
+  bool ints;   // the column's physical type is INT32 / INT64
+  int grow(int which, uint64_t want) {
+    need[0] = need[1] = need[2] = 0;
+    need[which] = want;
+    return NVT_PQ_DELTA_GROW;
+  }
+};
+
+// One values region [q, q + nbytes) of `count` values at `type_size` bytes, the page's first value at
+// `pos` of the column's packed values: one page record, one record per needed miniblock, and the
+// region's bytes up to the end of the last needed miniblock.  Every header of the region is read
+// here, once per block; what the device later reads is exactly what this walk has seen inside the
+// region.
+int delta_stage_page(DeltaFill &f, const uint8_t *q, uint64_t nbytes, int type_size, uint64_t count, uint64_t pos) {
+  nvt_pq_delta_stage *st = f.st;
+  TReader r{q, q + nbytes};
+  const uint64_t block_size = r.varint(), mpb = r.varint(), total = r.varint();
+  const int64_t first = r.zigzag();
+  if (!r.ok) {
+    set_error("nvt_pq_decode_chunk_delta: the header of a delta page runs past the page");
+    return NVT_EINVAL;
+  }
+  if (block_size == 0 || block_size % 128 || mpb == 0 || block_size % mpb || (block_size / mpb) % 32 ||
+      block_size > (1ull << 31)) {
+    set_error("nvt_pq_decode_chunk_delta: blocks of %llu values in %llu miniblocks (a multiple of 128, miniblocks "
+              "of a multiple of 32)", (unsigned long long)block_size, (unsigned long long)mpb);
+    return NVT_EINVAL;
+  }
+  const uint64_t vpm = block_size / mpb;
+  if (vpm > NVT_PQ_DELTA_TILE) {
+    set_error("nvt_pq_decode_chunk_delta: miniblocks of %llu values (up to %u are decoded here)",
+              (unsigned long long)vpm, NVT_PQ_DELTA_TILE);
+    return NVT_EUNSUPPORTED;
+  }
+  if (total != count) {
+    set_error("nvt_pq_decode_chunk_delta: a delta page of %llu values, its levels say %llu",
+              (unsigned long long)total, (unsigned long long)count);
+    return NVT_EINVAL;
+  }
+  if (count == 0) return NVT_OK;
+  if (count >= (1ull << 32)) {
+    set_error("nvt_pq_decode_chunk_delta: a page of %llu values", (unsigned long long)count);
+    return NVT_EINVAL;
+  }
+  const uint64_t nmb = (count - 1 + vpm - 1) / vpm;
+  if (f.npages + 1 > st->pages_cap) return f.grow(1, f.npages + 1);
+  if (f.nmbs + nmb > st->mbs_cap) return f.grow(2, f.nmbs + nmb);
+  uint64_t *rec = st->mbs + 2 * f.nmbs;
+  for (uint64_t done = 0; done < nmb;) {
+    const int64_t min_delta = r.zigzag();
+    const uint8_t *widths = r.p;
+    r.skip_bytes(mpb);
+    if (!r.ok) {
+      set_error("nvt_pq_decode_chunk_delta: a block header runs past its page");
+      return NVT_EINVAL;
+    }
+    for (uint64_t m = 0; m < mpb && done < nmb; ++m, ++done, rec += 2) {
+      const uint64_t w = widths[m];
+      if (w > 8ull * (uint64_t)type_size) {
+        set_error("nvt_pq_decode_chunk_delta: a miniblock of bit width %llu in a column of %d bits",
+                  (unsigned long long)w, 8 * type_size);
+        return NVT_EINVAL;
+      }
+      const uint64_t nb = vpm * w / 8;   // (the last needed miniblock is padded to full length)
+      if ((uint64_t)(r.end - r.p) < nb) {
+        set_error("nvt_pq_decode_chunk_delta: a miniblock runs past its page");
+        return NVT_EINVAL;
+      }
+      rec[0] = (f.nbytes + (uint64_t)(r.p - q)) | (w << 56);
+      rec[1] = (uint64_t)min_delta;
+      r.p += nb;
+    }
+  }
+  const uint64_t used = (uint64_t)(r.p - q);
+  if (f.nbytes + used + 16 > st->bytes_cap) return f.grow(0, f.nbytes + used + 16);   // (far below 2^56)
+  memcpy(st->bytes + f.nbytes, q, used);
+  memset(st->bytes + f.nbytes + used, 0, 16);
+  uint64_t *pg = st->pages + NVT_PQ_DELTA_RECORD_WORDS * f.npages;
+  pg[0] = (uint64_t)first;
+  pg[1] = pos;
+  pg[2] = count | (vpm << 32);
+  pg[3] = f.nmbs;
+  pg[4] = f.nbytes;
+  f.nbytes += used;
+  f.npages += 1;
+  f.nmbs += nmb;
+  return NVT_OK;
+}
+
 // ---- snappy, raw block format (what parquet's SNAPPY codec holds per page) --------------------
 // -> uncompressed bytes written, or -1 on malformed input / a block that does not fit `cap`
 int64_t snappy_uncompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap) {
@@ -560,8 +662,11 @@ extern "C" {
 static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size, int max_def_level,
                      uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
                      uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch, uint64_t scratch_bytes,
-                     uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr) {
+                     uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr, DeltaFill *df = nullptr,
+                     uint64_t values_offset = 0) {
   // ls: a list chunk -- `rows` / expect_rows below count SLOTS, the levels go to the sink's streams
+  // df: DELTA_BINARY_PACKED pages are staged there and leave a hole in values_out, whose first value
+  //     is value `values_offset` of the column's packed values
   NVT_CHECK_ARG(chunk && values_out && rows_out && values_out_count, "null pointer");
   NVT_CHECK_ARG(type_size == 4 || type_size == 8, "values are 4 or 8 bytes");
   NVT_CHECK_ARG(ls || max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
@@ -637,7 +742,12 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       return NVT_EUNSUPPORTED;
     }
     const bool by_dict = h.encoding == 2 || h.encoding == 8;   // PLAIN_DICTIONARY / RLE_DICTIONARY
-    if (h.encoding != 0 && !by_dict) {
+    const bool by_delta = h.encoding == 5 && df != nullptr && ls == nullptr;   // DELTA_BINARY_PACKED
+    if (by_delta && !df->ints) {
+      set_error("nvt_pq_decode_chunk_delta: DELTA_BINARY_PACKED values in a column that is not INT32 / INT64");
+      return NVT_EINVAL;
+    }
+    if (h.encoding != 0 && !by_dict && !by_delta) {
       set_error("nvt_pq_decode_chunk: value encoding %d (PLAIN and dictionary indices are decoded here)", h.encoding);
       return NVT_EUNSUPPORTED;
     }
@@ -757,7 +867,10 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       set_error("nvt_pq_decode_chunk: values buffer too small");
       return NVT_EINVAL;
     }
-    if (!by_dict) {
+    if (by_delta) {   // staged as it is: the device fills the hole of pvalid values
+      const int rc = delta_stage_page(*df, q, (uint64_t)(pend - q), type_size, pvalid, values_offset + vals);
+      if (rc) return rc;
+    } else if (!by_dict) {
       const uint64_t vbytes = pvalid * (uint64_t)type_size;
       if ((uint64_t)(pend - q) < vbytes) {
         set_error("nvt_pq_decode_chunk: page holds fewer values than its levels say");
@@ -844,6 +957,39 @@ int nvt_pq_decode_chunk_codec(const uint8_t *chunk, uint64_t chunk_bytes, int co
                               uint64_t *values_out_count) {
   return pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out, valid_bit_offset,
                    values_out, values_cap_bytes, scratch, scratch_bytes, rows_out, values_out_count);
+}
+
+int nvt_pq_delta_stage_page(const uint8_t *region, uint64_t region_bytes, int type_size, uint64_t count,
+                            uint64_t pos, nvt_pq_delta_stage *stage, uint64_t *need) {
+  NVT_CHECK_ARG(region && stage && need, "null pointer");
+  NVT_CHECK_ARG(type_size == 4 || type_size == 8, "values are 4 or 8 bytes");
+  NVT_CHECK_ARG(stage->bytes && stage->pages && stage->mbs, "null staging buffer");
+  DeltaFill f{stage, stage->nbytes, stage->npages, stage->nmbs, need, true};
+  const int rc = delta_stage_page(f, region, region_bytes, type_size, count, pos);
+  if (rc) return rc;
+  stage->nbytes = f.nbytes;
+  stage->npages = f.npages;
+  stage->nmbs = f.nmbs;
+  return NVT_OK;
+}
+
+int nvt_pq_decode_chunk_delta(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int ptype, int max_def_level,
+                              uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                              uint8_t *values_out, uint64_t values_cap_bytes, uint64_t values_offset,
+                              nvt_pq_delta_stage *stage, uint8_t *scratch, uint64_t scratch_bytes,
+                              uint64_t *rows_out, uint64_t *values_count, uint64_t *need) {
+  NVT_CHECK_ARG(stage && need, "null pointer");
+  NVT_CHECK_ARG(ptype == 1 || ptype == 2 || ptype == 4 || ptype == 5, "physical type INT32, INT64, FLOAT or DOUBLE");
+  NVT_CHECK_ARG(stage->bytes && stage->pages && stage->mbs, "null staging buffer");
+  DeltaFill f{stage, stage->nbytes, stage->npages, stage->nmbs, need, ptype == 1 || ptype == 2};
+  const int rc = pq_decode(chunk, chunk_bytes, codec, (ptype == 1 || ptype == 4) ? 4 : 8, max_def_level, expect_rows,
+                           valid_out, valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
+                           values_count, nullptr, &f, values_offset);
+  if (rc) return rc;
+  stage->nbytes = f.nbytes;
+  stage->npages = f.npages;
+  stage->nmbs = f.nmbs;
+  return NVT_OK;
 }
 
 // ---- string columns: entries + run table + packed bytes ("String columns in the parquet

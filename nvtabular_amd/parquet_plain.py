@@ -65,7 +65,11 @@ today unless the codec makes it smaller ("Snappy pages in the PLAIN p
 The reading half also takes flat STRING columns (any writer's dictionary / PLAIN pages): their
 dictionary entries and index runs are staged as the file holds them and expanded, hashed and
 gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "String columns in
-the parquet reader").  Binary columns, lists of strings and DELTA encodings stay with pyarrow.
+the parquet reader"), and DELTA_BINARY_PACKED pages of flat INT32 / INT64 columns: their bytes are
+staged behind one record per page and miniblock and unpacked and prefix-summed on the device
+(``StagedDelta``, kernels_parquet_delta.py; DESIGN.md, "DELTA_BINARY_PACKED in the parquet reader").
+Binary columns, lists of strings, DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and
+delta pages of list leaves stay with pyarrow.
 parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver in front of the writer.
 """
 from __future__ import annotations
@@ -982,9 +986,17 @@ def _judge_chunk(cc, col, file_size):
     c = dict(offset=first, size=int(md.get(7, 0)), num_values=int(md.get(5, 0)), codec=int(md.get(4, 0)),
              raw_size=int(md.get(6, 0)), dictionary=bool(dpo is not None or (enc & {2, 8})), path=path)
     # codec 0 UNCOMPRESSED / 1 SNAPPY; encodings PLAIN 0, PLAIN_DICTIONARY 2, RLE 3, BIT_PACKED 4,
-    # RLE_DICTIONARY 8 (nvt_pq_decode_chunk_codec)
-    if not (md.get(4) in (0, 1) and enc <= {0, 2, 3, 4, 8} and cc.get(1) in (None, b"")):
+    # RLE_DICTIONARY 8 (nvt_pq_decode_chunk_codec), DELTA_BINARY_PACKED 5 (nvt_pq_decode_chunk_delta)
+    if not (md.get(4) in (0, 1) and enc <= {0, 2, 3, 4, 5, 8} and cc.get(1) in (None, b"")):
         return c, f"chunk of {md.get(3)}: codec {md.get(4)}, encodings {sorted(enc)}"
+    if 5 in enc:
+        # delta pages are decoded on the device for flat INT32 / INT64 chunks (int8 / int16 and
+        # TIMESTAMP annotations included); ``delta``: the chunk goes through nvt_pq_decode_chunk_delta
+        if len(path) > 1 or (col is not None and col["kind"] == "list"):
+            return c, f"chunk of {md.get(3)}: DELTA_BINARY_PACKED values in a list column"
+        if md.get(1) not in (1, 2):
+            return c, f"chunk of {md.get(3)}: DELTA_BINARY_PACKED values of physical type {md.get(1)}"
+        c["delta"] = True
     if len(path) > 1 and 4 in enc:
         return c, f"chunk of {md.get(3)}: BIT_PACKED level streams"
     if not (0 <= c["offset"] and 0 <= c["size"] and c["offset"] + c["size"] <= file_size):
@@ -1008,12 +1020,14 @@ class PlainParquetFile:
     inner names are not looked at), and every column chunk follows its column, with codec
     UNCOMPRESSED or SNAPPY, values PLAIN or dictionary-encoded (what pandas / pyarrow / cuDF write by
     default), encodings within {PLAIN, PLAIN_DICTIONARY, RLE, BIT_PACKED, RLE_DICTIONARY} and no
-    BIT_PACKED levels on a list chunk.  Otherwise ``why_pyarrow`` is the FIRST thing found that keeps
+    BIT_PACKED levels on a list chunk; a flat INT32 / INT64 chunk may also hold DELTA_BINARY_PACKED
+    pages (what the v2 writers of parquet-mr / Spark and DuckDB emit; its entry has ``delta``).  Otherwise ``why_pyarrow`` is the FIRST thing found that keeps
     the file with pyarrow (legacy two-level lists, lists of lists, maps, structs, binary / fixed-length
-    binary columns, string / bool / narrow / TIMESTAMP list leaves, DELTA encodings, other codecs).
-    ``readable`` / ``why_not`` keep the meaning they had before the reader knew strings: decodable
-    AND no string column (number columns and lists of numbers only); a string column is their first
-    reason like any other.  The reader goes by ``decodable``.
+    binary columns, string / bool / narrow / TIMESTAMP list leaves, the byte-array DELTA encodings,
+    delta pages of list leaves, other codecs).
+    ``readable`` / ``why_not`` keep the meaning they had before the reader knew strings and delta
+    pages: decodable AND no string column AND no DELTA_BINARY_PACKED chunk (number columns and lists
+    of numbers, PLAIN or dictionary-encoded, only); either is their first reason like any other.  The reader goes by ``decodable``.
     ``eligible``: readable and all columns flat number columns.
     ``columns[j]`` describes top-level column j: ``kind`` ("flat" / "string" / "list"), ``outer_optional``,
     ``elem_optional``, ``max_def`` (lists: O + 1 + E), ``leaf_level`` (O + 1), ``leaf_dtype`` and
@@ -1068,12 +1082,17 @@ class PlainParquetFile:
                 c, why = _judge_chunk(cc, self.columns[j] if j < len(self.columns) else None, size)
                 cols.append(c)
                 self._fail(why)
+                if why is None and c.get("delta"):
+                    # like a string column: the reader takes the chunk, ``readable`` / ``eligible`` keep
+                    # the meaning they had before it did
+                    self._fail(f"chunk of {c['path']}: DELTA_BINARY_PACKED values", strings=True)
             if len(cols) != len(self.columns):
                 self._fail("column chunks do not follow the schema order")
             self.row_groups.append(dict(num_rows=int(rg.get(3, 0)), columns=cols))
 
     def _fail(self, why, strings=False):
-        """strings: a reason that keeps the file from ``readable`` only (the reader takes it)."""
+        """strings: a reason that keeps the file from ``readable`` only (the reader takes it): a
+        string column, a DELTA_BINARY_PACKED chunk."""
         if why is not None and self.readable:   # (the first reason stays)
             self.readable, self.why_not = False, why
         if why is not None and self.decodable and not strings:
@@ -1106,10 +1125,14 @@ class StagedColumn:
     one unpack and one offsets tensor on the device), else None.
 
     A string column (``strs`` is not None) has no ``values``: ``strs`` (StagedStrings) holds its
-    entries, run table and packed index bytes, ``nvalid`` counts its non-null rows."""
+    entries, run table and packed index bytes, ``nvalid`` counts its non-null rows.
+
+    A flat INT32 / INT64 column with DELTA_BINARY_PACKED pages has ``delta`` (StagedDelta): the values of
+    those pages are HOLES in ``values`` that the device fills (kernels_parquet_delta.fill_holes)
+    before anything else looks at them."""
 
     __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical", "rep", "dfn", "width", "leaf_level",
-                 "max_def", "slots", "leaves", "same_as", "strs")
+                 "max_def", "slots", "leaves", "same_as", "strs", "delta")
 
     def __init__(self, values, valid, rows, nvalid, dtype, logical=None, rep=None, dfn=None, width=0, leaf_level=0,
                  max_def=0, slots=0, leaves=0):
@@ -1118,6 +1141,7 @@ class StagedColumn:
         self.rep, self.dfn, self.width, self.leaf_level, self.max_def = rep, dfn, width, leaf_level, max_def
         self.slots, self.leaves, self.same_as = slots, leaves, None
         self.strs = None
+        self.delta = None
 
     @property
     def is_list(self):
@@ -1200,6 +1224,82 @@ class StagedStrings:
         return int(self.c.nvalues)
 
 
+class StagedDelta:
+    """The staged DELTA_BINARY_PACKED pages of one column of a partition, as nvt_pq_decode_chunk_delta
+    fills them (include/nvt_hip.h, nvt_pq_delta_stage): ``bytes`` the pages' values regions (16 zero
+    bytes behind the last), ``pages`` 5 int64 words per page {first value, position of the page's first
+    value in the column's packed values, count | values per miniblock << 32, first miniblock record,
+    byte of ``bytes`` where the page's region starts},
+    ``mbs`` 2 words per needed miniblock {byte position | bit width << 56, min_delta}.  Sized from the
+    footer and enlarged when the decoder asks for it."""
+
+    def __init__(self, bytes_cap, pages_cap, mbs_cap, pinned=False):
+        import torch
+
+        from . import _lib
+
+        self.pinned, self.words = pinned, _lib.PQ_DELTA_RECORD_WORDS   # words per page record
+        self.bytes = torch.empty(((bytes_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
+        self.pages = torch.empty(self.words * max(1, pages_cap), dtype=torch.int64, pin_memory=pinned)
+        self.mbs = torch.empty(2 * max(1, mbs_cap), dtype=torch.int64, pin_memory=pinned)
+        self.c = _lib.PqDeltaStage()
+        self._bind()
+
+    def _bind(self):
+        c = self.c
+        c.bytes, c.pages, c.mbs = self.bytes.data_ptr(), self.pages.data_ptr(), self.mbs.data_ptr()
+        c.bytes_cap, c.mbs_cap = self.bytes.numel(), self.mbs.numel() // 2
+        c.pages_cap = self.pages.numel() // self.words
+
+    def grow(self, need):
+        """Enlarges the buffers named by ``need`` = (bytes, pages, mbs), 0 = large enough, keeping what
+        is filled."""
+        import torch
+
+        c, W = self.c, self.words
+        for which, want in enumerate(need):
+            if not want:
+                continue
+            name, used, words = (("bytes", c.nbytes, 1), ("pages", W * c.npages, W), ("mbs", 2 * c.nmbs, 2))[which]
+            old = getattr(self, name)
+            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
+            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
+            new[:used] = old[:used]
+            setattr(self, name, new)
+        self._bind()
+
+    def add_page(self, region, itemsize, count, pos):
+        """Stages ONE values region (bytes-like) of ``count`` values of ``itemsize`` bytes whose first
+        value is value ``pos`` of the column's packed values (nvt_pq_delta_stage_page: the walk that
+        nvt_pq_decode_chunk_delta runs on every delta page)."""
+        import ctypes as C
+
+        from . import _lib
+
+        lib = _lib.load()
+        buf = (C.c_uint8 * max(1, len(region))).from_buffer_copy(bytes(region) or b"\0")
+        need = (C.c_uint64 * 3)()
+        while True:
+            rc = lib.nvt_pq_delta_stage_page(buf, len(region), itemsize, count, pos, C.byref(self.c), need)
+            if rc != _lib.PQ_DELTA_GROW:
+                break
+            self.grow(tuple(int(x) for x in need))
+        if rc != 0:
+            raise _lib.NvtHipError(f"nvt_pq_delta_stage_page: {lib.nvt_last_error().decode()} (rc {rc})")
+
+    @property
+    def nbytes(self):
+        return int(self.c.nbytes)
+
+    @property
+    def npages(self):
+        return int(self.c.npages)
+
+    @property
+    def nmbs(self):
+        return int(self.c.nmbs)
+
+
 class StagedPartition:
     """A partition as ``read_row_groups_staged`` leaves it on the host: {column: StagedColumn}.
     ``to_device`` enqueues the copies on the CURRENT stream (the prefetcher's side stream) and
@@ -1222,6 +1322,15 @@ class StagedPartition:
         device = device or default_device()
         out = {}
         unpacked = {}   # list column -> (offsets, leaf bitmap): one unpack per distinct level streams
+        # columns with DELTA_BINARY_PACKED pages: their packed values travel with holes, which ONE call
+        # fills for all of them before the values are expanded, narrowed or handed over below
+        filled = {}
+        if device.type == "cuda" and any(sc.delta is not None for sc in self.columns.values()):
+            from . import kernels_parquet_delta as KPD
+
+            filled = {name: KPD.values_to_device(sc, device) for name, sc in self.columns.items()
+                      if sc.delta is not None}
+            KPD.fill_holes([(self.columns[name].delta, packed) for name, packed in filled.items()])
         for name, sc in self.columns.items():
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
                 raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
@@ -1232,7 +1341,7 @@ class StagedPartition:
 
                 out[name] = KPS.column_from_staged(sc, device)
                 continue
-            packed = sc.values[:sc.nvalid].to(device, non_blocking=True)
+            packed = filled[name] if name in filled else sc.values[:sc.nvalid].to(device, non_blocking=True)
             if sc.is_list:
                 # the level streams become offsets and the leaf bitmap on the device (columns with
                 # byte-equal streams share both tensors); the non-null leaves are then expanded to
@@ -1290,7 +1399,9 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
     (ctypes: GIL released) moves its values and validity bits to their place in the partition's
     (pinned) staging buffers; a list column's chunks go through nvt_pq_decode_list_chunk, which
     appends their levels to the column's two level streams instead, a string column's through
-    nvt_pq_decode_str_chunk, which appends entries, index runs and packed bytes to a StagedStrings."""
+    nvt_pq_decode_str_chunk, which appends entries, index runs and packed bytes to a StagedStrings, a
+    flat integer chunk whose footer lists DELTA_BINARY_PACKED through nvt_pq_decode_chunk_delta, which
+    stages its delta pages in a StagedDelta and leaves holes for their values."""
     import ctypes as C
 
     import torch
@@ -1401,9 +1512,29 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if pf.max_def[j]:
             valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         row_at = val_at = 0
+        delta = None
         for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
             r, v = C.c_uint64(), C.c_uint64()
-            if dt == BOOL_DTYPE:
+            if cc.get("delta"):   # (flat INT32 / INT64 chunks only: _judge_chunk)
+                # the footer lists DELTA_BINARY_PACKED: such pages are staged for the device and leave
+                # holes in ``vals``; the chunk's other pages are decoded as below
+                if delta is None:
+                    ccs = [pf.row_groups[x]["columns"][j] for x in groups if pf.row_groups[x]["num_rows"]]
+                    ccs = [x for x in ccs if x.get("delta")]
+                    nv = sum(x["num_values"] for x in ccs)
+                    delta = StagedDelta(sum(max(x.get("raw_size", 0), x["size"]) for x in ccs) + 64,
+                                        nv // 4096 + 4 * len(ccs) + 16, nv // 32 + 64 * len(ccs) + 64, pinned)
+                fn, need = "nvt_pq_decode_chunk_delta", (C.c_uint64 * 3)()
+                while True:
+                    rc = lib.nvt_pq_decode_chunk_delta(cbuf, cc["size"], cc.get("codec", 0), _PQ_TYPE[st], pf.max_def[j],
+                                                       rows, valid.data_ptr() if valid is not None else None, row_at,
+                                                       vals.data_ptr() + val_at * st.itemsize,
+                                                       (total - val_at) * st.itemsize, val_at, C.byref(delta.c),
+                                                       sbuf, sbytes, C.byref(r), C.byref(v), need)
+                    if rc != _lib.PQ_DELTA_GROW:
+                        break
+                    delta.grow(tuple(int(x) for x in need))
+            elif dt == BOOL_DTYPE:
                 fn = "nvt_pq_decode_bool_chunk"
                 rc = lib.nvt_pq_decode_bool_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
                                                   valid.data_ptr() if valid is not None else None, row_at,
@@ -1420,8 +1551,10 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
             row_at += rows
             val_at += int(v.value)
         logical = np.dtype(f"datetime64[{pf.units[j]}]") if pf.units[j] is not None else None
-        return StagedColumn(vals, valid if (valid is not None and val_at < total) else None, total, val_at, dt,
-                            logical)
+        sc = StagedColumn(vals, valid if (valid is not None and val_at < total) else None, total, val_at, dt,
+                          logical)
+        sc.delta = delta if (delta is not None and delta.npages) else None
+        return sc
 
     futs = []
     try:
