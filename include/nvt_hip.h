@@ -938,6 +938,87 @@ int nvt_pq_decode_chunk_delta(const uint8_t *chunk, uint64_t chunk_bytes, int co
 int nvt_pq_delta_decode(const nvt_pq_delta_page *pages, uint64_t npages, const uint32_t *tile_page, uint64_t ntiles,
                         uint64_t *tile_sums, void *stream);
 
+/* ---- parquet in: dictionary-encoded data pages of flat 4- and 8-byte number columns (DESIGN.md,
+ * "Dictionary pages of number columns in the parquet reader") ----
+ * The index stream of such a page (one byte bit width, then the RLE / bit-packed hybrid) is not
+ * resolved on the host.  Per partition and column the decoder fills a STAGE that travels to the
+ * device as it is --
+ *   dict    the dictionaries of the column's chunks, one behind the other.  Each chunk's part starts
+ *           on a 16-byte boundary with a 16-byte HEAD {uint64 entries of the chunk, uint64 0}; its
+ *           PLAIN values (type_size bytes each) follow.  An ENTRY POSITION counts type_size-byte
+ *           elements from the start of `dict`, heads included: the chunk's first entry is the
+ *           element behind its head.  ndict_bytes says how far it is filled.
+ *   runs    records of 4 uint32 {start, kind | width << 8, a, b} in value order, the format of the
+ *           string path: `start` the position of the run's first value among the column's packed
+ *           (non-null) values of the partition; a run ends where the next record starts; no run is
+ *           empty; the closing record {total, NVT_PQ_RUN_END, 0, 0} lies behind the nruns runs.
+ *             NVT_PQ_RUN_REPEAT  every value is the entry at position a (checked on the host)
+ *             NVT_PQ_RUN_PACKED  value k is entry a + (the width-bit number at bit k * width, LSB
+ *                                first, of the bytes from packed[4 * b] on); width 1 .. 32, a = the
+ *                                position of the chunk's first entry.  The device checks the number
+ *                                against the entries in the chunk's head.
+ *             NVT_PQ_RUN_KEEP    the host has decoded these values itself (PLAIN pages, the writer's
+ *                                fallback once its dictionary overflows): they are in place in the
+ *                                packed values and the device leaves them alone
+ *   packed  the bytes of the bit-packed runs as the file holds them, each run's on a 4-byte boundary
+ *           and clipped to the values its page still owes, 8 zero bytes behind the last.
+ *
+ * nvt_pq_decode_chunk_dict (HOST, no GPU call, thread-safe; one thread per stage):
+ * nvt_pq_decode_chunk_codec, but a dictionary-encoded data page is staged and its non-null values
+ * are a HOLE of that many values in values_out; values_offset = the position of values_out[0] among
+ * the column's packed values (the `start` of the records).  Everything that can be checked without
+ * unpacking is checked here and fails as in nvt_pq_decode_chunk_codec: the bit width, run lengths
+ * against what the page owes, bytes against the page, the dictionary count against its page, a
+ * REPEAT index against the dictionary.  The stage advances on NVT_OK only.  NVT_PQ_DICT_GROW: a
+ * staging buffer is too small -- need[3] = {dict bytes, runs, packed bytes} holds a capacity that
+ * reaches further for that buffer (0 for the others); the caller enlarges it, keeps the filled part
+ * and calls again with the same chunk.
+ *
+ * nvt_pq_dict_fill_many (device): fills the holes of EVERY staged column of a partition in one
+ * launch.  cols: ncols descriptors in DEVICE memory, every pointer in them a device pointer: runs
+ * (16-byte aligned, nruns records + the closing one), packed (16-byte aligned, packed_bytes readable,
+ * a multiple of 4), dict (16-byte aligned, ndict elements of type_size bytes, heads included), values
+ * (16-byte aligned, nvalues elements).  groups: ngroups pairs {column, first tile} (DEVICE, uint32):
+ * a workgroup takes the NVT_PQ_DICT_TILES_PER_WG consecutive tiles of NVT_PQ_DICT_TILE values from
+ * `first tile` on of that column, so that a dictionary of up to NVT_PQ_DICT_LDS_BYTES is staged in
+ * LDS once for all of them.  A packed index outside its chunk's entries writes 0 and is counted:
+ * *bad += their number (a device word the caller zeroes; one atomic per wave).  Positions of a KEEP
+ * run, positions no run covers and positions behind nvalues are never written.  Every read is
+ * bounded by nruns / packed_bytes / ndict whatever the tables say.  ngroups == 0 launches nothing.
+ * nvalues < 2^32 - NVT_PQ_DICT_TILE, ndict < 2^31, packed_bytes < 2^34.  No read-back; `stream`
+ * only. */
+#define NVT_PQ_RUN_KEEP 4u
+#define NVT_PQ_DICT_GROW 1
+#define NVT_PQ_DICT_TILE 4096u
+#define NVT_PQ_DICT_TILES_PER_WG 4u
+#define NVT_PQ_DICT_LDS_BYTES 32768u
+#define NVT_PQ_DICT_HEAD_BYTES 16u
+typedef struct nvt_pq_dict_stage {
+  uint8_t *dict;
+  uint32_t *runs;
+  uint8_t *packed;
+  uint64_t dict_cap, runs_cap, packed_cap;   /* bytes, records, bytes */
+  uint64_t ndict_bytes, nruns, npacked;
+} nvt_pq_dict_stage;
+typedef struct nvt_pq_dict_col {
+  const uint32_t *runs;
+  uint64_t nruns;
+  const uint8_t *packed;
+  uint64_t packed_bytes;
+  const void *dict;
+  uint64_t ndict;
+  uint64_t type_size;   /* 4 | 8 */
+  void *values;
+  uint64_t nvalues;
+} nvt_pq_dict_col;
+int nvt_pq_decode_chunk_dict(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size, int max_def_level,
+                             uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                             uint8_t *values_out, uint64_t values_cap_bytes, uint64_t values_offset,
+                             nvt_pq_dict_stage *stage, uint8_t *scratch, uint64_t scratch_bytes,
+                             uint64_t *rows_out, uint64_t *values_count, uint64_t *need);
+int nvt_pq_dict_fill_many(const nvt_pq_dict_col *cols, int ncols, const uint32_t *groups, uint64_t ngroups,
+                          uint32_t *bad, void *stream);
+
 /* ---- batched entry points: ONE call per operator per partition -----------------------
  * The reference hands a whole dataframe to the backend per operator call
  * (`df[cols].fillna(...)`, `for col in columns: _encode(...)` -- categorify.py:477-537,

@@ -497,6 +497,25 @@ SIGNATURES.update({
 })
 
 
+class PqDictStage(C.Structure):
+    """nvt_pq_dict_stage: the staged dictionaries, index runs and packed bytes of one number column of
+    a partition and how far the buffers are filled (nvt_pq_decode_chunk_dict)."""
+    _fields_ = [("dict", _vp), ("runs", _vp), ("packed", _vp), ("dict_cap", _u64), ("runs_cap", _u64),
+                ("packed_cap", _u64), ("ndict_bytes", _u64), ("nruns", _u64), ("npacked", _u64)]
+
+
+# include/nvt_hip.h NVT_PQ_RUN_KEEP / NVT_PQ_DICT_*; COL_WORDS: the 8-byte words of the device's
+# nvt_pq_dict_col (pinned by static_asserts in nvt_parquet_dict_in.hip)
+PQ_RUN_KEEP, PQ_DICT_GROW, PQ_DICT_TILE, PQ_DICT_TILES_PER_WG, PQ_DICT_LDS_BYTES = 4, 1, 4096, 4, 32768
+PQ_DICT_HEAD_BYTES, PQ_DICT_COL_WORDS = 16, 9
+SIGNATURES.update({
+    "nvt_pq_decode_chunk_dict": [_vp, _u64, _i32, _i32, _i32, _u64, _vp, _u64, _vp, _u64, _u64,
+                                 C.POINTER(PqDictStage), _vp, _u64, C.POINTER(_u64), C.POINTER(_u64),
+                                 C.POINTER(_u64)],
+    "nvt_pq_dict_fill_many": [_vp, _i32, _vp, _u64, _vp, _vp],
+})
+
+
 class PartitionSeg(C.Structure):
     """nvt_partition_seg: one segment of an output partition (a DEVICE array of these is passed)."""
     _fields_ = [("idx", _vp), ("start", _u64)]

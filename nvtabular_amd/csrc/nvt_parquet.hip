@@ -33,6 +33,11 @@
 //     record per page and per miniblock; the device unpacks and prefix-sums them into the hole the
 //     page leaves in the packed values (nvt_pq_delta_decode, nvt_parquet_delta.hip).
 //
+//   dictionary pages of flat 4- / 8-byte number columns: nvt_pq_decode_chunk_dict walks the same pages
+//     but resolves no index: it stages the chunk's dictionary, a run table and the bytes of the
+//     bit-packed runs, and the device fills the hole the page leaves (nvt_pq_dict_fill_many,
+//     nvt_parquet_dict_in.hip).
+//
 // Anything else in a chunk (other codecs / encodings, other nesting) is reported as
 // NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
 #include <hip/hip_runtime.h>
@@ -592,6 +597,119 @@ bool decode_dict_indices(const uint8_t *p, const uint8_t *end, uint64_t count, c
   return true;
 }
 
+// ---- dictionary pages of number columns: staged, not resolved ("Dictionary pages of
+// number columns in the parquet reader") -----------------------------------------------------------
+// the fill state of a nvt_pq_dict_stage during one chunk: committed to the stage on NVT_OK only, so a
+// chunk that asked for larger buffers is decoded again from its first byte
+struct DictFill {
+  nvt_pq_dict_stage *st;
+  uint64_t ndict_bytes, nruns, npacked;
+  uint64_t *need;
+  uint64_t base = 0;   // entry position of the chunk's first dictionary entry
+  int grow(int which, uint64_t want) {
+    need[0] = need[1] = need[2] = 0;
+    need[which] = want;
+    return NVT_PQ_DICT_GROW;
+  }
+  // the chunk's dictionary (ndict PLAIN values of type_size bytes) behind a head, on a 16-byte boundary
+  int dictionary(const uint8_t *d, uint64_t ndict, int type_size) {
+    const uint64_t at = (ndict_bytes + 15) & ~15ull, nb = ndict * (uint64_t)type_size;
+    if (at + NVT_PQ_DICT_HEAD_BYTES + nb > st->dict_cap) return grow(0, at + NVT_PQ_DICT_HEAD_BYTES + nb);
+    if ((at + NVT_PQ_DICT_HEAD_BYTES + nb) / (uint64_t)type_size >= (1ull << 31)) {
+      set_error("nvt_pq_decode_chunk_dict: 2^31 dictionary entries or more in one partition");
+      return NVT_EUNSUPPORTED;
+    }
+    memset(st->dict + ndict_bytes, 0, at - ndict_bytes);
+    const uint64_t head[2] = {ndict, 0};
+    memcpy(st->dict + at, head, sizeof head);
+    memcpy(st->dict + at + NVT_PQ_DICT_HEAD_BYTES, d, nb);
+    base = (at + NVT_PQ_DICT_HEAD_BYTES) / (uint64_t)type_size;
+    ndict_bytes = at + NVT_PQ_DICT_HEAD_BYTES + nb;
+    return NVT_OK;
+  }
+  // one record {start, kind | width << 8, a, b} of `count` values; a repeat run that continues the
+  // last record's entry and a KEEP run behind a KEEP run add nothing: a run ends where the next starts
+  int run(unsigned kind, unsigned width, uint32_t a, uint32_t b, uint64_t start, uint64_t count) {
+    if (count == 0) return NVT_OK;
+    if (start + count >= (1ull << 32) - NVT_PQ_DICT_TILE) {
+      set_error("nvt_pq_decode_chunk_dict: 2^32 values or more in one partition");
+      return NVT_EUNSUPPORTED;
+    }
+    uint32_t *rec = st->runs + 4 * nruns;
+    if (nruns > 0 && kind != NVT_PQ_RUN_PACKED && rec[-3] == kind && (kind == NVT_PQ_RUN_KEEP || rec[-2] == a))
+      return NVT_OK;
+    if (nruns + 2 > st->runs_cap) return grow(1, nruns + 2);   // (this record and the closing one)
+    rec[0] = (uint32_t)start;
+    rec[1] = kind | (width << 8);
+    rec[2] = a;
+    rec[3] = b;
+    ++nruns;
+    return NVT_OK;
+  }
+};
+
+// the dictionary indices of one page (`count` non-null values from packed value `start` on; one byte
+// bit width, then the RLE / bit-packed hybrid) -> run records; the bytes of bit-packed runs go to the
+// packed staging buffer, each run's on a 4-byte boundary.  Refuses what decode_dict_indices refuses,
+// but for the indices inside bit-packed runs, which the device checks.
+int dict_index_runs(DictFill &f, const uint8_t *p, const uint8_t *end, uint64_t count, uint64_t ndict,
+                    uint64_t start) {
+  if (count == 0) return NVT_OK;
+  if (p >= end) return NVT_EINVAL;
+  const unsigned bw = *p++;
+  if (bw > 32) return NVT_EINVAL;
+  const uint64_t mask = bw == 32 ? 0xFFFFFFFFull : ((1ull << bw) - 1ull);
+  TReader r{p, end};
+  uint64_t done = 0;
+  while (done < count) {
+    const uint64_t head = r.varint();
+    if (!r.ok) return NVT_EINVAL;
+    const uint64_t avail = (uint64_t)(r.end - r.p);
+    if (head & 1) {   // bit-packed: (head >> 1) groups of 8 values, `bw` bits each, LSB first
+      const uint64_t groups = head >> 1;
+      if (groups == 0 || groups > (1ull << 40)) return NVT_EINVAL;
+      uint64_t take = groups * 8;
+      if (take > count - done) take = count - done;   // (the last group is padded)
+      const uint64_t nb = (take * bw + 7) / 8;        // the bytes the values need
+      if (avail < nb) return NVT_EINVAL;
+      int rc;
+      if (bw == 0) {   // a one-entry dictionary: every index is 0
+        if (ndict == 0) return NVT_EINVAL;
+        rc = f.run(NVT_PQ_RUN_REPEAT, 0, (uint32_t)f.base, 0, start + done, take);
+      } else {
+        const uint64_t at = (f.npacked + 3) & ~3ull;
+        if (at + nb + 8 > f.st->packed_cap) return f.grow(2, at + nb + 8);
+        if (at + nb + 8 >= (1ull << 34)) {
+          set_error("nvt_pq_decode_chunk_dict: 16 GiB or more of packed indices in one partition");
+          return NVT_EUNSUPPORTED;
+        }
+        memset(f.st->packed + f.npacked, 0, at - f.npacked);
+        memcpy(f.st->packed + at, r.p, nb);
+        memset(f.st->packed + at + nb, 0, 8);
+        f.npacked = at + nb;
+        rc = f.run(NVT_PQ_RUN_PACKED, bw, (uint32_t)f.base, (uint32_t)(at / 4), start + done, take);
+      }
+      if (rc) return rc;
+      r.skip_bytes(groups * bw < avail ? groups * bw : avail);   // (a writer may cut the padding)
+      done += take;
+    } else {   // RLE: (head >> 1) times the value in the next ceil(bw / 8) bytes
+      uint64_t n = head >> 1;
+      const unsigned vb = (bw + 7) / 8;
+      if (n == 0 || avail < vb) return NVT_EINVAL;
+      uint64_t idx = 0;
+      memcpy(&idx, r.p, vb);
+      r.p += vb;
+      idx &= mask;
+      if (idx >= ndict) return NVT_EINVAL;
+      if (n > count - done) n = count - done;
+      const int rc = f.run(NVT_PQ_RUN_REPEAT, 0, (uint32_t)(f.base + idx), 0, start + done, n);
+      if (rc) return rc;
+      done += n;
+    }
+  }
+  return NVT_OK;
+}
+
 }  // namespace
 
 // out[i] = valid(i) ? packed[rank(i)] : 0 with rank(i) = valid rows in front of row i.
@@ -663,10 +781,12 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
                      uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
                      uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch, uint64_t scratch_bytes,
                      uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr, DeltaFill *df = nullptr,
-                     uint64_t values_offset = 0) {
+                     uint64_t values_offset = 0, DictFill *xf = nullptr) {
   // ls: a list chunk -- `rows` / expect_rows below count SLOTS, the levels go to the sink's streams
   // df: DELTA_BINARY_PACKED pages are staged there and leave a hole in values_out, whose first value
   //     is value `values_offset` of the column's packed values
+  // xf: dictionary-encoded pages are staged there (dictionary, runs, packed bytes) and leave a hole
+  //     in values_out like a delta page; the values of PLAIN pages get a KEEP record
   NVT_CHECK_ARG(chunk && values_out && rows_out && values_out_count, "null pointer");
   NVT_CHECK_ARG(type_size == 4 || type_size == 8, "values are 4 or 8 bytes");
   NVT_CHECK_ARG(ls || max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
@@ -733,6 +853,7 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       }
       dict = d;
       ndict = (uint64_t)h.dict_values;
+      if (xf && (rc = xf->dictionary(d, ndict, type_size))) return rc;
       if (codec != 0) scratch_at = ((uint64_t)h.uncompressed + 15) & ~15ull;   // (kept: pages go behind it)
       p = body + h.compressed;
       continue;
@@ -881,6 +1002,14 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
         return NVT_EINVAL;
       }
       memcpy(values_out + vals * (uint64_t)type_size, q, vbytes);
+      if (xf) {   // in place already: the device leaves these positions alone
+        const int rc = xf->run(NVT_PQ_RUN_KEEP, 0, 0, 0, values_offset + vals, pvalid);
+        if (rc) return rc;
+      }
+    } else if (xf) {   // staged as it is: the device fills the hole of pvalid values
+      const int rc = dict_index_runs(*xf, q, pend, pvalid, ndict, values_offset + vals);
+      if (rc == NVT_EINVAL) set_error("nvt_pq_decode_chunk: malformed dictionary indices");
+      if (rc) return rc;
     } else {
       const bool ok = type_size == 4
           ? decode_dict_indices<uint32_t>(q, pend, pvalid, reinterpret_cast<const uint32_t *>(dict), ndict,
@@ -989,6 +1118,31 @@ int nvt_pq_decode_chunk_delta(const uint8_t *chunk, uint64_t chunk_bytes, int co
   stage->nbytes = f.nbytes;
   stage->npages = f.npages;
   stage->nmbs = f.nmbs;
+  return NVT_OK;
+}
+
+int nvt_pq_decode_chunk_dict(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size, int max_def_level,
+                             uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
+                             uint8_t *values_out, uint64_t values_cap_bytes, uint64_t values_offset,
+                             nvt_pq_dict_stage *stage, uint8_t *scratch, uint64_t scratch_bytes,
+                             uint64_t *rows_out, uint64_t *values_count, uint64_t *need) {
+  NVT_CHECK_ARG(stage && need, "null pointer");
+  NVT_CHECK_ARG(stage->dict && stage->runs && stage->packed, "null staging buffer");
+  NVT_CHECK_ARG(stage->runs_cap >= 1 && stage->nruns < stage->runs_cap && stage->packed_cap >= 8 &&
+                    stage->npacked <= stage->packed_cap - 8 && stage->ndict_bytes <= stage->dict_cap,
+                "the stage's fill state does not fit its capacities");
+  DictFill f{stage, stage->ndict_bytes, stage->nruns, stage->npacked, need};
+  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out,
+                           valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
+                           values_count, nullptr, nullptr, values_offset, &f);
+  if (rc) return rc;
+  uint32_t *closing = stage->runs + 4 * f.nruns;   // (run() kept room for it)
+  closing[0] = (uint32_t)(values_offset + *values_count);
+  closing[1] = NVT_PQ_RUN_END;
+  closing[2] = closing[3] = 0;
+  stage->ndict_bytes = f.ndict_bytes;
+  stage->nruns = f.nruns;
+  stage->npacked = f.npacked;
   return NVT_OK;
 }
 

@@ -273,7 +273,8 @@ class Dataset:
             pf = plain_file(f)
             if pf is not None:
                 try:
-                    return StagedPartition(read_row_groups_staged(pf, groups, columns, pool=_plain_read_pool()))
+                    return StagedPartition(read_row_groups_staged(pf, groups, columns, pool=_plain_read_pool(),
+                                                                  device_dict=PQ_DEVICE_DICT))
                 except Exception as e:  # (a page kind the footer did not announce: pyarrow reads it)
                     from . import _lib
 
@@ -803,6 +804,11 @@ def _write_summary(output_path, files, schema, collector, cats, conts, labels, p
 PLAIN_PARQUET = os.environ.get("NVT_PLAIN_PARQUET", "1") != "0"
 PLAIN_PARQUET_READ = os.environ.get("NVT_PLAIN_PARQUET_READ", "1") != "0"
 PLAIN_READ_THREADS = int(os.environ.get("NVT_PARQUET_READ_THREADS", "32"))
+# dictionary pages of flat number columns: staged as the file holds them and filled on the device
+# (kernels_parquet_dict_in) instead of being resolved value by value on the host.  Off by default:
+# measured against the host route it was 5 - 8 % slower on the file it was built for
+# (profiles/parquet_dict_in_notes.md)
+PQ_DEVICE_DICT = os.environ.get("NVT_PQ_DEVICE_DICT", "0") == "1"
 _PLAIN_READ_POOL = None
 
 

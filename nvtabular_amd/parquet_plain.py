@@ -68,6 +68,10 @@ gathered on the device (``StagedStrings``, kernels_parquet_str.py; DESIGN.md, "S
 the parquet reader"), and DELTA_BINARY_PACKED pages of flat INT32 / INT64 columns: their bytes are
 staged behind one record per page and miniblock and unpacked and prefix-summed on the device
 (``StagedDelta``, kernels_parquet_delta.py; DESIGN.md, "DELTA_BINARY_PACKED in the parquet reader").
+With ``device_dict`` the dictionary pages of flat 4- and 8-byte number columns are not resolved on the
+host either: dictionary, index runs and packed bytes are staged and the device fills the values
+(``StagedDict``, kernels_parquet_dict_in.py; DESIGN.md, "Dictionary pages of number columns in the
+parquet reader").
 Binary columns, lists of strings, DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and
 delta pages of list leaves stay with pyarrow.
 parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver in front of the writer.
@@ -1129,10 +1133,14 @@ class StagedColumn:
 
     A flat INT32 / INT64 column with DELTA_BINARY_PACKED pages has ``delta`` (StagedDelta): the values of
     those pages are HOLES in ``values`` that the device fills (kernels_parquet_delta.fill_holes)
-    before anything else looks at them."""
+    before anything else looks at them.
+
+    A flat 4- / 8-byte number column read with ``device_dict`` has ``dict_stage`` (StagedDict): the
+    values of its dictionary-encoded pages are HOLES in ``values`` likewise
+    (kernels_parquet_dict_in.fill_holes); a column has ``delta`` or ``dict_stage``, never both."""
 
     __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical", "rep", "dfn", "width", "leaf_level",
-                 "max_def", "slots", "leaves", "same_as", "strs", "delta")
+                 "max_def", "slots", "leaves", "same_as", "strs", "delta", "dict_stage")
 
     def __init__(self, values, valid, rows, nvalid, dtype, logical=None, rep=None, dfn=None, width=0, leaf_level=0,
                  max_def=0, slots=0, leaves=0):
@@ -1142,6 +1150,7 @@ class StagedColumn:
         self.slots, self.leaves, self.same_as = slots, leaves, None
         self.strs = None
         self.delta = None
+        self.dict_stage = None
 
     @property
     def is_list(self):
@@ -1300,6 +1309,62 @@ class StagedDelta:
         return int(self.c.nmbs)
 
 
+class StagedDict:
+    """The staged dictionary pages of one number column of a partition, as nvt_pq_decode_chunk_dict
+    fills them (include/nvt_hip.h, nvt_pq_dict_stage): ``dict`` the chunks' dictionaries (each behind
+    a 16-byte head that holds its entry count), ``runs`` the run table (int32 words, 4 per record, the
+    closing record behind the ``nruns`` runs), ``packed`` the bytes of the bit-packed runs.  Sized
+    from the footer and enlarged when the decoder asks for it.  ``where`` names file and column for
+    error messages."""
+
+    def __init__(self, dict_cap, runs_cap, packed_cap, pinned, where):
+        import torch
+
+        from . import _lib
+
+        self.pinned, self.where = pinned, where
+        self.dict = torch.empty((dict_cap + 15) & ~15, dtype=torch.uint8, pin_memory=pinned)
+        self.runs = torch.empty(4 * max(1, runs_cap), dtype=torch.int32, pin_memory=pinned)
+        self.packed = torch.empty(((packed_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
+        self.c = _lib.PqDictStage()
+        self._bind()
+
+    def _bind(self):
+        c = self.c
+        c.dict, c.runs, c.packed = self.dict.data_ptr(), self.runs.data_ptr(), self.packed.data_ptr()
+        c.dict_cap, c.runs_cap, c.packed_cap = self.dict.numel(), self.runs.numel() // 4, self.packed.numel()
+
+    def grow(self, need):
+        """Enlarges the buffers named by ``need`` = (dict bytes, runs, packed bytes), 0 = large enough,
+        keeping what is filled."""
+        import torch
+
+        c = self.c
+        for which, want in enumerate(need):
+            if not want:
+                continue
+            name, used, words = (("dict", c.ndict_bytes, 1), ("runs", 4 * (c.nruns + 1), 4),
+                                 ("packed", c.npacked + 8, 1))[which]
+            old = getattr(self, name)
+            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
+            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
+            new[:used] = old[:used]
+            setattr(self, name, new)
+        self._bind()
+
+    @property
+    def ndict_bytes(self):
+        return int(self.c.ndict_bytes)
+
+    @property
+    def nruns(self):
+        return int(self.c.nruns)
+
+    @property
+    def npacked(self):
+        return int(self.c.npacked)
+
+
 class StagedPartition:
     """A partition as ``read_row_groups_staged`` leaves it on the host: {column: StagedColumn}.
     ``to_device`` enqueues the copies on the CURRENT stream (the prefetcher's side stream) and
@@ -1331,6 +1396,16 @@ class StagedPartition:
             filled = {name: KPD.values_to_device(sc, device) for name, sc in self.columns.items()
                       if sc.delta is not None}
             KPD.fill_holes([(self.columns[name].delta, packed) for name, packed in filled.items()])
+        # columns with staged dictionary pages: the same, and ONE launch for all of them; the count of
+        # indices outside their dictionaries is read once, behind everything else this call enqueues
+        dict_bad = None
+        if device.type == "cuda" and any(sc.dict_stage is not None for sc in self.columns.values()):
+            from . import kernels_parquet_dict_in as KDI
+
+            staged = {name: KDI.values_to_device(sc, device) for name, sc in self.columns.items()
+                      if sc.dict_stage is not None}
+            dict_bad = KDI.fill_holes([(self.columns[name].dict_stage, packed) for name, packed in staged.items()])
+            filled.update(staged)
         for name, sc in self.columns.items():
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
                 raise K._lib.NvtHipError("StagedPartition.to_device needs a GPU")
@@ -1369,6 +1444,11 @@ class StagedPartition:
             else:
                 bitmap = sc.valid[: ((sc.rows + 63) // 64) * 8].to(device, non_blocking=True)
                 out[name] = DeviceColumn(K.expand_valid(packed, bitmap, sc.rows), bitmap, logical=sc.logical)
+        if dict_bad is not None:
+            nbad = int(dict_bad.cpu().numpy()[0])
+            if nbad:
+                where = next(sc.dict_stage.where for sc in self.columns.values() if sc.dict_stage is not None)
+                raise ValueError(f"{where}: {nbad} dictionary indices outside the entries of their pages")
         return DeviceFrame(out)
 
 
@@ -1393,7 +1473,7 @@ def _scratch(slot: str, nbytes: int) -> bytearray:
 READER_CHUNKS = {"plain": 0, "pyarrow": 0}
 
 
-def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True):
+def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True, device_dict=False):
     """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of a decodable
     file.  One task per column: pread of a chunk into a scratch buffer, then nvt_pq_decode_chunk
     (ctypes: GIL released) moves its values and validity bits to their place in the partition's
@@ -1401,7 +1481,12 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
     appends their levels to the column's two level streams instead, a string column's through
     nvt_pq_decode_str_chunk, which appends entries, index runs and packed bytes to a StagedStrings, a
     flat integer chunk whose footer lists DELTA_BINARY_PACKED through nvt_pq_decode_chunk_delta, which
-    stages its delta pages in a StagedDelta and leaves holes for their values."""
+    stages its delta pages in a StagedDelta and leaves holes for their values.
+
+    ``device_dict``: a flat 4- / 8-byte number column (int8 / int16 and timestamps included) none of
+    whose chunks is flagged ``delta`` and one of whose chunks lists a dictionary encoding goes through
+    nvt_pq_decode_chunk_dict with ALL its chunks: dictionary pages are staged in a StagedDict
+    (``StagedColumn.dict_stage``) and leave holes in ``values``, PLAIN pages are decoded in place."""
     import ctypes as C
 
     import torch
@@ -1512,10 +1597,31 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if pf.max_def[j]:
             valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         row_at = val_at = 0
-        delta = None
+        delta = dstage = None
+        if device_dict and dt != BOOL_DTYPE:
+            ccs = [pf.row_groups[x]["columns"][j] for x in groups if pf.row_groups[x]["num_rows"]]
+            if any(x.get("dictionary") for x in ccs) and not any(x.get("delta") for x in ccs):
+                # from the footer: pyarrow keeps a dictionary under 1 MiB and its runs hold 8 values or
+                # more; a file that goes beyond makes the decoder ask
+                raw = [max(x.get("raw_size", 0), x["size"]) for x in ccs]
+                nv = sum(x["num_values"] for x in ccs)
+                dstage = StagedDict(sum(min(x, (1 << 20) + 4096) + 32 for x in raw),
+                                    min(sum(raw) // 2, nv // 8) + 1024, sum(raw) + nv // 64 + 4096, pinned,
+                                    f"{pf.path}: column {n!r}")
         for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
             r, v = C.c_uint64(), C.c_uint64()
-            if cc.get("delta"):   # (flat INT32 / INT64 chunks only: _judge_chunk)
+            if dstage is not None:
+                fn, need = "nvt_pq_decode_chunk_dict", (C.c_uint64 * 3)()
+                while True:
+                    rc = lib.nvt_pq_decode_chunk_dict(cbuf, cc["size"], cc.get("codec", 0), st.itemsize, pf.max_def[j],
+                                                      rows, valid.data_ptr() if valid is not None else None, row_at,
+                                                      vals.data_ptr() + val_at * st.itemsize,
+                                                      (total - val_at) * st.itemsize, val_at, C.byref(dstage.c),
+                                                      sbuf, sbytes, C.byref(r), C.byref(v), need)
+                    if rc != _lib.PQ_DICT_GROW:
+                        break
+                    dstage.grow(tuple(int(x) for x in need))
+            elif cc.get("delta"):   # (flat INT32 / INT64 chunks only: _judge_chunk)
                 # the footer lists DELTA_BINARY_PACKED: such pages are staged for the device and leave
                 # holes in ``vals``; the chunk's other pages are decoded as below
                 if delta is None:
@@ -1554,6 +1660,9 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         sc = StagedColumn(vals, valid if (valid is not None and val_at < total) else None, total, val_at, dt,
                           logical)
         sc.delta = delta if (delta is not None and delta.npages) else None
+        if dstage is not None:   # (KEEP records only: the host has decoded every page, nothing is staged)
+            kinds = dstage.runs[1: 4 * dstage.nruns: 4].numpy() & 0xFF
+            sc.dict_stage = dstage if bool((kinds != _lib.PQ_RUN_KEEP).any()) else None
         return sc
 
     futs = []
