@@ -1019,6 +1019,67 @@ int nvt_pq_decode_chunk_dict(const uint8_t *chunk, uint64_t chunk_bytes, int cod
 int nvt_pq_dict_fill_many(const nvt_pq_dict_col *cols, int ncols, const uint32_t *groups, uint64_t ngroups,
                           uint32_t *bad, void *stream);
 
+/* ---- parquet in: snappy bodies of PLAIN data pages, inflated on the device ("Snappy
+ * pages in the parquet reader") ----
+ * nvt_snappy_inflate_pages (device): page i's raw snappy stream src[src_at, src_at + src_bytes) --
+ * varint(inflated length) | elements -- is inflated by one wave, and its VALUES are written to
+ * dst[dst_at, dst_at + dst_bytes): the whole inflated stream, or with NVT_INFLATE_V1_LEVELS what
+ * follows its first 4 + L bytes (u32 L | L bytes of definition levels: a v1 data page of an optional
+ * column; those bytes may be copied from, they are never stored).  src, dst, pages and status are
+ * DEVICE memory; pages 8-byte aligned, status 4-byte aligned, src_at / dst_at at any alignment (a
+ * 16-byte aligned body loads fastest).  status[i] = 0, or the reason page i stopped:
+ *   NVT_INFLATE_TRUNCATED  the input ends inside an element (or holds no length)
+ *   NVT_INFLATE_OFFSET     a copy with offset 0 or an offset beyond the bytes produced so far
+ *   NVT_INFLATE_LENGTH     the elements produce more or fewer bytes than the varint says, or the
+ *                          inflated length minus the dropped prefix is not dst_bytes (a page WITH nulls
+ *                          fails here: its values are fewer than dst_bytes); sizes of 2^31 - 17 and more
+ *   NVT_INFLATE_FAR        a copy offset above 65536: the format allows it, the compressors that cut
+ *                          their input into 64 KiB blocks (google-snappy, snappy-java, Go) never emit it
+ * The first failing element in stream order decides.  A page that stops may have written a part of
+ * its own dst range; no byte outside [dst_at, dst_at + dst_bytes) is written for any page, and nothing
+ * outside [src_at, src_at + src_bytes) is read.  npages == 0 launches nothing; npages < 2^31.  No
+ * read-back; `stream` only.
+ *
+ * nvt_pq_decode_chunk_inflate (HOST, no GPU call, thread-safe; one thread per stage):
+ * nvt_pq_decode_chunk_codec, but a data page is NOT inflated when the chunk is SNAPPY, the page PLAIN
+ * with a non-empty body and known to hold no nulls: max_def_level == 0; a v2 header with num_nulls ==
+ * 0, is_compressed and a values region of num_values * type_size bytes; a v1 header whose statistics
+ * say null_count == 0; without page statistics, chunk_nulls == 0 (the footer's null_count of the
+ * chunk; -1: unknown).  Such a page's compressed body (v2: its values region) is appended to the
+ * stage on a 16-byte boundary with a record {src_at in `bytes`, src_bytes, dst_at = the byte position
+ * of its values among the column's packed values, values_offset = the position of values_out[0] among
+ * them, dst_bytes, flags}; its values are a HOLE in values_out and its rows' validity bits are set.
+ * Every other page is decoded in place.  The stage advances on NVT_OK only.  NVT_PQ_INFLATE_GROW: a
+ * staging buffer is too small -- need[2] = {bytes, pages} holds a capacity that reaches further for
+ * that buffer (0 for the other); the caller enlarges it, keeps the filled part and calls again with
+ * the same chunk. */
+#define NVT_INFLATE_V1_LEVELS 1u
+#define NVT_INFLATE_TRUNCATED 1u
+#define NVT_INFLATE_OFFSET 2u
+#define NVT_INFLATE_LENGTH 3u
+#define NVT_INFLATE_FAR 4u
+#define NVT_PQ_INFLATE_GROW 1
+typedef struct nvt_inflate_page {
+  uint64_t src_at, src_bytes;   /* the page's compressed body inside `src` */
+  uint64_t dst_at, dst_bytes;   /* where its VALUES go inside `dst`, and how many bytes */
+  uint32_t flags;               /* NVT_INFLATE_V1_LEVELS */
+  uint32_t pad;
+} nvt_inflate_page;
+typedef struct nvt_pq_inflate_stage {
+  uint8_t *bytes;
+  nvt_inflate_page *pages;
+  uint64_t bytes_cap, pages_cap;   /* bytes, records */
+  uint64_t nbytes, npages;
+} nvt_pq_inflate_stage;
+int nvt_snappy_inflate_pages(const uint8_t *src, uint8_t *dst, const nvt_inflate_page *pages, uint64_t npages,
+                             uint32_t *status, void *stream);
+int nvt_pq_decode_chunk_inflate(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
+                                int max_def_level, uint64_t expect_rows, uint8_t *valid_out,
+                                uint64_t valid_bit_offset, uint8_t *values_out, uint64_t values_cap_bytes,
+                                uint64_t values_offset, int64_t chunk_nulls, nvt_pq_inflate_stage *stage,
+                                uint8_t *scratch, uint64_t scratch_bytes, uint64_t *rows_out,
+                                uint64_t *values_count, uint64_t *need);
+
 /* ---- batched entry points: ONE call per operator per partition -----------------------
  * The reference hands a whole dataframe to the backend per operator call
  * (`df[cols].fillna(...)`, `for col in columns: _encode(...)` -- categorify.py:477-537,

@@ -516,6 +516,25 @@ SIGNATURES.update({
 })
 
 
+class PqInflateStage(C.Structure):
+    """nvt_pq_inflate_stage: the staged snappy bodies of one number column of a partition, their page
+    records and how far the buffers are filled (nvt_pq_decode_chunk_inflate)."""
+    _fields_ = [("bytes", _vp), ("pages", _vp), ("bytes_cap", _u64), ("pages_cap", _u64), ("nbytes", _u64),
+                ("npages", _u64)]
+
+
+# include/nvt_hip.h NVT_INFLATE_* / NVT_PQ_INFLATE_GROW; PAGE_WORDS: the 8-byte words of nvt_inflate_page
+# {src_at, src_bytes, dst_at, dst_bytes, flags | pad << 32} (pinned by a static_assert in nvt_snappy_inflate.hip)
+INFLATE_V1_LEVELS, PQ_INFLATE_GROW, INFLATE_PAGE_WORDS = 1, 1, 5
+INFLATE_ERRORS = {1: "TRUNCATED", 2: "OFFSET", 3: "LENGTH", 4: "FAR"}
+SIGNATURES.update({
+    "nvt_snappy_inflate_pages": [_vp, _vp, _vp, _u64, _vp, _vp],
+    "nvt_pq_decode_chunk_inflate": [_vp, _u64, _i32, _i32, _i32, _u64, _vp, _u64, _vp, _u64, _u64, C.c_int64,
+                                    C.POINTER(PqInflateStage), _vp, _u64, C.POINTER(_u64), C.POINTER(_u64),
+                                    C.POINTER(_u64)],
+})
+
+
 class PartitionSeg(C.Structure):
     """nvt_partition_seg: one segment of an output partition (a DEVICE array of these is passed)."""
     _fields_ = [("idx", _vp), ("start", _u64)]

@@ -38,6 +38,11 @@
 //     bit-packed runs, and the device fills the hole the page leaves (nvt_pq_dict_fill_many,
 //     nvt_parquet_dict_in.hip).
 //
+//   snappy bodies of PLAIN pages without nulls (flat 4- / 8-byte number columns):
+//     nvt_pq_decode_chunk_inflate walks the same pages but does not inflate such a body: it is staged
+//     compressed with a record per page, and the device inflates it into the hole the page leaves
+//     (nvt_snappy_inflate_pages, nvt_snappy_inflate.hip).
+//
 // Anything else in a chunk (other codecs / encodings, other nesting) is reported as
 // NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
 #include <hip/hip_runtime.h>
@@ -142,6 +147,7 @@ struct PageHead {
   int64_t uncompressed = 0, compressed = 0;
   int64_t num_values = 0;   // rows of the page (flat columns)
   int encoding = -1, def_encoding = -1, rep_encoding = -1;
+  int64_t stat_nulls = -1;  // v1: DataPageHeader.statistics.null_count, -1 when the header has none
   // v2
   int64_t num_nulls = -1, def_bytes = 0, rep_bytes = 0;
   bool v2_compressed = false;
@@ -163,7 +169,12 @@ bool read_page_header(TReader &r, PageHead &h) {
         else if (f2 == 2 && t2 == 5) h.encoding = (int)r.zigzag();
         else if (f2 == 3 && t2 == 5) h.def_encoding = (int)r.zigzag();
         else if (f2 == 4 && t2 == 5) h.rep_encoding = (int)r.zigzag();
-        else r.skip(t2);
+        else if (f2 == 5 && t2 == 12) {  // Statistics
+          int f3 = 0, t3 = 0;
+          while (r.field(f3, t3)) {
+            if (f3 == 3 && t3 == 6) h.stat_nulls = r.zigzag(); else r.skip(t3);
+          }
+        } else r.skip(t2);
       }
     } else if (fid == 7 && type == 12) {  // DictionaryPageHeader
       int f2 = 0, t2 = 0;
@@ -483,6 +494,35 @@ int delta_stage_page(DeltaFill &f, const uint8_t *q, uint64_t nbytes, int type_s
   return NVT_OK;
 }
 
+// ---- snappy bodies of PLAIN pages: staged, not inflated ("Snappy pages in the parquet
+// reader") ---------------------------------------------------------------------------------------
+// the fill state of a nvt_pq_inflate_stage during one chunk: committed to the stage on NVT_OK only, so
+// a chunk that asked for larger buffers is decoded again from its first byte
+struct InflateFill {
+  nvt_pq_inflate_stage *st;
+  uint64_t nbytes, npages;
+  uint64_t *need;
+  int64_t chunk_nulls;   // the footer's null_count of the chunk, -1: it has none
+  // one compressed body on a 16-byte boundary and its record
+  int page(const uint8_t *body, uint64_t n, uint64_t dst_at, uint64_t dst_bytes, uint32_t flags) {
+    const uint64_t at = (nbytes + 15) & ~15ull;
+    need[0] = need[1] = 0;
+    if (at + n > st->bytes_cap) {
+      need[0] = at + n;
+      return NVT_PQ_INFLATE_GROW;
+    }
+    if (npages + 1 > st->pages_cap) {
+      need[1] = npages + 1;
+      return NVT_PQ_INFLATE_GROW;
+    }
+    memset(st->bytes + nbytes, 0, at - nbytes);
+    memcpy(st->bytes + at, body, n);
+    st->pages[npages++] = nvt_inflate_page{at, n, dst_at, dst_bytes, flags, 0};
+    nbytes = at + n;
+    return NVT_OK;
+  }
+};
+
 // ---- snappy, raw block format (what parquet's SNAPPY codec holds per page) --------------------
 // -> uncompressed bytes written, or -1 on malformed input / a block that does not fit `cap`
 int64_t snappy_uncompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap) {
@@ -781,7 +821,9 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
                      uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
                      uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch, uint64_t scratch_bytes,
                      uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr, DeltaFill *df = nullptr,
-                     uint64_t values_offset = 0, DictFill *xf = nullptr) {
+                     uint64_t values_offset = 0, DictFill *xf = nullptr, InflateFill *zf = nullptr) {
+  // zf: the snappy body of a PLAIN page that holds no nulls is staged there as it is and leaves a hole
+  //     in values_out like a delta page; the page's rows are all valid
   // ls: a list chunk -- `rows` / expect_rows below count SLOTS, the levels go to the sink's streams
   // df: DELTA_BINARY_PACKED pages are staged there and leave a hole in values_out, whose first value
   //     is value `values_offset` of the column's packed values
@@ -883,7 +925,16 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
     }
     const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
     uint64_t pvalid = prow;
-    if (h.type == 0) {   // v1: levels and values are compressed together
+    // staged for the device: a non-empty snappy body of PLAIN values that is known to hold no nulls
+    bool staged = zf != nullptr && ls == nullptr && codec == 1 && h.encoding == 0 && prow > 0;
+    if (staged && h.type == 0)
+      // (levels in another encoding than the RLE hybrid have no u32 L in front: the host branch refuses them)
+      staged = h.compressed > 0 &&
+               (max_def_level == 0 ||
+                (h.def_encoding == 3 && (h.stat_nulls == 0 || (h.stat_nulls < 0 && zf->chunk_nulls == 0))));
+    if (staged && h.type == 0) {   // v1: the levels (u32 L | L bytes) are inside the body; the device drops them
+      if (max_def_level == 1) bits_fill(valid_out, valid_bit_offset + rows, prow, true);
+    } else if (h.type == 0) {   // v1: levels and values are compressed together
       const uint8_t *u = nullptr;
       int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
       if (rc) return rc;
@@ -952,7 +1003,11 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
         return NVT_EINVAL;
       }
       const uint64_t lbytes = (uint64_t)h.rep_bytes + (uint64_t)h.def_bytes;
-      if (ls) {
+      staged = staged && h.v2_compressed && (max_def_level == 0 || h.num_nulls == 0) &&
+               (uint64_t)h.compressed > lbytes && (uint64_t)h.uncompressed - lbytes == prow * (uint64_t)type_size;
+      if (staged) {   // all rows valid by num_nulls: the levels are not looked at
+        if (max_def_level == 1) bits_fill(valid_out, valid_bit_offset + rows, prow, true);
+      } else if (ls) {
         uint64_t rh[4] = {0, 0, 0, 0}, hist[4] = {0, 0, 0, 0};
         int bad = decode_levels_wide(body, (uint64_t)h.rep_bytes, prow, 1, 1, ls->rep, ls->slot0 + rows, rh);
         if (!bad)
@@ -972,13 +1027,15 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
           return NVT_EINVAL;
         }
       }
-      const uint8_t *u = nullptr;
       const uint64_t vcomp = (uint64_t)h.compressed - lbytes;
       const uint64_t vraw = (uint64_t)h.uncompressed - lbytes;
-      int rc = inflate(body + lbytes, vcomp, vraw, codec != 0 && h.v2_compressed, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + vraw;
+      if (!staged) {
+        const uint8_t *u = nullptr;
+        int rc = inflate(body + lbytes, vcomp, vraw, codec != 0 && h.v2_compressed, &u);
+        if (rc) return rc;
+        q = u;
+        pend = u + vraw;
+      }
     }
     if (ls && rows == 0 && prow > 0 && ((ls->rep[ls->slot0 >> 3] >> (ls->slot0 & 7)) & 1)) {
       set_error("nvt_pq_decode_list_chunk: the chunk's first slot continues a row");
@@ -988,7 +1045,13 @@ static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int 
       set_error("nvt_pq_decode_chunk: values buffer too small");
       return NVT_EINVAL;
     }
-    if (by_delta) {   // staged as it is: the device fills the hole of pvalid values
+    if (staged) {   // the compressed body (v2: its values region) as it is: the device fills the hole of prow values
+      const uint64_t lead = h.type == 3 ? (uint64_t)h.rep_bytes + (uint64_t)h.def_bytes : 0;
+      const int rc = zf->page(body + lead, (uint64_t)h.compressed - lead, (values_offset + vals) * (uint64_t)type_size,
+                              prow * (uint64_t)type_size,
+                              (h.type == 0 && max_def_level == 1) ? NVT_INFLATE_V1_LEVELS : 0u);
+      if (rc) return rc;
+    } else if (by_delta) {   // staged as it is: the device fills the hole of pvalid values
       const int rc = delta_stage_page(*df, q, (uint64_t)(pend - q), type_size, pvalid, values_offset + vals);
       if (rc) return rc;
     } else if (!by_dict) {
@@ -1143,6 +1206,26 @@ int nvt_pq_decode_chunk_dict(const uint8_t *chunk, uint64_t chunk_bytes, int cod
   stage->ndict_bytes = f.ndict_bytes;
   stage->nruns = f.nruns;
   stage->npacked = f.npacked;
+  return NVT_OK;
+}
+
+int nvt_pq_decode_chunk_inflate(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
+                                int max_def_level, uint64_t expect_rows, uint8_t *valid_out,
+                                uint64_t valid_bit_offset, uint8_t *values_out, uint64_t values_cap_bytes,
+                                uint64_t values_offset, int64_t chunk_nulls, nvt_pq_inflate_stage *stage,
+                                uint8_t *scratch, uint64_t scratch_bytes, uint64_t *rows_out,
+                                uint64_t *values_count, uint64_t *need) {
+  NVT_CHECK_ARG(stage && need, "null pointer");
+  NVT_CHECK_ARG(stage->bytes && stage->pages, "null staging buffer");
+  NVT_CHECK_ARG(stage->nbytes <= stage->bytes_cap && stage->npages <= stage->pages_cap,
+                "the stage's fill state does not fit its capacities");
+  InflateFill f{stage, stage->nbytes, stage->npages, need, chunk_nulls};
+  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out,
+                           valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
+                           values_count, nullptr, nullptr, values_offset, nullptr, &f);
+  if (rc) return rc;
+  stage->nbytes = f.nbytes;
+  stage->npages = f.npages;
   return NVT_OK;
 }
 

@@ -274,7 +274,8 @@ class Dataset:
             if pf is not None:
                 try:
                     return StagedPartition(read_row_groups_staged(pf, groups, columns, pool=_plain_read_pool(),
-                                                                  device_dict=PQ_DEVICE_DICT))
+                                                                  device_dict=PQ_DEVICE_DICT,
+                                                                  device_inflate=PQ_DEVICE_INFLATE))
                 except Exception as e:  # (a page kind the footer did not announce: pyarrow reads it)
                     from . import _lib
 
@@ -809,6 +810,11 @@ PLAIN_READ_THREADS = int(os.environ.get("NVT_PARQUET_READ_THREADS", "32"))
 # measured against the host route it was 5 - 8 % slower on the file it was built for
 # (profiles/parquet_dict_in_notes.md)
 PQ_DEVICE_DICT = os.environ.get("NVT_PQ_DEVICE_DICT", "0") == "1"
+# snappy bodies of PLAIN pages without nulls (flat 4- / 8-byte number columns): staged compressed and
+# inflated on the device (kernels_parquet_inflate) instead of by the read pool's threads.  Off by
+# default: measured against the parent commit no file read faster, pyarrow's default file 30 - 40 %
+# slower (profiles/parquet_inflate_notes.md)
+PQ_DEVICE_INFLATE = os.environ.get("NVT_PQ_DEVICE_INFLATE", "0") == "1"
 _PLAIN_READ_POOL = None
 
 

@@ -72,6 +72,9 @@ With ``device_dict`` the dictionary pages of flat 4- and 8-byte number columns a
 host either: dictionary, index runs and packed bytes are staged and the device fills the values
 (``StagedDict``, kernels_parquet_dict_in.py; DESIGN.md, "Dictionary pages of number columns in the
 parquet reader").
+With ``device_inflate`` the snappy bodies of PLAIN pages without nulls of such columns are not inflated
+on the host: they are staged compressed and the device inflates them into the values
+(``StagedInflate``, kernels_parquet_inflate.py; DESIGN.md, "Snappy pages in the parquet reader").
 Binary columns, lists of strings, DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and
 delta pages of list leaves stay with pyarrow.
 parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver in front of the writer.
@@ -989,6 +992,8 @@ def _judge_chunk(cc, col, file_size):
     path = [x.decode() for x in md.get(3, [])]
     c = dict(offset=first, size=int(md.get(7, 0)), num_values=int(md.get(5, 0)), codec=int(md.get(4, 0)),
              raw_size=int(md.get(6, 0)), dictionary=bool(dpo is not None or (enc & {2, 8})), path=path)
+    stats = md.get(12)   # ColumnMetaData.statistics; null_count: -1 where the footer does not say
+    c["null_count"] = int(stats[3]) if isinstance(stats, dict) and isinstance(stats.get(3), int) else -1
     # codec 0 UNCOMPRESSED / 1 SNAPPY; encodings PLAIN 0, PLAIN_DICTIONARY 2, RLE 3, BIT_PACKED 4,
     # RLE_DICTIONARY 8 (nvt_pq_decode_chunk_codec), DELTA_BINARY_PACKED 5 (nvt_pq_decode_chunk_delta)
     if not (md.get(4) in (0, 1) and enc <= {0, 2, 3, 4, 5, 8} and cc.get(1) in (None, b"")):
@@ -1137,10 +1142,15 @@ class StagedColumn:
 
     A flat 4- / 8-byte number column read with ``device_dict`` has ``dict_stage`` (StagedDict): the
     values of its dictionary-encoded pages are HOLES in ``values`` likewise
-    (kernels_parquet_dict_in.fill_holes); a column has ``delta`` or ``dict_stage``, never both."""
+    (kernels_parquet_dict_in.fill_holes); a column has ``delta`` or ``dict_stage``, never both.
+
+    A flat 4- / 8-byte number column read with ``device_inflate`` has ``inflate`` (StagedInflate) when
+    snappy bodies of its PLAIN pages were staged compressed: their values are HOLES in ``values``
+    likewise (kernels_parquet_inflate.fill_holes); such a column has neither ``delta`` nor
+    ``dict_stage``."""
 
     __slots__ = ("values", "valid", "rows", "nvalid", "dtype", "logical", "rep", "dfn", "width", "leaf_level",
-                 "max_def", "slots", "leaves", "same_as", "strs", "delta", "dict_stage")
+                 "max_def", "slots", "leaves", "same_as", "strs", "delta", "dict_stage", "inflate")
 
     def __init__(self, values, valid, rows, nvalid, dtype, logical=None, rep=None, dfn=None, width=0, leaf_level=0,
                  max_def=0, slots=0, leaves=0):
@@ -1151,6 +1161,7 @@ class StagedColumn:
         self.strs = None
         self.delta = None
         self.dict_stage = None
+        self.inflate = None
 
     @property
     def is_list(self):
@@ -1365,6 +1376,60 @@ class StagedDict:
         return int(self.c.npacked)
 
 
+class StagedInflate:
+    """The staged snappy bodies of one number column of a partition, as nvt_pq_decode_chunk_inflate
+    fills them (include/nvt_hip.h, nvt_pq_inflate_stage): ``bytes`` the compressed bodies of its PLAIN
+    pages without nulls, each on a 16-byte boundary, ``pages`` 5 int64 words per page (nvt_inflate_page:
+    {src_at in ``bytes``, src_bytes, dst_at = byte position among the column's packed values, dst_bytes,
+    flags}).  Sized from the footer and enlarged when the decoder asks for it.  ``where`` names file and
+    column for error messages."""
+
+    def __init__(self, bytes_cap, pages_cap, pinned, where):
+        import torch
+
+        from . import _lib
+
+        self.pinned, self.where, self.words = pinned, where, _lib.INFLATE_PAGE_WORDS
+        self.bytes = torch.empty(((bytes_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
+        self.pages = torch.empty(self.words * max(1, pages_cap), dtype=torch.int64, pin_memory=pinned)
+        self.c = _lib.PqInflateStage()
+        self._bind()
+
+    def _bind(self):
+        c = self.c
+        c.bytes, c.pages = self.bytes.data_ptr(), self.pages.data_ptr()
+        c.bytes_cap, c.pages_cap = self.bytes.numel(), self.pages.numel() // self.words
+
+    def grow(self, need):
+        """Enlarges the buffers named by ``need`` = (bytes, pages), 0 = large enough, keeping what is
+        filled."""
+        import torch
+
+        c, W = self.c, self.words
+        for which, want in enumerate(need):
+            if not want:
+                continue
+            name, used, words = (("bytes", c.nbytes, 1), ("pages", W * c.npages, W))[which]
+            old = getattr(self, name)
+            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
+            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
+            new[:used] = old[:used]
+            setattr(self, name, new)
+        self._bind()
+
+    @property
+    def nbytes(self):
+        return int(self.c.nbytes)
+
+    @property
+    def npages(self):
+        return int(self.c.npages)
+
+    def records(self):
+        """The page table: int64 [npages, 5] (a view of ``pages``)."""
+        return self.pages[: self.words * self.npages].numpy().reshape(-1, self.words)
+
+
 class StagedPartition:
     """A partition as ``read_row_groups_staged`` leaves it on the host: {column: StagedColumn}.
     ``to_device`` enqueues the copies on the CURRENT stream (the prefetcher's side stream) and
@@ -1405,6 +1470,16 @@ class StagedPartition:
             staged = {name: KDI.values_to_device(sc, device) for name, sc in self.columns.items()
                       if sc.dict_stage is not None}
             dict_bad = KDI.fill_holes([(self.columns[name].dict_stage, packed) for name, packed in staged.items()])
+            filled.update(staged)
+        # columns with staged snappy bodies: the same, ONE launch inflates all their pages; the status
+        # words are read once, behind everything else this call enqueues
+        inflated = None
+        if device.type == "cuda" and any(sc.inflate is not None for sc in self.columns.values()):
+            from . import kernels_parquet_inflate as KPI
+
+            staged = {name: KPI.values_to_device(sc, device) for name, sc in self.columns.items()
+                      if sc.inflate is not None}
+            inflated = KPI.fill_holes([(self.columns[name].inflate, packed) for name, packed in staged.items()])
             filled.update(staged)
         for name, sc in self.columns.items():
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
@@ -1449,6 +1524,8 @@ class StagedPartition:
             if nbad:
                 where = next(sc.dict_stage.where for sc in self.columns.values() if sc.dict_stage is not None)
                 raise ValueError(f"{where}: {nbad} dictionary indices outside the entries of their pages")
+        if inflated is not None:
+            KPI.raise_failed(inflated)
         return DeviceFrame(out)
 
 
@@ -1470,10 +1547,12 @@ def _scratch(slot: str, nbytes: int) -> bytearray:
 
 # column chunks decoded by the hand-written reader / left to pyarrow since the process started
 # (bench.py's end_to_end entry reports them: a fallback must not be silent)
-READER_CHUNKS = {"plain": 0, "pyarrow": 0}
+# "inflate_pages": data pages whose snappy bodies were staged for the device (device_inflate)
+READER_CHUNKS = {"plain": 0, "pyarrow": 0, "inflate_pages": 0}
 
 
-def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True, device_dict=False):
+def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None, pin=True, device_dict=False,
+                           device_inflate=False):
     """{column: StagedColumn} for the concatenation of `groups` (row-group indices) of a decodable
     file.  One task per column: pread of a chunk into a scratch buffer, then nvt_pq_decode_chunk
     (ctypes: GIL released) moves its values and validity bits to their place in the partition's
@@ -1486,7 +1565,13 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
     ``device_dict``: a flat 4- / 8-byte number column (int8 / int16 and timestamps included) none of
     whose chunks is flagged ``delta`` and one of whose chunks lists a dictionary encoding goes through
     nvt_pq_decode_chunk_dict with ALL its chunks: dictionary pages are staged in a StagedDict
-    (``StagedColumn.dict_stage``) and leave holes in ``values``, PLAIN pages are decoded in place."""
+    (``StagedColumn.dict_stage``) and leave holes in ``values``, PLAIN pages are decoded in place.
+
+    ``device_inflate``: the SNAPPY chunks of a flat 4- / 8-byte number column that would otherwise go
+    through nvt_pq_decode_chunk_codec (not bool, not flagged ``delta``, not on the ``device_dict``
+    route) go through nvt_pq_decode_chunk_inflate: the snappy bodies of their PLAIN pages without nulls
+    are staged compressed in a StagedInflate (``StagedColumn.inflate``) and leave holes in ``values``,
+    every other page is decoded in place.  ``READER_CHUNKS["inflate_pages"]`` counts the staged pages."""
     import ctypes as C
 
     import torch
@@ -1597,7 +1682,10 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if pf.max_def[j]:
             valid = torch.zeros(((total + 63) // 64) * 8 + 8, dtype=torch.uint8, pin_memory=pinned)
         row_at = val_at = 0
-        delta = dstage = None
+        delta = dstage = zstage = None
+        # (a column with a delta chunk keeps ONE kind of hole: its other chunks are inflated on the host)
+        inflate_ok = device_inflate and dt != BOOL_DTYPE and not any(
+            pf.row_groups[x]["columns"][j].get("delta") for x in groups if pf.row_groups[x]["num_rows"])
         if device_dict and dt != BOOL_DTYPE:
             ccs = [pf.row_groups[x]["columns"][j] for x in groups if pf.row_groups[x]["num_rows"]]
             if any(x.get("dictionary") for x in ccs) and not any(x.get("delta") for x in ccs):
@@ -1640,6 +1728,26 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
                     if rc != _lib.PQ_DELTA_GROW:
                         break
                     delta.grow(tuple(int(x) for x in need))
+            elif inflate_ok and cc.get("codec", 0) == 1:
+                # PLAIN pages without nulls keep their snappy bodies: staged for the device, they leave
+                # holes in ``vals``; the chunk's other pages are decoded as below
+                if zstage is None:
+                    ccs = [pf.row_groups[x]["columns"][j] for x in groups if pf.row_groups[x]["num_rows"]]
+                    # from the footer: the compressed chunks, and pyarrow's pages hold 1 MiB of values
+                    zstage = StagedInflate(sum(x["size"] + 64 for x in ccs),
+                                           sum(x.get("raw_size", 0) for x in ccs) // (1 << 20) + 4 * len(ccs) + 16,
+                                           pinned, f"{pf.path}: column {n!r}")
+                fn, need = "nvt_pq_decode_chunk_inflate", (C.c_uint64 * 2)()
+                while True:
+                    rc = lib.nvt_pq_decode_chunk_inflate(cbuf, cc["size"], 1, st.itemsize, pf.max_def[j], rows,
+                                                         valid.data_ptr() if valid is not None else None, row_at,
+                                                         vals.data_ptr() + val_at * st.itemsize,
+                                                         (total - val_at) * st.itemsize, val_at,
+                                                         cc.get("null_count", -1), C.byref(zstage.c), sbuf, sbytes,
+                                                         C.byref(r), C.byref(v), need)
+                    if rc != _lib.PQ_INFLATE_GROW:
+                        break
+                    zstage.grow(tuple(int(x) for x in need))
             elif dt == BOOL_DTYPE:
                 fn = "nvt_pq_decode_bool_chunk"
                 rc = lib.nvt_pq_decode_bool_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
@@ -1663,6 +1771,9 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         if dstage is not None:   # (KEEP records only: the host has decoded every page, nothing is staged)
             kinds = dstage.runs[1: 4 * dstage.nruns: 4].numpy() & 0xFF
             sc.dict_stage = dstage if bool((kinds != _lib.PQ_RUN_KEEP).any()) else None
+        if zstage is not None and zstage.npages:
+            sc.inflate = zstage
+            READER_CHUNKS["inflate_pages"] += zstage.npages
         return sc
 
     futs = []
