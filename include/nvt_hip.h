@@ -2159,6 +2159,45 @@ int nvt_csv_parse_datetime(const uint8_t *text, uint64_t nbytes, const uint32_t 
                            void *stream);
 int nvt_csv_parse_datetime_host(const char *text, int len, int64_t *out_ns);
 
+/* ---- row-wise sparse similarity (nvtabular_amd/kernels_similarity.py, ops.ColumnSimilarity) ----
+ * A feature matrix is prepared once from its COO form (entries in any order, duplicates and stored
+ * zeros allowed) into the canonical CSR the similarity reads:
+ *   nvt_similarity_prepare: weights entry by entry -- NVT_SIM_TFIDF: w = data * log(n_rows /
+ *     cnt[col]) with cnt the stored entries of the column; NVT_SIM_TFIDF and NVT_SIM_COSINE: w /=
+ *     sqrt(sum of w^2 over the entries of the row); NVT_SIM_INNER: w = data -- and orders them by
+ *     (row, col).  state[0] = the number of distinct (row, col) pairs, state[1] = the entries whose
+ *     row or col lies outside the shape (the caller raises; nothing is addressed through them).
+ *     rows / cols int64, data float64, nnz < 2^30, n_rows and n_cols 1 .. 2^31 - 1; ws 256-byte
+ *     aligned, nvt_similarity_prepare_ws_bytes bytes, and kept for nvt_similarity_coalesce.
+ *   nvt_similarity_coalesce: after the caller has read state[0] (= nnz_out >= 1): equal (row, col)
+ *     pairs summed into indices[nnz_out] / weights[nnz_out], and indptr[n_rows + 1].
+ * nvt_row_similarity: out[i] = dot product of row left[i] of left_csr and row right[i] of right_csr;
+ *   NaN where an id is null (clear bit in its bitmap) or outside [0, rows), 0.0 where either row has
+ *   no entry.  left / right: n ids of `dtype` NVT_I32 or NVT_I64; bitmaps NULL or ceil(n / 8) bytes;
+ *   n < 2^31; the CSR as nvt_similarity_coalesce writes it (column indices ascending and distinct
+ *   within a row); ws 256-byte aligned, nvt_row_similarity_ws_bytes(n) bytes.  Rows are classed by
+ *   the shorter of their two CSR rows (<= 8, <= 64, longer) and served by groups of 4, 16 or 64
+ *   lanes that search the longer row.  Stream-ordered, no host synchronisation; n = 0 is a no-op. */
+#define NVT_SIM_INNER 0
+#define NVT_SIM_COSINE 1
+#define NVT_SIM_TFIDF 2
+typedef struct nvt_csr {
+  const int64_t *indptr;  /* [rows + 1] */
+  const int32_t *indices; /* [indptr[rows]] */
+  const double *weights;  /* [indptr[rows]] */
+  uint64_t rows;
+} nvt_csr;
+int nvt_similarity_prepare_ws_bytes(uint64_t nnz, uint64_t n_rows, uint64_t n_cols, uint64_t *bytes);
+int nvt_similarity_prepare(const int64_t *rows, const int64_t *cols, const double *data, uint64_t nnz,
+                           uint64_t n_rows, uint64_t n_cols, int metric, void *ws, uint64_t ws_bytes,
+                           uint64_t *state, void *stream);
+int nvt_similarity_coalesce(const void *ws, uint64_t ws_bytes, uint64_t nnz, uint64_t n_rows, uint64_t n_cols,
+                            uint64_t nnz_out, int64_t *indptr, int32_t *indices, double *weights, void *stream);
+int nvt_row_similarity_ws_bytes(uint64_t n, uint64_t *bytes);
+int nvt_row_similarity(const void *left, const uint8_t *left_valid, const void *right, const uint8_t *right_valid,
+                       int dtype, uint64_t n, const nvt_csr *left_csr, const nvt_csr *right_csr, double *out,
+                       void *ws, uint64_t ws_bytes, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -12,7 +12,7 @@ for _name in ("ops", "workflow", "io", "schema", "selector", "node", "graph_json
 for _sub in ("categorify", "normalize", "fill", "join_groupby", "target_encoding", "hash_bucket",
              "lambdaop", "groupby", "clip_log", "hashed_cross", "bucketize", "filter", "dropna", "join_external",
              "list_slice", "value_counts", "difference_lag", "reduce_dtype_size", "data_stats",
-             "drop_low_cardinality", "add_metadata"):
+             "drop_low_cardinality", "add_metadata", "column_similarity"):
     try:
         sys.modules[f"{__name__}.ops.{_sub}"] = importlib.import_module(f"nvtabular_amd.ops.{_sub}")
     except ImportError:  # (an operator module this engine does not carry)

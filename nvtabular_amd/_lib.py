@@ -619,6 +619,20 @@ SIGNATURES.update({
     "nvt_csv_parse_datetime_host": [C.c_char_p, _i32, C.POINTER(_i64)],
 })
 
+class Csr(C.Structure):
+    """nvt_csr: a prepared feature matrix read by nvt_row_similarity."""
+    _fields_ = [("indptr", _vp), ("indices", _vp), ("weights", _vp), ("rows", _u64)]
+
+
+SIM_INNER, SIM_COSINE, SIM_TFIDF = 0, 1, 2   # include/nvt_hip.h NVT_SIM_*
+SIGNATURES.update({
+    "nvt_similarity_prepare_ws_bytes": [_u64, _u64, _u64, C.POINTER(_u64)],
+    "nvt_similarity_prepare": [_vp, _vp, _vp, _u64, _u64, _u64, _i32, _vp, _u64, _vp, _vp],
+    "nvt_similarity_coalesce": [_vp, _u64, _u64, _u64, _u64, _u64, _vp, _vp, _vp, _vp],
+    "nvt_row_similarity_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_row_similarity": [_vp, _vp, _vp, _vp, _i32, _u64, C.POINTER(Csr), C.POINTER(Csr), _vp, _vp, _u64, _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

@@ -427,7 +427,7 @@ _REGISTRY: Dict[str, tuple] = {}
 _LATER: Dict[str, tuple] = {}
 _SELECTION = "merlin.dag.ops.selection.SelectionOp"
 # exist in the reference too, but its JSON serializer defers them (:920-930)
-_DEFERRED = {"SubsetColumns", "SubtractionOp", "HashedCross", "Groupby", "JoinExternal"}
+_DEFERRED = {"SubsetColumns", "SubtractionOp", "HashedCross", "Groupby", "JoinExternal", "ColumnSimilarity"}
 
 
 def _registry():

@@ -7,6 +7,7 @@ from .base import Operator, StatOperator  # noqa: F401
 from .bucketize import Bucketize  # noqa: F401
 from .categorify import Categorify, get_embedding_sizes  # noqa: F401
 from .clip_log import Clip, LogOp  # noqa: F401
+from .column_similarity import ColumnSimilarity  # noqa: F401
 from .data_stats import DataStats  # noqa: F401
 from .difference_lag import DifferenceLag  # noqa: F401
 from .drop_low_cardinality import DropLowCardinality  # noqa: F401
