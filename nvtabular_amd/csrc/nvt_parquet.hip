@@ -1,400 +1,84 @@
-// Parquet in: the input half of Dataset -> HBM for column chunks of flat int32 / int64 / float /
-// double columns: PLAIN or dictionary-encoded (PLAIN_DICTIONARY / RLE_DICTIONARY) values, codec
-// UNCOMPRESSED or SNAPPY, data pages v1 / v2 -- what pandas, pyarrow, cuDF and the reference
-// write by default (round 6; before: PLAIN + uncompressed only, i.e. parquet_plain.py's own files).  Reference contract: merlin.io.Dataset(engine=
+// Parquet in: the input half of Dataset -> HBM.  Reference contract: merlin.io.Dataset(engine=
 // "parquet") feeding Workflow.fit / transform (tests/unit/workflow/test_cpu_workflow.py:67-81,
 // bench/examples/dask-nvtabular-criteo-benchmark.py:216-237); the reference's backend (cuDF /
 // pyarrow) decodes pages on its side of that call.
 //
-//   host (a pool thread per column chunk, GIL released): pread the chunk -> nvt_pq_decode_chunk:
-//     walk the thrift-compact page headers, turn the definition levels (RLE / bit-packed hybrid
-//     at bit width 1) into the Arrow validity bitmap, and move the pages' values -- PLAIN stores
-//     only the non-null ones -- behind each other into a pinned staging buffer;
-//   device: values + bitmap arrive by hipMemcpyAsync on the copy stream; a column WITH nulls is
-//     expanded to one slot per row there (nvt_expand_valid: rank of a row = popcount prefix of
-//     the bitmap), so the PCIe link carries the packed values only.
+// Host (a pool thread per column, GIL released): pread a column chunk, then ONE walk over its pages
+// (walk_pages, nvt_pq_page.hpp): thrift-compact page headers, bounds, codec UNCOMPRESSED / SNAPPY,
+// data pages v1 / v2 split into levels and values, row accounting.  The walk hands the levels to a
+// level sink and the dictionary page and the values to a value sink; every entry point is a pair of
+// sinks.  Anything else in a chunk (other codecs / encodings, other nesting) is NVT_EUNSUPPORTED and
+// the caller reads that file with pyarrow.  Device: values and bitmap arrive by hipMemcpyAsync; a
+// column WITH nulls is expanded to one slot per row there (nvt_expand_valid below: rank of a row =
+// popcount prefix of the bitmap), so the PCIe link carries the packed values only.
 //
-//     snappy blocks are decompressed and dictionary indices (RLE / bit-packed hybrid, width <= 32)
-//     resolved through the chunk's dictionary in the same task, so the staging buffer always holds
-//     packed PLAIN values.
-//
-//   list columns (the standard three-level list of such leaves): nvt_pq_decode_list_chunk walks the
-//     same pages and appends their repetition / definition levels to two bit streams that are
-//     continuous over the partition (1 and W bits per slot); the device turns them into offsets and
-//     the leaf bitmap (nvt_pqlist_unpack, nvt_parquet_list.hip).
-//
-//   string columns (flat BYTE_ARRAY annotated UTF8 / STRING): nvt_pq_decode_str_chunk walks the same
-//     pages but expands nothing: dictionary and PLAIN values become entries of an Arrow string table,
-//     the index streams a run table plus the bytes of their bit-packed runs; the device expands the
-//     runs to entry ids (nvt_pq_expand_runs, nvt_parquet_str.hip) and hashes every entry once.
-//
-//   DELTA_BINARY_PACKED pages of flat INT32 / INT64 columns: nvt_pq_decode_chunk_delta walks the same
-//     pages and the block headers of a delta page, checks them and stages the page's bytes with a
-//     record per page and per miniblock; the device unpacks and prefix-sums them into the hole the
-//     page leaves in the packed values (nvt_pq_delta_decode, nvt_parquet_delta.hip).
-//
-//   dictionary pages of flat 4- / 8-byte number columns: nvt_pq_decode_chunk_dict walks the same pages
-//     but resolves no index: it stages the chunk's dictionary, a run table and the bytes of the
-//     bit-packed runs, and the device fills the hole the page leaves (nvt_pq_dict_fill_many,
-//     nvt_parquet_dict_in.hip).
-//
-//   snappy bodies of PLAIN pages without nulls (flat 4- / 8-byte number columns):
-//     nvt_pq_decode_chunk_inflate walks the same pages but does not inflate such a body: it is staged
-//     compressed with a record per page, and the device inflates it into the hole the page leaves
-//     (nvt_snappy_inflate_pages, nvt_snappy_inflate.hip).
-//
-// Anything else in a chunk (other codecs / encodings, other nesting) is reported as
-// NVT_EUNSUPPORTED and the caller reads that file with pyarrow.
+//   entry point                  level sink   value sink     device counterpart
+//   nvt_pq_decode_chunk[_codec]  FlatLevels   PlainValues    nvt_expand_valid (here)
+//   nvt_pq_decode_list_chunk     ListLevels   PlainValues    nvt_pqlist_unpack (nvt_parquet_list.hip)
+//   nvt_pq_decode_chunk_delta    FlatLevels   DeltaValues    nvt_pq_delta_decode (nvt_parquet_delta.hip)
+//   nvt_pq_decode_chunk_dict     FlatLevels   DictValues     nvt_pq_dict_fill_many (nvt_parquet_dict_in.hip)
+//   nvt_pq_decode_chunk_inflate  FlatLevels   InflateValues  nvt_snappy_inflate_pages (nvt_snappy_inflate.hip)
+//   nvt_pq_decode_bool_chunk     FlatLevels   BoolValues     nvt_expand_narrow (nvt_parquet_narrow.hip)
+//   nvt_pq_decode_str_chunk      FlatLevels   StrValues (nvt_parquet_str_in.hip)
+//                                                            nvt_pq_expand_runs (nvt_parquet_str.hip)
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/nvt_hip.h"
 #include "nvt_common.hpp"
 #include "nvt_internal.hpp"
+#include "nvt_pq_page.hpp"
 #include "nvt_prof.hpp"
 #include "nvt_scan.hpp"
 
 namespace nvt {
 namespace {
 
-// ---- thrift compact protocol, reading side (parquet-format's PageHeader) ----------------------
-struct TReader {
-  const uint8_t *p, *end;
-  bool ok = true;
-  uint64_t varint() {
-    uint64_t v = 0;
-    int sh = 0;
-    while (p < end) {
-      const uint8_t b = *p++;
-      v |= (uint64_t)(b & 0x7F) << sh;
-      if (!(b & 0x80)) return v;
-      sh += 7;
-      if (sh > 63) break;
-    }
-    ok = false;
-    return 0;
-  }
-  int64_t zigzag() {
-    const uint64_t v = varint();
-    return (int64_t)(v >> 1) ^ -(int64_t)(v & 1);
-  }
-  void skip_bytes(uint64_t n) {
-    if ((uint64_t)(end - p) < n) {
-      ok = false;
-      p = end;
-    } else {
-      p += n;
-    }
-  }
-  // compact types: 1 / 2 bool, 3 byte, 4 i16, 5 i32, 6 i64, 7 double, 8 binary, 9 list, 10 set,
-  // 11 map, 12 struct
-  void skip(int type, int depth = 0) {
-    if (!ok || depth > 16) {
-      ok = false;
-      return;
-    }
-    switch (type) {
-      case 1: case 2: break;
-      case 3: skip_bytes(1); break;
-      case 4: case 5: case 6: (void)varint(); break;
-      case 7: skip_bytes(8); break;
-      case 8: skip_bytes(varint()); break;
-      case 9: case 10: {
-        if (p >= end) { ok = false; return; }
-        const uint8_t h = *p++;
-        uint64_t n = h >> 4;
-        if (n == 15) n = varint();
-        const int et = h & 0x0F;
-        for (uint64_t i = 0; i < n && ok; ++i) skip(et, depth + 1);
-        break;
-      }
-      case 11: {
-        const uint64_t n = varint();
-        if (n == 0) break;
-        if (p >= end) { ok = false; return; }
-        const uint8_t kv = *p++;
-        for (uint64_t i = 0; i < n && ok; ++i) {
-          skip(kv >> 4, depth + 1);
-          skip(kv & 0x0F, depth + 1);
-        }
-        break;
-      }
-      case 12: skip_struct(depth + 1); break;
-      default: ok = false;
-    }
-  }
-  // next field header of a struct: false at the stop byte
-  bool field(int &fid, int &type) {
-    if (p >= end) {
-      ok = false;
-      return false;
-    }
-    const uint8_t h = *p++;
-    if (h == 0) return false;
-    const int d = h >> 4;
-    type = h & 0x0F;
-    if (d == 0) fid = (int)zigzag(); else fid += d;
-    return ok;
-  }
-  void skip_struct(int depth = 0) {
-    int fid = 0, type = 0;
-    while (ok && field(fid, type)) skip(type, depth);
-  }
-};
-
-struct PageHead {
-  int type = -1;            // 0 data page, 2 dictionary page, 3 data page v2
-  int64_t uncompressed = 0, compressed = 0;
-  int64_t num_values = 0;   // rows of the page (flat columns)
-  int encoding = -1, def_encoding = -1, rep_encoding = -1;
-  int64_t stat_nulls = -1;  // v1: DataPageHeader.statistics.null_count, -1 when the header has none
-  // v2
-  int64_t num_nulls = -1, def_bytes = 0, rep_bytes = 0;
-  bool v2_compressed = false;
-  // dictionary page
-  int64_t dict_values = 0;
-  int dict_encoding = -1;
-};
-
-bool read_page_header(TReader &r, PageHead &h) {
-  int fid = 0, type = 0;
-  while (r.field(fid, type)) {
-    if (fid == 1 && type == 5) h.type = (int)r.zigzag();
-    else if (fid == 2 && type == 5) h.uncompressed = r.zigzag();
-    else if (fid == 3 && type == 5) h.compressed = r.zigzag();
-    else if (fid == 5 && type == 12) {  // DataPageHeader
-      int f2 = 0, t2 = 0;
-      while (r.field(f2, t2)) {
-        if (f2 == 1 && t2 == 5) h.num_values = r.zigzag();
-        else if (f2 == 2 && t2 == 5) h.encoding = (int)r.zigzag();
-        else if (f2 == 3 && t2 == 5) h.def_encoding = (int)r.zigzag();
-        else if (f2 == 4 && t2 == 5) h.rep_encoding = (int)r.zigzag();
-        else if (f2 == 5 && t2 == 12) {  // Statistics
-          int f3 = 0, t3 = 0;
-          while (r.field(f3, t3)) {
-            if (f3 == 3 && t3 == 6) h.stat_nulls = r.zigzag(); else r.skip(t3);
-          }
-        } else r.skip(t2);
-      }
-    } else if (fid == 7 && type == 12) {  // DictionaryPageHeader
-      int f2 = 0, t2 = 0;
-      while (r.field(f2, t2)) {
-        if (f2 == 1 && t2 == 5) h.dict_values = r.zigzag();
-        else if (f2 == 2 && t2 == 5) h.dict_encoding = (int)r.zigzag();
-        else r.skip(t2);
-      }
-    } else if (fid == 8 && type == 12) {  // DataPageHeaderV2
-      int f2 = 0, t2 = 0;
-      h.v2_compressed = true;  // the field's default
-      while (r.field(f2, t2)) {
-        if (f2 == 1 && t2 == 5) h.num_values = r.zigzag();
-        else if (f2 == 2 && t2 == 5) h.num_nulls = r.zigzag();
-        else if (f2 == 4 && t2 == 5) h.encoding = (int)r.zigzag();
-        else if (f2 == 5 && t2 == 5) h.def_bytes = r.zigzag();
-        else if (f2 == 6 && t2 == 5) h.rep_bytes = r.zigzag();
-        else if (f2 == 7 && (t2 == 1 || t2 == 2)) h.v2_compressed = (t2 == 1);
-        else r.skip(t2);
-      }
-    } else {
-      r.skip(type);
-    }
-  }
-  return r.ok;
-}
-
-// ---- validity bitmap writing (LSB first) -----------------------------------------------------
-inline void bits_fill(uint8_t *bm, uint64_t pos, uint64_t count, bool one) {
-  while (count && (pos & 7)) {  // head
-    if (one) bm[pos >> 3] |= (uint8_t)(1u << (pos & 7)); else bm[pos >> 3] &= (uint8_t)~(1u << (pos & 7));
-    ++pos;
-    --count;
-  }
-  const uint64_t nbytes = count >> 3;
-  if (nbytes) memset(bm + (pos >> 3), one ? 0xFF : 0x00, nbytes);
-  pos += nbytes << 3;
-  count -= nbytes << 3;
-  while (count) {  // tail
-    if (one) bm[pos >> 3] |= (uint8_t)(1u << (pos & 7)); else bm[pos >> 3] &= (uint8_t)~(1u << (pos & 7));
-    ++pos;
-    --count;
-  }
-}
-
-// copies `count` bits of src (from its bit 0) to bm at bit `pos`; -> number of one bits copied
-inline uint64_t bits_copy(uint8_t *bm, uint64_t pos, const uint8_t *src, uint64_t count) {
-  uint64_t ones = 0;
-  const unsigned sh = (unsigned)(pos & 7);
-  const uint64_t full = count >> 3;
-  uint8_t *dst = bm + (pos >> 3);
-  if (sh == 0) {
-    memcpy(dst, src, full);
-    for (uint64_t i = 0; i < full; ++i) ones += (uint64_t)__builtin_popcount(src[i]);
-    dst += full;
-  } else {
-    for (uint64_t i = 0; i < full; ++i) {
-      const uint8_t b = src[i];
-      ones += (uint64_t)__builtin_popcount(b);
-      dst[0] = (uint8_t)((dst[0] & ((1u << sh) - 1u)) | (uint8_t)(b << sh));
-      dst[1] = (uint8_t)(b >> (8 - sh));
-      ++dst;
-    }
-  }
-  const unsigned rem = (unsigned)(count & 7);
-  if (rem) {
-    const uint8_t b = (uint8_t)(src[full] & ((1u << rem) - 1u));
-    ones += (uint64_t)__builtin_popcount(b);
-    uint64_t q = pos + (full << 3);
-    for (unsigned j = 0; j < rem; ++j, ++q) {
-      if ((b >> j) & 1) bm[q >> 3] |= (uint8_t)(1u << (q & 7)); else bm[q >> 3] &= (uint8_t)~(1u << (q & 7));
-    }
-  }
-  return ones;
-}
-
-// definition levels of one page (max level 1, RLE / bit-packed hybrid, bit width 1) -> bits
-// [pos, pos + rows) of the bitmap; *valid = rows with level 1
-bool decode_levels(const uint8_t *lv, uint64_t nbytes, uint64_t rows, uint8_t *bm, uint64_t pos,
-                   uint64_t *valid) {
-  TReader r{lv, lv + nbytes};
-  uint64_t done = 0, ones = 0;
-  while (done < rows) {
-    const uint64_t head = r.varint();
-    if (!r.ok) return false;
-    if (head & 1) {  // bit-packed run: (head >> 1) groups of 8 levels, one bit each
-      const uint64_t groups = head >> 1, nb = groups;
-      if ((uint64_t)(r.end - r.p) < nb) return false;
-      uint64_t take = groups * 8;
-      if (take > rows - done) take = rows - done;  // (the last group is padded)
-      ones += bits_copy(bm, pos + done, r.p, take);
-      r.p += nb;
-      done += take;
-    } else {  // RLE run: (head >> 1) times the value in the next byte (bit width 1 -> 1 byte)
-      uint64_t count = head >> 1;
-      if (r.p >= r.end || count == 0) return false;
-      const uint8_t v = *r.p++;
-      if (v > 1) return false;
-      if (count > rows - done) count = rows - done;
-      bits_fill(bm, pos + done, count, v == 1);
-      ones += v ? count : 0;
-      done += count;
-    }
-  }
-  *valid = ones;
-  return true;
-}
-
-// ---- level streams of list columns ------------------------------------------------------------
-// The staging streams hold one level per slot at `bw` bits (1 or 2), LSB first, continuous over the
-// pages, chunks and row groups of a partition: a page's levels land at an arbitrary bit position.
-// They are written 64 bits at a time through the words that hold them (memcpy: no alignment is
-// asked of the buffer, which is ceil(bits / 64) words long).
-inline void put_bits(uint8_t *dst, uint64_t bitpos, uint64_t v, unsigned n) {  // n in 1 .. 64, v < 2^n
-  uint8_t *at = dst + (bitpos >> 6) * 8;
-  const unsigned sh = (unsigned)(bitpos & 63);
-  const uint64_t mask = n == 64 ? ~0ull : ((1ull << n) - 1ull);
-  uint64_t w;
-  memcpy(&w, at, 8);
-  w = (w & ~(mask << sh)) | (v << sh);
-  memcpy(at, &w, 8);
-  if (sh + n > 64) {
-    const uint64_t m2 = (1ull << (sh + n - 64)) - 1ull;
-    memcpy(&w, at + 8, 8);
-    w = (w & ~m2) | (v >> (64 - sh));
-    memcpy(at + 8, &w, 8);
-  }
-}
-
-// levels per value in `nbits` bits of w (its other bits 0): hist[v] += count
-inline void hist_add(uint64_t w, unsigned nbits, unsigned bw, uint64_t hist[4]) {
-  if (bw == 1) {
-    const uint64_t ones = (uint64_t)__builtin_popcountll(w);
-    hist[1] += ones;
-    hist[0] += nbits - ones;
-  } else {
-    const uint64_t lo = w & 0x5555555555555555ull, hi = (w >> 1) & 0x5555555555555555ull;
-    const uint64_t c3 = (uint64_t)__builtin_popcountll(lo & hi);
-    const uint64_t c1 = (uint64_t)__builtin_popcountll(lo) - c3, c2 = (uint64_t)__builtin_popcountll(hi) - c3;
-    hist[1] += c1;
-    hist[2] += c2;
-    hist[3] += c3;
-    hist[0] += nbits / 2 - c1 - c2 - c3;
-  }
-}
-
-// `nbits` bits of src (from its bit 0; ceil(nbits / 8) bytes readable) -> dst at bit `pos`, counted
-inline void bits_copy_count(uint8_t *dst, uint64_t pos, const uint8_t *src, uint64_t nbits, unsigned bw,
-                            uint64_t hist[4]) {
-  uint64_t done = 0;
-  for (; done + 64 <= nbits; done += 64) {
-    uint64_t w;
-    memcpy(&w, src + (done >> 3), 8);
-    hist_add(w, 64, bw, hist);
-    put_bits(dst, pos + done, w, 64);
-  }
-  if (done < nbits) {
-    const unsigned rem = (unsigned)(nbits - done);
-    uint64_t w = 0;
-    memcpy(&w, src + (done >> 3), (rem + 7) / 8);
-    w &= (1ull << rem) - 1ull;
-    hist_add(w, rem, bw, hist);
-    put_bits(dst, pos + done, w, rem);
-  }
-}
-
-inline void bits_fill_value(uint8_t *dst, uint64_t pos, uint64_t nbits, unsigned bw, unsigned v) {
-  const uint64_t pat = bw == 1 ? (v ? ~0ull : 0ull) : (uint64_t)v * 0x5555555555555555ull;
-  uint64_t done = 0;
-  for (; done + 64 <= nbits; done += 64) put_bits(dst, pos + done, pat, 64);  // (64 is a multiple of bw)
-  if (done < nbits) put_bits(dst, pos + done, pat & ((1ull << (nbits - done)) - 1ull), (unsigned)(nbits - done));
-}
-
-// One level stream of a page (RLE / bit-packed hybrid at bit width `bw`, nbytes long, n levels) ->
-// slots [slot, slot + n) of `out`; hist[v] += levels of value v.  A bit-packed run is a shifting bit
-// copy (the padding of its last group is not copied), an RLE run a fill.
-// -> 0, or 1: a run leaves the stream's bytes, 2: a level above max_level
-int decode_levels_wide(const uint8_t *lv, uint64_t nbytes, uint64_t n, unsigned bw, unsigned max_level,
-                       uint8_t *out, uint64_t slot, uint64_t hist[4]) {
-  TReader r{lv, lv + nbytes};
-  uint64_t done = 0;
-  uint64_t h[4] = {0, 0, 0, 0};
-  while (done < n) {
-    const uint64_t head = r.varint();
-    if (!r.ok) return 1;
-    if (head & 1) {
-      const uint64_t groups = head >> 1;
-      if (groups == 0 || groups > (1ull << 40)) return 1;
-      uint64_t take = groups * 8;
-      if (take > n - done) take = n - done;
-      const uint64_t avail = (uint64_t)(r.end - r.p);
-      if (avail < groups * bw && avail * 8 < take * bw) return 1;   // (a writer may cut the last group's padding)
-      bits_copy_count(out, (slot + done) * bw, r.p, take * bw, bw, h);
-      r.skip_bytes(groups * bw < avail ? groups * bw : avail);
-      done += take;
-    } else {
-      uint64_t count = head >> 1;
-      if (count == 0 || r.p >= r.end) return 1;
-      const unsigned v = *r.p++;
-      if (v > max_level) return 2;
-      if (count > n - done) count = n - done;
-      bits_fill_value(out, (slot + done) * bw, count * bw, bw, v);
-      h[v] += count;
-      done += count;
-    }
-  }
-  for (unsigned v = max_level + 1; v < 4; ++v)
-    if (h[v]) return 2;
-  for (int v = 0; v < 4; ++v) hist[v] += h[v];
-  return 0;
-}
-
-// what a list chunk adds to the page walk of pq_decode
-struct ListSink {
+// ---- list columns: the level sink ("List columns in the parquet reader") --------------
+// Repetition and definition levels of the pages -> the partition's two staging streams, from slot
+// `slot0` on (the walk's rows are SLOTS); counts the row starts and the leaf slots on the way.
+struct ListLevels {
+  static constexpr bool kNested = true;
   uint8_t *rep, *def;          // the partition's staging streams
-  uint64_t slot0, slot_cap;    // the chunk's first slot; slots the streams hold
+  uint64_t slot0;              // the chunk's first slot
   unsigned width;              // bits per definition level (1 or 2)
   unsigned leaf_level, max_def;
   uint64_t expect_rows;
   uint64_t starts = 0, leaves = 0;
+  const char *bad_args() const { return rep && def ? nullptr : "null pointer"; }
+  bool has(int) const { return true; }
+  int v1_encodings(const char *who, const PageHead &h) const {
+    if (h.rep_encoding == 3 && h.def_encoding == 3) return NVT_OK;
+    set_error("%s: level encodings %d / %d (the RLE hybrid is decoded here)", who, h.rep_encoding, h.def_encoding);
+    return NVT_EUNSUPPORTED;
+  }
+  int stream(const char *who, int s, const uint8_t *lv, uint64_t nbytes, uint64_t slot, uint64_t n, uint64_t *pvalid) {
+    uint64_t hist[4] = {0, 0, 0, 0};
+    const int bad = s == 0 ? decode_levels_wide(lv, nbytes, n, 1, 1, rep, slot0 + slot, hist)
+                           : decode_levels_wide(lv, nbytes, n, width, max_def, def, slot0 + slot, hist);
+    if (bad) {
+      set_error(bad == 1 ? "%s: level runs leave their stream" : "%s: a level above the column's maximum", who);
+      return NVT_EINVAL;
+    }
+    if (s == 0) {
+      starts += hist[0];
+      return NVT_OK;
+    }
+    *pvalid = hist[max_def];
+    for (unsigned v = leaf_level; v <= max_def; ++v) leaves += hist[v];
+    if (slot == 0 && n > 0 && ((rep[slot0 >> 3] >> (slot0 & 7)) & 1)) {
+      set_error("%s: the chunk's first slot continues a row", who);
+      return NVT_EINVAL;
+    }
+    return NVT_OK;
+  }
+  void all_valid(uint64_t, uint64_t) {}
+  int close(const char *who) {
+    if (starts == expect_rows) return NVT_OK;
+    set_error("%s: %llu row starts in the pages, %llu expected", who, (unsigned long long)starts,
+              (unsigned long long)expect_rows);
+    return NVT_EINVAL;
+  }
 };
 
 // ---- DELTA_BINARY_PACKED pages: staged, not decoded ("DELTA_BINARY_PACKED in the parquet
@@ -523,7 +207,10 @@ struct InflateFill {
   }
 };
 
-// ---- snappy, raw block format (what parquet's SNAPPY codec holds per page) --------------------
+}  // namespace
+
+// ---- snappy, raw block format (what parquet's SNAPPY codec holds per page; declared in
+// nvt_pq_page.hpp for the walk) -------------------------------------------------------------------
 // -> uncompressed bytes written, or -1 on malformed input / a block that does not fit `cap`
 int64_t snappy_uncompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap) {
   TReader r{src, src + n};
@@ -578,6 +265,8 @@ int64_t snappy_uncompress(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t
   }
   return o == want ? (int64_t)o : -1;
 }
+
+namespace {
 
 // `count` dictionary indices (RLE / bit-packed hybrid behind a one-byte bit width) resolved through
 // `dict` (ndict values of T) into out[0 .. count)
@@ -750,6 +439,161 @@ int dict_index_runs(DictFill &f, const uint8_t *p, const uint8_t *end, uint64_t 
   return NVT_OK;
 }
 
+// ---- the value sinks of number columns -------------------------------------------------------------
+// The default: PLAIN values are moved behind each other into `out` -- PLAIN stores only the non-null
+// ones -- and dictionary indices resolved through the chunk's dictionary (in the chunk or at the
+// bottom of the scratch), so `out` holds packed PLAIN values.
+struct PlainValues : ValueSink {
+  static constexpr bool kKeepsDictionary = true;
+  int type_size;
+  uint8_t *out;
+  uint64_t cap_bytes;
+  bool exact;   // list chunks: the levels say how many PLAIN values a page holds, exactly
+  uint64_t vals = 0;
+  const uint8_t *dict = nullptr;   // PLAIN values of the dictionary page
+  uint64_t ndict = 0;
+  PlainValues(int type_size_, uint8_t *out_, uint64_t cap_bytes_, bool exact_ = false)
+      : type_size(type_size_), out(out_), cap_bytes(cap_bytes_), exact(exact_) {}
+  bool takes_dictionary(const PageHead &h) const { return h.dict_values >= 0; }
+  int dictionary(const char *who, const PageHead &h, const uint8_t *d) {
+    // compared by division: a count of 2^61 must not wrap
+    if ((uint64_t)h.dict_values > (uint64_t)h.uncompressed / (uint64_t)type_size) {
+      set_error("%s: dictionary page holds fewer values than it says", who);
+      return NVT_EINVAL;
+    }
+    dict = d;
+    ndict = (uint64_t)h.dict_values;
+    return NVT_OK;
+  }
+  int accepts(const char *who, const PageHead &h, bool have_dict) const { return plain_or_dictionary(who, h, have_dict); }
+  int room(const char *who, uint64_t count) const {
+    if ((vals + count) * (uint64_t)type_size <= cap_bytes) return NVT_OK;
+    set_error("%s: values buffer too small", who);
+    return NVT_EINVAL;
+  }
+  int page(const char *who, const PageHead &h, const uint8_t *q, const uint8_t *pend, uint64_t pvalid) {
+    if (const int rc = room(who, pvalid)) return rc;
+    if (by_dictionary(h)) {
+      const bool ok = type_size == 4
+          ? decode_dict_indices<uint32_t>(q, pend, pvalid, reinterpret_cast<const uint32_t *>(dict), ndict,
+                                          reinterpret_cast<uint32_t *>(out) + vals)
+          : decode_dict_indices<uint64_t>(q, pend, pvalid, reinterpret_cast<const uint64_t *>(dict), ndict,
+                                          reinterpret_cast<uint64_t *>(out) + vals);
+      if (!ok) {
+        set_error("%s: malformed dictionary indices", who);
+        return NVT_EINVAL;
+      }
+    } else {
+      const uint64_t vbytes = pvalid * (uint64_t)type_size;
+      if ((uint64_t)(pend - q) < vbytes) {
+        set_error("%s: page holds fewer values than its levels say", who);
+        return NVT_EINVAL;
+      }
+      if (exact && (uint64_t)(pend - q) != vbytes) {
+        set_error("%s: page holds more values than its levels say", who);
+        return NVT_EINVAL;
+      }
+      memcpy(out + vals * (uint64_t)type_size, q, vbytes);
+    }
+    vals += pvalid;
+    return NVT_OK;
+  }
+};
+
+// The three sinks that leave HOLES in `out` for the device to fill: what they stage goes to their
+// fill, every other page is decoded in place as above.  `values_offset`: out[0] is this value of the
+// column's packed values.
+struct DeltaValues : PlainValues {   // DELTA_BINARY_PACKED pages (nvt_pq_delta_decode)
+  DeltaFill f;
+  uint64_t values_offset;
+  DeltaValues(const PlainValues &base, const DeltaFill &f_, uint64_t values_offset_)
+      : PlainValues(base), f(f_), values_offset(values_offset_) {}
+  int accepts(const char *who, const PageHead &h, bool have_dict) const {
+    if (h.encoding != 5) return PlainValues::accepts(who, h, have_dict);
+    if (f.ints) return NVT_OK;
+    set_error("%s: DELTA_BINARY_PACKED values in a column that is not INT32 / INT64", who);
+    return NVT_EINVAL;
+  }
+  int page(const char *who, const PageHead &h, const uint8_t *q, const uint8_t *pend, uint64_t pvalid) {
+    if (h.encoding != 5) return PlainValues::page(who, h, q, pend, pvalid);
+    int rc = room(who, pvalid);
+    if (!rc) rc = delta_stage_page(f, q, (uint64_t)(pend - q), type_size, pvalid, values_offset + vals);
+    if (!rc) vals += pvalid;
+    return rc;
+  }
+};
+
+struct DictValues : PlainValues {   // dictionary-encoded pages (nvt_pq_dict_fill_many)
+  DictFill f;
+  uint64_t values_offset;
+  DictValues(const PlainValues &base, const DictFill &f_, uint64_t values_offset_)
+      : PlainValues(base), f(f_), values_offset(values_offset_) {}
+  int dictionary(const char *who, const PageHead &h, const uint8_t *d) {
+    const int rc = PlainValues::dictionary(who, h, d);
+    return rc ? rc : f.dictionary(d, ndict, type_size);
+  }
+  int page(const char *who, const PageHead &h, const uint8_t *q, const uint8_t *pend, uint64_t pvalid) {
+    const uint64_t start = values_offset + vals;
+    if (!by_dictionary(h)) {   // in place: the device leaves these positions alone
+      const int rc = PlainValues::page(who, h, q, pend, pvalid);
+      return rc ? rc : f.run(NVT_PQ_RUN_KEEP, 0, 0, 0, start, pvalid);
+    }
+    int rc = room(who, pvalid);
+    if (!rc) {
+      rc = dict_index_runs(f, q, pend, pvalid, ndict, start);
+      if (rc == NVT_EINVAL) set_error("%s: malformed dictionary indices", who);
+    }
+    if (!rc) vals += pvalid;
+    return rc;
+  }
+};
+
+struct InflateValues : PlainValues {   // snappy bodies of PLAIN pages without nulls (nvt_snappy_inflate_pages)
+  InflateFill f;
+  uint64_t values_offset;
+  int max_def;
+  InflateValues(const PlainValues &base, const InflateFill &f_, uint64_t values_offset_, int max_def_)
+      : PlainValues(base), f(f_), values_offset(values_offset_), max_def(max_def_) {}
+  // a non-empty snappy body of PLAIN values that is known to hold no nulls (the walk asks for SNAPPY
+  // chunks and pages with rows only)
+  bool stays_compressed(const PageHead &h, uint64_t lbytes, uint64_t prow) const {
+    if (h.encoding != 0) return false;
+    if (h.type == 0)   // (levels in another encoding than the RLE hybrid have no u32 L in front: left to the host)
+      return h.compressed > 0 &&
+             (max_def == 0 ||
+              (h.def_encoding == 3 && (h.stat_nulls == 0 || (h.stat_nulls < 0 && f.chunk_nulls == 0))));
+    return h.v2_compressed && (max_def == 0 || h.num_nulls == 0) && (uint64_t)h.compressed > lbytes &&
+           (uint64_t)h.uncompressed - lbytes == prow * (uint64_t)type_size;
+  }
+  // v1: the levels (u32 L | L bytes) are inside the body; the device drops them
+  int compressed_page(const char *who, const PageHead &h, const uint8_t *body, uint64_t n, uint64_t prow) {
+    int rc = room(who, prow);
+    if (!rc)
+      rc = f.page(body, n, (values_offset + vals) * (uint64_t)type_size, prow * (uint64_t)type_size,
+                  (h.type == 0 && max_def == 1) ? NVT_INFLATE_V1_LEVELS : 0u);
+    if (!rc) vals += prow;
+    return rc;
+  }
+};
+
+// One chunk of a number column through the walk: the argument checks and outputs that its entry
+// points share.  *rows_out counts what w.expect_rows counts.
+template <typename Levels, typename Values>
+int decode_numbers(const PageWalk &w, Levels &lv, Values &vs, uint64_t *rows_out, uint64_t *values_count) {
+  const char *bad = !(w.chunk && vs.out && rows_out && values_count) ? "null pointer"
+                    : (vs.type_size != 4 && vs.type_size != 8)      ? "values are 4 or 8 bytes"
+                                                                     : lv.bad_args();
+  if (bad) {
+    set_error("%s: %s", w.who, bad);
+    return NVT_EINVAL;
+  }
+  const int rc = walk_pages(w, lv, vs);
+  if (rc) return rc;
+  *rows_out = w.expect_rows;
+  *values_count = vs.vals;
+  return NVT_OK;
+}
+
 }  // namespace
 
 // out[i] = valid(i) ? packed[rank(i)] : 0 with rank(i) = valid rows in front of row i.
@@ -814,295 +658,6 @@ using namespace nvt;
 
 extern "C" {
 
-// codec: parquet CompressionCodec (0 UNCOMPRESSED, 1 SNAPPY).  scratch: room for the chunk's
-// dictionary + its largest page uncompressed (2 * total_uncompressed_size + 64 always suffices);
-// may be null for an uncompressed chunk without a dictionary page.
-static int pq_decode(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size, int max_def_level,
-                     uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
-                     uint8_t *values_out, uint64_t values_cap_bytes, uint8_t *scratch, uint64_t scratch_bytes,
-                     uint64_t *rows_out, uint64_t *values_out_count, ListSink *ls = nullptr, DeltaFill *df = nullptr,
-                     uint64_t values_offset = 0, DictFill *xf = nullptr, InflateFill *zf = nullptr) {
-  // zf: the snappy body of a PLAIN page that holds no nulls is staged there as it is and leaves a hole
-  //     in values_out like a delta page; the page's rows are all valid
-  // ls: a list chunk -- `rows` / expect_rows below count SLOTS, the levels go to the sink's streams
-  // df: DELTA_BINARY_PACKED pages are staged there and leave a hole in values_out, whose first value
-  //     is value `values_offset` of the column's packed values
-  // xf: dictionary-encoded pages are staged there (dictionary, runs, packed bytes) and leave a hole
-  //     in values_out like a delta page; the values of PLAIN pages get a KEEP record
-  NVT_CHECK_ARG(chunk && values_out && rows_out && values_out_count, "null pointer");
-  NVT_CHECK_ARG(type_size == 4 || type_size == 8, "values are 4 or 8 bytes");
-  NVT_CHECK_ARG(ls || max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
-  NVT_CHECK_ARG(ls || max_def_level == 0 || valid_out, "null validity buffer");
-  if (codec != 0 && codec != 1) {
-    set_error("nvt_pq_decode_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
-    return NVT_EUNSUPPORTED;
-  }
-  const uint8_t *p = chunk, *end = chunk + chunk_bytes;
-  uint64_t rows = 0, vals = 0;
-  const uint8_t *dict = nullptr;   // PLAIN values of the dictionary page (in the chunk or in scratch)
-  uint64_t ndict = 0;
-  uint64_t scratch_at = 0;         // scratch below this offset holds the dictionary
-  // page body -> uncompressed bytes (`want` of them): the body itself, or scratch behind the dictionary
-  auto inflate = [&](const uint8_t *src, uint64_t nsrc, uint64_t want, bool compressed,
-                     const uint8_t **out) -> int {
-    if (!compressed) {
-      if (nsrc != want) {
-        set_error("nvt_pq_decode_chunk: an uncompressed page of %llu bytes that says %llu",
-                  (unsigned long long)nsrc, (unsigned long long)want);
-        return NVT_EINVAL;
-      }
-      *out = src;
-      return NVT_OK;
-    }
-    if (scratch == nullptr || scratch_bytes - scratch_at < want || scratch_bytes < scratch_at) {
-      set_error("nvt_pq_decode_chunk: scratch too small for a page of %llu bytes", (unsigned long long)want);
-      return NVT_EINVAL;
-    }
-    if (snappy_uncompress(src, nsrc, scratch + scratch_at, want) != (int64_t)want) {
-      set_error("nvt_pq_decode_chunk: malformed snappy block");
-      return NVT_EINVAL;
-    }
-    *out = scratch + scratch_at;
-    return NVT_OK;
-  };
-  while (p < end && rows < expect_rows) {
-    TReader r{p, end};
-    PageHead h;
-    if (!read_page_header(r, h)) {
-      set_error("nvt_pq_decode_chunk: malformed page header at byte %llu", (unsigned long long)(p - chunk));
-      return NVT_EINVAL;
-    }
-    const uint8_t *body = r.p;
-    if (h.compressed < 0 || h.uncompressed < 0 || (uint64_t)(end - body) < (uint64_t)h.compressed) {
-      set_error("nvt_pq_decode_chunk: page of %lld bytes runs past the chunk", (long long)h.compressed);
-      return NVT_EINVAL;
-    }
-    if (h.type == 1) {  // index page: nothing for us
-      p = body + h.compressed;
-      continue;
-    }
-    if (h.type == 2) {  // dictionary page: PLAIN values (encoding 0; 2 = PLAIN_DICTIONARY, the old name)
-      if (dict != nullptr || (h.dict_encoding != 0 && h.dict_encoding != 2) || h.dict_values < 0) {
-        set_error("nvt_pq_decode_chunk: dictionary page (encoding %d, second %d)", h.dict_encoding, dict != nullptr);
-        return NVT_EUNSUPPORTED;
-      }
-      const uint8_t *d = nullptr;
-      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &d);
-      if (rc) return rc;
-      if ((uint64_t)h.dict_values * (uint64_t)type_size > (uint64_t)h.uncompressed) {
-        set_error("nvt_pq_decode_chunk: dictionary page holds fewer values than it says");
-        return NVT_EINVAL;
-      }
-      dict = d;
-      ndict = (uint64_t)h.dict_values;
-      if (xf && (rc = xf->dictionary(d, ndict, type_size))) return rc;
-      if (codec != 0) scratch_at = ((uint64_t)h.uncompressed + 15) & ~15ull;   // (kept: pages go behind it)
-      p = body + h.compressed;
-      continue;
-    }
-    if (h.type != 0 && h.type != 3) {
-      set_error("nvt_pq_decode_chunk: page type %d", h.type);
-      return NVT_EUNSUPPORTED;
-    }
-    const bool by_dict = h.encoding == 2 || h.encoding == 8;   // PLAIN_DICTIONARY / RLE_DICTIONARY
-    const bool by_delta = h.encoding == 5 && df != nullptr && ls == nullptr;   // DELTA_BINARY_PACKED
-    if (by_delta && !df->ints) {
-      set_error("nvt_pq_decode_chunk_delta: DELTA_BINARY_PACKED values in a column that is not INT32 / INT64");
-      return NVT_EINVAL;
-    }
-    if (h.encoding != 0 && !by_dict && !by_delta) {
-      set_error("nvt_pq_decode_chunk: value encoding %d (PLAIN and dictionary indices are decoded here)", h.encoding);
-      return NVT_EUNSUPPORTED;
-    }
-    if (by_dict && dict == nullptr) {
-      set_error("nvt_pq_decode_chunk: dictionary indices without a dictionary page");
-      return NVT_EINVAL;
-    }
-    const uint64_t prow = (uint64_t)h.num_values;
-    if (h.num_values < 0 || prow > expect_rows - rows) {
-      set_error("nvt_pq_decode_chunk: more rows than the row group holds");
-      return NVT_EINVAL;
-    }
-    const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
-    uint64_t pvalid = prow;
-    // staged for the device: a non-empty snappy body of PLAIN values that is known to hold no nulls
-    bool staged = zf != nullptr && ls == nullptr && codec == 1 && h.encoding == 0 && prow > 0;
-    if (staged && h.type == 0)
-      // (levels in another encoding than the RLE hybrid have no u32 L in front: the host branch refuses them)
-      staged = h.compressed > 0 &&
-               (max_def_level == 0 ||
-                (h.def_encoding == 3 && (h.stat_nulls == 0 || (h.stat_nulls < 0 && zf->chunk_nulls == 0))));
-    if (staged && h.type == 0) {   // v1: the levels (u32 L | L bytes) are inside the body; the device drops them
-      if (max_def_level == 1) bits_fill(valid_out, valid_bit_offset + rows, prow, true);
-    } else if (h.type == 0) {   // v1: levels and values are compressed together
-      const uint8_t *u = nullptr;
-      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + h.uncompressed;
-      if (ls) {
-        if (h.rep_encoding != 3 || h.def_encoding != 3) {
-          set_error("nvt_pq_decode_list_chunk: level encodings %d / %d (the RLE hybrid is decoded here)",
-                    h.rep_encoding, h.def_encoding);
-          return NVT_EUNSUPPORTED;
-        }
-        uint64_t hist[4] = {0, 0, 0, 0};
-        for (int pass = 0; pass < 2; ++pass) {   // u32 length | repetition levels, then the same for definition
-          uint32_t lb;
-          if (pend - q < 4) {
-            set_error("nvt_pq_decode_list_chunk: page too short for its level streams");
-            return NVT_EINVAL;
-          }
-          memcpy(&lb, q, 4);
-          q += 4;
-          int bad = (uint64_t)(pend - q) < lb ? 1 : 0;
-          if (!bad && pass == 0) {
-            uint64_t rh[4] = {0, 0, 0, 0};
-            bad = decode_levels_wide(q, lb, prow, 1, 1, ls->rep, ls->slot0 + rows, rh);
-            ls->starts += rh[0];
-          } else if (!bad) {
-            bad = decode_levels_wide(q, lb, prow, ls->width, ls->max_def, ls->def, ls->slot0 + rows, hist);
-          }
-          if (bad) {
-            set_error(bad == 1 ? "nvt_pq_decode_list_chunk: level runs leave their stream"
-                               : "nvt_pq_decode_list_chunk: a level above the column's maximum");
-            return NVT_EINVAL;
-          }
-          q += lb;
-        }
-        pvalid = hist[ls->max_def];
-        for (unsigned v = ls->leaf_level; v <= ls->max_def; ++v) ls->leaves += hist[v];
-      } else if (max_def_level == 1) {
-        if (h.def_encoding != 3) {  // RLE (the hybrid)
-          set_error("nvt_pq_decode_chunk: definition level encoding %d", h.def_encoding);
-          return NVT_EUNSUPPORTED;
-        }
-        if (pend - q < 4) return NVT_EINVAL;
-        uint32_t lb;
-        memcpy(&lb, q, 4);
-        q += 4;
-        if ((uint64_t)(pend - q) < lb || !decode_levels(q, lb, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-          set_error("nvt_pq_decode_chunk: malformed definition levels");
-          return NVT_EINVAL;
-        }
-        q += lb;
-      }
-    } else {  // v2: repetition levels (none for flat columns), then definition levels -- never
-              // compressed, no length prefix --, then the values (compressed when the header says so)
-      if (h.rep_bytes != 0 && !ls) {
-        set_error("nvt_pq_decode_chunk: repetition levels (nested column)");
-        return NVT_EUNSUPPORTED;
-      }
-      // (each length is checked on its own before the sum: both are below 2^31 then)
-      if (h.def_bytes < 0 || h.rep_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes || (uint64_t)h.compressed < (uint64_t)h.rep_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.rep_bytes ||
-          (uint64_t)h.compressed < (uint64_t)h.def_bytes + (uint64_t)h.rep_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes + (uint64_t)h.rep_bytes) {
-        set_error("nvt_pq_decode_chunk: definition levels run past the page");
-        return NVT_EINVAL;
-      }
-      const uint64_t lbytes = (uint64_t)h.rep_bytes + (uint64_t)h.def_bytes;
-      staged = staged && h.v2_compressed && (max_def_level == 0 || h.num_nulls == 0) &&
-               (uint64_t)h.compressed > lbytes && (uint64_t)h.uncompressed - lbytes == prow * (uint64_t)type_size;
-      if (staged) {   // all rows valid by num_nulls: the levels are not looked at
-        if (max_def_level == 1) bits_fill(valid_out, valid_bit_offset + rows, prow, true);
-      } else if (ls) {
-        uint64_t rh[4] = {0, 0, 0, 0}, hist[4] = {0, 0, 0, 0};
-        int bad = decode_levels_wide(body, (uint64_t)h.rep_bytes, prow, 1, 1, ls->rep, ls->slot0 + rows, rh);
-        if (!bad)
-          bad = decode_levels_wide(body + h.rep_bytes, (uint64_t)h.def_bytes, prow, ls->width, ls->max_def, ls->def,
-                                   ls->slot0 + rows, hist);
-        if (bad) {
-          set_error(bad == 1 ? "nvt_pq_decode_list_chunk: level runs leave their stream"
-                             : "nvt_pq_decode_list_chunk: a level above the column's maximum");
-          return NVT_EINVAL;
-        }
-        ls->starts += rh[0];
-        pvalid = hist[ls->max_def];
-        for (unsigned v = ls->leaf_level; v <= ls->max_def; ++v) ls->leaves += hist[v];
-      } else if (max_def_level == 1) {
-        if (!decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-          set_error("nvt_pq_decode_chunk: malformed definition levels");
-          return NVT_EINVAL;
-        }
-      }
-      const uint64_t vcomp = (uint64_t)h.compressed - lbytes;
-      const uint64_t vraw = (uint64_t)h.uncompressed - lbytes;
-      if (!staged) {
-        const uint8_t *u = nullptr;
-        int rc = inflate(body + lbytes, vcomp, vraw, codec != 0 && h.v2_compressed, &u);
-        if (rc) return rc;
-        q = u;
-        pend = u + vraw;
-      }
-    }
-    if (ls && rows == 0 && prow > 0 && ((ls->rep[ls->slot0 >> 3] >> (ls->slot0 & 7)) & 1)) {
-      set_error("nvt_pq_decode_list_chunk: the chunk's first slot continues a row");
-      return NVT_EINVAL;
-    }
-    if ((vals + pvalid) * (uint64_t)type_size > values_cap_bytes) {
-      set_error("nvt_pq_decode_chunk: values buffer too small");
-      return NVT_EINVAL;
-    }
-    if (staged) {   // the compressed body (v2: its values region) as it is: the device fills the hole of prow values
-      const uint64_t lead = h.type == 3 ? (uint64_t)h.rep_bytes + (uint64_t)h.def_bytes : 0;
-      const int rc = zf->page(body + lead, (uint64_t)h.compressed - lead, (values_offset + vals) * (uint64_t)type_size,
-                              prow * (uint64_t)type_size,
-                              (h.type == 0 && max_def_level == 1) ? NVT_INFLATE_V1_LEVELS : 0u);
-      if (rc) return rc;
-    } else if (by_delta) {   // staged as it is: the device fills the hole of pvalid values
-      const int rc = delta_stage_page(*df, q, (uint64_t)(pend - q), type_size, pvalid, values_offset + vals);
-      if (rc) return rc;
-    } else if (!by_dict) {
-      const uint64_t vbytes = pvalid * (uint64_t)type_size;
-      if ((uint64_t)(pend - q) < vbytes) {
-        set_error("nvt_pq_decode_chunk: page holds fewer values than its levels say");
-        return NVT_EINVAL;
-      }
-      if (ls && (uint64_t)(pend - q) != vbytes) {   // (the levels say how many PLAIN values follow: exactly)
-        set_error("nvt_pq_decode_list_chunk: page holds more values than its levels say");
-        return NVT_EINVAL;
-      }
-      memcpy(values_out + vals * (uint64_t)type_size, q, vbytes);
-      if (xf) {   // in place already: the device leaves these positions alone
-        const int rc = xf->run(NVT_PQ_RUN_KEEP, 0, 0, 0, values_offset + vals, pvalid);
-        if (rc) return rc;
-      }
-    } else if (xf) {   // staged as it is: the device fills the hole of pvalid values
-      const int rc = dict_index_runs(*xf, q, pend, pvalid, ndict, values_offset + vals);
-      if (rc == NVT_EINVAL) set_error("nvt_pq_decode_chunk: malformed dictionary indices");
-      if (rc) return rc;
-    } else {
-      const bool ok = type_size == 4
-          ? decode_dict_indices<uint32_t>(q, pend, pvalid, reinterpret_cast<const uint32_t *>(dict), ndict,
-                                          reinterpret_cast<uint32_t *>(values_out) + vals)
-          : decode_dict_indices<uint64_t>(q, pend, pvalid, reinterpret_cast<const uint64_t *>(dict), ndict,
-                                          reinterpret_cast<uint64_t *>(values_out) + vals);
-      if (!ok) {
-        set_error("nvt_pq_decode_chunk: malformed dictionary indices");
-        return NVT_EINVAL;
-      }
-    }
-    vals += pvalid;
-    rows += prow;
-    p = body + h.compressed;
-  }
-  if (rows != expect_rows) {
-    set_error("nvt_pq_decode_chunk: %llu rows in the pages, %llu expected", (unsigned long long)rows,
-              (unsigned long long)expect_rows);
-    return NVT_EINVAL;
-  }
-  if (ls && ls->starts != ls->expect_rows) {
-    set_error("nvt_pq_decode_list_chunk: %llu row starts in the pages, %llu expected", (unsigned long long)ls->starts,
-              (unsigned long long)ls->expect_rows);
-    return NVT_EINVAL;
-  }
-  *rows_out = rows;
-  *values_out_count = vals;
-  return NVT_OK;
-}
-
 int nvt_pq_decode_list_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
                              int leaf_level, int max_def_level, uint64_t expect_slots, uint64_t expect_rows,
                              uint8_t *rep_out, uint8_t *def_out, uint64_t slot_offset, uint64_t slot_cap,
@@ -1114,22 +669,16 @@ int nvt_pq_decode_list_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int cod
                 "max_def_level is leaf_level (+ 1 for optional leaves)");
   NVT_CHECK_ARG(slot_offset <= slot_cap && expect_slots <= slot_cap - slot_offset, "the slots do not fit the level streams");
   NVT_CHECK_ARG(slot_cap < (1ull << 60), "slot_cap too large");
-  ListSink ls;
-  ls.rep = rep_out;
-  ls.def = def_out;
-  ls.slot0 = slot_offset;
-  ls.slot_cap = slot_cap;
-  ls.width = max_def_level == 1 ? 1u : 2u;
-  ls.leaf_level = (unsigned)leaf_level;
-  ls.max_def = (unsigned)max_def_level;
-  ls.expect_rows = expect_rows;
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_slots, scratch, scratch_bytes};
+  ListLevels lv{rep_out, def_out, slot_offset, max_def_level == 1 ? 1u : 2u, (unsigned)leaf_level,
+                (unsigned)max_def_level, expect_rows};
+  PlainValues vs(type_size, values_out, values_cap_bytes, true);
   uint64_t slots = 0, vals = 0;
-  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_slots, nullptr, 0, values_out,
-                           values_cap_bytes, scratch, scratch_bytes, &slots, &vals, &ls);
+  const int rc = decode_numbers(w, lv, vs, &slots, &vals);
   if (rc) return rc;
   counts[0] = slots;
-  counts[1] = ls.starts;
-  counts[2] = ls.leaves;
+  counts[1] = lv.starts;
+  counts[2] = lv.leaves;
   counts[3] = vals;
   return NVT_OK;
 }
@@ -1138,8 +687,10 @@ int nvt_pq_decode_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int type_siz
                         uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
                         uint8_t *values_out, uint64_t values_cap_bytes, uint64_t *rows_out,
                         uint64_t *values_out_count) {
-  return pq_decode(chunk, chunk_bytes, 0, type_size, max_def_level, expect_rows, valid_out, valid_bit_offset,
-                   values_out, values_cap_bytes, nullptr, 0, rows_out, values_out_count);
+  const PageWalk w{__func__, chunk, chunk_bytes, 0, expect_rows, nullptr, 0};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  PlainValues vs(type_size, values_out, values_cap_bytes);
+  return decode_numbers(w, lv, vs, rows_out, values_out_count);
 }
 
 int nvt_pq_decode_chunk_codec(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int type_size,
@@ -1147,8 +698,10 @@ int nvt_pq_decode_chunk_codec(const uint8_t *chunk, uint64_t chunk_bytes, int co
                               uint64_t valid_bit_offset, uint8_t *values_out, uint64_t values_cap_bytes,
                               uint8_t *scratch, uint64_t scratch_bytes, uint64_t *rows_out,
                               uint64_t *values_out_count) {
-  return pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out, valid_bit_offset,
-                   values_out, values_cap_bytes, scratch, scratch_bytes, rows_out, values_out_count);
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_rows, scratch, scratch_bytes};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  PlainValues vs(type_size, values_out, values_cap_bytes);
+  return decode_numbers(w, lv, vs, rows_out, values_out_count);
 }
 
 int nvt_pq_delta_stage_page(const uint8_t *region, uint64_t region_bytes, int type_size, uint64_t count,
@@ -1173,14 +726,16 @@ int nvt_pq_decode_chunk_delta(const uint8_t *chunk, uint64_t chunk_bytes, int co
   NVT_CHECK_ARG(stage && need, "null pointer");
   NVT_CHECK_ARG(ptype == 1 || ptype == 2 || ptype == 4 || ptype == 5, "physical type INT32, INT64, FLOAT or DOUBLE");
   NVT_CHECK_ARG(stage->bytes && stage->pages && stage->mbs, "null staging buffer");
-  DeltaFill f{stage, stage->nbytes, stage->npages, stage->nmbs, need, ptype == 1 || ptype == 2};
-  const int rc = pq_decode(chunk, chunk_bytes, codec, (ptype == 1 || ptype == 4) ? 4 : 8, max_def_level, expect_rows,
-                           valid_out, valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
-                           values_count, nullptr, &f, values_offset);
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_rows, scratch, scratch_bytes};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  DeltaValues vs(PlainValues((ptype == 1 || ptype == 4) ? 4 : 8, values_out, values_cap_bytes),
+                 DeltaFill{stage, stage->nbytes, stage->npages, stage->nmbs, need, ptype == 1 || ptype == 2},
+                 values_offset);
+  const int rc = decode_numbers(w, lv, vs, rows_out, values_count);
   if (rc) return rc;
-  stage->nbytes = f.nbytes;
-  stage->npages = f.npages;
-  stage->nmbs = f.nmbs;
+  stage->nbytes = vs.f.nbytes;
+  stage->npages = vs.f.npages;
+  stage->nmbs = vs.f.nmbs;
   return NVT_OK;
 }
 
@@ -1194,11 +749,13 @@ int nvt_pq_decode_chunk_dict(const uint8_t *chunk, uint64_t chunk_bytes, int cod
   NVT_CHECK_ARG(stage->runs_cap >= 1 && stage->nruns < stage->runs_cap && stage->packed_cap >= 8 &&
                     stage->npacked <= stage->packed_cap - 8 && stage->ndict_bytes <= stage->dict_cap,
                 "the stage's fill state does not fit its capacities");
-  DictFill f{stage, stage->ndict_bytes, stage->nruns, stage->npacked, need};
-  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out,
-                           valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
-                           values_count, nullptr, nullptr, values_offset, &f);
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_rows, scratch, scratch_bytes};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  DictValues vs(PlainValues(type_size, values_out, values_cap_bytes),
+                DictFill{stage, stage->ndict_bytes, stage->nruns, stage->npacked, need}, values_offset);
+  const int rc = decode_numbers(w, lv, vs, rows_out, values_count);
   if (rc) return rc;
+  const DictFill &f = vs.f;
   uint32_t *closing = stage->runs + 4 * f.nruns;   // (run() kept room for it)
   closing[0] = (uint32_t)(values_offset + *values_count);
   closing[1] = NVT_PQ_RUN_END;
@@ -1219,347 +776,14 @@ int nvt_pq_decode_chunk_inflate(const uint8_t *chunk, uint64_t chunk_bytes, int 
   NVT_CHECK_ARG(stage->bytes && stage->pages, "null staging buffer");
   NVT_CHECK_ARG(stage->nbytes <= stage->bytes_cap && stage->npages <= stage->pages_cap,
                 "the stage's fill state does not fit its capacities");
-  InflateFill f{stage, stage->nbytes, stage->npages, need, chunk_nulls};
-  const int rc = pq_decode(chunk, chunk_bytes, codec, type_size, max_def_level, expect_rows, valid_out,
-                           valid_bit_offset, values_out, values_cap_bytes, scratch, scratch_bytes, rows_out,
-                           values_count, nullptr, nullptr, values_offset, nullptr, &f);
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_rows, scratch, scratch_bytes};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  InflateValues vs(PlainValues(type_size, values_out, values_cap_bytes),
+                   InflateFill{stage, stage->nbytes, stage->npages, need, chunk_nulls}, values_offset, max_def_level);
+  const int rc = decode_numbers(w, lv, vs, rows_out, values_count);
   if (rc) return rc;
-  stage->nbytes = f.nbytes;
-  stage->npages = f.npages;
-  return NVT_OK;
-}
-
-// ---- string columns: entries + run table + packed bytes ("String columns in the parquet
-// reader") ------------------------------------------------------------------------------------------
-namespace {
-
-// the fill state of a nvt_pq_str_stage during one chunk: committed to the stage on NVT_OK only, so a
-// chunk that asked for larger buffers is decoded again from its first byte
-struct StrFill {
-  nvt_pq_str_stage *st;
-  uint64_t entries, nchars, nruns, npacked, nvalues;
-  uint64_t *need;
-  // -> NVT_OK, or NVT_PQ_STR_GROW with need[which] = the least capacity that would have sufficed here
-  int room(int which, uint64_t want, uint64_t cap) {
-    if (want <= cap) return NVT_OK;
-    need[which] = want;
-    set_error("nvt_pq_decode_str_chunk: staging buffer %d holds %llu, %llu needed", which, (unsigned long long)cap,
-              (unsigned long long)want);
-    return NVT_PQ_STR_GROW;
-  }
-  // one record [start = nvalues, kind | width << 8, a, b]; a repeat run that continues the last
-  // record's entry, or a sequence that continues its entries, adds nothing: a run ends where the next
-  // record starts
-  int run(unsigned kind, unsigned width, uint32_t a, uint32_t b, uint64_t count) {
-    if (count == 0) return NVT_OK;
-    uint32_t *rec = st->runs + 4 * nruns;
-    bool merged = false;
-    if (nruns > 0) {
-      const uint32_t *last = rec - 4;
-      if (kind == NVT_PQ_RUN_REPEAT && last[1] == NVT_PQ_RUN_REPEAT && last[2] == a) merged = true;
-      if (kind == NVT_PQ_RUN_SEQUENCE && last[1] == NVT_PQ_RUN_SEQUENCE &&
-          (uint64_t)last[2] + (nvalues - last[0]) == (uint64_t)a)
-        merged = true;
-    }
-    if (!merged) {
-      const int rc = room(2, nruns + 2, st->runs_cap);   // (this record and the closing one)
-      if (rc) return rc;
-      rec[0] = (uint32_t)nvalues;
-      rec[1] = kind | (width << 8);
-      rec[2] = a;
-      rec[3] = b;
-      ++nruns;
-    }
-    nvalues += count;
-    return NVT_OK;
-  }
-};
-
-// `count` PLAIN BYTE_ARRAY values (u32 length | bytes, each) in [q, pend) -> appended entries
-int str_append_plain(StrFill &f, const uint8_t *q, const uint8_t *pend, uint64_t count) {
-  int rc = f.room(0, f.entries + count, f.st->entries_cap);
-  if (rc) return rc;
-  for (uint64_t i = 0; i < count; ++i) {
-    if ((uint64_t)(pend - q) < 4) {
-      set_error("nvt_pq_decode_str_chunk: a length prefix past its page");
-      return NVT_EINVAL;
-    }
-    uint32_t len;
-    memcpy(&len, q, 4);
-    q += 4;
-    if ((uint64_t)(pend - q) < len) {
-      set_error("nvt_pq_decode_str_chunk: a value of %u bytes runs past its page", len);
-      return NVT_EINVAL;
-    }
-    if ((rc = f.room(1, ((f.nchars + len + 3) & ~3ull), f.st->chars_cap))) return rc;
-    memcpy(f.st->chars + f.nchars, q, len);
-    q += len;
-    f.nchars += len;
-    f.st->offsets[++f.entries] = (int64_t)f.nchars;
-  }
-  return NVT_OK;
-}
-
-// the dictionary indices of one page (`count` non-null values; one byte bit width, then the RLE /
-// bit-packed hybrid) -> run records; the bytes of bit-packed runs go to the packed staging buffer,
-// each run's on a 4-byte boundary
-int str_index_runs(StrFill &f, const uint8_t *p, const uint8_t *end, uint64_t count, uint64_t base,
-                   uint64_t ndict) {
-  if (count == 0) return NVT_OK;
-  if (p >= end) {
-    set_error("nvt_pq_decode_str_chunk: an index page without its bit width");
-    return NVT_EINVAL;
-  }
-  const unsigned bw = *p++;
-  if (bw > 32) {
-    set_error("nvt_pq_decode_str_chunk: dictionary indices of bit width %u", bw);
-    return NVT_EINVAL;
-  }
-  const uint32_t kBadId = 0xFFFFFFFFu;   // (entries stay below 2^31: the device counts this id as bad)
-  if (bw == 0)   // a one-entry dictionary: every value is its entry, whatever runs the page spells out
-    return f.run(NVT_PQ_RUN_REPEAT, 0, ndict ? (uint32_t)base : kBadId, 0, count);
-  const uint64_t mask = bw == 32 ? 0xFFFFFFFFull : ((1ull << bw) - 1ull);
-  TReader r{p, end};
-  uint64_t done = 0;
-  while (done < count) {
-    const uint64_t head = r.varint();
-    if (!r.ok) {
-      set_error("nvt_pq_decode_str_chunk: the index runs end before the page's values");
-      return NVT_EINVAL;
-    }
-    const uint64_t avail = (uint64_t)(r.end - r.p);
-    if (head & 1) {   // bit-packed: (head >> 1) groups of 8 values, `bw` bits each, LSB first
-      const uint64_t groups = head >> 1;
-      if (groups > (1ull << 40)) {
-        set_error("nvt_pq_decode_str_chunk: a bit-packed run of %llu groups", (unsigned long long)groups);
-        return NVT_EINVAL;
-      }
-      uint64_t take = groups * 8;
-      if (take > count - done) take = count - done;   // (the last group is padded)
-      const uint64_t nb = (take * bw + 7) / 8;        // the bytes the values need
-      if (avail < nb) {
-        set_error("nvt_pq_decode_str_chunk: a bit-packed run past its page");
-        return NVT_EINVAL;
-      }
-      if (take) {
-        const uint64_t at = (f.npacked + 3) & ~3ull;
-        int rc = f.room(3, at + nb + 8, f.st->packed_cap);
-        if (rc) return rc;
-        if (at / 4 > 0xFFFFFFFFull || base > 0x7FFFFFFFull) {
-          set_error("nvt_pq_decode_str_chunk: more than 16 GiB of packed indices in one partition");
-          return NVT_EUNSUPPORTED;
-        }
-        memset(f.st->packed + f.npacked, 0, at - f.npacked);
-        memcpy(f.st->packed + at, r.p, nb);
-        f.npacked = at + nb;
-        if ((rc = f.run(NVT_PQ_RUN_PACKED, bw, (uint32_t)base, (uint32_t)(at / 4), take))) return rc;
-      }
-      r.skip_bytes(groups * bw < avail ? groups * bw : avail);   // (a writer may cut the padding)
-      done += take;
-    } else {   // RLE: (head >> 1) times the value in the next ceil(bw / 8) bytes
-      uint64_t n = head >> 1;
-      const unsigned vb = (bw + 7) / 8;
-      if (avail < vb) {
-        set_error("nvt_pq_decode_str_chunk: a repeat run past its page");
-        return NVT_EINVAL;
-      }
-      uint64_t idx = 0;
-      memcpy(&idx, r.p, vb);
-      r.p += vb;
-      idx &= mask;
-      if (n > count - done) n = count - done;
-      const int rc = f.run(NVT_PQ_RUN_REPEAT, 0, idx < ndict ? (uint32_t)(base + idx) : kBadId, 0, n);
-      if (rc) return rc;
-      done += n;
-    }
-  }
-  return NVT_OK;
-}
-
-}  // namespace
-
-int nvt_pq_decode_str_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
-                            uint64_t expect_rows, uint8_t *valid_out, uint64_t valid_bit_offset,
-                            nvt_pq_str_stage *stage, uint8_t *scratch, uint64_t scratch_bytes, uint64_t *need) {
-  NVT_CHECK_ARG(chunk && stage && need, "null pointer");
-  NVT_CHECK_ARG(stage->offsets && stage->chars && stage->runs && stage->packed, "null staging buffer");
-  NVT_CHECK_ARG(max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
-  NVT_CHECK_ARG(max_def_level == 0 || valid_out, "null validity buffer");
-  NVT_CHECK_ARG(stage->runs_cap >= 1 && stage->nruns < stage->runs_cap && stage->packed_cap >= 8 &&
-                    stage->npacked <= stage->packed_cap - 8 && stage->entries <= stage->entries_cap &&
-                    stage->nchars <= stage->chars_cap && (stage->chars_cap & 3) == 0,
-                "the stage's fill state does not fit its capacities");
-  if (codec != 0 && codec != 1) {
-    set_error("nvt_pq_decode_str_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
-    return NVT_EUNSUPPORTED;
-  }
-  need[0] = need[1] = need[2] = need[3] = 0;
-  StrFill f{stage, stage->entries, stage->nchars, stage->nruns, stage->npacked, stage->nvalues, need};
-  if (f.entries == 0) stage->offsets[0] = 0;
-  // page body -> `want` uncompressed bytes: the body itself, or the scratch buffer (a string chunk
-  // keeps nothing between pages: the dictionary's values are appended to the entries at once)
-  auto inflate = [&](const uint8_t *src, uint64_t nsrc, uint64_t want, bool compressed, const uint8_t **out) -> int {
-    if (!compressed) {
-      if (nsrc != want) {
-        set_error("nvt_pq_decode_str_chunk: an uncompressed page of %llu bytes that says %llu",
-                  (unsigned long long)nsrc, (unsigned long long)want);
-        return NVT_EINVAL;
-      }
-      *out = src;
-      return NVT_OK;
-    }
-    if (scratch == nullptr || scratch_bytes < want) {
-      set_error("nvt_pq_decode_str_chunk: scratch too small for a page of %llu bytes", (unsigned long long)want);
-      return NVT_EINVAL;
-    }
-    if (snappy_uncompress(src, nsrc, scratch, want) != (int64_t)want) {
-      set_error("nvt_pq_decode_str_chunk: malformed snappy block");
-      return NVT_EINVAL;
-    }
-    *out = scratch;
-    return NVT_OK;
-  };
-  const uint8_t *p = chunk, *end = chunk + chunk_bytes;
-  uint64_t rows = 0;
-  bool have_dict = false;
-  uint64_t base = 0, ndict = 0;   // the chunk's dictionary: entries [base, base + ndict)
-  while (p < end && rows < expect_rows) {
-    TReader r{p, end};
-    PageHead h;
-    if (!read_page_header(r, h)) {
-      set_error("nvt_pq_decode_str_chunk: malformed page header at byte %llu", (unsigned long long)(p - chunk));
-      return NVT_EINVAL;
-    }
-    const uint8_t *body = r.p;
-    if (h.compressed < 0 || h.uncompressed < 0 || (uint64_t)(end - body) < (uint64_t)h.compressed) {
-      set_error("nvt_pq_decode_str_chunk: page of %lld bytes runs past the chunk", (long long)h.compressed);
-      return NVT_EINVAL;
-    }
-    if (h.type == 1) {  // index page: nothing for us
-      p = body + h.compressed;
-      continue;
-    }
-    if (h.type == 2) {  // dictionary page: PLAIN values (encoding 0; 2 = PLAIN_DICTIONARY, the old name)
-      if (have_dict || (h.dict_encoding != 0 && h.dict_encoding != 2)) {
-        set_error("nvt_pq_decode_str_chunk: dictionary page (encoding %d, second %d)", h.dict_encoding, (int)have_dict);
-        return NVT_EUNSUPPORTED;
-      }
-      const uint8_t *d = nullptr;
-      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &d);
-      if (rc) return rc;
-      // every value holds a 4-byte length: compared by division, a count of 2^61 must not wrap
-      if (h.dict_values < 0 || (uint64_t)h.dict_values > (uint64_t)h.uncompressed / 4) {
-        set_error("nvt_pq_decode_str_chunk: dictionary page holds fewer values than it says");
-        return NVT_EINVAL;
-      }
-      have_dict = true;
-      base = f.entries;
-      ndict = (uint64_t)h.dict_values;
-      if ((rc = str_append_plain(f, d, d + h.uncompressed, ndict))) return rc;
-      p = body + h.compressed;
-      continue;
-    }
-    if (h.type != 0 && h.type != 3) {
-      set_error("nvt_pq_decode_str_chunk: page type %d", h.type);
-      return NVT_EUNSUPPORTED;
-    }
-    const bool by_dict = h.encoding == 2 || h.encoding == 8;   // PLAIN_DICTIONARY / RLE_DICTIONARY
-    if (h.encoding != 0 && !by_dict) {
-      set_error("nvt_pq_decode_str_chunk: value encoding %d (PLAIN and dictionary indices are decoded here)",
-                h.encoding);
-      return NVT_EUNSUPPORTED;
-    }
-    if (by_dict && !have_dict) {
-      set_error("nvt_pq_decode_str_chunk: dictionary indices without a dictionary page");
-      return NVT_EINVAL;
-    }
-    const uint64_t prow = (uint64_t)h.num_values;
-    if (h.num_values < 0 || prow > expect_rows - rows) {
-      set_error("nvt_pq_decode_str_chunk: more rows than the row group holds");
-      return NVT_EINVAL;
-    }
-    const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
-    uint64_t pvalid = prow;
-    if (h.type == 0) {   // v1: levels and values are compressed together
-      const uint8_t *u = nullptr;
-      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + h.uncompressed;
-      if (max_def_level == 1) {
-        if (h.def_encoding != 3) {  // RLE (the hybrid)
-          set_error("nvt_pq_decode_str_chunk: definition level encoding %d", h.def_encoding);
-          return NVT_EUNSUPPORTED;
-        }
-        uint32_t lb = 0;
-        if (pend - q >= 4) memcpy(&lb, q, 4);
-        if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb ||
-            !decode_levels(q + 4, lb, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-          set_error("nvt_pq_decode_str_chunk: malformed definition levels");
-          return NVT_EINVAL;
-        }
-        q += 4 + (uint64_t)lb;
-      }
-    } else {  // v2: definition levels uncompressed in front, no length prefix
-      if (h.rep_bytes != 0) {
-        set_error("nvt_pq_decode_str_chunk: repetition levels (nested column)");
-        return NVT_EUNSUPPORTED;
-      }
-      if (h.def_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes) {
-        set_error("nvt_pq_decode_str_chunk: definition levels run past the page");
-        return NVT_EINVAL;
-      }
-      if (max_def_level == 1 &&
-          !decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-        set_error("nvt_pq_decode_str_chunk: malformed definition levels");
-        return NVT_EINVAL;
-      }
-      const uint8_t *u = nullptr;
-      const uint64_t lbytes = (uint64_t)h.def_bytes;
-      int rc = inflate(body + lbytes, (uint64_t)h.compressed - lbytes, (uint64_t)h.uncompressed - lbytes,
-                       codec != 0 && h.v2_compressed, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + ((uint64_t)h.uncompressed - lbytes);
-    }
-    if (pvalid > prow) {
-      set_error("nvt_pq_decode_str_chunk: more valid rows than rows");
-      return NVT_EINVAL;
-    }
-    int rc;
-    if (by_dict) {
-      rc = str_index_runs(f, q, pend, pvalid, base, ndict);
-    } else {
-      const uint64_t first = f.entries;
-      rc = str_append_plain(f, q, pend, pvalid);
-      if (!rc) rc = f.run(NVT_PQ_RUN_SEQUENCE, 0, (uint32_t)first, 0, pvalid);
-    }
-    if (rc) return rc;
-    if (f.entries > 0x7FFFFFFEull || f.nvalues > 0x7FFFFFFEull) {
-      set_error("nvt_pq_decode_str_chunk: more than 2^31 - 2 entries or values in one partition");
-      return NVT_EUNSUPPORTED;
-    }
-    rows += prow;
-    p = body + h.compressed;
-  }
-  if (rows != expect_rows) {
-    set_error("nvt_pq_decode_str_chunk: %llu rows in the pages, %llu expected", (unsigned long long)rows,
-              (unsigned long long)expect_rows);
-    return NVT_EINVAL;
-  }
-  // the closing record (the next chunk writes over it) and the 8 readable bytes behind the packed runs
-  uint32_t *close = stage->runs + 4 * f.nruns;
-  close[0] = (uint32_t)f.nvalues;
-  close[1] = NVT_PQ_RUN_END;
-  close[2] = close[3] = 0;
-  memset(stage->packed + f.npacked, 0, 8);
-  memset(stage->chars + f.nchars, 0, ((f.nchars + 3) & ~3ull) - f.nchars);
-  stage->entries = f.entries;
-  stage->nchars = f.nchars;
-  stage->nruns = f.nruns;
-  stage->npacked = f.npacked;
-  stage->nvalues = f.nvalues;
+  stage->nbytes = vs.f.nbytes;
+  stage->npages = vs.f.npages;
   return NVT_OK;
 }
 
@@ -1603,6 +827,43 @@ bool decode_bool_rle(const uint8_t *p, const uint8_t *end, uint64_t count, uint8
   return true;
 }
 
+// the value sink: PLAIN bits or RLE runs -> one byte per non-null value.  Parquet has no bool
+// dictionaries: a dictionary page is refused.
+struct BoolValues : ValueSink {
+  uint8_t *out;
+  uint64_t cap;
+  uint64_t vals = 0;
+  BoolValues(uint8_t *out_, uint64_t cap_) : out(out_), cap(cap_) {}
+  int accepts(const char *who, const PageHead &h, bool) const {
+    if (h.encoding == 0 || h.encoding == 3) return NVT_OK;   // PLAIN (bit-packed) / RLE
+    set_error("%s: value encoding %d (PLAIN and RLE are decoded here)", who, h.encoding);
+    return NVT_EUNSUPPORTED;
+  }
+  int page(const char *who, const PageHead &h, const uint8_t *q, const uint8_t *pend, uint64_t pvalid) {
+    if (pvalid > cap - vals) {
+      set_error("%s: values buffer too small", who);
+      return NVT_EINVAL;
+    }
+    if (h.encoding == 0) {
+      if ((uint64_t)(pend - q) < (pvalid + 7) / 8) {
+        set_error("%s: page holds fewer values than its levels say", who);
+        return NVT_EINVAL;
+      }
+      bits_to_bytes(q, pvalid, out + vals);
+    } else if (pvalid) {
+      // RLE: u32 length | runs of the hybrid at bit width 1
+      uint32_t lb = 0;
+      if (pend - q >= 4) memcpy(&lb, q, 4);
+      if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb || !decode_bool_rle(q + 4, q + 4 + lb, pvalid, out + vals)) {
+        set_error("%s: malformed RLE values", who);
+        return NVT_EINVAL;
+      }
+    }
+    vals += pvalid;
+    return NVT_OK;
+  }
+};
+
 }  // namespace
 
 int nvt_pq_decode_bool_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int codec, int max_def_level,
@@ -1610,142 +871,17 @@ int nvt_pq_decode_bool_chunk(const uint8_t *chunk, uint64_t chunk_bytes, int cod
                              uint8_t *values_out, uint64_t values_cap, uint8_t *scratch, uint64_t scratch_bytes,
                              uint64_t *rows_out, uint64_t *values_count) {
   NVT_CHECK_ARG(chunk && values_out && rows_out && values_count, "null pointer");
-  NVT_CHECK_ARG(max_def_level == 0 || max_def_level == 1, "flat columns: max definition level 0 / 1");
-  NVT_CHECK_ARG(max_def_level == 0 || valid_out, "null validity buffer");
-  if (codec != 0 && codec != 1) {
-    set_error("nvt_pq_decode_bool_chunk: codec %d (UNCOMPRESSED and SNAPPY are decoded here)", codec);
-    return NVT_EUNSUPPORTED;
-  }
-  // page body -> `want` uncompressed bytes: the body itself, or the scratch buffer
-  auto inflate = [&](const uint8_t *src, uint64_t nsrc, uint64_t want, bool compressed, const uint8_t **out) -> int {
-    if (!compressed) {
-      if (nsrc != want) {
-        set_error("nvt_pq_decode_bool_chunk: an uncompressed page of %llu bytes that says %llu",
-                  (unsigned long long)nsrc, (unsigned long long)want);
-        return NVT_EINVAL;
-      }
-      *out = src;
-      return NVT_OK;
-    }
-    if (scratch == nullptr || scratch_bytes < want) {
-      set_error("nvt_pq_decode_bool_chunk: scratch too small for a page of %llu bytes", (unsigned long long)want);
-      return NVT_EINVAL;
-    }
-    if (snappy_uncompress(src, nsrc, scratch, want) != (int64_t)want) {
-      set_error("nvt_pq_decode_bool_chunk: malformed snappy block");
-      return NVT_EINVAL;
-    }
-    *out = scratch;
-    return NVT_OK;
-  };
-  const uint8_t *p = chunk, *end = chunk + chunk_bytes;
-  uint64_t rows = 0, vals = 0;
-  while (p < end && rows < expect_rows) {
-    TReader r{p, end};
-    PageHead h;
-    if (!read_page_header(r, h)) {
-      set_error("nvt_pq_decode_bool_chunk: malformed page header at byte %llu", (unsigned long long)(p - chunk));
-      return NVT_EINVAL;
-    }
-    const uint8_t *body = r.p;
-    if (h.compressed < 0 || h.uncompressed < 0 || (uint64_t)(end - body) < (uint64_t)h.compressed) {
-      set_error("nvt_pq_decode_bool_chunk: page of %lld bytes runs past the chunk", (long long)h.compressed);
-      return NVT_EINVAL;
-    }
-    if (h.type == 1) {  // index page: nothing for us
-      p = body + h.compressed;
-      continue;
-    }
-    if (h.type != 0 && h.type != 3) {   // (a dictionary page too: parquet has no bool dictionaries)
-      set_error("nvt_pq_decode_bool_chunk: page type %d", h.type);
-      return NVT_EUNSUPPORTED;
-    }
-    if (h.encoding != 0 && h.encoding != 3) {   // PLAIN (bit-packed) / RLE
-      set_error("nvt_pq_decode_bool_chunk: value encoding %d (PLAIN and RLE are decoded here)", h.encoding);
-      return NVT_EUNSUPPORTED;
-    }
-    const uint64_t prow = (uint64_t)h.num_values;
-    if (h.num_values < 0 || prow > expect_rows - rows) {
-      set_error("nvt_pq_decode_bool_chunk: more rows than the row group holds");
-      return NVT_EINVAL;
-    }
-    const uint8_t *q = nullptr, *pend = nullptr;   // the values (behind the levels), uncompressed
-    uint64_t pvalid = prow;
-    if (h.type == 0) {   // v1: levels and values are compressed together
-      const uint8_t *u = nullptr;
-      int rc = inflate(body, (uint64_t)h.compressed, (uint64_t)h.uncompressed, codec != 0, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + h.uncompressed;
-      if (max_def_level == 1) {
-        if (h.def_encoding != 3) {  // RLE (the hybrid)
-          set_error("nvt_pq_decode_bool_chunk: definition level encoding %d", h.def_encoding);
-          return NVT_EUNSUPPORTED;
-        }
-        uint32_t lb = 0;
-        if (pend - q >= 4) memcpy(&lb, q, 4);
-        if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb ||
-            !decode_levels(q + 4, lb, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-          set_error("nvt_pq_decode_bool_chunk: malformed definition levels");
-          return NVT_EINVAL;
-        }
-        q += 4 + (uint64_t)lb;
-      }
-    } else {  // v2: definition levels uncompressed in front, no length prefix
-      if (h.rep_bytes != 0) {
-        set_error("nvt_pq_decode_bool_chunk: repetition levels (nested column)");
-        return NVT_EUNSUPPORTED;
-      }
-      if (h.def_bytes < 0 || (uint64_t)h.compressed < (uint64_t)h.def_bytes ||
-          (uint64_t)h.uncompressed < (uint64_t)h.def_bytes) {
-        set_error("nvt_pq_decode_bool_chunk: definition levels run past the page");
-        return NVT_EINVAL;
-      }
-      if (max_def_level == 1 &&
-          !decode_levels(body, (uint64_t)h.def_bytes, prow, valid_out, valid_bit_offset + rows, &pvalid)) {
-        set_error("nvt_pq_decode_bool_chunk: malformed definition levels");
-        return NVT_EINVAL;
-      }
-      const uint8_t *u = nullptr;
-      const uint64_t lbytes = (uint64_t)h.def_bytes;
-      int rc = inflate(body + lbytes, (uint64_t)h.compressed - lbytes, (uint64_t)h.uncompressed - lbytes,
-                       codec != 0 && h.v2_compressed, &u);
-      if (rc) return rc;
-      q = u;
-      pend = u + ((uint64_t)h.uncompressed - lbytes);
-    }
-    if (pvalid > prow || vals > values_cap || pvalid > values_cap - vals) {
-      set_error("nvt_pq_decode_bool_chunk: values buffer too small");
-      return NVT_EINVAL;
-    }
-    if (h.encoding == 0) {
-      if ((uint64_t)(pend - q) < (pvalid + 7) / 8) {
-        set_error("nvt_pq_decode_bool_chunk: page holds fewer values than its levels say");
-        return NVT_EINVAL;
-      }
-      bits_to_bytes(q, pvalid, values_out + vals);
-    } else if (pvalid) {
-      // RLE: u32 length | runs of the hybrid at bit width 1
-      uint32_t lb = 0;
-      if (pend - q >= 4) memcpy(&lb, q, 4);
-      if (pend - q < 4 || (uint64_t)(pend - q - 4) < lb || !decode_bool_rle(q + 4, q + 4 + lb, pvalid, values_out + vals)) {
-        set_error("nvt_pq_decode_bool_chunk: malformed RLE values");
-        return NVT_EINVAL;
-      }
-    }
-    vals += pvalid;
-    rows += prow;
-    p = body + h.compressed;
-  }
-  if (rows != expect_rows) {
-    set_error("nvt_pq_decode_bool_chunk: %llu rows in the pages, %llu expected", (unsigned long long)rows,
-              (unsigned long long)expect_rows);
-    return NVT_EINVAL;
-  }
-  *rows_out = rows;
-  *values_count = vals;
+  const PageWalk w{__func__, chunk, chunk_bytes, codec, expect_rows, scratch, scratch_bytes};
+  FlatLevels lv{valid_out, valid_bit_offset, max_def_level};
+  NVT_CHECK_ARG(lv.bad_args() == nullptr, lv.bad_args());
+  BoolValues vs(values_out, values_cap);
+  const int rc = walk_pages(w, lv, vs);
+  if (rc) return rc;
+  *rows_out = expect_rows;
+  *values_count = vs.vals;
   return NVT_OK;
 }
+
 
 int nvt_expand_valid_ws_bytes(uint64_t n, uint64_t *bytes) {
   NVT_CHECK_ARG(bytes, "null out");

@@ -1,5 +1,5 @@
 // Parquet in, string columns: the dictionary-index streams of a partition are expanded on the device.
-// The host decoder (nvt_pq_decode_str_chunk, nvt_parquet.hip) leaves a run table and the bytes of
+// The host decoder (nvt_pq_decode_str_chunk, nvt_parquet_str_in.hip) leaves a run table and the bytes of
 // the bit-packed runs as the file holds them (include/nvt_hip.h, "parquet in: string columns");
 // nvt_pq_expand_runs turns them into one entry id per non-null value:
 //

@@ -81,6 +81,7 @@ parquet_thrift.py holds the thrift compact protocol, parquet_write.py the driver
 """
 from __future__ import annotations
 
+import importlib
 import os
 import struct
 import threading
@@ -1171,122 +1172,126 @@ class StagedColumn:
 _MAX_STR_CHARS = (1 << 32) - 2   # kernels_strings._MAX_CHARS: the dict's strings are gathered with 32-bit sums
 
 
-class StagedStrings:
+class _Staged:
+    """The staging buffers of one column of a partition, filled by a nvt_pq_decode_* entry point through
+    a stage struct of include/nvt_hip.h (``self.c``, the ctypes struct ``STRUCT`` of _lib) and enlarged
+    when the decoder answers ``GROW`` (its name in _lib).
+
+    ``BUFFERS`` lists the buffers in the order of the decoder's ``need[]``: (attribute = pointer field of
+    the struct, capacity field, dtype, words per record -- a number or the name of an instance
+    attribute --, words in use given the struct, multiple the size is rounded up to when the buffer
+    grows, words behind that).  ``COUNTS``: the struct's fill state, readable as properties."""
+
+    STRUCT = GROW = None
+    BUFFERS = COUNTS = ()
+
+    def __init_subclass__(cls):
+        for name in cls.COUNTS:
+            setattr(cls, name, property(lambda self, name=name: int(getattr(self.c, name))))
+
+    def __init__(self, pinned, sizes):
+        """``sizes``: the elements of every buffer, in the order of ``BUFFERS``."""
+        import torch
+
+        from . import _lib
+
+        self.pinned = pinned
+        for (attr, _, dtype, *_), size in zip(self.BUFFERS, sizes):
+            setattr(self, attr, torch.empty(size, dtype=getattr(torch, dtype), pin_memory=pinned))
+        self.c = getattr(_lib, self.STRUCT)()
+        self._bind()
+
+    def _words(self, words):
+        return getattr(self, words) if isinstance(words, str) else words
+
+    def _bind(self):
+        for attr, cap, _, words, _, _, extra in self.BUFFERS:
+            buf = getattr(self, attr)
+            setattr(self.c, attr, buf.data_ptr())
+            setattr(self.c, cap, (buf.numel() - extra) // self._words(words))
+
+    def _clamp(self, attr, size):
+        return size
+
+    def grow(self, need):
+        """Enlarges the buffers named by ``need`` (one entry per buffer, 0 = large enough), keeping what
+        is filled."""
+        import torch
+
+        for (attr, _, _, words, used, unit, extra), want in zip(self.BUFFERS, need):
+            if not want:
+                continue
+            old, keep = getattr(self, attr), used(self)
+            size = self._clamp(attr, max(int(want) * self._words(words), 2 * old.numel()))
+            new = torch.empty(-(-size // unit) * unit + extra, dtype=old.dtype, pin_memory=self.pinned)
+            new[:keep] = old[:keep]
+            setattr(self, attr, new)
+        self._bind()
+
+    def decode(self, fn, need, *args):
+        """``fn(*args)``, a decode entry point that fills this stage and reports in ``need`` (a ctypes
+        array) what it lacks: called until it stops answering ``GROW``, the buffers enlarged in between.
+        -> its return code."""
+        from . import _lib
+
+        while True:
+            rc = fn(*args)
+            if rc != getattr(_lib, self.GROW):
+                return rc
+            self.grow(tuple(int(x) for x in need))
+
+
+class StagedStrings(_Staged):
     """The staging buffers of one string column of a partition, as nvt_pq_decode_str_chunk fills them
     (include/nvt_hip.h, nvt_pq_str_stage): ``offsets`` (int64) / ``chars`` the entries, ``runs`` the run
     table (int32 words, 4 per record, the closing record behind the ``nruns`` runs), ``packed`` the
     bytes of the bit-packed runs.  Sized from the footer and enlarged when the decoder asks for it.
     ``where`` names file and column for error messages."""
 
+    STRUCT, GROW = "PqStrStage", "PQ_STR_GROW"
+    BUFFERS = (("offsets", "entries_cap", "int64", 1, lambda s: s.c.entries + 1, 1, 1),
+               ("chars", "chars_cap", "uint8", 1, lambda s: s.c.nchars, 8, 0),
+               ("runs", "runs_cap", "int32", 4, lambda s: 4 * (s.c.nruns + 1), 4, 0),
+               ("packed", "packed_cap", "uint8", 1, lambda s: s.c.npacked + 8, 8, 0))
+    COUNTS = ("entries", "nchars", "nruns", "npacked", "nvalues")
+
     def __init__(self, entries_cap, chars_cap, runs_cap, packed_cap, pinned, where):
-        import torch
-
-        from . import _lib
-
-        self.pinned, self.where = pinned, where
-        self.offsets = torch.empty(entries_cap + 1, dtype=torch.int64, pin_memory=pinned)
-        self.chars = torch.empty((chars_cap + 7) & ~7, dtype=torch.uint8, pin_memory=pinned)
-        self.runs = torch.empty(4 * runs_cap, dtype=torch.int32, pin_memory=pinned)
-        self.packed = torch.empty(((packed_cap + 7) & ~7) + 8, dtype=torch.uint8, pin_memory=pinned)
+        self.where = where
+        super().__init__(pinned, (entries_cap + 1, (chars_cap + 7) & ~7, 4 * runs_cap, ((packed_cap + 7) & ~7) + 8))
         self.offsets[0] = 0
-        self.c = _lib.PqStrStage()
-        self._bind()
 
-    def _bind(self):
-        c = self.c
-        c.offsets, c.chars, c.runs, c.packed = (self.offsets.data_ptr(), self.chars.data_ptr(), self.runs.data_ptr(),
-                                                self.packed.data_ptr())
-        c.entries_cap, c.chars_cap = self.offsets.numel() - 1, self.chars.numel()
-        c.runs_cap, c.packed_cap = self.runs.numel() // 4, self.packed.numel()
+    def _clamp(self, attr, size):
+        return min(size, _MAX_STR_CHARS + 2) if attr == "chars" else size
 
     def grow(self, need):
-        """Enlarges the buffers named by ``need`` = (entries, chars, runs, packed), 0 = large enough,
-        keeping what is filled."""
-        import torch
-
+        """``need`` = (entries, chars, runs, packed)."""
         from . import _lib
 
-        c = self.c
-        for which, want in enumerate(need):
-            if not want:
-                continue
-            name, used, unit, extra = (("offsets", c.entries + 1, 1, 1), ("chars", c.nchars, 8, 0),
-                                       ("runs", 4 * (c.nruns + 1), 4, 0), ("packed", c.npacked + 8, 8, 0))[which]
-            old = getattr(self, name)
-            if which == 1 and want > _MAX_STR_CHARS + 2:
-                raise _lib.NvtHipError(f"{self.where}: more than {_MAX_STR_CHARS} bytes of strings in one partition")
-            size = max(int(want) * (4 if which == 2 else 1), 2 * old.numel())
-            if which == 1:
-                size = min(size, _MAX_STR_CHARS + 2)
-            new = torch.empty(((size + unit - 1) // unit) * unit + extra, dtype=old.dtype, pin_memory=self.pinned)
-            new[:used] = old[:used]
-            setattr(self, name, new)
-        self._bind()
-
-    @property
-    def entries(self):
-        return int(self.c.entries)
-
-    @property
-    def nchars(self):
-        return int(self.c.nchars)
-
-    @property
-    def nruns(self):
-        return int(self.c.nruns)
-
-    @property
-    def npacked(self):
-        return int(self.c.npacked)
-
-    @property
-    def nvalues(self):
-        return int(self.c.nvalues)
+        if need[1] > _MAX_STR_CHARS + 2:
+            raise _lib.NvtHipError(f"{self.where}: more than {_MAX_STR_CHARS} bytes of strings in one partition")
+        super().grow(need)
 
 
-class StagedDelta:
+class StagedDelta(_Staged):
     """The staged DELTA_BINARY_PACKED pages of one column of a partition, as nvt_pq_decode_chunk_delta
     fills them (include/nvt_hip.h, nvt_pq_delta_stage): ``bytes`` the pages' values regions (16 zero
     bytes behind the last), ``pages`` 5 int64 words per page {first value, position of the page's first
     value in the column's packed values, count | values per miniblock << 32, first miniblock record,
     byte of ``bytes`` where the page's region starts},
     ``mbs`` 2 words per needed miniblock {byte position | bit width << 56, min_delta}.  Sized from the
-    footer and enlarged when the decoder asks for it."""
+    footer and enlarged when the decoder asks for it (``need`` = (bytes, pages, mbs))."""
+
+    STRUCT, GROW = "PqDeltaStage", "PQ_DELTA_GROW"
+    BUFFERS = (("bytes", "bytes_cap", "uint8", 1, lambda s: s.c.nbytes, 16, 0),
+               ("pages", "pages_cap", "int64", "words", lambda s: s.words * s.c.npages, 16, 0),
+               ("mbs", "mbs_cap", "int64", 2, lambda s: 2 * s.c.nmbs, 16, 0))
+    COUNTS = ("nbytes", "npages", "nmbs")
 
     def __init__(self, bytes_cap, pages_cap, mbs_cap, pinned=False):
-        import torch
-
         from . import _lib
 
-        self.pinned, self.words = pinned, _lib.PQ_DELTA_RECORD_WORDS   # words per page record
-        self.bytes = torch.empty(((bytes_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
-        self.pages = torch.empty(self.words * max(1, pages_cap), dtype=torch.int64, pin_memory=pinned)
-        self.mbs = torch.empty(2 * max(1, mbs_cap), dtype=torch.int64, pin_memory=pinned)
-        self.c = _lib.PqDeltaStage()
-        self._bind()
-
-    def _bind(self):
-        c = self.c
-        c.bytes, c.pages, c.mbs = self.bytes.data_ptr(), self.pages.data_ptr(), self.mbs.data_ptr()
-        c.bytes_cap, c.mbs_cap = self.bytes.numel(), self.mbs.numel() // 2
-        c.pages_cap = self.pages.numel() // self.words
-
-    def grow(self, need):
-        """Enlarges the buffers named by ``need`` = (bytes, pages, mbs), 0 = large enough, keeping what
-        is filled."""
-        import torch
-
-        c, W = self.c, self.words
-        for which, want in enumerate(need):
-            if not want:
-                continue
-            name, used, words = (("bytes", c.nbytes, 1), ("pages", W * c.npages, W), ("mbs", 2 * c.nmbs, 2))[which]
-            old = getattr(self, name)
-            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
-            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
-            new[:used] = old[:used]
-            setattr(self, name, new)
-        self._bind()
+        self.words = _lib.PQ_DELTA_RECORD_WORDS   # words per page record
+        super().__init__(pinned, (((bytes_cap + 15) & ~15) + 16, self.words * max(1, pages_cap), 2 * max(1, mbs_cap)))
 
     def add_page(self, region, itemsize, count, pos):
         """Stages ONE values region (bytes-like) of ``count`` values of ``itemsize`` bytes whose first
@@ -1299,131 +1304,49 @@ class StagedDelta:
         lib = _lib.load()
         buf = (C.c_uint8 * max(1, len(region))).from_buffer_copy(bytes(region) or b"\0")
         need = (C.c_uint64 * 3)()
-        while True:
-            rc = lib.nvt_pq_delta_stage_page(buf, len(region), itemsize, count, pos, C.byref(self.c), need)
-            if rc != _lib.PQ_DELTA_GROW:
-                break
-            self.grow(tuple(int(x) for x in need))
+        rc = self.decode(lib.nvt_pq_delta_stage_page, need, buf, len(region), itemsize, count, pos, C.byref(self.c),
+                         need)
         if rc != 0:
             raise _lib.NvtHipError(f"nvt_pq_delta_stage_page: {lib.nvt_last_error().decode()} (rc {rc})")
 
-    @property
-    def nbytes(self):
-        return int(self.c.nbytes)
 
-    @property
-    def npages(self):
-        return int(self.c.npages)
-
-    @property
-    def nmbs(self):
-        return int(self.c.nmbs)
-
-
-class StagedDict:
+class StagedDict(_Staged):
     """The staged dictionary pages of one number column of a partition, as nvt_pq_decode_chunk_dict
     fills them (include/nvt_hip.h, nvt_pq_dict_stage): ``dict`` the chunks' dictionaries (each behind
     a 16-byte head that holds its entry count), ``runs`` the run table (int32 words, 4 per record, the
     closing record behind the ``nruns`` runs), ``packed`` the bytes of the bit-packed runs.  Sized
-    from the footer and enlarged when the decoder asks for it.  ``where`` names file and column for
-    error messages."""
+    from the footer and enlarged when the decoder asks for it (``need`` = (dict bytes, runs, packed
+    bytes)).  ``where`` names file and column for error messages."""
+
+    STRUCT, GROW = "PqDictStage", "PQ_DICT_GROW"
+    BUFFERS = (("dict", "dict_cap", "uint8", 1, lambda s: s.c.ndict_bytes, 16, 0),
+               ("runs", "runs_cap", "int32", 4, lambda s: 4 * (s.c.nruns + 1), 16, 0),
+               ("packed", "packed_cap", "uint8", 1, lambda s: s.c.npacked + 8, 16, 0))
+    COUNTS = ("ndict_bytes", "nruns", "npacked")
 
     def __init__(self, dict_cap, runs_cap, packed_cap, pinned, where):
-        import torch
-
-        from . import _lib
-
-        self.pinned, self.where = pinned, where
-        self.dict = torch.empty((dict_cap + 15) & ~15, dtype=torch.uint8, pin_memory=pinned)
-        self.runs = torch.empty(4 * max(1, runs_cap), dtype=torch.int32, pin_memory=pinned)
-        self.packed = torch.empty(((packed_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
-        self.c = _lib.PqDictStage()
-        self._bind()
-
-    def _bind(self):
-        c = self.c
-        c.dict, c.runs, c.packed = self.dict.data_ptr(), self.runs.data_ptr(), self.packed.data_ptr()
-        c.dict_cap, c.runs_cap, c.packed_cap = self.dict.numel(), self.runs.numel() // 4, self.packed.numel()
-
-    def grow(self, need):
-        """Enlarges the buffers named by ``need`` = (dict bytes, runs, packed bytes), 0 = large enough,
-        keeping what is filled."""
-        import torch
-
-        c = self.c
-        for which, want in enumerate(need):
-            if not want:
-                continue
-            name, used, words = (("dict", c.ndict_bytes, 1), ("runs", 4 * (c.nruns + 1), 4),
-                                 ("packed", c.npacked + 8, 1))[which]
-            old = getattr(self, name)
-            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
-            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
-            new[:used] = old[:used]
-            setattr(self, name, new)
-        self._bind()
-
-    @property
-    def ndict_bytes(self):
-        return int(self.c.ndict_bytes)
-
-    @property
-    def nruns(self):
-        return int(self.c.nruns)
-
-    @property
-    def npacked(self):
-        return int(self.c.npacked)
+        self.where = where
+        super().__init__(pinned, ((dict_cap + 15) & ~15, 4 * max(1, runs_cap), ((packed_cap + 15) & ~15) + 16))
 
 
-class StagedInflate:
+class StagedInflate(_Staged):
     """The staged snappy bodies of one number column of a partition, as nvt_pq_decode_chunk_inflate
     fills them (include/nvt_hip.h, nvt_pq_inflate_stage): ``bytes`` the compressed bodies of its PLAIN
     pages without nulls, each on a 16-byte boundary, ``pages`` 5 int64 words per page (nvt_inflate_page:
     {src_at in ``bytes``, src_bytes, dst_at = byte position among the column's packed values, dst_bytes,
-    flags}).  Sized from the footer and enlarged when the decoder asks for it.  ``where`` names file and
-    column for error messages."""
+    flags}).  Sized from the footer and enlarged when the decoder asks for it (``need`` = (bytes,
+    pages)).  ``where`` names file and column for error messages."""
+
+    STRUCT, GROW = "PqInflateStage", "PQ_INFLATE_GROW"
+    BUFFERS = (("bytes", "bytes_cap", "uint8", 1, lambda s: s.c.nbytes, 16, 0),
+               ("pages", "pages_cap", "int64", "words", lambda s: s.words * s.c.npages, 16, 0))
+    COUNTS = ("nbytes", "npages")
 
     def __init__(self, bytes_cap, pages_cap, pinned, where):
-        import torch
-
         from . import _lib
 
-        self.pinned, self.where, self.words = pinned, where, _lib.INFLATE_PAGE_WORDS
-        self.bytes = torch.empty(((bytes_cap + 15) & ~15) + 16, dtype=torch.uint8, pin_memory=pinned)
-        self.pages = torch.empty(self.words * max(1, pages_cap), dtype=torch.int64, pin_memory=pinned)
-        self.c = _lib.PqInflateStage()
-        self._bind()
-
-    def _bind(self):
-        c = self.c
-        c.bytes, c.pages = self.bytes.data_ptr(), self.pages.data_ptr()
-        c.bytes_cap, c.pages_cap = self.bytes.numel(), self.pages.numel() // self.words
-
-    def grow(self, need):
-        """Enlarges the buffers named by ``need`` = (bytes, pages), 0 = large enough, keeping what is
-        filled."""
-        import torch
-
-        c, W = self.c, self.words
-        for which, want in enumerate(need):
-            if not want:
-                continue
-            name, used, words = (("bytes", c.nbytes, 1), ("pages", W * c.npages, W))[which]
-            old = getattr(self, name)
-            size = (max(int(want) * words, 2 * old.numel()) + 15) & ~15
-            new = torch.empty(size, dtype=old.dtype, pin_memory=self.pinned)
-            new[:used] = old[:used]
-            setattr(self, name, new)
-        self._bind()
-
-    @property
-    def nbytes(self):
-        return int(self.c.nbytes)
-
-    @property
-    def npages(self):
-        return int(self.c.npages)
+        self.where, self.words = where, _lib.INFLATE_PAGE_WORDS
+        super().__init__(pinned, (((bytes_cap + 15) & ~15) + 16, self.words * max(1, pages_cap)))
 
     def records(self):
         """The page table: int64 [npages, 5] (a view of ``pages``)."""
@@ -1452,34 +1375,21 @@ class StagedPartition:
         device = device or default_device()
         out = {}
         unpacked = {}   # list column -> (offsets, leaf bitmap): one unpack per distinct level streams
-        # columns with DELTA_BINARY_PACKED pages: their packed values travel with holes, which ONE call
-        # fills for all of them before the values are expanded, narrowed or handed over below
-        filled = {}
-        if device.type == "cuda" and any(sc.delta is not None for sc in self.columns.values()):
-            from . import kernels_parquet_delta as KPD
-
-            filled = {name: KPD.values_to_device(sc, device) for name, sc in self.columns.items()
-                      if sc.delta is not None}
-            KPD.fill_holes([(self.columns[name].delta, packed) for name, packed in filled.items()])
-        # columns with staged dictionary pages: the same, and ONE launch for all of them; the count of
-        # indices outside their dictionaries is read once, behind everything else this call enqueues
-        dict_bad = None
-        if device.type == "cuda" and any(sc.dict_stage is not None for sc in self.columns.values()):
-            from . import kernels_parquet_dict_in as KDI
-
-            staged = {name: KDI.values_to_device(sc, device) for name, sc in self.columns.items()
-                      if sc.dict_stage is not None}
-            dict_bad = KDI.fill_holes([(self.columns[name].dict_stage, packed) for name, packed in staged.items()])
-            filled.update(staged)
-        # columns with staged snappy bodies: the same, ONE launch inflates all their pages; the status
-        # words are read once, behind everything else this call enqueues
-        inflated = None
-        if device.type == "cuda" and any(sc.inflate is not None for sc in self.columns.values()):
-            from . import kernels_parquet_inflate as KPI
-
-            staged = {name: KPI.values_to_device(sc, device) for name, sc in self.columns.items()
-                      if sc.inflate is not None}
-            inflated = KPI.fill_holes([(self.columns[name].inflate, packed) for name, packed in staged.items()])
+        # columns with DELTA_BINARY_PACKED pages, staged dictionary pages or staged snappy bodies: their
+        # packed values travel with holes, which ONE launch per kind fills for all its columns before the
+        # values are expanded, narrowed or handed over below.  What a fill reports (dictionary: the count
+        # of indices outside their dictionaries, inflate: the status words) is read once, behind
+        # everything else this call enqueues.
+        filled, reports = {}, {}
+        for attr, module in (("delta", "kernels_parquet_delta"), ("dict_stage", "kernels_parquet_dict_in"),
+                             ("inflate", "kernels_parquet_inflate")):
+            if device.type != "cuda" or all(getattr(sc, attr) is None for sc in self.columns.values()):
+                continue
+            KF = importlib.import_module("." + module, __package__)
+            staged = {name: KF.values_to_device(sc, device) for name, sc in self.columns.items()
+                      if getattr(sc, attr) is not None}
+            reports[attr] = KF.fill_holes([(getattr(self.columns[name], attr), packed)
+                                           for name, packed in staged.items()])
             filled.update(staged)
         for name, sc in self.columns.items():
             if device.type != "cuda":   # (host-only use: tests of the reader itself)
@@ -1519,13 +1429,15 @@ class StagedPartition:
             else:
                 bitmap = sc.valid[: ((sc.rows + 63) // 64) * 8].to(device, non_blocking=True)
                 out[name] = DeviceColumn(K.expand_valid(packed, bitmap, sc.rows), bitmap, logical=sc.logical)
-        if dict_bad is not None:
-            nbad = int(dict_bad.cpu().numpy()[0])
+        if reports.get("dict_stage") is not None:
+            nbad = int(reports["dict_stage"].cpu().numpy()[0])
             if nbad:
                 where = next(sc.dict_stage.where for sc in self.columns.values() if sc.dict_stage is not None)
                 raise ValueError(f"{where}: {nbad} dictionary indices outside the entries of their pages")
-        if inflated is not None:
-            KPI.raise_failed(inflated)
+        if reports.get("inflate") is not None:
+            from . import kernels_parquet_inflate as KPI
+
+            KPI.raise_failed(reports["inflate"])
         return DeviceFrame(out)
 
 
@@ -1649,13 +1561,9 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
         row_at = 0
         need = (C.c_uint64 * 4)()
         for g, cc, rows, cbuf, sbuf, sbytes in chunks(n, j):
-            while True:
-                rc = lib.nvt_pq_decode_str_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
-                                                 valid.data_ptr() if valid is not None else None, row_at,
-                                                 C.addressof(st.c), sbuf, sbytes, need)
-                if rc != _lib.PQ_STR_GROW:
-                    break
-                st.grow(tuple(int(x) for x in need))
+            rc = st.decode(lib.nvt_pq_decode_str_chunk, need, cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,
+                           valid.data_ptr() if valid is not None else None, row_at, C.addressof(st.c), sbuf, sbytes,
+                           need)
             decoded("nvt_pq_decode_str_chunk", rc, n, g)
             if st.nchars > _MAX_STR_CHARS:
                 raise _lib.NvtHipError(f"{st.where}: more than {_MAX_STR_CHARS} bytes of strings in one partition")
@@ -1700,15 +1608,10 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
             r, v = C.c_uint64(), C.c_uint64()
             if dstage is not None:
                 fn, need = "nvt_pq_decode_chunk_dict", (C.c_uint64 * 3)()
-                while True:
-                    rc = lib.nvt_pq_decode_chunk_dict(cbuf, cc["size"], cc.get("codec", 0), st.itemsize, pf.max_def[j],
-                                                      rows, valid.data_ptr() if valid is not None else None, row_at,
-                                                      vals.data_ptr() + val_at * st.itemsize,
-                                                      (total - val_at) * st.itemsize, val_at, C.byref(dstage.c),
-                                                      sbuf, sbytes, C.byref(r), C.byref(v), need)
-                    if rc != _lib.PQ_DICT_GROW:
-                        break
-                    dstage.grow(tuple(int(x) for x in need))
+                rc = dstage.decode(lib.nvt_pq_decode_chunk_dict, need, cbuf, cc["size"], cc.get("codec", 0), st.itemsize,
+                                   pf.max_def[j], rows, valid.data_ptr() if valid is not None else None, row_at,
+                                   vals.data_ptr() + val_at * st.itemsize, (total - val_at) * st.itemsize, val_at,
+                                   C.byref(dstage.c), sbuf, sbytes, C.byref(r), C.byref(v), need)
             elif cc.get("delta"):   # (flat INT32 / INT64 chunks only: _judge_chunk)
                 # the footer lists DELTA_BINARY_PACKED: such pages are staged for the device and leave
                 # holes in ``vals``; the chunk's other pages are decoded as below
@@ -1719,15 +1622,10 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
                     delta = StagedDelta(sum(max(x.get("raw_size", 0), x["size"]) for x in ccs) + 64,
                                         nv // 4096 + 4 * len(ccs) + 16, nv // 32 + 64 * len(ccs) + 64, pinned)
                 fn, need = "nvt_pq_decode_chunk_delta", (C.c_uint64 * 3)()
-                while True:
-                    rc = lib.nvt_pq_decode_chunk_delta(cbuf, cc["size"], cc.get("codec", 0), _PQ_TYPE[st], pf.max_def[j],
-                                                       rows, valid.data_ptr() if valid is not None else None, row_at,
-                                                       vals.data_ptr() + val_at * st.itemsize,
-                                                       (total - val_at) * st.itemsize, val_at, C.byref(delta.c),
-                                                       sbuf, sbytes, C.byref(r), C.byref(v), need)
-                    if rc != _lib.PQ_DELTA_GROW:
-                        break
-                    delta.grow(tuple(int(x) for x in need))
+                rc = delta.decode(lib.nvt_pq_decode_chunk_delta, need, cbuf, cc["size"], cc.get("codec", 0), _PQ_TYPE[st],
+                                  pf.max_def[j], rows, valid.data_ptr() if valid is not None else None, row_at,
+                                  vals.data_ptr() + val_at * st.itemsize, (total - val_at) * st.itemsize, val_at,
+                                  C.byref(delta.c), sbuf, sbytes, C.byref(r), C.byref(v), need)
             elif inflate_ok and cc.get("codec", 0) == 1:
                 # PLAIN pages without nulls keep their snappy bodies: staged for the device, they leave
                 # holes in ``vals``; the chunk's other pages are decoded as below
@@ -1738,16 +1636,11 @@ def read_row_groups_staged(pf: PlainParquetFile, groups, columns=None, pool=None
                                            sum(x.get("raw_size", 0) for x in ccs) // (1 << 20) + 4 * len(ccs) + 16,
                                            pinned, f"{pf.path}: column {n!r}")
                 fn, need = "nvt_pq_decode_chunk_inflate", (C.c_uint64 * 2)()
-                while True:
-                    rc = lib.nvt_pq_decode_chunk_inflate(cbuf, cc["size"], 1, st.itemsize, pf.max_def[j], rows,
-                                                         valid.data_ptr() if valid is not None else None, row_at,
-                                                         vals.data_ptr() + val_at * st.itemsize,
-                                                         (total - val_at) * st.itemsize, val_at,
-                                                         cc.get("null_count", -1), C.byref(zstage.c), sbuf, sbytes,
-                                                         C.byref(r), C.byref(v), need)
-                    if rc != _lib.PQ_INFLATE_GROW:
-                        break
-                    zstage.grow(tuple(int(x) for x in need))
+                rc = zstage.decode(lib.nvt_pq_decode_chunk_inflate, need, cbuf, cc["size"], 1, st.itemsize, pf.max_def[j],
+                                   rows, valid.data_ptr() if valid is not None else None, row_at,
+                                   vals.data_ptr() + val_at * st.itemsize, (total - val_at) * st.itemsize, val_at,
+                                   cc.get("null_count", -1), C.byref(zstage.c), sbuf, sbytes, C.byref(r), C.byref(v),
+                                   need)
             elif dt == BOOL_DTYPE:
                 fn = "nvt_pq_decode_bool_chunk"
                 rc = lib.nvt_pq_decode_bool_chunk(cbuf, cc["size"], cc.get("codec", 0), pf.max_def[j], rows,

@@ -1,6 +1,6 @@
 // Host-only sanitizer harness of the parquet list decoder (nvt_pq_decode_list_chunk, the host C of
-// nvtabular_amd/csrc/nvt_parquet.hip): decodes the list chunks of a file as they are, then a few
-// thousand byte-mutated copies of each (fixed seed).  Every call must return NVT_OK or an error;
+// nvtabular_amd/csrc/nvt_parquet.hip over the page walk of nvt_pq_page.hpp): decodes the list chunks
+// of a file as they are, then a few thousand byte-mutated copies of each (fixed seed).  Every call must return NVT_OK or an error;
 // AddressSanitizer / UBSan watch the reads of the chunk and the writes of the outputs, which are
 // heap blocks of exactly the documented sizes.  Runs on the CPU: nothing here touches a GPU.
 //

@@ -1,6 +1,6 @@
 // Host-only sanitizer harness of the parquet string decoder (nvt_pq_decode_str_chunk, the host C of
-// nvtabular_amd/csrc/nvt_parquet.hip): decodes the string chunks of a file as they are, then a few
-// thousand byte-mutated copies of each (fixed seed).  Every call must return NVT_OK or an error;
+// nvtabular_amd/csrc/nvt_parquet_str_in.hip over the page walk of nvt_pq_page.hpp): decodes the string
+// chunks of a file as they are, then a few thousand byte-mutated copies of each (fixed seed).  Every call must return NVT_OK or an error;
 // AddressSanitizer / UBSan watch the reads of the chunk and the writes of the staging buffers, which
 // are heap blocks of exactly the documented sizes.  Every chunk is decoded twice: into buffers sized
 // generously from the footer, and from capacities of almost nothing, enlarged as the decoder asks
@@ -8,7 +8,8 @@
 // touches a GPU.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
-//       tools/pq_str_fuzz.cpp nvtabular_amd/csrc/nvt_parquet.hip nvtabular_amd/csrc/nvt_util.hip -ldl -o tools/pq_str_fuzz
+//       tools/pq_str_fuzz.cpp nvtabular_amd/csrc/nvt_parquet_str_in.hip nvtabular_amd/csrc/nvt_parquet.hip \
+//       nvtabular_amd/csrc/nvt_util.hip -ldl -o tools/pq_str_fuzz
 //   tools/pq_str_fuzz FILE $(python tools/pq_str_fuzz_chunks.py FILE) [mutations per chunk, default 4000]
 //
 // A chunk is offset:size:codec:max_def:rows:raw_size (pq_str_fuzz_chunks.py prints them from the footer).
