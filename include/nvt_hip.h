@@ -1684,6 +1684,39 @@ int nvt_pq_dict_pack(const void *values, int dtype, uint64_t n, uint64_t max_ent
                      const int64_t *page_start, uint64_t npages, uint64_t *state, uint8_t *out,
                      uint64_t out_cap, void *ws, uint64_t ws_bytes, void *stream);
 
+/* ---- parquet out: DELTA_BINARY_PACKED pages: Dataset.to_parquet(column_encoding=...) ----
+ * One flat column chunk's n NON-NULL values (NVT_I32 / NVT_I64; every bit pattern is a value), cut
+ * into pages at page_start[npages + 1] (on the device, in value positions; page p holds values
+ * [page_start[p], page_start[p + 1])), become parquet DELTA_BINARY_PACKED values regions with block
+ * size NVT_PQ_DELTA_OUT_BLOCK (128) and 4 miniblocks of 32.  Every page is self-contained:
+ *     varint 128 | varint 4 | varint nv | zigzag first value | blocks over the nv - 1 deltas
+ *     block = zigzag min_delta | 4 width bytes | the miniblocks that hold a delta, LSB first
+ * Deltas, min_delta and the relative deltas wrap in the column's width; min_delta is zigzag-encoded
+ * from its sign-extended value; a width is the bit length of the largest relative delta of its
+ * miniblock; the last used miniblock is padded to 32 values with zero bits; a miniblock without
+ * deltas has width byte 0 and no bytes; a page without values has count 0 and first value 0.
+ * nvt_pq_delta_out_size: table[NVT_PQ_DELTA_OUT_STATE_WORDS + 2 * npages] on the device receives
+ *   state = {total: the sum of the regions' bytes, pays, error, used: the bytes of `out` in use},
+ *   then at[npages] (the byte at which page p's region starts in `out`: 16 * sum_{q<p}
+ *   ceil(len[q] / 16)) and len[npages] (its bytes).  THE CHUNK RULE: pays = 1 iff n > 0, no error
+ *   and total < n * itemsize.  error = 1: page_start is negative, descending or past n (the pages are
+ *   then clamped into [0, n] for the sizes, and nothing is packed).
+ * nvt_pq_delta_out_pack: the same values and page table, `table` and `ws` as nvt_pq_delta_out_size
+ *   left them.  pays = 0: returns at once on the device, `out` is not touched.  pays = 1: writes the
+ *   regions; the bytes between a region's end and the next 16-byte boundary are not written.
+ *   out_cap >= n * itemsize + 16 * npages (pays implies used < that), out 16-byte aligned.  Every
+ *   store lies inside a region: bytes narrow, whole dwords only where they lie inside one block.
+ * ws: nvt_pq_delta_out_ws_bytes(n, npages) bytes, 16-byte aligned, the same buffer for both calls.
+ * n < 2^28, 1 <= npages < 2^31.  Stream-ordered, no allocation, no synchronisation. */
+#define NVT_PQ_DELTA_OUT_BLOCK 128
+#define NVT_PQ_DELTA_OUT_STATE_WORDS 4
+int nvt_pq_delta_out_ws_bytes(uint64_t n, uint64_t npages, uint64_t *bytes);
+int nvt_pq_delta_out_size(const void *values, int dtype, uint64_t n, const int64_t *page_start, uint64_t npages,
+                          int64_t *table, void *ws, uint64_t ws_bytes, void *stream);
+int nvt_pq_delta_out_pack(const void *values, int dtype, uint64_t n, const int64_t *page_start, uint64_t npages,
+                          const int64_t *table, uint8_t *out, uint64_t out_cap, const void *ws, uint64_t ws_bytes,
+                          void *stream);
+
 /* ---- parquet out: string columns (PLAIN BYTE_ARRAY pages) ----
  * A string column is int64 surrogates and a host dict {surrogate -> string}.  The dict travels to
  * the device once as an ENTRY TABLE: keys[n_entries] ascending, and the entries in key order as Arrow

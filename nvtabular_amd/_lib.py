@@ -389,6 +389,13 @@ SIGNATURES.update({
     "nvt_pq_dict_build": [_vp, _i32, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
     "nvt_pq_dict_pack": [_vp, _i32, _u64, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp],
 })
+# include/nvt_hip.h NVT_PQ_DELTA_OUT_BLOCK / NVT_PQ_DELTA_OUT_STATE_WORDS (kernels_parquet_delta_out.py)
+PQ_DELTA_OUT_BLOCK, PQ_DELTA_OUT_STATE_WORDS = 128, 4
+SIGNATURES.update({
+    "nvt_pq_delta_out_ws_bytes": [_u64, _u64, C.POINTER(_u64)],
+    "nvt_pq_delta_out_size": [_vp, _i32, _u64, _vp, _u64, _vp, _vp, _u64, _vp],
+    "nvt_pq_delta_out_pack": [_vp, _i32, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp],
+})
 # parquet out: string columns (kernels_parquet_str_out.py)
 SIGNATURES.update({
     "nvt_pq_str_entry_ids": [_vp, _u64, _vp, _u64, _vp, _vp, _vp],

@@ -20,7 +20,8 @@ import pandas as pd
 from .device import DeviceFrame, as_device_frame
 from .parquet_plain import READER_CHUNKS, PlainParquetFile, StagedPartition, read_row_groups_staged
 from .kernels_parquet_str_out import StringTables
-from .parquet_write import LAST_TIMING, device_permutation, dictionary_columns, plain_eligible, write_plain  # noqa: F401
+from .parquet_write import (LAST_TIMING, check_column_encoding, delta_columns, device_permutation,  # noqa: F401
+                            dictionary_columns, plain_eligible, write_plain)
 from .schema import ColumnSchema, Schema
 
 
@@ -464,7 +465,7 @@ class Dataset:
     def to_parquet(self, output_path, shuffle=None, out_files_per_proc=None, dtypes=None,
                    cats=None, conts=None, labels=None, preserve_files=False, suffix=".parquet",
                    num_threads=0, compression=None, statistics=False, use_dictionary=None,
-                   device_compression=None, partition_on=None, max_partitions=1024, **_):
+                   device_compression=None, partition_on=None, max_partitions=1024, column_encoding=None, **_):
         """Write the (transformed) dataset as parquet (merlin.io.Dataset.to_parquet; contract in
         tests/unit/workflow/test_workflow.py:171-187,363-396,444-500 and
         bench/datasets/tools/nvt_etl.py:154-171 of the reference).
@@ -522,6 +523,25 @@ class Dataset:
           still selects pyarrow's writer.  When the frame goes to pyarrow's writer anyway, the value
           is handed to pyarrow as its ``compression`` ("Snappy pages in the PLAIN parquet
           writer").
+        * ``column_encoding`` (pyarrow's name and value shapes): ``None`` (default) writes exactly the
+          files described above.  A dict ``{column: "DELTA_BINARY_PACKED" | "PLAIN"}`` offers the columns
+          it gives ``"DELTA_BINARY_PACKED"`` to the PLAIN writer's delta encoding, which runs on the
+          device; the bare string ``"DELTA_BINARY_PACKED"`` offers every eligible column that is not also
+          offered to ``use_dictionary``.  Eligible: flat int32 / int64 columns (after a ``dtypes``
+          cast), flat int8 / int16 columns (the file's INT32) and datetime columns (int64 counts), on
+          the device; floats, bools, strings, list columns and columns of a frame on the host are not.
+          A name that is no column, a named column that is not eligible, any other encoding, or a
+          column offered to both ``use_dictionary`` and ``column_encoding`` raises ``ValueError`` before
+          any file or directory is created.  An offered column chunk is written as DELTA_BINARY_PACKED
+          data pages (block size 128, 4 miniblocks, every page self-contained, cut where the PLAIN
+          pages are) only when it has values and its delta regions are smaller than its values --
+          otherwise that chunk stays PLAIN, so the option never makes a file larger: a near-monotone
+          timestamp or id column shrinks to a few bits per value, a full-range random id column costs
+          one sizing pass and nothing on disk.  Min / max and null counts still come from the values.
+          Under ``device_compression="snappy"`` a delta chunk is written uncompressed; a chunk that
+          falls back to PLAIN goes through the snappy rule as before.  When the frame goes to
+          pyarrow's writer anyway, the value is handed to pyarrow as its own ``column_encoding``
+          (DESIGN.md, "DELTA_BINARY_PACKED in the PLAIN parquet writer").
         * ``partition_on``: ``None`` (default) writes exactly the files described above.  A column name
           or a list of 1 to 4 names writes a hive-partitioned dataset, laid out as
           ``pyarrow.parquet.write_to_dataset`` does: every input partition is split by the key tuple
@@ -558,8 +578,8 @@ class Dataset:
                 raise ValueError("to_parquet: compression= selects pyarrow's writer and device_compression= the PLAIN "
                                  f"writer's codec: pass one of them, not both ({compression!r}, {device_compression!r})")
             device_compression = "snappy"
+        check_column_encoding(column_encoding)
         keys = self._partition_keys(partition_on, out_files_per_proc, shuffle, max_partitions)
-        os.makedirs(str(output_path), exist_ok=True)
         output_path = str(output_path)
         rank, world = dist.rank(), dist.world_size()
         k = int(out_files_per_proc) if out_files_per_proc else None
@@ -585,18 +605,22 @@ class Dataset:
         # (a frame on the host has nothing to compress its pages with: pyarrow gets the codec)
         on_host = device_compression is not None and first is not None and \
             not all(col.data.is_cuda for _, col in first.items())
-        if first is not None and PLAIN_PARQUET and compression is None and not on_host and \
-                not (shuffle == Shuffle.PER_WORKER and k) and plain_eligible(first, dtypes, tables):
+        plain = first is not None and PLAIN_PARQUET and compression is None and not on_host and \
+            not (shuffle == Shuffle.PER_WORKER and k) and plain_eligible(first, dtypes, tables)
+        if plain:   # (argument errors that need the frame: raised before any file or directory exists)
+            offered = dictionary_columns(first, dtypes, use_dictionary)
+            delta = delta_columns(first, dtypes, column_encoding, offered)
+        os.makedirs(output_path, exist_ok=True)
+        if plain:
             # fixed-width numeric columns, lists of them and flat string columns on the device: PLAIN
             # pages written straight from pinned column buffers (parquet_write.py; a string column's
             # BYTE_ARRAY pages are filled on the device from its surrogates and its dict's entries) --
             # no compression, no statistics, dictionary pages only on request.  Lists of strings,
             # string columns on the host, with a dtypes= entry or with a dict value that is no str,
             # bools and narrow leaves go to pyarrow below
-            offered = dictionary_columns(first, dtypes, use_dictionary)   # (raises before any file exists)
             names, rows, order = write_plain(parts, output_path, fname, k, shuffle, dtypes, bool(statistics),
                                              PLAIN_ROW_GROUP, PLAIN_INFLIGHT, PLAIN_WRITE_THREADS, offered, tables,
-                                             snappy=device_compression is not None, splitter=splitter)
+                                             snappy=device_compression is not None, splitter=splitter, delta=delta)
             collector = [pq.read_metadata(os.path.join(output_path, names[j])) for j in order]
             schema = pq.read_schema(os.path.join(output_path, names[order[0]])) if order else None
         else:
@@ -604,6 +628,8 @@ class Dataset:
             pq_kw = {} if codec is None else {"compression": codec}
             if use_dictionary is not None:
                 pq_kw["use_dictionary"] = use_dictionary
+            if column_encoding is not None:
+                pq_kw["column_encoding"] = column_encoding
             names, rows, order, schema, collector = _write_pyarrow(parts, output_path, fname, k, shuffle, dtypes, pq_kw,
                                                                    splitter)
         for md, j in zip(collector, order):

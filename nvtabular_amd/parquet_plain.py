@@ -56,7 +56,13 @@ RLE_DICTIONARY), handed over as ``DictPages``: dictionary and indices are made o
 (kernels_parquet_dict, csrc/nvt_parquet_dict.hip), and ``dict_pays`` keeps a chunk PLAIN unless
 the dictionary makes it smaller ("Dictionary pages in the PLAIN parquet writer").  A string
 chunk's dictionary page is the PLAIN BYTE_ARRAY encoding of its distinct entries.  Not
-done: float and bool dictionaries, RLE runs inside the index stream, DELTA encodings.
+done: float and bool dictionaries, RLE runs inside the index stream.
+With ``to_parquet(column_encoding=...)`` a flat int32 / int64 column chunk (int8 / int16 and datetime
+counts too) may instead hold DELTA_BINARY_PACKED data pages of the same cut (encoding 5; block size
+128, 4 miniblocks, every page self-contained), handed over as ``DeltaPages``: the regions are made on
+the device (kernels_parquet_delta_out, csrc/nvt_parquet_delta_out.hip), and ``delta_pays`` keeps a
+chunk PLAIN unless the delta regions are smaller than the values ("DELTA_BINARY_PACKED in
+the PLAIN parquet writer").  Not done: delta pages of list leaves, the byte-array DELTA encodings.
 With ``to_parquet(device_compression="snappy")`` a column chunk may be written SNAPPY (codec 1): the
 same pages, every body the snappy raw stream ``varint(U) | one literal holding the level bytes | the
 elements of the values region`` with the elements made on the device (kernels_snappy,
@@ -145,7 +151,7 @@ def timestamp_unit(logical) -> Optional[str]:
 
 def _page_header(num_values: int, page_bytes: int, encoding: int = 0, compressed: Optional[int] = None) -> bytes:
     """``compressed``: the bytes of the body as it is written (None: ``page_bytes``, no codec)."""
-    dph = _Struct().i32(1, num_values).i32(2, encoding).i32(3, 3).i32(4, 3).done()  # PLAIN / RLE_DICTIONARY, RLE, RLE
+    dph = _Struct().i32(1, num_values).i32(2, encoding).i32(3, 3).i32(4, 3).done()  # PLAIN / DELTA_BINARY_PACKED / RLE_DICTIONARY, RLE, RLE
     return (_Struct().i32(1, 0).i32(2, page_bytes).i32(3, page_bytes if compressed is None else compressed)
             .struct(5, dph).done())
 
@@ -246,6 +252,47 @@ def dict_pays(d: int, nv, itemsize: int) -> bool:
     m = sum(int(x) for x in nv)
     return m > 0 and d <= DICT_MAX_ENTRIES and \
         d * itemsize + dict_index_bytes(nv, dict_index_width(d)) < m * itemsize
+
+
+def delta_pays(lengths, nv, itemsize: int) -> bool:
+    """The chunk rule of ``column_encoding``: a chunk of sum(nv) non-null values whose pages' delta
+    regions take ``lengths`` bytes is written DELTA_BINARY_PACKED iff it has values and the regions
+    together are SMALLER than the values.  The device applies the same comparison to the same numbers
+    (nvt_pq_delta_out_size) before it packs anything."""
+    m = sum(int(x) for x in nv)
+    return m > 0 and sum(int(x) for x in lengths) < m * int(itemsize)
+
+
+class DeltaPages:
+    """One DELTA_BINARY_PACKED column chunk of a flat int32 / int64 column, as ``write_row_group``
+    takes it in the place of the values: ``packed`` (bytes-like, uint8) holds the values regions of
+    the chunk's data pages -- page p's ``length[p]`` bytes at ``at[p]``: varint 128 | varint 4 |
+    varint nv[p] | zigzag first value | blocks -- and ``nv[p]`` is the number of non-null values of
+    data page p (the pages are cut where a PLAIN chunk's are).  ``dtype``: the column's physical one.
+    The device packs the regions (kernels_parquet_delta_out; tests/delta_reference.py restates the
+    format).  Like the values, ``packed`` may still be in flight when the row group is laid out, the
+    tables not."""
+
+    __slots__ = ("dtype", "packed", "at", "length", "nv")
+
+    def __init__(self, dtype, packed, at, length, nv):
+        self.dtype, self.packed = np.dtype(dtype), packed
+        self.at, self.length, self.nv = [int(x) for x in at], [int(x) for x in length], [int(x) for x in nv]
+        if self.dtype not in (np.dtype("int32"), np.dtype("int64")):
+            raise TypeError(f"DeltaPages: {self.dtype} values (int32 / int64 only)")
+        if not (len(self.at) == len(self.length) == len(self.nv) >= 1):
+            raise ValueError(f"DeltaPages: {len(self.at)} offsets, {len(self.length)} lengths, {len(self.nv)} pages")
+        for p, (a, l, k) in enumerate(zip(self.at, self.length, self.nv)):
+            # (the shortest region: 128 | 4 | count | first value = 5 bytes; a delta takes at most 9 bytes with headers)
+            if a < 0 or k < 0 or l < 5 or a + l > len(packed) or l > MAX_PAGE_BYTES:
+                raise ValueError(f"DeltaPages: page {p} holds {k} values in {l} bytes at {a} of {len(packed)}")
+
+    def page(self, p, nv):
+        """The values region of data page p (bytes-like)."""
+        if not 0 <= p < len(self.nv) or self.nv[p] != nv:
+            raise ValueError(f"PlainParquetWriter: page {p} has {nv} non-null values, its DeltaPages say "
+                             f"{self.nv[p] if 0 <= p < len(self.nv) else 'nothing'}")
+        return memoryview(self.packed).cast("B")[self.at[p]: self.at[p] + self.length[p]]
 
 
 class DictPages:
@@ -524,6 +571,8 @@ class PlainParquetWriter:
             return self._plan_dict_column(values, valid, n, dt, start)
         if isinstance(values, BoolPages) or dt == BOOL_DTYPE:
             return self._plan_bool_column(values, valid, n, dt, start)
+        if isinstance(values, DeltaPages):
+            return self._plan_delta_column(values, valid, n, dt, start)
         bp = values if isinstance(values, ByteArrayPages) else None
         if (bp is not None) != (dt == STRING_DTYPE):
             raise TypeError(f"PlainParquetWriter: column buffer is {getattr(values, 'dtype', type(values))}, "
@@ -577,6 +626,24 @@ class PlainParquetWriter:
         if done_vals != bp.nvalues:
             raise ValueError("PlainParquetWriter: the values do not match the validity bitmap "
                              f"({bp.nvalues} values, {done_vals} valid rows)")
+        return segs, at - start, start
+
+    def _plan_delta_column(self, dp, valid, n, dt, start):
+        """A flat chunk of DELTA_BINARY_PACKED pages: page = header (encoding 5) | def levels | region."""
+        if dp.dtype != dt:
+            raise TypeError(f"PlainParquetWriter: DeltaPages of {dp.dtype}, the file's column is {dt}")
+        segs, at, p = [], start, 0
+        for rows, page_valid, nv in _flat_pages(valid, n, PAGE_VALUES):
+            prefix, bitmap = _def_levels(rows, page_valid)
+            payload = dp.page(p, nv)
+            body = len(prefix) + (len(bitmap) if bitmap is not None else 0) + len(payload)
+            for buf in (_page_header(rows, body, 5) + prefix, bitmap, payload):
+                if buf is not None and len(buf):
+                    segs.append((at, buf))
+                    at += len(buf)
+            p += 1
+        if p != len(dp.nv):
+            raise ValueError(f"PlainParquetWriter: {p} data pages, the DeltaPages hold {len(dp.nv)}")
         return segs, at - start, start
 
     def _plan_dict_column(self, dp, valid, n, dt, start):
@@ -721,7 +788,8 @@ class PlainParquetWriter:
         """columns[j] = (values, valid): `values` a 1-D numpy array of the column's dtype holding
         the NON-NULL values in row order, `valid` None or the Arrow validity bitmap (uint8, LSB
         first, >= ceil(n / 8) bytes) of the n rows.  A list column: (values, levels) with the
-        non-null LEAVES of the n rows in order and their ``ListLevels``.  A string column: a
+        non-null LEAVES of the n rows in order and their ``ListLevels``.  A DELTA_BINARY_PACKED chunk of
+        a flat int32 / int64 column: a ``DeltaPages`` in the place of ``values``.  A string column: a
         ``ByteArrayPages`` in the place of ``values``, a bool column: a ``BoolPages``; an int8 / int16
         column: its values sign-extended to int32.  A dictionary-encoded chunk
         (of any kind): a ``DictPages`` in the place of ``values``.  A SNAPPY chunk (of any kind, also
@@ -761,11 +829,12 @@ class PlainParquetWriter:
             pos += size
             is_dict = isinstance(values, DictPages) or (raw_size is not None and values.W is not None)
             if raw_size is None:
-                nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages)) else \
+                nvalid = sum(values.nv) if isinstance(values, (DictPages, ByteArrayPages, DeltaPages)) else \
                     values.nvalues if isinstance(values, BoolPages) else int(np.asarray(values).size)
             chunks.append(dict(name=name, dt=dt, n=nv, size=size, start=start, nulls=nv - nvalid,
                                minmax=stats[j] if (stats is not None and nvalid > 0) else None,
                                is_list=self.lists[j], first_data=first if is_dict else None,
+                               delta=isinstance(values, DeltaPages),
                                raw_size=size if raw_size is None else raw_size, codec=0 if raw_size is None else 1))
             total += chunks[-1]["raw_size"]   # (a row group's total_byte_size counts uncompressed bytes)
         self.pos = pos
@@ -806,9 +875,10 @@ class PlainParquetWriter:
         path = [name, "list", "element"] if c.get("is_list") else [name]
         # a dictionary chunk: encodings PLAIN, RLE, RLE_DICTIONARY; data_page_offset (9) is its first
         # data page, dictionary_page_offset (11) the chunk's start; the sizes include the dictionary
+        # a delta chunk: encodings DELTA_BINARY_PACKED, RLE
         first = c.get("first_data")
         meta = (_Struct().i32(1, _ptype(dt))
-                .list(2, _CT_I32, [_zigzag(0), _zigzag(3)] + ([_zigzag(8)] if first is not None else []))
+                .list(2, _CT_I32, [_zigzag(5 if c.get("delta") else 0), _zigzag(3)] + ([_zigzag(8)] if first is not None else []))
                 .list(3, _CT_BINARY, [_varint(len(x.encode())) + x.encode() for x in path])
                 .i32(4, c.get("codec", 0)).i64(5, c["n"]).i64(6, c.get("raw_size", c["size"])).i64(7, c["size"])
                 .i64(9, c["start"] if first is None else first))

@@ -16,6 +16,12 @@ ONE read-back per row group brings their state records {d, overflow} and page st
 rule (``parquet_plain.dict_pays``) is applied on the host, and each chunk then copies out what it
 really needs: dictionary + packed indices, or the plain values ("Dictionary pages in
 the PLAIN parquet writer").
+Delta pages (``column_encoding``): the non-null values of every column OFFERED to DELTA_BINARY_PACKED go
+through kernels_parquet_delta_out (sizing, scan and pack enqueued next to the dictionary builds; the
+chunk rule runs on the device, so a chunk that stays PLAIN costs the sizing pass alone); their page
+tables ride in the SAME read-back as the dictionary states, ``parquet_plain.delta_pays`` restates the
+rule on the host, and each chunk copies out its packed regions or the plain values (DESIGN.md,
+"DELTA_BINARY_PACKED in the PLAIN parquet writer").
 String columns: the column's {surrogate -> str} dict goes to the device once per to_parquet call as an
 entry table (kernels_parquet_str_out.StringTables); per row group the non-null surrogates become entry
 ids and a byte plan, the page table and the count of unknown surrogates ride in the read-back of the
@@ -41,6 +47,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from . import kernels_parquet_delta_out as KDO
 from . import kernels_parquet_dict as KPD
 from . import kernels_parquet_list as KPL
 from . import kernels_parquet_narrow as KPN
@@ -48,13 +55,15 @@ from . import kernels_parquet_str_out as KSO
 from . import kernels_snappy as KS
 from . import parquet_plain as PP
 from .device import pack_bitmap_device
-from .parquet_plain import BoolPages, ByteArrayPages, DictPages, ListLevels, PlainParquetWriter, SnappyPages
+from .parquet_plain import (BoolPages, ByteArrayPages, DeltaPages, DictPages, ListLevels, PlainParquetWriter,
+                            SnappyPages)
 
 # seconds of the last plain write: staging (enqueue + pinned allocation), waiting for copies, writing;
 # snappy_s (a part of stage_s): plan, compress and gather of a row group's chunks, the read-back of
 # their page sizes and the enqueueing of the copies behind it;
 # levels_s (a part of stage_s): packing the levels of list columns and waiting for their page tables;
-# dict_s (a part of stage_s): enqueueing dictionary build + pack and waiting for the state records;
+# dict_s (a part of stage_s): enqueueing dictionary build + pack (and the delta encodes) and waiting for
+# the state records;
 # strings_s (a part of stage_s): entry ids, byte plans and fills of string columns, and the read-back
 # of their dictionary page sizes
 LAST_TIMING = {}
@@ -73,6 +82,7 @@ class _Column(NamedTuple):
     bitmap: Optional[torch.Tensor] = None    # leaf bitmap of a list column (what `mask` unpacks)
     offered: bool = False                    # its chunks are dictionary-encoded where that pays
     table: Any = None                        # EntryTable of a string column (``data``: its surrogates)
+    delta: bool = False                      # its chunks are written DELTA_BINARY_PACKED where that pays
 
 
 class _HostColumn(NamedTuple):
@@ -174,6 +184,59 @@ def dictionary_columns(frame, dtypes, use_dictionary):
     return frozenset(names)
 
 
+DELTA_ENCODINGS = ("DELTA_BINARY_PACKED", "PLAIN")   # what ``column_encoding`` takes
+
+
+def _delta_eligible(col, dtypes, name) -> bool:
+    """A column of a plain-eligible frame whose chunks can be DELTA_BINARY_PACKED: flat, on the device,
+    int32 / int64 after the requested cast, int8 / int16 (the file's INT32) or datetime counts."""
+    if col.strings is not None or col.offsets is not None or not col.data.is_cuda:
+        return False
+    if dtypes and name in dtypes:
+        return np.dtype(dtypes[name]) in (np.dtype("int32"), np.dtype("int64"))
+    return col.data.dtype in (torch.int32, torch.int64, torch.int8, torch.int16)
+
+
+def check_column_encoding(column_encoding):
+    """What can be refused from ``to_parquet(column_encoding=...)`` alone: its shape and the encodings."""
+    if column_encoding is None:
+        return
+    named = column_encoding.values() if isinstance(column_encoding, dict) else [column_encoding]
+    for enc in named:
+        if not isinstance(enc, str) or enc not in DELTA_ENCODINGS:
+            raise ValueError(f"to_parquet: column_encoding takes None, an encoding or a dict {{column: encoding}} with "
+                             f"the encodings {DELTA_ENCODINGS}, not {enc!r}")
+
+
+def delta_columns(frame, dtypes, column_encoding, offered=frozenset()):
+    """``to_parquet(column_encoding=...)`` for a frame ``plain_eligible`` takes -> the names of the
+    columns offered to DELTA_BINARY_PACKED.  None / "PLAIN": none; "DELTA_BINARY_PACKED": every eligible
+    column that is not offered to ``use_dictionary`` (``offered``); a dict {column: encoding}: the columns
+    it gives "DELTA_BINARY_PACKED" -- a name that is no column, a column that is not eligible, another
+    encoding, or a column that is also offered to ``use_dictionary`` raises ValueError."""
+    check_column_encoding(column_encoding)
+    if column_encoding is None or column_encoding == "PLAIN":
+        return frozenset()
+    eligible = [name for name, col in frame.items() if _delta_eligible(col, dtypes, name)]
+    if isinstance(column_encoding, str):
+        return frozenset(name for name in eligible if name not in offered)
+    cols = [name for name, _ in frame.items()]
+    names = []
+    for name, enc in column_encoding.items():
+        if name not in cols:
+            raise ValueError(f"to_parquet: column_encoding names '{name}', which is no column of {cols}")
+        if name in offered:
+            raise ValueError(f"to_parquet: column '{name}' is offered to use_dictionary and to column_encoding: "
+                             "a chunk takes one of them")
+        if enc == "PLAIN":
+            continue
+        if name not in eligible:
+            raise ValueError(f"to_parquet: column_encoding names '{name}': only flat int8 / int16 / int32 / int64 and "
+                             f"datetime columns on the device are written DELTA_BINARY_PACKED (these: {eligible})")
+        names.append(name)
+    return frozenset(names)
+
+
 def device_permutation(n: int, frame):
     return torch.randperm(n, device=next((col.data.device for _, col in frame.items()), None))
 
@@ -186,10 +249,11 @@ def _to_host(t):
     return h
 
 
-def _prepare(part, n, dtypes, offered=frozenset(), tables=None):
+def _prepare(part, n, dtypes, offered=frozenset(), tables=None, delta=frozenset()):
     """-> ([_Column] of a partition of n rows, [[list columns that share one offsets tensor]]: they share
     plan, page table and repetition stream).  ``offered``: names of the columns whose chunks may be
-    dictionary-encoded.  ``tables``: the StringTables of the call."""
+    dictionary-encoded.  ``tables``: the StringTables of the call.  ``delta``: names of the columns whose
+    chunks may be written DELTA_BINARY_PACKED."""
     cols, groups = [], {}
     tables = tables if tables is not None else KSO.StringTables()
     for name, col in part.items():
@@ -214,8 +278,9 @@ def _prepare(part, n, dtypes, offered=frozenset(), tables=None):
         if dtypes and name in dtypes:
             data = data.to(_TORCH_OF[str(np.dtype(dtypes[name]))])
         mask = K.unpack_bitmap(col.valid, n) if col.valid is not None else None
-        cols.append(_Column(name, data, mask, col.logical, offered=name in offered and data.is_cuda and
-                            data.dtype in (torch.int32, torch.int64, torch.int8, torch.int16)))
+        is_int = data.is_cuda and data.dtype in (torch.int32, torch.int64, torch.int8, torch.int16)
+        cols.append(_Column(name, data, mask, col.logical, offered=name in offered and is_int,
+                            delta=name in delta and is_int))
     return cols, list(groups.values())
 
 
@@ -312,10 +377,11 @@ def _widen_narrow(cols, staged, rows, keep):
     return staged, bools
 
 
-def _stage_column(c: _Column, vals, valid, encoded, statistics, keep, packed=None):
+def _stage_column(c: _Column, vals, valid, encoded, statistics, keep, packed=None, delta=None):
     """One column of a row group on its way to the host -> (_HostColumn, min / max or None).
     ``encoded``: None, or (DeviceDict, d, overflow, page starts) of an offered column after the read-back.
-    ``packed``: the bytes of a bool chunk's pages on the device (``_widen_narrow``)."""
+    ``packed``: the bytes of a bool chunk's pages on the device (``_widen_narrow``).
+    ``delta``: None, or the DeviceDelta of a column offered to DELTA_BINARY_PACKED after the read-back."""
     hv = None
     if packed is not None:   # (a bool chunk: a null count, no min / max)
         hp = _to_host(packed)   # (ceil(nv / 8) + pages bytes: the bound; the host lays the pages out from the bitmap)
@@ -330,6 +396,10 @@ def _stage_column(c: _Column, vals, valid, encoded, statistics, keep, packed=Non
             hd, hp = _to_host(dd.dictionary[:d]), _to_host(dd.packed[:PP.dict_page_offsets(nv, W)[1]])
             hv = DictPages(hd.numpy(), hp.numpy(), W, nv)
             keep.append((dd, hd, hp))
+    if delta is not None and delta.pays:   # (the device packed the chunk: the same rule on the same numbers)
+        hp = _to_host(delta.packed[:delta.used])
+        hv = DeltaPages(str(vals.dtype).replace("torch.", ""), hp.numpy(), delta.at, delta.lengths, delta.nv)
+        keep.append((delta, hp))
     if hv is None:
         hv = _to_host(vals).numpy()
     hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
@@ -417,13 +487,15 @@ def _snappy_geometry(rows, page_rows, nulls, levels):
     return [(b - a, PP.flat_level_bytes(b - a, nulls)) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
-def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep, bools):
+def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep, bools, deltas):
     """``device_compression="snappy"``: every chunk of the row group in the form it takes (after
     ``dict_pays``) -> ([_HostColumn], [min / max or None]).  Plan, compress and gather are enqueued for
     the values regions of ALL chunks at once (a dictionary chunk: its dictionary page), ONE read-back
     brings their per-page compressed sizes (and the page starts only the device has),
     ``parquet_plain.snappy_pays`` decides per chunk on the host, and every chunk then copies out
-    only what it needs: the dense compressed bytes, or the raw values as today."""
+    only what it needs: the dense compressed bytes, or the raw values as today.  A chunk the delta
+    rule took (``deltas``) is written as it is, uncompressed; one it left PLAIN goes through the snappy
+    rule like any other."""
     forms = _fill_strings(strs, dicts, states, keep)
     dev = next((v.device for v, _, _ in staged if v.is_cuda), None)
     whole = torch.arange(2, dtype=torch.int64, device=dev) if dev is not None else None   # one page: [0, 1] units
@@ -441,18 +513,19 @@ def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep, boo
                 plan = dict(kind="plain", geo=geo, raw=np.diff(sc.page_at_host), region=KS.Region(form[1], sc.page_at, 1, 4))
             else:
                 continue
-        elif not vals.numel() or not vals.is_cuda or ci in bools:   # (bool chunks are written uncompressed)
-            continue
+        elif not vals.numel() or not vals.is_cuda or ci in bools or (ci in deltas and deltas[ci].pays):
+            continue   # (bool and delta chunks are written uncompressed)
         else:
             size = vals.element_size()
             geo = _snappy_geometry(rows, PP.PAGE_VALUES, nulls, levels)
-            d, overflow, ps = states[ci] if ci in dicts else (0, 1, None)
+            d, overflow, ps = states[ci] if ci in dicts else (0, 1, deltas[ci].starts if ci in deltas else None)
             if ci in dicts and not overflow and PP.dict_pays(d, np.diff(ps), size):
                 plan = dict(kind="dict", geo=geo, nv=np.diff(ps), d=d, W=PP.dict_index_width(d), dd=dicts[ci], raw=d * size,
                             region=KS.Region(dicts[ci].dictionary[:d], whole, d * size, size))
             else:
                 src = vals.contiguous()
-                dps = dicts[ci].page_start if ci in dicts else _page_start(src, valid, m, rows)
+                dps = dicts[ci].page_start if ci in dicts else deltas[ci].page_start if ci in deltas else \
+                    _page_start(src, valid, m, rows)
                 plan = dict(kind="plain", geo=geo, raw=None if ps is None else np.diff(ps) * size,
                             region=KS.Region(src, dps, size, size))
                 if ps is None:
@@ -509,7 +582,7 @@ def _stage_snappy(cols, staged, strs, dicts, states, rows, statistics, keep, boo
             mm = None   # (no min / max for string chunks)
         elif hv is None:
             hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics, keep,
-                                   bools.get(ci))
+                                   bools.get(ci), deltas.get(ci))
         else:
             hb = valid if isinstance(valid, ListLevels) or valid is None else _to_host(valid).numpy()
             mm = _min_max(vals) if statistics else None
@@ -565,21 +638,25 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) 
         dicts = {ci: KPD.encode(strs[ci].ids, strs[ci].page_start) if ci in strs else
                  KPD.encode(vals.contiguous(), _page_start(vals, valid, m, s1 - s0))
                  for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)) if c.offered and vals.numel()}
-        if strs:
-            got, more = KPD.read_back_states(list(dicts.values()), [t for sc in strs.values() for t in sc.device_words()])
-            for sc in strs.values():
+        # delta pages: sizing + scan + pack of every column offered to them; their page tables ride along too
+        deltas = {ci: KDO.encode(vals.contiguous(), _page_start(vals, valid, m, s1 - s0))
+                  for ci, (c, (vals, valid, m)) in enumerate(zip(cols, staged)) if c.delta and vals.numel()}
+        if strs or deltas:
+            got, more = KPD.read_back_states(list(dicts.values()), [t for sc in list(strs.values()) + list(deltas.values())
+                                                                    for t in sc.device_words()])
+            for sc in list(strs.values()) + list(deltas.values()):
                 sc.take_words(more)
         else:
             got = KPD.read_back_states(list(dicts.values()))
         states = dict(zip(dicts, got))
-        if dicts:
+        if dicts or deltas:
             LAST_TIMING["dict_s"] += time.perf_counter() - t_dc
         elif strs:   # (the read-back waited for entry ids and plans alone)
             LAST_TIMING["strings_s"] += time.perf_counter() - t_dc
         t_ss = time.perf_counter()
         if snappy:
             # snappy pages: plan + compress + gather of every chunk in the form it takes, ONE read-back
-            host, mms = _stage_snappy(cols, staged, strs, dicts, states, s1 - s0, statistics, keep, bools)
+            host, mms = _stage_snappy(cols, staged, strs, dicts, states, s1 - s0, statistics, keep, bools, deltas)
             stats = mms if statistics else None
             LAST_TIMING["snappy_s"] += time.perf_counter() - t_ss
             staged = []   # (every column is staged)
@@ -591,7 +668,7 @@ def _stage_row_group(j, cols, groups, s0, s1, copy_s, statistics, snappy=False) 
                 hc, mm = hosts[ci], None   # (no min / max for string chunks)
             else:
                 hc, mm = _stage_column(c, vals, valid, (dicts[ci],) + states[ci] if ci in dicts else None, statistics,
-                                       keep, bools.get(ci))
+                                       keep, bools.get(ci), deltas.get(ci))
             host.append(hc)
             if statistics:
                 stats.append(mm)
@@ -698,11 +775,12 @@ def _piece_ranges(pieces, row_group):
 
 
 def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_group, max_inflight, threads,
-                offered=frozenset(), tables=None, snappy=False, splitter=None):
+                offered=frozenset(), tables=None, snappy=False, splitter=None, delta=frozenset()):
     """Dataset.to_parquet for the frames ``plain_eligible`` takes: partition i goes to file i, or
     with ``k`` is cut into k pieces for files 0 .. k-1; every piece is cut into row groups of
     ``row_group`` rows, each staged and handed to its file's writer while the next is staged.
     ``offered``: the columns whose chunks are dictionary-encoded where that makes them smaller.
+    ``delta``: the columns whose chunks are written DELTA_BINARY_PACKED where that makes them smaller.
     ``tables``: the StringTables ``plain_eligible`` judged the first partition with (None: a fresh one).
     ``snappy``: ``device_compression="snappy"`` -- chunks on the device are written SNAPPY where that
     makes them smaller.
@@ -728,7 +806,7 @@ def write_plain(parts, output_path, fname, k, shuffle, dtypes, statistics, row_g
                     part, pieces = splitter.split(part)
                     if not pieces:
                         continue
-                cols, groups = _prepare(part, n, dtypes, offered, tables)
+                cols, groups = _prepare(part, n, dtypes, offered, tables, delta)
                 on_gpu = any(c.data.is_cuda for c in cols)
                 if on_gpu and copy_s is None:
                     copy_s = torch.cuda.Stream()
