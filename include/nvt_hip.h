@@ -2231,6 +2231,72 @@ int nvt_row_similarity(const void *left, const uint8_t *left_valid, const void *
                        int dtype, uint64_t n, const nvt_csr *left_csr, const nvt_csr *right_csr, double *out,
                        void *ws, uint64_t ws_bytes, void *stream);
 
+/* ---- column expressions (nvtabular_amd/kernels_expr.py, series.py: LambdaOp UDFs, Filter) ----
+ * What a UDF does to its columns, recorded as a three-address program and run by ONE launch: one
+ * read of every input column (bitmap included), one write of the result.
+ * Program: 1 .. NVT_EXPR_MAX_INSTR instructions over NVT_EXPR_MAX_REGS registers; every register has
+ *   a class (NVT_EXPR_I64 / _F64 / _F32 / _BOOL), fixed by the instruction that writes it.
+ *   NVT_EXPR_LOAD   dst = input column `a`, as class `cls`: _F64 with NaN under a cleared bit when
+ *                   the input has a bitmap, else _F32 / _F64 / _BOOL by dtype and _I64 for integers
+ *   NVT_EXPR_CAST   dst = register `a` of class `b` converted to class `cls`
+ *   NVT_EXPR_SELECT dst = a ? b : c; `a` is _BOOL, b and c have class `cls`
+ *   NVT_EXPR_ADD .. NVT_EXPR_TANH   dst = op(a, b) in class `cls`, the class of a and b; the result
+ *                   has class `cls`, that of NVT_EXPR_EQ .. NVT_EXPR_ISNAN is _BOOL
+ *   DIV, ISNAN and ROUND .. TANH take floats only, NOT / AND / OR / XOR _I64 or _BOOL; _BOOL takes
+ *   nothing but those four, EQ and NE.  FLOORDIV and MOD follow torch.div(rounding_mode="floor")
+ *   and torch.remainder on floats; on _I64 the divisor is a non-zero constant and the quotient is
+ *   rounded down.  MAX / MIN propagate a NaN, CLIPLO / CLIPHI (a bound in b) keep one.
+ *   flags: NVT_EXPR_B_CONST / _C_CONST make b / c an index into consts[NVT_EXPR_MAX_CONSTS], bit
+ *   patterns of the operand's class (int64, double, or float in the low 32 bits);
+ *   NVT_EXPR_SWAP computes op(b, a), for a constant on the left of SUB, DIV, FLOORDIV or MOD.
+ *   wrap: 0, 8, 16 or 32: an _I64 result is truncated to that many bits and sign-extended, so an
+ *   int32-typed value wraps as int32 does.
+ * The register written by the last instruction is stored as out_dtype: _I64 as NVT_I8 / _I16 / _I32
+ *   / _I64 (truncated), _F32 as NVT_F32, _F64 as NVT_F64, _BOOL as NVT_EXPR_DT_BOOL (one byte 0 / 1).
+ * Inputs: 0 .. NVT_EXPR_MAX_INPUTS columns of n elements, dtype NVT_F32 .. NVT_I16 or
+ *   NVT_EXPR_DT_BOOL, aligned to their element; input_valid[i] NULL or a bitmap of ceil(n / 8) bytes.
+ * A workgroup of one wave takes NVT_EXPR_TILE elements at a time, 8 per lane.  Stream-ordered, no
+ * host synchronisation; n = 0 is a no-op.  nvt_expr_eval_host: the same program over host memory. */
+#define NVT_EXPR_MAX_INSTR 64
+#define NVT_EXPR_MAX_INPUTS 8
+#define NVT_EXPR_MAX_REGS 16
+#define NVT_EXPR_MAX_CONSTS 16
+#define NVT_EXPR_TILE 512
+#define NVT_EXPR_I64 0
+#define NVT_EXPR_F64 1
+#define NVT_EXPR_F32 2
+#define NVT_EXPR_BOOL 3
+#define NVT_EXPR_DT_BOOL 7 /* dtype code of a bool column, after NVT_F32 .. NVT_I16 */
+#define NVT_EXPR_B_CONST 1
+#define NVT_EXPR_C_CONST 2
+#define NVT_EXPR_SWAP 4
+enum {
+  NVT_EXPR_LOAD = 0, NVT_EXPR_CAST, NVT_EXPR_SELECT,
+  NVT_EXPR_ADD, NVT_EXPR_SUB, NVT_EXPR_MUL, NVT_EXPR_DIV, NVT_EXPR_FLOORDIV, NVT_EXPR_MOD,
+  NVT_EXPR_NEG, NVT_EXPR_ABS, NVT_EXPR_MAX, NVT_EXPR_MIN, NVT_EXPR_CLIPLO, NVT_EXPR_CLIPHI,
+  NVT_EXPR_SIGN, NVT_EXPR_NOT, NVT_EXPR_AND, NVT_EXPR_OR, NVT_EXPR_XOR,
+  NVT_EXPR_EQ, NVT_EXPR_NE, NVT_EXPR_LT, NVT_EXPR_LE, NVT_EXPR_GT, NVT_EXPR_GE, NVT_EXPR_ISNAN,
+  NVT_EXPR_ROUND, NVT_EXPR_FLOOR, NVT_EXPR_CEIL, NVT_EXPR_SQRT, NVT_EXPR_LOG, NVT_EXPR_LOG1P,
+  NVT_EXPR_LOG2, NVT_EXPR_LOG10, NVT_EXPR_EXP, NVT_EXPR_EXPM1, NVT_EXPR_SIN, NVT_EXPR_COS,
+  NVT_EXPR_TANH, NVT_EXPR_NOPS
+};
+typedef struct nvt_expr_instr {
+  uint8_t op;    /* NVT_EXPR_LOAD .. NVT_EXPR_TANH                     */
+  uint8_t cls;   /* NVT_EXPR_I64 .. NVT_EXPR_BOOL                      */
+  uint8_t dst;   /* register written                                   */
+  uint8_t a;     /* register read; NVT_EXPR_LOAD: the input's index    */
+  uint8_t b;     /* register or constant; NVT_EXPR_CAST: a's class     */
+  uint8_t c;     /* register or constant (NVT_EXPR_SELECT)             */
+  uint8_t flags; /* NVT_EXPR_B_CONST | _C_CONST | NVT_EXPR_SWAP       */
+  uint8_t wrap;  /* 0, 8, 16, 32                                       */
+} nvt_expr_instr;
+int nvt_expr_eval(const nvt_expr_instr *program, int ninstr, const uint64_t *consts, const void *const *inputs,
+                  const int32_t *input_dtypes, const uint8_t *const *input_valid, int ninputs, uint64_t n,
+                  void *out, int out_dtype, void *stream);
+int nvt_expr_eval_host(const nvt_expr_instr *program, int ninstr, const uint64_t *consts,
+                       const void *const *inputs, const int32_t *input_dtypes,
+                       const uint8_t *const *input_valid, int ninputs, uint64_t n, void *out, int out_dtype);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -640,6 +640,27 @@ SIGNATURES.update({
     "nvt_row_similarity": [_vp, _vp, _vp, _vp, _i32, _u64, C.POINTER(Csr), C.POINTER(Csr), _vp, _vp, _u64, _vp],
 })
 
+class ExprInstr(C.Structure):
+    """nvt_expr_instr: one three-address instruction of nvt_expr_eval."""
+    _fields_ = [(f, C.c_uint8) for f in ("op", "cls", "dst", "a", "b", "c", "flags", "wrap")]
+
+
+# include/nvt_hip.h NVT_EXPR_*
+EXPR_MAX_INSTR, EXPR_MAX_INPUTS, EXPR_MAX_REGS, EXPR_MAX_CONSTS, EXPR_TILE = 64, 8, 16, 16, 512
+EXPR_I64, EXPR_F64, EXPR_F32, EXPR_BOOL = range(4)
+EXPR_DT_BOOL = 7
+EXPR_B_CONST, EXPR_C_CONST, EXPR_SWAP = 1, 2, 4
+EXPR_OPS = ("load", "cast", "select", "add", "sub", "mul", "div", "floordiv", "mod", "neg", "abs", "max", "min",
+            "cliplo", "cliphi", "sign", "not", "and", "or", "xor", "eq", "ne", "lt", "le", "gt", "ge", "isnan",
+            "round", "floor", "ceil", "sqrt", "log", "log1p", "log2", "log10", "exp", "expm1", "sin", "cos", "tanh")
+EXPR_OP = {name: code for code, name in enumerate(EXPR_OPS)}   # NVT_EXPR_LOAD .. NVT_EXPR_TANH
+SIGNATURES.update({
+    "nvt_expr_eval": [C.POINTER(ExprInstr), _i32, C.POINTER(_u64), _pp, C.POINTER(C.c_int32), _pp, _i32, _u64, _vp,
+                      _i32, _vp],
+    "nvt_expr_eval_host": [C.POINTER(ExprInstr), _i32, C.POINTER(_u64), _pp, C.POINTER(C.c_int32), _pp, _i32, _u64,
+                           _vp, _i32],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,

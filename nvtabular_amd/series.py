@@ -4,11 +4,16 @@ The reference's LambdaOp (nvtabular/ops/lambdaop.py:19 -> merlin.dag.ops.udf.UDF
 ``f(col)`` / ``f(col, df)`` with dataframe columns; on its GPU path those are cuDF Series whose
 operators run as device kernels.  ``DeviceSeries`` plays that role here for numeric columns:
 arithmetic, comparisons, ``astype``, ``fillna``, ``clip``, ``abs``, ``where``, ``isna`` and numpy
-ufuncs (``np.log(col + 1)``) run on the HBM-resident buffer through torch-ROCm elementwise
-kernels (plumbing: a UDF is arbitrary Python, there is no fixed kernel to hand-write), with pandas'
-semantics: an integer column that has nulls behaves as float64 with NaN, ``/`` is float64 true
-division, comparisons against a null are False.  Anything else (``.str``, ``.map``,
-``.apply`` ...) raises ``HostFallback`` and LambdaOp re-runs the UDF on pandas on the host.
+ufuncs (``np.log(col + 1)``) are recorded as an expression DAG (kernels_expr.py) and run as ONE
+launch of the expression kernel (csrc/nvt_expr.hip) when the values are needed: ``.values``,
+``to_column()``, a ``Filter`` mask.  A UDF is arbitrary Python, but what it does to its columns is a
+small program: one read of each input column, bitmap included, one write of the result.  pandas'
+semantics hold: an integer column that has nulls behaves as float64 with NaN, ``/`` is float64 true
+division, comparisons against a null are False.  What the program cannot express (``**``,
+``round(2)``, ``astype`` of floats to integers, whose NaN check needs the values, a DAG beyond the
+kernel's caps) evaluates its operands and runs as a torch elementwise call, as everything did
+before.  Anything else (``.str``, ``.map``, ``.apply`` ...) raises ``HostFallback`` and LambdaOp
+re-runs the UDF on pandas on the host.
 
 A datetime column (``DeviceColumn.logical``) is handed over as a ``DatetimeSeries``: int64 counts
 with a validity mask of their own -- NaN in float64 cannot hold a nanosecond count.  Its calendar
@@ -22,6 +27,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import kernels_expr as KE
 from .device import DeviceColumn, DeviceFrame, torch_dtype
 
 
@@ -36,11 +42,22 @@ def _unpack_valid(col: DeviceColumn) -> torch.Tensor:
 
 
 class DeviceSeries:
+    """``_x`` is the column's tensor or a pending expression (kernels_expr.Expr); ``_t`` is the
+    tensor, evaluating the expression with one launch when it is still pending."""
     __array_priority__ = 1000  # numpy defers binary operators to us
 
-    def __init__(self, data: torch.Tensor, name=None):
-        self._t = data
+    def __init__(self, data, name=None):
+        self._x = data
         self.name = name
+
+    @property
+    def _t(self) -> torch.Tensor:
+        if not isinstance(self._x, torch.Tensor):
+            self._x = KE.evaluate(self._x)
+        return self._x
+
+    def _expr(self) -> "KE.Expr":
+        return KE.leaf(self._x) if isinstance(self._x, torch.Tensor) else self._x
 
     # ---- construction ------------------------------------------------------------------
     @staticmethod
@@ -50,15 +67,11 @@ class DeviceSeries:
         if col.logical is not None:
             return DatetimeSeries.from_column(col, name)
         col = col.materialize()
-        t = col.data
-        if t.dtype == torch.uint8:
-            t = t.to(torch.int64)
-        if col.valid is not None:
-            ok = _unpack_valid(col)
-            # pandas' view of a numeric column with nulls: float64 with NaN
-            t = torch.where(ok, t.to(torch.float64), torch.full((), float("nan"), dtype=torch.float64,
-                                                                device=t.device))
-        return DeviceSeries(t, name)
+        if col.valid is None and col.data.dtype != torch.uint8:
+            return DeviceSeries(col.data, name)
+        # pandas' view of a numeric column with nulls: float64 with NaN (the bitmap is tested inside
+        # the load of the expression kernel); a uint8 column reads as int64
+        return DeviceSeries(KE.leaf(col.data, col.valid), name)
 
     def to_column(self) -> DeviceColumn:
         t = self._t
@@ -71,14 +84,14 @@ class DeviceSeries:
     def dtype(self):
         from .device import numpy_dtype
 
-        return numpy_dtype(self._t.dtype)
+        return numpy_dtype(self._x.dtype) if isinstance(self._x, torch.Tensor) else self._x.dtype
 
     @property
     def values(self):
         return self._t
 
     def __len__(self):
-        return int(self._t.numel())
+        return int(self._x.numel()) if isinstance(self._x, torch.Tensor) else self._x.n
 
     def _wrap(self, t) -> "DeviceSeries":
         return DeviceSeries(t, self.name)
@@ -93,7 +106,29 @@ class DeviceSeries:
             return other
         raise HostFallback(f"operand of type {type(other).__name__}")
 
-    def _bin(self, other, fn, swap=False):
+    @staticmethod
+    def _operand(other):
+        """``other`` for an expression builder: an Expr or a Python scalar."""
+        if isinstance(other, DeviceSeries):
+            return other._expr()
+        if isinstance(other, torch.Tensor):
+            return KE.leaf(other)
+        return DeviceSeries._raw(other)
+
+    def _fused(self, build):
+        """The series of the expression ``build()`` gives, or None when the program cannot
+        express it: the caller then evaluates the operands and takes the torch operator."""
+        try:
+            return self._wrap(build())
+        except KE.NotFusable:
+            return None
+
+    def _bin(self, other, fn, swap=False, op=None):
+        if op is not None:
+            build = KE.truediv if op == "div" else lambda a, b, s: KE.arith(op, a, b, s)
+            r = self._fused(lambda: build(self._expr(), self._operand(other), swap))
+            if r is not None:
+                return r
         a, b = self._t, self._raw(other)
         # numpy / pandas promotion, not torch's: float32 (op) int64 -> float64, and an integer
         # column (op) a Python float -> float64 (torch would give float32 in both cases)
@@ -111,55 +146,63 @@ class DeviceSeries:
     def _f64(x):
         return x.to(torch.float64) if isinstance(x, torch.Tensor) else float(x)
 
-    def __add__(self, o): return self._bin(o, torch.add)
-    def __radd__(self, o): return self._bin(o, torch.add, True)
-    def __sub__(self, o): return self._bin(o, torch.sub)
-    def __rsub__(self, o): return self._bin(o, lambda a, b: torch.sub(torch.as_tensor(a, device=b.device) if not isinstance(a, torch.Tensor) else a, b), True)
-    def __mul__(self, o): return self._bin(o, torch.mul)
-    def __rmul__(self, o): return self._bin(o, torch.mul, True)
+    def __add__(self, o): return self._bin(o, torch.add, op="add")
+    def __radd__(self, o): return self._bin(o, torch.add, True, "add")
+    def __sub__(self, o): return self._bin(o, torch.sub, op="sub")
+    def __rsub__(self, o): return self._bin(o, lambda a, b: torch.sub(torch.as_tensor(a, device=b.device) if not isinstance(a, torch.Tensor) else a, b), True, "sub")
+    def __mul__(self, o): return self._bin(o, torch.mul, op="mul")
+    def __rmul__(self, o): return self._bin(o, torch.mul, True, "mul")
 
     def __truediv__(self, o):  # pandas: always float64 true division
-        return self._bin(o, lambda a, b: torch.div(self._f64(a), self._f64(b)))
+        return self._bin(o, lambda a, b: torch.div(self._f64(a), self._f64(b)), op="div")
 
     def __rtruediv__(self, o):
-        return self._bin(o, lambda a, b: torch.div(torch.as_tensor(self._f64(a), device=b.device), self._f64(b)), True)
+        return self._bin(o, lambda a, b: torch.div(torch.as_tensor(self._f64(a), device=b.device), self._f64(b)), True, "div")
 
     def _int_divisor_guard(self, o):
         """pandas turns integer // 0 and integer % 0 into inf / NaN (float64); integer division
         by zero on the device is undefined.  A zero scalar, or a whole integer column as the
         divisor (it may hold zeros; checking would be a host synchronisation), goes to the
         host path."""
-        b = self._raw(o)
-        if self._t.is_floating_point():
+        if self.dtype.kind == "f":
             return
-        if isinstance(b, torch.Tensor):
-            if not b.is_floating_point():
+        if isinstance(o, DeviceSeries):
+            o = o._x
+        if isinstance(o, (torch.Tensor, KE.Expr)):
+            if not (o.is_floating_point() if isinstance(o, torch.Tensor) else o.dtype.kind == "f"):
                 raise HostFallback("integer // or % by an integer column")
-        elif not isinstance(b, float) and b == 0:
+            return
+        b = self._raw(o)
+        if not isinstance(b, float) and b == 0:
             raise HostFallback("integer // or % by zero")
 
     def __floordiv__(self, o):
         self._int_divisor_guard(o)
-        return self._bin(o, lambda a, b: torch.div(a, b, rounding_mode="floor"))
+        return self._bin(o, lambda a, b: torch.div(a, b, rounding_mode="floor"), op="floordiv")
 
     def __mod__(self, o):
         self._int_divisor_guard(o)
-        return self._bin(o, torch.remainder)
+        return self._bin(o, torch.remainder, op="mod")
     def __pow__(self, o): return self._bin(o, torch.pow)
-    def __neg__(self): return self._wrap(-self._t)
-    def __abs__(self): return self._wrap(self._t.abs())
-    def __invert__(self): return self._wrap(~self._t)
-    def __and__(self, o): return self._bin(o, torch.bitwise_and)
-    def __or__(self, o): return self._bin(o, torch.bitwise_or)
-    def __xor__(self, o): return self._bin(o, torch.bitwise_xor)
+
+    def _unary(self, op, fn):
+        r = self._fused(lambda: KE.unary(op, self._expr()))
+        return r if r is not None else self._wrap(fn(self._t))
+
+    def __neg__(self): return self._unary("neg", torch.neg)
+    def __abs__(self): return self._unary("abs", torch.abs)
+    def __invert__(self): return self._unary("not", torch.bitwise_not)
+    def __and__(self, o): return self._bin(o, torch.bitwise_and, op="and")
+    def __or__(self, o): return self._bin(o, torch.bitwise_or, op="or")
+    def __xor__(self, o): return self._bin(o, torch.bitwise_xor, op="xor")
 
     # comparisons: NaN (null) compares False, like pandas
-    def __eq__(self, o): return self._bin(o, torch.eq)  # noqa: E704
-    def __ne__(self, o): return self._bin(o, torch.ne)
-    def __lt__(self, o): return self._bin(o, torch.lt)
-    def __le__(self, o): return self._bin(o, torch.le)
-    def __gt__(self, o): return self._bin(o, torch.gt)
-    def __ge__(self, o): return self._bin(o, torch.ge)
+    def __eq__(self, o): return self._bin(o, torch.eq, op="eq")  # noqa: E704
+    def __ne__(self, o): return self._bin(o, torch.ne, op="ne")
+    def __lt__(self, o): return self._bin(o, torch.lt, op="lt")
+    def __le__(self, o): return self._bin(o, torch.le, op="le")
+    def __gt__(self, o): return self._bin(o, torch.gt, op="gt")
+    def __ge__(self, o): return self._bin(o, torch.ge, op="ge")
     __hash__ = None
 
     def abs(self): return abs(self)
@@ -174,32 +217,45 @@ class DeviceSeries:
             dt = torch_dtype(np.dtype(dtype))
         except Exception:
             raise HostFallback(f"astype({dtype!r})") from None
-        t = self._t
+        r = self._fused(lambda: KE.cast(self._expr(), np.dtype(dtype)))
+        if r is not None:
+            return r
+        t = self._t   # float -> integer: the NaN check needs the values
         if dt in (torch.int32, torch.int64) and t.is_floating_point() and bool(torch.isnan(t).any()):
             raise ValueError("Cannot convert non-finite values (NA or inf) to integer")  # pandas' error
         return self._wrap(t.to(dt))
 
     def isna(self):
+        r = self._fused(lambda: KE.isna(self._expr()))
+        if r is not None:
+            return r
         t = self._t
         return self._wrap(torch.isnan(t) if t.is_floating_point() else torch.zeros_like(t, dtype=torch.bool))
 
     isnull = isna
 
     def notna(self):
-        return self._wrap(~self.isna()._t)
+        return ~self.isna()
 
     notnull = notna
 
     def fillna(self, value):
-        t = self._t
-        if not t.is_floating_point():
+        if self.dtype.kind != "f":
             return self
+        r = self._fused(lambda: KE.fillna(self._expr(), value))
+        if r is not None:
+            return r
+        t = self._t
         return self._wrap(torch.where(torch.isnan(t), torch.as_tensor(value, dtype=t.dtype, device=t.device), t))
 
     def clip(self, lower=None, upper=None):
-        return self._wrap(torch.clamp(self._t, min=lower, max=upper))
+        r = self._fused(lambda: KE.clip(self._expr(), lower, upper))
+        return r if r is not None else self._wrap(torch.clamp(self._t, min=lower, max=upper))
 
     def where(self, cond, other=float("nan")):
+        r = self._fused(lambda: KE.where(self._expr(), self._operand(cond), self._operand(other)))
+        if r is not None:
+            return r
         c = self._raw(cond)
         o = self._raw(other)
         t = self._t
@@ -210,9 +266,15 @@ class DeviceSeries:
         return self._wrap(torch.where(c, t, o))
 
     def mask(self, cond, other=float("nan")):
-        return self.where(~DeviceSeries(self._raw(cond)), other)
+        if not isinstance(cond, DeviceSeries):
+            cond = DeviceSeries(self._raw(cond))
+        return self.where(~cond, other)
 
     def round(self, decimals=0):
+        if decimals == 0 and self.dtype.kind == "f":
+            r = self._fused(lambda: KE.math("round", self._expr()))
+            if r is not None:
+                return r
         return self._wrap(torch.round(self._t, decimals=decimals))
 
     # numpy ufuncs: np.log(col), np.sqrt(col), np.exp(col) ...
@@ -225,11 +287,47 @@ class DeviceSeries:
         np.add: torch.add, np.subtract: torch.sub, np.multiply: torch.mul, np.maximum: torch.maximum,
         np.minimum: torch.minimum, np.power: torch.pow,
     }
+    # the same ufuncs as expression ops (np.power has none)
+    _UFUNC_OPS = {
+        np.log: "log", np.log1p: "log1p", np.log2: "log2", np.log10: "log10", np.exp: "exp", np.expm1: "expm1",
+        np.sqrt: "sqrt", np.abs: "abs", np.absolute: "abs", np.negative: "neg", np.sin: "sin", np.cos: "cos",
+        np.tanh: "tanh", np.floor: "floor", np.ceil: "ceil", np.sign: "sign", np.square: "square",
+        np.isnan: "isnan", np.add: "add", np.subtract: "sub", np.multiply: "mul", np.maximum: "max",
+        np.minimum: "min",
+    }
+
+    def _ufunc_expr(self, op, inputs):
+        """The expression of a ufunc call.  Two operands are fused where torch's promotion (the
+        eager path hands it 0-dim tensors for scalars) and numpy's agree: two series of one dtype,
+        or a scalar that leaves the series' dtype alone."""
+        xs = [self._operand(x) for x in inputs]
+        if len(xs) == 1:
+            a = xs[0]
+            if op == "isnan":
+                return KE.isna(a)
+            if op in ("abs", "neg", "sign", "square"):
+                return KE.unary(op, a) if a.dtype.kind != "b" else KE.unary(op, KE.cast(a, np.float64))
+            return KE.math(op, a)
+        a, b = xs
+        swap = not isinstance(a, KE.Expr)
+        if swap:
+            a, b = b, a
+        if isinstance(b, KE.Expr):
+            if a.dtype != b.dtype:
+                raise KE.NotFusable("ufunc between dtypes")
+        elif isinstance(b, float) and a.dtype.kind != "f":
+            raise KE.NotFusable("ufunc of an integer series and a float")
+        return KE.arith(op, a, b, swap)
 
     def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
         fn = self._UFUNCS.get(ufunc)
         if fn is None or method != "__call__" or kwargs:
             raise HostFallback(f"numpy ufunc {getattr(ufunc, '__name__', ufunc)}")
+        op = self._UFUNC_OPS.get(ufunc)
+        if op is not None and len(inputs) <= 2:
+            r = self._fused(lambda: self._ufunc_expr(op, inputs))
+            if r is not None:
+                return r
         args = []
         dev = self._t.device
         for x in inputs:
