@@ -2297,6 +2297,65 @@ int nvt_expr_eval_host(const nvt_expr_instr *program, int ninstr, const uint64_t
                        const void *const *inputs, const int32_t *input_dtypes,
                        const uint8_t *const *input_valid, int ninputs, uint64_t n, void *out, int out_dtype);
 
+/* ---- embedding layers (nvtabular_amd/kernels_embedding.py, framework_utils.torch.layers) ----------
+ * The tables of a layer: float32 [rows, dim], row-major, one allocation each, described by a HOST array
+ * of at most NVT_EMB_MAX_TABLES nvt_emb_table.  Table c fills columns [out_col, out_col + dim) of a
+ * float32 [batch, out_cols] matrix.  A table whose dim and out_col are multiples of 4, in a matrix whose
+ * out_cols is one, is read and written as float4: the table and the matrix must then be 16-byte
+ * aligned.  The tables of a layer hold at most 2^32 - 2 rows together, a call handles fewer than 2^30
+ * ids / bag values (the device word sort) and batch < 2^31; all of this, null pointers, dim 0 and
+ * slices that end behind out_cols are NVT_EINVAL before any launch.
+ * An id outside [0, rows) is never used as an address: its slice is zeros (a bag skips it), it gets no
+ * gradient, and the forward calls add the number of such ids to *out_of_range (device int64).
+ *   nvt_emb_gather_cat: ids[batch, ntables] (id_dtype NVT_I32 / NVT_I64, row-major) -> out, one launch.
+ *   nvt_emb_bag: column c has values[nvalues] (id_dtype) and offsets[batch + 1] (int64); bag b of the
+ *     column is values[offsets[b] .. offsets[b + 1]) with both ends clamped to [0, nvalues].  Its slice
+ *     is the sum of the rows in value order, NVT_EMB_MEAN: times 1 / length; zeros for an empty bag.
+ *   nvt_emb_grad_plan: exactly one of ids (single-hot) and cols (bags) is given.  Orders the entries of
+ *     the batch by table row and writes state[5 + ntables] (device int64): {unique rows, units, reduce
+ *     workgroups, fold workgroups, floats of partial sums, unique rows of table 0 .. ntables - 1}.  A
+ *     unit is a run of at most NVT_EMB_CHUNK entries of one row.  ws: 256-byte aligned,
+ *     nvt_emb_grad_ws_bytes(entries) bytes (entries = batch * ntables, or all nvalues together), kept
+ *     for nvt_emb_grad_reduce.
+ *   nvt_emb_grad_reduce: after the caller has read state into HOST memory (counts).  Table c gets the
+ *     sum over its entries of grad_out[b, slice] (NVT_EMB_MEAN: / length of the bag) in position order,
+ *     rows of more than one unit through `partials` (16-byte aligned, counts[4] floats) in unit order:
+ *     the same bits on every run.  outs[c].ids != NULL: ids[count] ascending unique rows and
+ *     values[count, dim], count = counts[5 + c]; NULL: values is a zeroed [rows, dim] gradient whose
+ *     touched rows are written once.  tables / out_cols / ids dtype as given to the plan. */
+#define NVT_EMB_MAX_TABLES 64
+#define NVT_EMB_CHUNK 256
+#define NVT_EMB_SUM 0
+#define NVT_EMB_MEAN 1
+typedef struct nvt_emb_table {
+  const float *weight;
+  uint64_t rows;
+  uint32_t dim;
+  uint32_t out_col;
+} nvt_emb_table;
+typedef struct nvt_emb_bag_col {
+  const void *values;
+  const int64_t *offsets;
+  uint64_t nvalues;
+} nvt_emb_bag_col;
+typedef struct nvt_emb_grad_out {
+  int64_t *ids;
+  float *values;
+  uint64_t count;
+} nvt_emb_grad_out;
+int nvt_emb_gather_cat(const void *ids, int id_dtype, uint64_t batch, const nvt_emb_table *tables, int ntables,
+                       float *out, uint64_t out_cols, int64_t *out_of_range, void *stream);
+int nvt_emb_bag(const nvt_emb_bag_col *cols, int id_dtype, uint64_t batch, const nvt_emb_table *tables, int ntables,
+                int mode, float *out, uint64_t out_cols, int64_t *out_of_range, void *stream);
+int nvt_emb_grad_ws_bytes(uint64_t entries, uint64_t *bytes);
+int nvt_emb_grad_plan(const void *ids, const nvt_emb_bag_col *cols, int id_dtype, uint64_t batch,
+                      const nvt_emb_table *tables, int ntables, uint64_t out_cols, void *ws, uint64_t ws_bytes,
+                      int64_t *state, void *stream);
+int nvt_emb_grad_reduce(int bags, uint64_t batch, uint64_t entries, const nvt_emb_table *tables, int ntables, int mode,
+                        const float *grad_out, uint64_t out_cols, const void *ws, uint64_t ws_bytes,
+                        const int64_t *counts, float *partials, uint64_t partial_floats,
+                        const nvt_emb_grad_out *outs, void *stream);
+
 /* ---- small utilities used by the host layer ---- */
 /* widen an int32/uint8 key column to int64 (multi-key tables take int64 components) */
 int nvt_widen_i64(const void *src, int dtype, uint64_t n, int64_t *out, void *stream);

@@ -661,6 +661,32 @@ SIGNATURES.update({
                            _vp, _i32],
 })
 
+class EmbTable(C.Structure):
+    """nvt_emb_table: one embedding table of a layer and its slice of the output."""
+    _fields_ = [("weight", _vp), ("rows", _u64), ("dim", C.c_uint32), ("out_col", C.c_uint32)]
+
+
+class EmbBagCol(C.Structure):
+    """nvt_emb_bag_col: the CSR values and batch + 1 offsets of one multi-hot column."""
+    _fields_ = [("values", _vp), ("offsets", _vp), ("nvalues", _u64)]
+
+
+class EmbGradOut(C.Structure):
+    """nvt_emb_grad_out: where one table's gradient goes (ids NULL: a zeroed dense gradient)."""
+    _fields_ = [("ids", _vp), ("values", _vp), ("count", _u64)]
+
+
+# include/nvt_hip.h NVT_EMB_*
+EMB_MAX_TABLES, EMB_CHUNK, EMB_SUM, EMB_MEAN = 64, 256, 0, 1
+SIGNATURES.update({
+    "nvt_emb_gather_cat": [_vp, _i32, _u64, C.POINTER(EmbTable), _i32, _vp, _u64, _vp, _vp],
+    "nvt_emb_bag": [C.POINTER(EmbBagCol), _i32, _u64, C.POINTER(EmbTable), _i32, _i32, _vp, _u64, _vp, _vp],
+    "nvt_emb_grad_ws_bytes": [_u64, C.POINTER(_u64)],
+    "nvt_emb_grad_plan": [_vp, C.POINTER(EmbBagCol), _i32, _u64, C.POINTER(EmbTable), _i32, _u64, _vp, _u64, _vp, _vp],
+    "nvt_emb_grad_reduce": [_i32, _u64, _u64, C.POINTER(EmbTable), _i32, _i32, _vp, _u64, _vp, _u64,
+                            C.POINTER(C.c_int64), _vp, _u64, C.POINTER(EmbGradOut), _vp],
+})
+
 _RESTYPES = {
     "nvt_last_error": C.c_char_p,
     "nvt_moments_scratch_bytes": C.c_uint64,
